@@ -16,6 +16,11 @@ north-star 100,000-sequence pool at EVERY N: one GPU holds all of it (205 MB of 
 contiguous batch-aligned shards of it (12,500 rows each at N = 8).  Weak scaling in the unit of the metric: every
 rank encodes its own G x 32 queries per step and scans its shard for the queries of all ranks, so per-GPU work is
 fixed as N grows.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (``roofline`` and ``cpu_baseline`` null).  ``--full`` adds
+everything else after the timed steps: rooflines, the other arithmetics, the CPU baseline and the verification runs.
+``--dump-outputs DIR`` writes the last timed step's top-k to DIR as .npy; inputs are seeded, so runs with the same
+arguments can be compared output for output.
 """
 import hashlib
 import argparse
@@ -356,6 +361,14 @@ def gemm_zero_operand_probe(shape, rows, device, reps=20):
     return out
 
 
+def dump_outputs(out_dir, out):
+    """What a caller of the timed path receives from its last step: the merged top-k of every query of the step (all ranks'
+    queries at N > 1).  Indices are global pool rows, exact in float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "topk_values.npy"), out[0].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "topk_indices.npy"), out[1].cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -388,11 +401,21 @@ def main():
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the second timed run on the exact-f32 MFMA kernels (extras.exact_f32)")
     ap.add_argument("--headline-only", action="store_true",
                     help="profiling aid: warm-up + timed steps and nothing else, so that a rocprofv3 --kernel-trace --stats of this "
-                         "command averages the headline launches only")
+                         "command averages the headline launches only (what a run without --full does anyway)")
     ap.add_argument("--no-verify", action="store_true",
                     help="N > 1: skip the post-run check that the sharded top-k equals a one-GPU recomputation on rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything the headline does not need: the HIP-event roofline pass, the "
+                         "other arithmetics, the scan rooflines, the zero-operand probe, the length-bucketed run, the CPU baseline "
+                         "and the verification against the oracle (N = 1) or a one-GPU recomputation (N > 1); the --no-* options "
+                         "switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's top-k (topk_values.npy float32, topk_indices.npy float64; [queries, topk]) "
+                         "to DIR")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.headline_only or not args.full:
         args.no_roofline = args.no_bucketed = args.no_exact_f32 = args.no_cpu_baseline = args.no_verify = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -599,6 +622,8 @@ def main():
     range_word = ops.take_range_flag()
     if range_word:
         raise SystemExit(f"[bench] range guard word {range_word:#x} after the timed region: results are not valid")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     roofline, kernels = None, {}
     if not args.no_roofline:

@@ -14,7 +14,7 @@ ARGS="--shape $R4D_PROFILE_SHAPE --gemm $GEMM --steps 32 --warmup 16 --random-po
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # an ordinary run first (HIP-event roofline of the same steps): its flop_per_launch goes beside the rocprofv3 average
-python3 $R/bench.py --shape $R4D_PROFILE_SHAPE --gemm $GEMM --steps 32 --warmup 16 --random-pool --no-cpu-baseline --no-bucketed --no-exact-f32 > $OUT.line.json 2>> $OUT.bench.log
+python3 $R/bench.py --shape $R4D_PROFILE_SHAPE --gemm $GEMM --steps 32 --warmup 16 --random-pool --full --no-cpu-baseline --no-bucketed --no-exact-f32 > $OUT.line.json 2>> $OUT.bench.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py $ARGS >> $OUT.bench.log 2>&1
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" \
            "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"; do

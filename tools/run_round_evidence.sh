@@ -42,9 +42,9 @@ elif [ "$PART" = lines ]; then
     [ -f profiles/$src ] && [ "$src" != "$dst" ] && cp profiles/$src profiles/$dst
   done
   echo "== bench UCI_13" >> $LOG
-  python bench.py > $EV/${TAG}_bench_line.json 2>> $LOG
+  python bench.py --full > $EV/${TAG}_bench_line.json 2>> $LOG
   echo "== bench wikiv2" >> $LOG
-  python bench.py --shape wikiv2 > $EV/${TAG}_bench_line_wikiv2.json 2>> $LOG
+  python bench.py --full --shape wikiv2 > $EV/${TAG}_bench_line_wikiv2.json 2>> $LOG
   echo "== acceptance table + GEMM shapes + end-to-end CLI timings" >> $LOG
   python tools/s3_acceptance.py > $EV/${TAG}_h2_acceptance.md 2>> $LOG
   python tools/s3_bench.py auto 2>> $LOG | grep "^{" > $EV/${TAG}_gemm_shapes.jsonl
