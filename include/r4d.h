@@ -284,7 +284,9 @@ int r4d_conv1d_h2p_f32(const uint16_t* x_lines_d, const uint16_t* planes_d, cons
  *   bit 0 (R4D_RANGE_NONFINITE_HIDDEN) is OR-ed in by the ln_f / mean-pool kernel of r4d_gpt2_encode_* for every row of the
  *         final residual stream that is non-finite or whose variance overflowed (any arithmetic; in f16x2 mode this is how an
  *         out-of-range activation surfaces);
- *   bit 1 (R4D_RANGE_BAD_NORM) by r4d_normalize_rows_f32 for every row whose norm is NaN, inf or zero.
+ *   bit 1 (R4D_RANGE_BAD_NORM) by r4d_normalize_rows_f32 for every row whose norm is NaN, inf or zero;
+ *   bit 2 (R4D_RANGE_BAD_LABEL) by r4d_lm_ce_f32 / r4d_gpt2_lm_train_step_f32 for a label outside [0, V) that is not the
+ *         ignore_index -100 (such a row is not counted; torch's cross_entropy would raise).
  * The calls stay asynchronous: the caller reads the word at its own synchronisation points.  What the Python host mirror does
  * with it (rag4dyg_amd/ops.py, retrieval.py, gpt2.py): retrieval.encode_batches and GPT2Model.forward re-run an f16x2 call whose
  * bit 0 came up ONCE under bf16x3 (fp32's exponent range) with a warning and raise R4DError if the bit comes up again;
@@ -292,6 +294,7 @@ int r4d_conv1d_h2p_f32(const uint16_t* x_lines_d, const uint16_t* planes_d, cons
  * whole timed region.  encode_* called directly leave the check to the caller (ops.take_range_flag). */
 #define R4D_RANGE_NONFINITE_HIDDEN 1u
 #define R4D_RANGE_BAD_NORM 2u
+#define R4D_RANGE_BAD_LABEL 4u
 int r4d_set_range_flag(uint32_t* flag_d);
 
 /* --- single ops, exported for per-op parity tests (same kernels the encoder launches) --- */
@@ -497,6 +500,47 @@ size_t r4d_retriever_losses_workspace_bytes(int32_t B);
 int r4d_retriever_losses_f32(const float* emb_d, const float* t_anchor_d, const float* t_pos_d, const float* t_neg_d, int32_t B,
                              int32_t d, float temperature, float lambda_decay, float alpha, float grad_scale, float* losses_d,
                              float* d_emb_d, void* workspace_d, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * SimpleDyG LM TRAINING (additive ABI v6 entries): the LM head logits = h . wte^T over every position, the shifted cross
+ * entropy of models/modeling_gpt2.py:604-615 (labels == inputs) and its gradient back into the tied wte and into h.
+ * ---------------------------------------------------------------------------------------------- */
+/* r4d_gpt2_train_forward_f32 / _backward_f32 with a per-row output: out_hidden_d f32 [sum(Bs*Ts), d] = the ln_f output of every
+ * position (rows of all batches in call order); the backward takes d_hidden_d of the same shape.  Same workspace query. */
+int r4d_gpt2_train_forward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int32_t n_groups,
+                                      const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, float* out_hidden_d,
+                                      const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream);
+int r4d_gpt2_train_backward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
+                                       int32_t n_groups, const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts,
+                                       const float* d_hidden_d, const r4d_train_dropout* dropout,
+                                       void* workspace_d, size_t workspace_bytes, void* stream);
+/* Fused shifted cross entropy over logits_d f32 [N, ldV] (N = B*T rows, columns [V, ldV) padding, ldV % 4 == 0, V <= ldV <= 15872).
+ * Label of row (b, t): src[b, t + 1] with src = labels_d when given (int64 [B, T]) else ids_d (int64 [B, T]); row t = T - 1 has
+ * none; a label outside [0, V) (ignore_index -100) is not counted; any other such label also raises R4D_RANGE_BAD_LABEL.  loss_d f32[1] <- mean over the counted rows (the count is
+ * taken on the device: NaN when no row counts, as torch); logits_d is OVERWRITTEN with grad_scale * (softmax - onehot) / n_counted,
+ * exact zeros in uncounted rows and pad columns.  Fixed-order sums: the same bits on every launch. */
+size_t r4d_lm_ce_workspace_bytes(int32_t N);
+int r4d_lm_ce_f32(float* logits_d, int32_t N, int32_t V, int32_t ldV, const int64_t* ids_d, const int64_t* labels_d, int32_t T,
+                  float grad_scale, float* loss_d, void* workspace_d, size_t workspace_bytes, void* stream);
+/* The tied LM head operand: wte_pad_d f32 [ldV, d] = wte in rows [0, V), ZERO rows up to ldV (ldV = V rounded up to 128); the
+ * optional planes of it (r4d_split3_planes_bf16 / r4d_split2_planes_f16 of wte_pad_d): w3_d [3][ldV][d] (transposed = 1) and
+ * h2_d [ldV][d/32][2][32] for the logits GEMM, w3t_d [3][d][ldV] (wte_pad_d as a [K = ldV, N = d] weight, transposed = 0) for
+ * dh = dlogits . wte.  Refresh them with the layer planes after every optimizer step. */
+typedef struct {
+    const float* wte_pad;
+    int32_t ldV;
+    const uint16_t* w3;
+    const uint16_t* w3t;
+    const uint16_t* h2;
+} r4d_lm_head;
+/* One SimpleDyG training step on one right-padded id batch ids_d int64 [B, T] (labels == inputs): forward_hidden -> logits (the
+ * forward GEMM family of the current r4d_set_gemm_split3 mode) -> r4d_lm_ce_f32 -> dh = dlogits . wte (bf16x3 like every data
+ * gradient) and dwte_head = dlogits^T . h (the weight-gradient GEMM) -> backward_hidden.  grads->wte = embedding scatter +
+ * dwte_head, added in that fixed order.  loss_d f32[1] stays on the device.  grad_scale scales every gradient (1 / accumulation
+ * steps), not the loss. */
+size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t T, int32_t ldV);
+int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
+                               const r4d_lm_head* head, const int64_t* ids_d, int32_t B, int32_t T, float grad_scale, float* loss_d,
+                               const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream);
 /* Single backward ops, exported for per-op parity tests (the kernels the step launches). */
 /* Conv1D parameter gradients (modeling_utils.py:1267-1271 under autograd): dw_d [in,out] = x^T . dy, db_d [out] (nullable) =
  * column sums of dy, for x_d [rows,in] and dy_d [rows,out]; in / out multiples of 4. */

@@ -2,8 +2,9 @@
 """Drop-in for the reference ``main_SimpleDyG.py`` (flags of ``utils/args_parser_SimpleDyG.py``): the SimpleDyG
 GPT-2 FORWARD on the MI355X -- ``--do_eval`` runs the reference's greedy link-prediction evaluation
 (``get_eval_metrics``, ``utils/Evaluation_SimpleDyG.py:53-211``: NDCG@5 / Jaccard, as ``main_SimpleDyG.py:485-487``) for
-every checkpoint and also reports the LM loss over ``--eval_data_file`` (``evaluate``, :345-372).  LM training
-(``train``/``train_epoch`` :148-343, backward pass) is not part of this build and raises."""
+every checkpoint and also reports the LM loss over ``--eval_data_file`` (``evaluate``, :345-372).  ``--do_train`` runs the LM
+training (``train``/``train_epoch`` :148-343) on the device: ``rag4dyg_amd.lm_training.train``.  ``--fp16`` (apex) and
+``--should_continue`` are not built and raise."""
 import glob
 import os
 
@@ -61,7 +62,14 @@ def main(argv=None):
                         args.per_gpu_train_batch_size, args.learning_rate, args.seed]
     model, tokenizer, model_class, args = get_model_tokenizer(args, MODEL_CLASSES)
     if args.do_train:
-        raise NotImplementedError("SimpleDyG LM training (backward pass) is outside the encode-and-retrieve hot path")
+        from rag4dyg_amd.lm_training import train
+        if args.fp16:
+            raise NotImplementedError("SimpleDyG training: --fp16 (apex mixed precision) is not built; the path is fp32")
+        if args.should_continue:
+            raise NotImplementedError("SimpleDyG training: --should_continue (resuming from a checkpoint) is not built")
+        train_dataset = LineByLineTextDataset(tokenizer, args, file_path=args.train_data_file, block_size=args.block_size)
+        global_step, train_loss = train(args, train_dataset, model, tokenizer)
+        print(" global_step = {}, average loss = {}".format(global_step, train_loss))
     results = {}
     if args.do_eval:
         checkpoints = [args.output_dir]

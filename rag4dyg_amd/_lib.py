@@ -50,6 +50,10 @@ class GPT2GradsC(Structure):
                 ("layers", POINTER(GPT2LayerGradsC))]
 
 
+class LMHeadC(Structure):                       # r4d_lm_head
+    _fields_ = [("wte_pad", c_void_p), ("ldV", c_int32), ("w3", c_void_p), ("w3t", c_void_p), ("h2", c_void_p)]
+
+
 class GPT2WeightsC(Structure):
     _fields_ = [("wte", c_void_p), ("wpe", c_void_p), ("ln_f_w", c_void_p), ("ln_f_b", c_void_p),
                 ("layers", POINTER(GPT2LayerC)), ("lm_head", c_void_p)]
@@ -126,6 +130,16 @@ PROTOTYPES = {
                                              POINTER(c_int32), _P, POINTER(TrainDropoutC), _P, c_size_t, _P]),
     "r4d_gpt2_train_backward_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(GPT2GradsC), c_int32, POINTER(_P),
                                               POINTER(c_int32), POINTER(c_int32), _P, POINTER(TrainDropoutC), _P, c_size_t, _P]),
+    "r4d_gpt2_train_forward_hidden_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), c_int32, POINTER(_P), POINTER(c_int32),
+                                                    POINTER(c_int32), _P, POINTER(TrainDropoutC), _P, c_size_t, _P]),
+    "r4d_gpt2_train_backward_hidden_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(GPT2GradsC), c_int32,
+                                                     POINTER(_P), POINTER(c_int32), POINTER(c_int32), _P, POINTER(TrainDropoutC), _P,
+                                                     c_size_t, _P]),
+    "r4d_lm_ce_workspace_bytes": (c_size_t, [c_int32]),
+    "r4d_lm_ce_f32": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P, c_int32, c_float, _P, _P, c_size_t, _P]),
+    "r4d_gpt2_lm_train_workspace_bytes": (c_size_t, [POINTER(GPT2ConfigC), c_int32, c_int32, c_int32]),
+    "r4d_gpt2_lm_train_step_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(GPT2GradsC), POINTER(LMHeadC), _P,
+                                             c_int32, c_int32, c_float, _P, POINTER(TrainDropoutC), _P, c_size_t, _P]),
     "r4d_retriever_losses_workspace_bytes": (c_size_t, [c_int32]),
     "r4d_retriever_losses_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_float, c_float, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     "r4d_dropout_f32": (c_int32, [_P, _P, c_int64, _P, c_float, c_uint64, c_uint64, c_uint32, c_uint64, _P]),

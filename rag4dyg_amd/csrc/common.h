@@ -43,7 +43,7 @@ enum ProfClass {
     PK_GEMM_128x128_NN = 0, PK_GEMM_128x128_NT, PK_GEMM_128x64_NN, PK_GEMM_128x64_NT, PK_GEMM_64x64_NN,
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
-    PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_COUNT
+    PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -93,7 +93,7 @@ extern unsigned long long g_branch_hits[BR_COUNT];
 #define R4D_BRANCH(id) (++r4d::g_branch_hits[r4d::BR_##id])
 
 // range guard (include/r4d.h: r4d_set_range_flag)
-extern unsigned* g_range_flag;         // bits: R4D_RANGE_NONFINITE_HIDDEN, R4D_RANGE_BAD_NORM
+extern unsigned* g_range_flag;         // bits: R4D_RANGE_NONFINITE_HIDDEN, R4D_RANGE_BAD_NORM, R4D_RANGE_BAD_LABEL
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -185,6 +185,17 @@ struct DropKey { unsigned seed_lo, seed_hi, step_lo, step_hi; };      // Philox 
 // out = (resid ? resid : 0) + dropout_p(x): element i uses counter (base + i) / 4 of `site`; out may alias x / resid
 int launch_dropout(const float* x, const float* resid, long long n, float* out, float p, DropKey key, unsigned site,
                    unsigned long long base, hipStream_t s);
+
+// ------------------------------------------------------------------ train.hip (the training forward / backward, shared with lm_head.hip)
+size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts);
+// output: EITHER out_meanpool_d [sum B, d] OR out_hidden_d [rows, d] (the ln_f output); the backward takes the matching gradient
+int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
+                       const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
+                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s);
+int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr, int n_groups,
+                        const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
+                        const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
+                        hipStream_t s);
 
 // ------------------------------------------------------------------ topk.hip
 // rows x n values -> rows x k best (value, global index), canonical order; `counters_zeroed`: the caller already cleared

@@ -303,14 +303,39 @@ size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_grou
 int r4d_gpt2_train_forward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int32_t n_groups,
                                const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d,
                                const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream) {
+    R4D_REQUIRE(out_meanpool_d, "gpt2 train: null pointer");
+    return gpt2_train_forward(cfg, w, n_groups, ids_d, Bs, Ts, out_meanpool_d, nullptr, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
+}
+
+int r4d_gpt2_train_backward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr,
+                                int32_t n_groups, const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts,
+                                const float* d_meanpool_d, const r4d_train_dropout* dropout, void* workspace_d,
+                                size_t workspace_bytes, void* stream) {
+    R4D_REQUIRE(d_meanpool_d, "gpt2 train backward: null pointer");
+    return gpt2_train_backward(cfg, w, gr, n_groups, ids_d, Bs, Ts, d_meanpool_d, nullptr, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace r4d {
+
+size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts) {
+    std::vector<TrainGroup> gs((size_t)n_groups);
+    for (int g = 0; g < n_groups; ++g) gs[g] = TrainGroup{nullptr, Bs[g], Ts[g], 0, 0, 0};
+    return layout(cfg, gs.data(), n_groups).total;
+}
+
+// The training forward; its output is EITHER the mean pool per sequence (retriever) OR the ln_f output per row (LM head)
+int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
+                       const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
+                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s) {
     if (g_train_fuse_gelu < 0) { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); g_train_fuse_gelu = e ? atoi(e) : 1; }
-    hipStream_t s = (hipStream_t)stream;
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
     DropCtx dc;
     if ((rc = drop_ctx(dropout, dc))) return rc;
-    R4D_REQUIRE(w && w->wte && w->wpe && w->ln_f_w && w->ln_f_b && w->layers && out_meanpool_d, "gpt2 train: null pointer");
+    R4D_REQUIRE(w && w->wte && w->wpe && w->ln_f_w && w->ln_f_b && w->layers && (out_meanpool_d || out_hidden_d), "gpt2 train: null pointer");
     const TrainLayout t = layout(cfg, gs.data(), n_groups);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -356,22 +381,22 @@ int r4d_gpt2_train_forward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weight
             if ((rc = launch_dropout(branch, x_mid, (long long)M * d, x_next, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
         } else if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, x_mid, M, 4 * d, d, EPI_RESIDUAL, x_next, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
     }
-    return launch_lnf_meanpool_groups(R, ws + t.x_out, w->ln_f_w, w->ln_f_b, d, cfg->ln_eps, nullptr, out_meanpool_d,
+    return launch_lnf_meanpool_groups(R, ws + t.x_out, w->ln_f_w, w->ln_f_b, d, cfg->ln_eps, out_hidden_d, out_meanpool_d,
                                       ws + t.pool_scratch, s);
 }
 
-int r4d_gpt2_train_backward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr,
-                                int32_t n_groups, const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts,
-                                const float* d_meanpool_d, const r4d_train_dropout* dropout, void* workspace_d,
-                                size_t workspace_bytes, void* stream) {
+// Backward of gpt2_train_forward from EITHER d(mean pool) [sum B, d] OR d(ln_f output) [rows, d]
+int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr, int n_groups,
+                        const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
+                        const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
+                        hipStream_t s) {
     if (g_train_fuse_gelu < 0) { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); g_train_fuse_gelu = e ? atoi(e) : 1; }
-    hipStream_t s = (hipStream_t)stream;
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
     DropCtx dc;
     if ((rc = drop_ctx(dropout, dc))) return rc;
-    R4D_REQUIRE(w && w->layers && gr && gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b && d_meanpool_d,
+    R4D_REQUIRE(w && w->layers && gr && gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b && (d_meanpool_d || d_hidden_d),
                 "gpt2 train backward: null pointer");
     const TrainLayout t = layout(cfg, gs.data(), n_groups);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
@@ -381,10 +406,13 @@ int r4d_gpt2_train_backward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weigh
     float* ws = (float*)workspace_d;
     const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M, L = cfg->n_layer;
     float *dx = ws + t.dx, *dy = ws + t.dy, *dbig = ws + t.dbig, *dqkv = ws + t.dqkv, *xT = ws + t.xT, *red = ws + t.red;
-    // mean over T -> ln_f
-    for (const TrainGroup& G : gs)
-        if ((rc = launch_meanpool_bwd(d_meanpool_d + G.seq0 * d, (long long)G.B * G.T, G.T, d, dy + G.row0 * d, s))) return rc;
-    if ((rc = launch_ln_bwd(ws + t.x_out, w->ln_f_w, dy, nullptr, M, d, cfg->ln_eps, dx, gr->ln_f_w, gr->ln_f_b, red, 0, s))) return rc;
+    // mean over T -> ln_f (or the caller's per-row gradient of the ln_f output)
+    if (d_meanpool_d) {
+        for (const TrainGroup& G : gs)
+            if ((rc = launch_meanpool_bwd(d_meanpool_d + G.seq0 * d, (long long)G.B * G.T, G.T, d, dy + G.row0 * d, s))) return rc;
+    }
+    const float* dlnf = d_meanpool_d ? dy : d_hidden_d;
+    if ((rc = launch_ln_bwd(ws + t.x_out, w->ln_f_w, dlnf, nullptr, M, d, cfg->ln_eps, dx, gr->ln_f_w, gr->ln_f_b, red, 0, s))) return rc;
     for (int l = L - 1; l >= 0; --l) {
         const r4d_gpt2_layer& Lw = w->layers[l];
         const r4d_gpt2_layer_grads& Lg = gr->layers[l];
@@ -437,4 +465,4 @@ int r4d_gpt2_train_backward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weigh
     return launch_embedding_fix_to_f32(acc, (long long)cfg->vocab * d, (long long)M, gr->wte, s);
 }
 
-}  // extern "C"
+}  // namespace r4d

@@ -309,7 +309,7 @@ def lm_logits(hidden, wte):
 
 
 # ------------------------------------------------------------------------------------------- range guard (include/r4d.h, ABI v6)
-RANGE_NONFINITE_HIDDEN, RANGE_BAD_NORM = 1, 2
+RANGE_NONFINITE_HIDDEN, RANGE_BAD_NORM, RANGE_BAD_LABEL = 1, 2, 4
 _RANGE_FLAG = None
 
 
@@ -345,6 +345,8 @@ def check_range(what):
                        "|x| >= 2^18 in gemm mode 'f16x2'; 'bf16x3' and 'f32' have fp32's exponent range)")
         if v & RANGE_BAD_NORM:
             why.append("an embedding row could not be normalised (NaN, inf or zero norm)")
+        if v & RANGE_BAD_LABEL:
+            why.append("a token id outside [0, vocab) reached the LM cross entropy")
         raise _lib.R4DError(f"{what}: " + "; ".join(why) + " -- no ranking was produced from it")
 
 

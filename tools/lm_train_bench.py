@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""SimpleDyG LM-training step (``LMTrainer.step``: forward, LM head, shifted cross entropy, backward) at the reference's script
+shapes: ms per step and tokens/s, the per-class breakdown of ``r4d_profile_*``, the CE kernel's bytes / time against the 8 TB/s HBM
+spec, the head's share of the step (step minus forward_hidden + backward_hidden timed alone; eval mode, no dropout), and as a yardstick the same head (h . wte^T, F.cross_entropy, backward) in torch autograd.
+
+    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = {"uci13": dict(L=6, H=8, d=768, V=1800, B=32, Ts=(128, 340)),
+          "wikiv2": dict(L=2, H=6, d=768, V=8814, B=32, Ts=(128, 512))}
+HBM_BPS = 8e12
+
+
+def _profile(lib):
+    out = {}
+    for c in range(lib.r4d_profile_num_classes()):
+        ms, n, w = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+        lib.r4d_profile_read(c, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(w))
+        if n.value:
+            out[lib.r4d_profile_class_name(c).decode()] = dict(ms=ms.value, launches=n.value, work=w.value)
+    return out
+
+
+def _time(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    from oracle import gpt2_ref
+    from rag4dyg_amd import _lib, ops
+    from rag4dyg_amd.gpt2 import GPT2Config, GPT2LMHeadModel
+    from rag4dyg_amd.lm_training import LMTrainer
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--shapes", default="uci13,wikiv2")
+    ap.add_argument("--one-step", type=int, default=0, metavar="T",
+                    help="run one warm-up and ONE timed step at T of the first shape, print nothing else (for a kernel trace)")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    lib = _lib.load()
+    for name in a.shapes.split(","):
+        s = SHAPES[name]
+        sd = gpt2_ref.make_state_dict(s["L"], s["d"], s["V"], n_positions=1024, seed=1, random_affine=True)
+        sd.pop("lm_head.weight", None)
+        cfg = GPT2Config(vocab_size=s["V"], n_positions=1024, n_ctx=1024, n_embd=s["d"], n_layer=s["L"], n_head=s["H"])
+        m = GPT2LMHeadModel(cfg)
+        m.load_state_dict(sd, strict=False)
+        m.tie_weights()
+        # eval mode: no dropout launches, so that the step and its body (timed alone below) differ by the head only
+        m = m.to(dev).eval()
+        tr = LMTrainer(m)
+        if a.one_step:
+            ids = torch.randint(0, s["V"], (s["B"], a.one_step), device=dev)
+            tr.step(ids)
+            torch.cuda.synchronize()
+            tr.step(ids)
+            torch.cuda.synchronize()
+            return
+        for T in s["Ts"]:
+            B, V, d = s["B"], s["V"], s["d"]
+            ids = torch.randint(0, V, (B, T), device=dev)
+            ms = _time(lambda: tr.step(ids), a.steps, a.warmup)
+            lib.r4d_profile_enable(1)
+            tr.step(ids)
+            torch.cuda.synchronize()
+            prof = _profile(lib)
+            lib.r4d_profile_enable(0)
+            N, ldV = B * T, tr.ldV
+            ce = prof.get("lm_ce", {})
+            ce_bytes = 2.0 * N * V * 4
+            head_flop = 3 * 2.0 * N * ldV * d
+            # the step without its head: forward_hidden + backward_hidden alone (same workspace layout); head = step - body
+            c, w, g, keep = tr.enc._structs()
+            Bs, Ts = (ctypes.c_int32 * 1)(B), (ctypes.c_int32 * 1)(T)
+            ptrs = (ctypes.c_void_p * 1)(ids.data_ptr())
+            ws = torch.empty(lib.r4d_gpt2_train_workspace_bytes(ctypes.byref(c), 1, Bs, Ts), dtype=torch.uint8, device=dev)
+            h = torch.empty(N, d, device=dev)
+            dh = torch.randn(N, d, device=dev) * 1e-4
+            stream = torch.cuda.current_stream().cuda_stream
+
+            def body():
+                _lib.check(lib.r4d_gpt2_train_forward_hidden_f32(ctypes.byref(c), ctypes.byref(w), 1, ptrs, Bs, Ts, h.data_ptr(), None,
+                                                                 ws.data_ptr(), ws.numel(), stream), "fwd")
+                _lib.check(lib.r4d_gpt2_train_backward_hidden_f32(ctypes.byref(c), ctypes.byref(w), ctypes.byref(g), 1, ptrs, Bs, Ts,
+                                                                  dh.data_ptr(), None, ws.data_ptr(), ws.numel(), stream), "bwd")
+            body_ms = _time(body, a.steps, a.warmup)
+            del ws
+            hr = h.clone().requires_grad_(True)
+            wr = m.transformer.wte.weight.detach().clone().requires_grad_(True)
+            lab = ids.view(B, T)[:, 1:].reshape(-1)
+
+            def torch_head():
+                lg = (hr @ wr.t()).view(B, T, V)[:, :-1].reshape(-1, V)
+                torch.nn.functional.cross_entropy(lg, lab).backward()
+            torch_ms = _time(torch_head, a.steps, a.warmup)
+            lib.r4d_profile_enable(1)
+            tr.step(ids)
+            torch.cuda.synchronize()
+            prof2 = _profile(lib)
+            lib.r4d_profile_enable(0)
+            total_prof = sum(v["ms"] for v in prof2.values())
+            head_like = {k: v for k, v in prof2.items() if v["work"] > 0}
+            rec = dict(shape=name, mode=ops.gemm_mode(), L=s["L"], H=s["H"], d=d, V=V, ldV=ldV, B=B, T=T, ms_per_step=ms,
+                       tokens_per_s=N / (ms / 1e3), ce_ms=ce.get("ms"), ce_bytes=ce_bytes,
+                       ce_hbm_fraction=(ce_bytes / (ce["ms"] / 1e3) / HBM_BPS) if ce else None,
+                       head_flop=head_flop, body_ms=body_ms, head_ms=ms - body_ms, head_share=(ms - body_ms) / ms,
+                       head_tflops=head_flop / ((ms - body_ms) / 1e3) / 1e12, torch_head_ms=torch_ms, profiled_ms=total_prof,
+                       classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"]) for k, v in sorted(head_like.items(), key=lambda kv: -kv[1]["ms"])})
+            print(json.dumps(rec))
+            del h, dh, hr, wr
+
+
+if __name__ == "__main__":
+    main()
