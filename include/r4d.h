@@ -541,6 +541,38 @@ size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, 
 int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                                const r4d_lm_head* head, const int64_t* ids_d, int32_t B, int32_t T, float grad_scale, float* loss_d,
                                const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * RAG generator training (train/train_generator.py, utils/model.py:105-224; csrc/rag_train.hip).  One step on a SPLICED batch:
+ * aug_ids_d int64 [B, Ta] holds the token ids with -100 at the r fused positions 2 .. 2 + r - 1 of every sequence (Ta = T + r);
+ * the input rows there are fused_d f32 [B, r, d] instead of wte rows.  aug_ids_d is also the label array of the shifted cross
+ * entropy (ignore_index -100) and the index array of the wte scatter (negative ids add nothing).
+ *   grads == NULL: the transformer is FROZEN -- no weight GEMM, no LayerNorm gain / shift sums, no embedding scatter; the data
+ *                  gradients still run down to the embeddings.
+ *   head_mode:     where dW_head = dlogits^T . h goes: R4D_HEAD_GRAD_UNTIED -> head_grad_d f32 [V, d] (overwritten);
+ *                  R4D_HEAD_GRAD_TIED -> added into grads->wte after the token scatter; R4D_HEAD_GRAD_NONE -> nowhere.
+ *                  `head` is the padded operand of the head in use (lm_head.weight when untied), as r4d_lm_head describes.
+ *   d_fused_d:     (nullable) f32 [B, r, d] <- the gradient of the spliced rows (behind the embedding dropout's mask).
+ *   hidden_out_d:  (nullable) f32 [B * Ta, d] <- the ln_f output rows (the logits are overwritten by their gradient).
+ * grads == NULL and d_fused_d == NULL: forward and loss only (the evaluation loss).  loss_d f32[1] stays on the device;
+ * grad_scale scales every gradient, not the loss.  Same bits on every launch. */
+#define R4D_HEAD_GRAD_UNTIED 0
+#define R4D_HEAD_GRAD_TIED 1
+#define R4D_HEAD_GRAD_NONE 2
+size_t r4d_rag_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t Ta, int32_t ldV);
+int r4d_rag_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads, const r4d_lm_head* head,
+                           int32_t head_mode, float* head_grad_d, const int64_t* aug_ids_d, const float* fused_d, int32_t B, int32_t Ta,
+                           int32_t r, float grad_scale, float* loss_d, float* d_fused_d, float* hidden_out_d,
+                           const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream);
+/* Weighted bags (the one-layer GCN's mean pool, c^T X): out_d f32 [n_bags, d] row q = sum over j in [offsets_d[q], offsets_d[q+1])
+ * of weights_d[j] * table_d[ids_d[j]], j ascending per a fixed split; d % 4 == 0.  No atomics. */
+int r4d_weighted_bag_f32(const float* table_d, int32_t vocab, int32_t d, const int64_t* ids_d, const float* weights_d,
+                         const int32_t* offsets_d, int32_t n_bags, float* out_d, void* stream);
+/* Deterministic scatter into a token table: out_d f32 [vocab, d] (OVERWRITTEN) row v = sum over k with ids_d[k] == v of
+ * weights_d[k] * src_d[row_of_d[k]] (weights_d NULL: 1; row_of_d NULL: row k), through a 64-bit fixed-point table whose scale
+ * follows max |term| (the embedding backward's sums): the same bits whatever the order.  A NaN / Inf term makes out_d NaN. */
+size_t r4d_embedding_scatter_workspace_bytes(int32_t vocab, int32_t d);
+int r4d_embedding_scatter_f32(const float* src_d, const int32_t* row_of_d, const float* weights_d, const int64_t* ids_d, int32_t n,
+                              int32_t d, int32_t vocab, float* out_d, void* workspace_d, size_t workspace_bytes, void* stream);
 /* Single backward ops, exported for per-op parity tests (the kernels the step launches). */
 /* Conv1D parameter gradients (modeling_utils.py:1267-1271 under autograd): dw_d [in,out] = x^T . dy, db_d [out] (nullable) =
  * column sums of dy, for x_d [rows,in] and dy_d [rows,out]; in / out multiples of 4. */

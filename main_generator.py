@@ -5,7 +5,8 @@
 retrieved training sequences (``*_index.gen`` written by this build's ``main_retriever.py``), greedy link prediction,
 R@5 / NDCG@5 / Jaccard (``utils/Evaluation_generator.py:49-265``) -- on the MI355X kernels; launched with
 ``python -m torch.distributed.run --nproc-per-node N`` the test queries are decoded data-parallel, one process per GPU.
-Generator TRAINING (``train/train_generator.py``, backward pass) is not part of this build and raises."""
+``--do_train`` trains the generator (``train/train_generator.py``; ``rag4dyg_amd/generator_training.py``): graph pooling with one
+GCN layer and ``--m 1``, the configuration of every shipped script, with or without ``--freeze``."""
 import glob
 import os
 
@@ -55,9 +56,19 @@ def main(argv=None):
         model.get_mlp(512, args.m, args.mlp_layers)                                   # main_generator.py:81-82
     if "graphpooling" in args.fusion:
         model.get_gnn(args.n_embed, int(args.n_embed / 2), args.n_embed, args.gnn_layers, 0.2)      # :84-85
-    if args.do_train:
-        raise NotImplementedError("generator training (GNN/MLP fusion + LM head, backward pass) is outside this build; "
-                                  "train with the reference and evaluate the checkpoints here")
+    if args.do_train:                                # main_generator.py:88-106
+        from rag4dyg_amd import generator_training
+        generator_training.check_supported(args)
+        model.to(args.device)
+        if args.freeze:
+            if not args.simpledyg_checkpoint:
+                raise ValueError("--freeze needs --simpledyg_checkpoint (the SimpleDyG checkpoint-0 whose transformer is frozen)")
+            generator_training.load_and_freeze_params(model, args.simpledyg_checkpoint)
+        from rag4dyg_amd.generator import load_and_cache_examples
+        train_dataset = load_and_cache_examples(args, tokenizer, evaluate=False)
+        global_step, tr_loss = generator_training.train(args, train_dataset, model, tokenizer)
+        if rank0:
+            print(" global_step = {}, average loss = {}".format(global_step, tr_loss))
     results = {}
     if args.do_eval:
         checkpoints = [args.output_dir]

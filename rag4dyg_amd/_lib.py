@@ -10,6 +10,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("R4D_LIB_PATH") or os.path.join(PKG, "librag4dyg_hip.so")   # override: tools/ A/B tuning only
 
 R4D_ABI_VERSION = 6
+HEAD_GRAD_UNTIED, HEAD_GRAD_TIED, HEAD_GRAD_NONE = 0, 1, 2          # r4d_rag_train_step_f32 head_mode
 
 
 class R4DError(RuntimeError):
@@ -140,6 +141,12 @@ PROTOTYPES = {
     "r4d_gpt2_lm_train_workspace_bytes": (c_size_t, [POINTER(GPT2ConfigC), c_int32, c_int32, c_int32]),
     "r4d_gpt2_lm_train_step_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(GPT2GradsC), POINTER(LMHeadC), _P,
                                              c_int32, c_int32, c_float, _P, POINTER(TrainDropoutC), _P, c_size_t, _P]),
+    "r4d_rag_train_workspace_bytes": (c_size_t, [POINTER(GPT2ConfigC), c_int32, c_int32, c_int32]),
+    "r4d_rag_train_step_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(GPT2GradsC), POINTER(LMHeadC), c_int32, _P,
+                                         _P, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, POINTER(TrainDropoutC), _P, c_size_t, _P]),
+    "r4d_weighted_bag_f32": (c_int32, [_P, c_int32, c_int32, _P, _P, _P, c_int32, _P, _P]),
+    "r4d_embedding_scatter_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "r4d_embedding_scatter_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),
     "r4d_retriever_losses_workspace_bytes": (c_size_t, [c_int32]),
     "r4d_retriever_losses_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_float, c_float, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     "r4d_dropout_f32": (c_int32, [_P, _P, c_int64, _P, c_float, c_uint64, c_uint64, c_uint32, c_uint64, _P]),

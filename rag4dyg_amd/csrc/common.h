@@ -43,7 +43,8 @@ enum ProfClass {
     PK_GEMM_128x128_NN = 0, PK_GEMM_128x128_NT, PK_GEMM_128x64_NN, PK_GEMM_128x64_NT, PK_GEMM_64x64_NN,
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
-    PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE, PK_COUNT
+    PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
+    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -185,17 +186,49 @@ struct DropKey { unsigned seed_lo, seed_hi, step_lo, step_hi; };      // Philox 
 // out = (resid ? resid : 0) + dropout_p(x): element i uses counter (base + i) / 4 of `site`; out may alias x / resid
 int launch_dropout(const float* x, const float* resid, long long n, float* out, float p, DropKey key, unsigned site,
                    unsigned long long base, hipStream_t s);
+// 64-bit fixed-point token-gradient tables (train_ops.hip, embedding backward): S with |g| 2^S M < 2^62 for every |g| <= max,
+// M = 2^lg_rows >= the contributions that can meet in one element
+constexpr int EMB_SUM_BITS = 62;
+__device__ __forceinline__ int emb_scale_exp(unsigned max_bits, int lg_rows) {
+    const int e = (int)((max_bits >> 23) & 255u) - 126;                                  // max < 2^e (exponent field 0: a subnormal)
+    return EMB_SUM_BITS - lg_rows - e;
+}
+static inline int emb_lg_rows(long long table_rows) {
+    int lg = 0;
+    while ((1LL << lg) < table_rows) ++lg;
+    return lg;
+}
+int launch_embedding_fix_to_f32(const unsigned long long* acc, long long n, long long table_rows, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------ train.hip (the training forward / backward, shared with lm_head.hip)
 size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts);
 // output: EITHER out_meanpool_d [sum B, d] OR out_hidden_d [rows, d] (the ln_f output); the backward takes the matching gradient
+// `sp` (nullable, one batch only): a SPLICED input (RAG generator): ids_d[0] holds -100 at the positions 2 .. 2 + r - 1, whose
+// embedding rows are sp->fused [B, r, d] instead of wte rows (rag_train.hip: launch_splice_embed_ln)
+struct SpliceIn { const float* fused; int r; };
 int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
-                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s);
+                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s,
+                       const SpliceIn* sp = nullptr);
+// `gr` == nullptr: FROZEN transformer -- no parameter gradient at all (no weight GEMM, no LayerNorm gain / shift sums, no
+// embedding scatter), only the data gradients down to the embeddings; `d_fused` must then be given.  `d_fused` (with `sp`):
+// [B, r, d] <- the gradient of the spliced rows (behind the embedding dropout's mask)
 int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr, int n_groups,
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
-                        hipStream_t s);
+                        hipStream_t s, const SpliceIn* sp = nullptr, float* d_fused = nullptr);
+int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, const float* wte, const float* wpe, int vocab, int B,
+                           int T, int d, const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s);
+
+// ------------------------------------------------------------------ lm_head.hip (the LM head of the training steps)
+struct LMLayout { size_t train, h, logits, dh, dwte, tn, ce, total; };
+LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV);
+int check_ce(int N, int V, int ldV, int T);
+// logits = h . wte_pad^T, loss and dlogits (in place; label of row r: src[r + 1] within a sequence of T rows), then -- when `dh`
+// is given -- dh = dlogits . wte_pad and -- when `dwte` is given -- dwte [ldV, d] = dlogits^T . h
+int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale, float* loss,
+                  float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s);
+int launch_add_inplace(float* y, const float* x, long long n, hipStream_t s);      // y += x (n % 4 == 0, 16-byte aligned)
 
 // ------------------------------------------------------------------ topk.hip
 // rows x n values -> rows x k best (value, global index), canonical order; `counters_zeroed`: the caller already cleared

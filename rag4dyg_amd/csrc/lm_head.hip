@@ -170,15 +170,14 @@ static int lm_ce(float* logits, int N, int V, int ldV, const int64_t* src, int T
     return R4D_OK;
 }
 
-static int check_ce(int N, int V, int ldV, int T) {
+int check_ce(int N, int V, int ldV, int T) {
     R4D_REQUIRE(N >= 1 && T >= 1 && N % T == 0, "lm_ce: N=%d is not a multiple of T=%d", N, T);
     R4D_REQUIRE(V >= 1 && ldV >= V && ldV % 4 == 0 && ldV <= CE_MAX_LDV, "lm_ce: V=%d ldV=%d (V <= ldV <= %d, ldV %% 4 == 0)", V, ldV,
                 CE_MAX_LDV);
     return R4D_OK;
 }
 
-struct LMLayout { size_t train, h, logits, dh, dwte, tn, ce, total; };
-static LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
+LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
     LMLayout t;
     const size_t N = (size_t)B * T, d = cfg->n_embd;
     size_t off = 0;
@@ -188,6 +187,43 @@ static LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
     t.tn = take(gemm_tn_scratch_floats(ldV, (int)d, (int)N)); t.ce = take(ce_ws_floats((int)N));
     t.total = off;
     return t;
+}
+
+int launch_add_inplace(float* y, const float* x, long long n, hipStream_t s) {
+    const long long n4 = n / 4;
+    hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(y),
+                       reinterpret_cast<const float4*>(x), n4);
+    R4D_CHECK_LAUNCH("lm_wte_add");
+    return R4D_OK;
+}
+
+// The head of both training steps (the LM step below, the RAG step of rag_train.hip): logits on the mode's forward GEMM family,
+// the cross entropy, then dh = dlogits . wte_pad (bf16x3 like every data gradient) and dwte = dlogits^T . h
+int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale, float* loss,
+                  float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s) {
+    const int ldV = head->ldV;
+    int rc;
+    // logits = h . wte_pad^T: wte_pad [ldV, d] IS the k-contiguous [N, K] operand (planes when the mode has them)
+    if ((rc = conv1d(h, nullptr, head->wte_pad, nullptr, nullptr, N, d, ldV, EPI_NONE, logits, s, nullptr, false, head->w3, head->h2)))
+        return rc;
+    if ((rc = lm_ce(logits, N, V, ldV, src, T, gscale, loss, ce_ws, s))) return rc;
+    // dh = dlogits . wte_pad  (K = ldV: the pad columns of dlogits are zero)
+    if (dh && head->w3t && g_gemm_split3 && gemm_s3_supported(N, ldV, d)) {
+        S3Args a;
+        memset(&a, 0, sizeof(a));
+        a.A = logits; a.planes = head->w3t; a.C = dh; a.M = N; a.N = d; a.K = ldV; a.lda = ldV; a.ldc = d; a.ldr = d;
+        a.epilogue = EPI_NONE;
+        if ((rc = launch_gemm_s3(a, s))) return rc;
+    } else if (dh) {
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.A = logits; g.B = head->wte_pad; g.C = dh;
+        g.M = N; g.N = d; g.K = ldV; g.lda = ldV; g.ldb = d; g.ldc = d;
+        g.b_trans = 0; g.b_rows = ldV; g.nbatch = 1; g.nb1 = 1; g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+    }
+    // dwte [ldV, d] = dlogits^T . h
+    return dwte ? launch_gemm_f32_tn(logits, h, dwte, ldV, d, N, ldV, d, tn_scratch, s) : R4D_OK;
 }
 
 }  // namespace r4d
@@ -254,34 +290,10 @@ int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weight
     const size_t train_bytes = (t.h - t.train) * sizeof(float);
     const int64_t* const ids[1] = {ids_d};
     if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &T, nullptr, h, dropout, ws + t.train, train_bytes, s))) return rc;
-    // logits = h . wte_pad^T: wte_pad [ldV, d] IS the k-contiguous [N, K] operand (planes when the mode has them)
-    if ((rc = conv1d(h, nullptr, head->wte_pad, nullptr, nullptr, N, d, ldV, EPI_NONE, logits, s, nullptr, false, head->w3, head->h2)))
-        return rc;
-    if ((rc = lm_ce(logits, N, V, ldV, ids_d, T, grad_scale, loss_d, ws + t.ce, s))) return rc;
-    // dh = dlogits . wte_pad  (K = ldV: the pad columns of dlogits are zero)
-    if (head->w3t && g_gemm_split3 && gemm_s3_supported(N, ldV, d)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = logits; a.planes = head->w3t; a.C = dh; a.M = N; a.N = d; a.K = ldV; a.lda = ldV; a.ldc = d; a.ldr = d;
-        a.epilogue = EPI_NONE;
-        if ((rc = launch_gemm_s3(a, s))) return rc;
-    } else {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = logits; g.B = head->wte_pad; g.C = dh;
-        g.M = N; g.N = d; g.K = ldV; g.lda = ldV; g.ldb = d; g.ldc = d;
-        g.b_trans = 0; g.b_rows = ldV; g.nbatch = 1; g.nb1 = 1; g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-        if ((rc = launch_gemm_f32(g, s))) return rc;
-    }
-    // dwte_head [ldV, d] = dlogits^T . h
-    if ((rc = launch_gemm_f32_tn(logits, h, dwte, ldV, d, N, ldV, d, ws + t.tn, s))) return rc;
+    if ((rc = lm_head_train(h, N, V, d, head, ids_d, T, grad_scale, loss_d, logits, dh, dwte, ws + t.tn, ws + t.ce, s))) return rc;
     if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &T, nullptr, dh, dropout, ws + t.train, train_bytes, s))) return rc;
     // tied weight: the embedding scatter (written by the backward) + the head's part, in this fixed order
-    const long long n4 = (long long)V * d / 4;
-    hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(grads->wte),
-                       reinterpret_cast<const float4*>(dwte), n4);
-    R4D_CHECK_LAUNCH("lm_wte_add");
-    return R4D_OK;
+    return launch_add_inplace(grads->wte, dwte, (long long)V * d, s);
 }
 
 }  // extern "C"

@@ -328,11 +328,12 @@ size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, con
 // The training forward; its output is EITHER the mean pool per sequence (retriever) OR the ln_f output per row (LM head)
 int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
-                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s) {
+                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s, const SpliceIn* sp) {
     if (g_train_fuse_gelu < 0) { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); g_train_fuse_gelu = e ? atoi(e) : 1; }
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
+    R4D_REQUIRE(!sp || n_groups == 1, "gpt2 train: a spliced input is one batch");
     DropCtx dc;
     if ((rc = drop_ctx(dropout, dc))) return rc;
     R4D_REQUIRE(w && w->wte && w->wpe && w->ln_f_w && w->ln_f_b && w->layers && (out_meanpool_d || out_hidden_d), "gpt2 train: null pointer");
@@ -349,7 +350,10 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
         R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
         float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
         float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
-        if (l == 0)
+        if (l == 0 && sp)                                            // cat(wte[tok[:, :2]], fused, wte[tok[:, 2:]]) + wpe
+            rc = launch_splice_embed_ln(ids_d[0], sp->fused, sp->r, w->wte, w->wpe, cfg->vocab, Bs[0], Ts[0], d, Lw.ln_1_w, Lw.ln_1_b,
+                                        cfg->ln_eps, x_in, ln1, s);
+        else if (l == 0)
             rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, Lw.ln_1_w, Lw.ln_1_b, cfg->ln_eps, x_in, ln1, s);
         else
             rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s);
@@ -389,14 +393,15 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
 int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr, int n_groups,
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
-                        hipStream_t s) {
+                        hipStream_t s, const SpliceIn* sp, float* d_fused) {
     if (g_train_fuse_gelu < 0) { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); g_train_fuse_gelu = e ? atoi(e) : 1; }
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
     DropCtx dc;
     if ((rc = drop_ctx(dropout, dc))) return rc;
-    R4D_REQUIRE(w && w->layers && gr && gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b && (d_meanpool_d || d_hidden_d),
+    R4D_REQUIRE(w && w->layers && (d_meanpool_d || d_hidden_d) && (!sp || n_groups == 1) && (!d_fused || sp) &&
+                (gr ? gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b : d_fused != nullptr),
                 "gpt2 train backward: null pointer");
     const TrainLayout t = layout(cfg, gs.data(), n_groups);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
@@ -412,11 +417,14 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_meanpool_bwd(d_meanpool_d + G.seq0 * d, (long long)G.B * G.T, G.T, d, dy + G.row0 * d, s))) return rc;
     }
     const float* dlnf = d_meanpool_d ? dy : d_hidden_d;
-    if ((rc = launch_ln_bwd(ws + t.x_out, w->ln_f_w, dlnf, nullptr, M, d, cfg->ln_eps, dx, gr->ln_f_w, gr->ln_f_b, red, 0, s))) return rc;
+    const bool frozen = gr == nullptr;                               // data gradients only (RAG generator under --freeze)
+    if ((rc = launch_ln_bwd(ws + t.x_out, w->ln_f_w, dlnf, nullptr, M, d, cfg->ln_eps, dx, frozen ? nullptr : gr->ln_f_w,
+                            frozen ? nullptr : gr->ln_f_b, red, 0, s))) return rc;
     for (int l = L - 1; l >= 0; --l) {
         const r4d_gpt2_layer& Lw = w->layers[l];
-        const r4d_gpt2_layer_grads& Lg = gr->layers[l];
-        R4D_REQUIRE(Lg.ln_1_w && Lg.ln_1_b && Lg.c_attn_w && Lg.c_attn_b && Lg.attn_proj_w && Lg.attn_proj_b && Lg.ln_2_w &&
+        static const r4d_gpt2_layer_grads kNone{};
+        const r4d_gpt2_layer_grads& Lg = frozen ? kNone : gr->layers[l];
+        R4D_REQUIRE(frozen || Lg.ln_1_w && Lg.ln_1_b && Lg.c_attn_w && Lg.c_attn_b && Lg.attn_proj_w && Lg.attn_proj_b && Lg.ln_2_w &&
                     Lg.ln_2_b && Lg.c_fc_w && Lg.c_fc_b && Lg.mlp_proj_w && Lg.mlp_proj_b, "gpt2 train backward: null gradient in layer %d", l);
         float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
         float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
@@ -426,7 +434,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dy, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
             dbr = dy;
         }
-        if ((rc = bwd_weight(f, dbr, M, 4 * d, d, Lg.mlp_proj_w, Lg.mlp_proj_b, xT, red, s))) return rc;
+        if (!frozen && (rc = bwd_weight(f, dbr, M, 4 * d, d, Lg.mlp_proj_w, Lg.mlp_proj_b, xT, red, s))) return rc;
         if (g_train_fuse_gelu && Lw.mlp_proj_w3t && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
             // d(pre) = (d(branch) . Wp^T) * gelu_new'(pre): the derivative is applied in the GEMM's epilogue
             if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, pre))) return rc;
@@ -434,7 +442,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t))) return rc;                    // d(f)
             if ((rc = launch_gelu_bwd(pre, dbig, (long long)M * 4 * d, dbig, s))) return rc;              // d(pre), in place
         }
-        if ((rc = bwd_weight(ln2, dbig, M, d, 4 * d, Lg.c_fc_w, Lg.c_fc_b, xT, red, s))) return rc;
+        if (!frozen && (rc = bwd_weight(ln2, dbig, M, d, 4 * d, Lg.c_fc_w, Lg.c_fc_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dbig, Lw.c_fc_w, M, d, 4 * d, dy, s, Lw.c_fc_w3t))) return rc;                              // d(ln_2 out)
         if ((rc = launch_ln_bwd(x_mid, Lw.ln_2_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_2_w, Lg.ln_2_b, red, 0, s))) return rc;   // dx = d(x_mid)
         // ---- attention: x_mid = x_in + attn(ln_1(x_in)) Wo + bo
@@ -443,19 +451,24 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dbig, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
             dbr = dbig;
         }
-        if ((rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s))) return rc;
+        if (!frozen && (rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dbr, Lw.attn_proj_w, M, d, d, dy, s, Lw.attn_proj_w3t))) return rc;                              // d(att), merged heads
         for (const TrainGroup& G : gs)
             if ((rc = attn_bwd(qkv + G.row0 * 3 * d, ws + t.P[l] + G.p0, dy + G.row0 * d, G.B, G.T, H, d, dqkv + G.row0 * 3 * d,
                                ws + t.dP, ws + t.PT, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
-        if ((rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s))) return rc;
+        if (!frozen && (rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dqkv, Lw.c_attn_w, M, d, 3 * d, dy, s, Lw.c_attn_w3t))) return rc;                            // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)
     }
     // embeddings: x_in[0] = drop(wte[ids] + wpe[0..T-1])
     if (dc.embd_p > 0.f && (rc = launch_dropout(dx, nullptr, (long long)M * d, dx, dc.embd_p, dc.key, R4D_DROPOUT_SITE_EMBD, 0, s)))
         return rc;
-    // deterministic sums (train_ops.hip): tokens through a 64-bit fixed-point table, positions as ordered column sums
+    if (d_fused)                                                     // rows 2 .. 2 + r - 1 of every spliced sequence
+        R4D_HIP(hipMemcpy2DAsync(d_fused, (size_t)sp->r * d * sizeof(float), dx + 2 * (size_t)d, (size_t)gs[0].T * d * sizeof(float),
+                                 (size_t)sp->r * d * sizeof(float), (size_t)gs[0].B, hipMemcpyDeviceToDevice, s));
+    if (frozen) return R4D_OK;
+    // deterministic sums (train_ops.hip): tokens through a 64-bit fixed-point table (negative ids -- the spliced rows -- add
+    // nothing), positions as ordered column sums
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + t.emb_acc);
     R4D_HIP(hipMemsetAsync(acc, 0, ((size_t)cfg->vocab * d + 2) * sizeof(unsigned long long), s));       // table + poison word + max word
     R4D_HIP(hipMemsetAsync(gr->wpe, 0, (size_t)cfg->n_positions * d * sizeof(float), s));

@@ -228,11 +228,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 //     A NON-FINITE contribution has no fixed-point image: the maximum is then Inf / NaN, the POISON word behind the table is set and
 //     the conversion writes NaN into the whole gradient -- a diverged step stays as loud as with float atomics (NaN gradient norm,
 //     NaN parameters after the clip) instead of turning into a finite, wrong update.
-constexpr int EMB_SUM_BITS = 62;
-__device__ __forceinline__ int emb_scale_exp(unsigned max_bits, int lg_rows) {          // S: |g| 2^S M < 2^62 for every |g| <= max
-    const int e = (int)((max_bits >> 23) & 255u) - 126;                                  // max < 2^e (exponent field 0: a subnormal)
-    return EMB_SUM_BITS - lg_rows - e;
-}
+// (EMB_SUM_BITS, emb_scale_exp, emb_lg_rows: common.h, shared with the weighted scatter of rag_train.hip)
 // max |x| as the bit pattern of a non-negative float (NaN counts as Inf); *max_bits zeroed by the caller
 __global__ __launch_bounds__(256) void embedding_absmax_kernel(const float* __restrict__ x, long long n, unsigned* __restrict__ max_bits) {
     unsigned m = 0u;
@@ -431,8 +427,9 @@ int launch_ln_bwd(const float* x, const float* w, const float* dy, const float* 
     else if (nv <= 16) rc = launch_ln_bwd_nv<16>(x, w, dy, add, rows, rpw, nwg, d, eps, dx, pw, pb, s);
     else rc = launch_ln_bwd_nv<32>(x, w, dy, add, rows, rpw, nwg, d, eps, dx, pw, pb, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(d, 64)), dim3(1024), 0, s, pw, nwg, d, dw, accumulate);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(d, 64)), dim3(1024), 0, s, pb, nwg, d, db, accumulate);
+    if (!dw && !db) return R4D_OK;                                   // a frozen LayerNorm: dx only (its partial rows go unread)
+    if (dw) hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(d, 64)), dim3(1024), 0, s, pw, nwg, d, dw, accumulate);
+    if (db) hipLaunchKernelGGL(colsum_final_kernel, dim3(cdiv(d, 64)), dim3(1024), 0, s, pb, nwg, d, db, accumulate);
     R4D_CHECK_LAUNCH("ln_bwd colsum");
     return R4D_OK;
 }
@@ -485,11 +482,6 @@ int launch_transpose(const float* in, int rows, int cols, long long ld_in, long 
                        ld_in, stride_in, out, ld_out, stride_out);
     R4D_CHECK_LAUNCH("transpose");
     return R4D_OK;
-}
-static int emb_lg_rows(long long table_rows) {
-    int lg = 0;
-    while ((1LL << lg) < table_rows) ++lg;
-    return lg;
 }
 // once per backward call, before the batches: max |dx| over ALL token rows of the step into the max word behind the table
 // (`acc_wte` [vocab * d] + poison word + max word, zeroed by the caller)

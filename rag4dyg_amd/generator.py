@@ -14,7 +14,7 @@ Differences from the reference, all value-preserving:
     of torch_geometric's scatter -- same sums, ``D^-1/2 (A+I) D^-1/2`` as GCNConv's defaults define it;
   * GNNs with more than one layer: the reference applies ``F.dropout`` with ``training=True`` even at inference
     (``modeling_rag.py:69``, stochastic); this build applies none (the expectation).  Shipped scripts use one layer.
-Training (``train/train_generator.py``) is out of scope: ``main_generator.py --do_train`` raises.
+Training (``train/train_generator.py``) lives in ``generator_training.py`` (``main_generator.py --do_train``).
 """
 import json
 import os
@@ -158,6 +158,23 @@ def fusion_rows(args, model, tokenizer, dataset, idxs_sim, top_k):
     raise ValueError(f"unknown fusion {args.fusion!r} (mlp | graphpooling)")
 
 
+def star_bag_weights(retrieval_sources, idxs):
+    """Nodes of one query's union-of-stars graph and the one-layer GCN's pooling weights over them (float64):
+    c_j = (1/n) sum_i A_norm[i, j] = d_j^-1/2 (d_j^-1/2 + sum_{i in N(j)} d_i^-1/2) / n, so that
+    mean_i (A_norm X W^T + b)_i = c^T X W^T + b."""
+    order, edges = star_union_graph(retrieval_sources, [int(v) for v in idxs])
+    n = len(order)
+    e = np.asarray([p for p in edges if p[0] != p[1]], dtype=np.int64).reshape(-1, 2)
+    deg = np.ones(n, dtype=np.float64)
+    np.add.at(deg, e[:, 0], 1.0)
+    np.add.at(deg, e[:, 1], 1.0)
+    dinv = deg ** -0.5
+    acc = dinv.copy()                                                  # self loop
+    np.add.at(acc, e[:, 0], dinv[e[:, 1]])
+    np.add.at(acc, e[:, 1], dinv[e[:, 0]])
+    return order, dinv * acc / n
+
+
 @torch.no_grad()
 def fusion_host_prep(args, model, dataset, index_lists, top_k):
     """Host half of ``fusion_rows_batch`` for one-layer graph pooling: the union-of-stars graphs of all queries and their
@@ -168,18 +185,9 @@ def fusion_host_prep(args, model, dataset, index_lists, top_k):
         return None
     nodes_all, spans, weights = [], [], []
     for ix in index_lists:
-        order, edges = star_union_graph(dataset.retrieval_sources, [int(v) for v in ix][:top_k])
-        n = len(order)
-        e = np.asarray([p for p in edges if p[0] != p[1]], dtype=np.int64).reshape(-1, 2)
-        deg = np.ones(n, dtype=np.float64)
-        np.add.at(deg, e[:, 0], 1.0)
-        np.add.at(deg, e[:, 1], 1.0)
-        dinv = deg ** -0.5
-        acc = dinv.copy()                                              # self loop
-        np.add.at(acc, e[:, 0], dinv[e[:, 1]])
-        np.add.at(acc, e[:, 1], dinv[e[:, 0]])
-        weights.append(dinv * acc / n)
-        spans.append((len(nodes_all), n))
+        order, c = star_bag_weights(dataset.retrieval_sources, [int(v) for v in ix][:top_k])
+        weights.append(c)
+        spans.append((len(nodes_all), len(order)))
         nodes_all += order
     ntot = (len(nodes_all) + 3) // 4 * 4                               # 16-byte GEMM rows
     C = np.zeros((len(index_lists), ntot), dtype=np.float32)

@@ -26,6 +26,39 @@ def padded_vocab(V):
     return (int(V) + 127) // 128 * 128
 
 
+class HeadOperand:
+    """The padded LM-head operand ``pad`` [ldV, d] (the head weight in rows [0, V), zero rows up to ldV) and its GEMM planes, as
+    ``r4d_lm_head`` describes them: bf16x3 planes when the split modes are on, f16x2 planes in f16x2 mode.  Shared by the
+    SimpleDyG and the RAG-generator training steps; ``refresh(weight)`` after every change of the head weight."""
+
+    def __init__(self, V, d, device, use_s3, use_h2):
+        self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
+        self.pad = torch.zeros(self.ldV, self.d, dtype=torch.float32, device=device)
+        self._w3 = self._w3t = self._h2 = None
+        if use_s3 and self.d % 32 == 0:
+            self._w3 = torch.empty(3, self.ldV, self.d, dtype=torch.int16, device=device)
+            self._w3t = torch.empty(3, self.d, self.ldV, dtype=torch.int16, device=device)
+            if use_h2:
+                self._h2 = torch.empty(self.ldV, self.d // 32, 2, 32, dtype=torch.int16, device=device)
+
+    @torch.no_grad()
+    def refresh(self, weight):
+        self.pad[:self.V].copy_(weight)
+        if self._w3 is not None:
+            lib = _lib.load()
+            stream = torch.cuda.current_stream().cuda_stream
+            p = self.pad.data_ptr()
+            _lib.check(lib.r4d_split3_planes_bf16(p, self.d, self.ldV, 1, self._w3.data_ptr(), stream), "split3_planes")
+            _lib.check(lib.r4d_split3_planes_bf16(p, self.ldV, self.d, 0, self._w3t.data_ptr(), stream), "split3_planes")
+            if self._h2 is not None:
+                _lib.check(lib.r4d_split2_planes_f16(p, self.d, self.ldV, 1, self._h2.data_ptr(), stream), "split2_planes")
+
+    def struct(self):
+        h2 = self._h2 is not None and ops.gemm_mode() == "f16x2"
+        return _lib.LMHeadC(self.pad.data_ptr(), self.ldV, self._w3.data_ptr() if self._w3 is not None else None,
+                            self._w3t.data_ptr() if self._w3t is not None else None, self._h2.data_ptr() if h2 else None)
+
+
 class LMTrainer:
     """One SimpleDyG training micro-step on the device.  Built on :class:`training.EncoderTrainer` (the flat gradient buffer,
     the per-layer weight copies / planes, the dropout struct, ``accumulate`` / ``take_accumulated`` / ``all_reduce_mean``) plus
@@ -43,13 +76,7 @@ class LMTrainer:
         V, d = wte.shape
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
         dev = wte.device
-        self.wte_pad = torch.zeros(self.ldV, self.d, dtype=torch.float32, device=dev)
-        self._w3 = self._w3t = self._h2 = None
-        if self.enc.use_s3 and self.d % 32 == 0:
-            self._w3 = torch.empty(3, self.ldV, self.d, dtype=torch.int16, device=dev)
-            self._w3t = torch.empty(3, self.d, self.ldV, dtype=torch.int16, device=dev)
-            if self.enc.use_h2:
-                self._h2 = torch.empty(self.ldV, self.d // 32, 2, 32, dtype=torch.int16, device=dev)
+        self.head = HeadOperand(V, d, dev, self.enc.use_s3, self.enc.use_h2)
         self._ws = None
         self._stamp = None
         ops.range_flag(dev)                                     # registered: the CE kernel reports out-of-range labels there
@@ -84,21 +111,8 @@ class LMTrainer:
     def refresh(self):
         """Bring the layer copies / planes and the LM-head operand and planes up to date with the parameters."""
         self.enc.refresh_transposed()
-        self.wte_pad[:self.V].copy_(self.enc.params["transformer.wte.weight"])
-        if self._w3 is not None:
-            lib = _lib.load()
-            stream = torch.cuda.current_stream().cuda_stream
-            p = self.wte_pad.data_ptr()
-            _lib.check(lib.r4d_split3_planes_bf16(p, self.d, self.ldV, 1, self._w3.data_ptr(), stream), "split3_planes")
-            _lib.check(lib.r4d_split3_planes_bf16(p, self.ldV, self.d, 0, self._w3t.data_ptr(), stream), "split3_planes")
-            if self._h2 is not None:
-                _lib.check(lib.r4d_split2_planes_f16(p, self.d, self.ldV, 1, self._h2.data_ptr(), stream), "split2_planes")
+        self.head.refresh(self.enc.params["transformer.wte.weight"])
         self._stamp = self._current_stamp()
-
-    def _head_struct(self):
-        h2 = self._h2 is not None and ops.gemm_mode() == "f16x2"
-        return _lib.LMHeadC(self.wte_pad.data_ptr(), self.ldV, self._w3.data_ptr() if self._w3 is not None else None,
-                            self._w3t.data_ptr() if self._w3t is not None else None, self._h2.data_ptr() if h2 else None)
 
     @torch.no_grad()
     def step(self, ids, grad_scale=1.0):
@@ -112,7 +126,7 @@ class LMTrainer:
         B, T = int(ids.shape[0]), int(ids.shape[1])
         lib = _lib.load()
         c, w, g, keep = self.enc._structs()
-        head = self._head_struct()
+        head = self.head.struct()
         nbytes = lib.r4d_gpt2_lm_train_workspace_bytes(ctypes.byref(c), B, T, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("lm train step: bad batch shape")

@@ -132,8 +132,9 @@ class EncoderTrainer:
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0):
-        """``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
+    def __init__(self, model, dropout=None, seed=0, want_grads=True):
+        """``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
+        ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
         (embd_p, attn_p, resid_p).  ``seed`` keys the counter-based mask generator; every forward advances its step."""
         self.model = model
@@ -156,8 +157,8 @@ class EncoderTrainer:
             offs[n] = total
             total += (p.numel() + 63) // 64 * 64
         dev = tr.wte.weight.device
-        self.flat_grads = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grads = {n: self.flat_grads[offs[n]:offs[n] + p.numel()].view_as(p) for n, p in self.params.items()}
+        self.flat_grads = torch.zeros(total, dtype=torch.float32, device=dev) if want_grads else None
+        self.grads = {n: self.flat_grads[offs[n]:offs[n] + p.numel()].view_as(p) for n, p in self.params.items()} if want_grads else None
         self.flat_accum = None
         self._ws = None
         self._saved = None
@@ -225,10 +226,12 @@ class EncoderTrainer:
                 for f, name in zip(fs, ("c_attn", "attn_proj", "c_fc", "mlp_proj")):
                     if (i, f) in self._h2:
                         setattr(layers[i], name + "_h2", self._h2[(i, f)].data_ptr())
-            glayers[i] = _lib.GPT2LayerGradsC(*[self.grads[f"transformer.h.{i}.{name}"].data_ptr() for _f, name in _LAYER_PARAMS])
+            if self.grads is not None:
+                glayers[i] = _lib.GPT2LayerGradsC(*[self.grads[f"transformer.h.{i}.{name}"].data_ptr() for _f, name in _LAYER_PARAMS])
         w = _lib.GPT2WeightsC(tr.wte.weight.data_ptr(), tr.wpe.weight.data_ptr(), tr.ln_f.weight.data_ptr(),
                               tr.ln_f.bias.data_ptr(), layers, None)
-        g = _lib.GPT2GradsC(self.grads["transformer.wte.weight"].data_ptr(), self.grads["transformer.wpe.weight"].data_ptr(),
+        g = None if self.grads is None else \
+            _lib.GPT2GradsC(self.grads["transformer.wte.weight"].data_ptr(), self.grads["transformer.wpe.weight"].data_ptr(),
                             self.grads["transformer.ln_f.weight"].data_ptr(), self.grads["transformer.ln_f.bias"].data_ptr(), glayers)
         return c, w, g, (layers, glayers)
 
