@@ -475,8 +475,19 @@ typedef struct {
 int r4d_dropout_f32(const float* x_d, const float* resid_d, int64_t n, float* out_d, float p, uint64_t seed, uint64_t step,
                     uint32_t site, uint64_t index_base, void* stream);
 
+/* How the training steps keep the attention probabilities P (process-wide, like r4d_set_gemm_split3; additive ABI v6 entries).
+ *   0 stored (default): the forward keeps P [B*H, T, ceil128(T)] of every layer and batch in the workspace;
+ *   1 recompute:        no kept P -- the backward forms it again with the forward's own two launches and two fused row kernels
+ *                       replace the element-wise passes around it.  Every GEMM reads the bits it reads in mode 0, so every
+ *                       output and gradient is bit-identical; the workspace shrinks by (n_layer * sum P - max P) floats.
+ * Any other value is R4D_ERR_INVALID.  The mode is read by the three workspace queries and by every training forward / backward /
+ * step call: set it BEFORE the size query and keep it until the step's backward has been issued.  A backward on the workspace of
+ * the most recent training forward under a different mode is refused (R4D_ERR_INVALID). */
+int r4d_set_train_attention(int32_t mode);
+int r4d_get_train_attention(void);
+
 /* Scratch of one step: the activations the backward pass needs (16 * rows * d floats per layer + the attention
- * probabilities) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */
+ * probabilities in stored mode) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts);
 /* Forward over up to 16 right-padded id batches (one launch sequence over their concatenated rows) that keeps every
  * activation the backward pass reads.  The optional wT copies of the layers are USED when present (faster forward GEMMs): the
@@ -590,6 +601,16 @@ int r4d_gelu_new_bwd_f32(const float* pre_d, const float* dy_d, int64_t n, float
  * dLoss/d(raw Q.K^T logits) on return (the logits were divided by scale_div before the softmax, modeling_gpt2.py:143);
  * columns right of the diagonal are written as zero. */
 int r4d_causal_softmax_bwd_f32(const float* p_d, float* dp_d, int32_t nbh, int32_t T, int32_t ld, float scale_div, void* stream);
+/* The two row kernels of r4d_set_train_attention(1), exported like the ops above.  p_d [nbh,T,ld] as above, ld % 32 == 0,
+ * ld <= 1024; the dropout mask of element (bh, i, j) is that of r4d_dropout_f32 at index_base + (bh * T + i) * ld + j (attn_p == 0:
+ * the identity); index_base % 4 == 0.
+ * (a) dp_d <- dS = softmax backward of (mask * dp_d / (1 - attn_p)), in place, zeros right of the diagonal up to ld;
+ *     dst_d [nbh,T,ld] <- its transpose: row j holds dS[.][j] in columns [0, T) and zeros in [T, ld).
+ * (b) out_d [nbh,T,ld] <- the transpose of mask * p_d / (1 - attn_p), zeros in columns [T, ld); p_d 16-byte aligned. */
+int r4d_softmax_dropout_bwd_transpose_f32(const float* p_d, float* dp_d, float* dst_d, int32_t nbh, int32_t T, int32_t ld, float scale_div,
+                                          float attn_p, uint64_t seed, uint64_t step, uint32_t site, uint64_t index_base, void* stream);
+int r4d_dropout_transpose_f32(const float* p_d, float* out_d, int32_t nbh, int32_t T, int32_t ld, float attn_p, uint64_t seed,
+                              uint64_t step, uint32_t site, uint64_t index_base, void* stream);
 /* accum_d[0] += sum x^2 (total gradient norm of clip_grad_norm_, train_retriever.py:210; zero accum_d[0] first).  accum_d is
  * f32[R4D_SUMSQ_FLOATS]: element 0 the running total, the rest scratch of the two-stage sum (no atomics: the same bits on
  * every data-parallel rank). */

@@ -34,11 +34,22 @@ int launch_gelu_bwd(const float* pre, const float* dy, long long n, float* dx, h
 int launch_softmax_bwd(const float* P, float* dP, int nbh, int T, int ld, float scale_div, hipStream_t s);
 int launch_transpose(const float* in, int rows, int cols, long long ld_in, long long stride_in, float* out, long long ld_out,
                      long long stride_out, int nbatch, hipStream_t s);
+// recompute mode only: dropout backward + softmax backward in place on dP and its transpose into dst; dropout + transpose of P
+int launch_softmax_bwd_t(const float* P, float* dP, float* dst, int nbh, int T, int ld, float scale_div, float attn_p, DropKey key,
+                         unsigned site, unsigned long long pbase, hipStream_t s);
+int launch_dropout_transpose(const float* P, float* out, int nbh, int T, int ld, float attn_p, DropKey key, unsigned site,
+                             unsigned long long pbase, hipStream_t s);
 int launch_embedding_bwd(const float* dx, const int64_t* ids, int B, int T, int d, int vocab, unsigned long long* acc_wte, float* dwpe,
                          int first_group, long long table_rows, hipStream_t s);
 int launch_embedding_fix_to_f32(const unsigned long long* acc, long long n, long long table_rows, float* out, hipStream_t s);
 int launch_embedding_absmax(const float* dx, long long n, unsigned long long* acc_wte, long long table_elems, hipStream_t s);
 int launch_meanpool_bwd(const float* d_pool, long long rows, int T, int d, float* dh, hipStream_t s);
+
+// r4d_set_train_attention: 0 stored (the forward keeps P of every layer), 1 recompute (the backward forms P again with the
+// forward's two launches; no per-layer P blocks).  Read by layout(), so the size queries, the forward and the backward follow it.
+static int g_train_attention = 0;
+static const void* g_last_fwd_ws = nullptr;   // workspace and mode of the most recent training forward: a backward on that
+static int g_last_fwd_mode = 0;               // workspace under another mode would read the wrong layout -> refused
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -52,8 +63,9 @@ struct TrainLayout {
     // per layer (offsets in floats)
     std::vector<size_t> x_in, ln1, qkv, att, x_mid, ln2, pre, f, P;
     size_t x_out, pool_scratch;
-    // backward temporaries
-    size_t dx, dy, dbig, dqkv, xT, dP, PT, red;
+    bool recompute;                                     // no P blocks; scratch pA holds the P of the batch at hand
+    // backward temporaries (pA: recompute mode only; dP / PT are its scratch blocks B / C)
+    size_t dx, dy, dbig, dqkv, xT, pA, dP, PT, red;
     size_t emb_acc;                                     // [vocab, d] 64-bit fixed-point token-gradient table (two floats per entry)
     size_t total;
 };
@@ -61,6 +73,7 @@ struct TrainLayout {
 static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int n) {
     TrainLayout t;
     t.L = cfg->n_layer; t.d = cfg->n_embd;
+    t.recompute = g_train_attention == 1;
     const size_t d = t.d;
     t.M = 0; t.Ptot = 0; t.pmax = 0;
     size_t pool = 0;
@@ -76,7 +89,7 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
     for (int l = 0; l < t.L; ++l) {
         t.x_in.push_back(take(t.M * d)); t.ln1.push_back(take(t.M * d)); t.qkv.push_back(take(t.M * 3 * d));
         t.att.push_back(take(t.M * d)); t.x_mid.push_back(take(t.M * d)); t.ln2.push_back(take(t.M * d));
-        t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take(t.M * 4 * d)); t.P.push_back(take(t.Ptot));
+        t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take(t.M * 4 * d)); t.P.push_back(t.recompute ? 0 : take(t.Ptot));
     }
     t.x_out = take(t.M * d);
     t.pool_scratch = take(pool);
@@ -88,6 +101,7 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
         for (size_t v : o) if (v > sk) sk = v;
         t.xT = take(sk);
     }
+    t.pA = t.recompute ? take(t.pmax) : 0;
     t.dP = take(t.pmax); t.PT = take(t.pmax);
     size_t red = ln_bwd_scratch_floats((int)t.M, t.d);
     const size_t cs = colsum_scratch_floats((long long)t.M, 4 * t.d);
@@ -174,9 +188,8 @@ static int drop_ctx(const r4d_train_dropout* dp, DropCtx& c) {
     return R4D_OK;
 }
 
-// `Pdrop` (with attn_p > 0): scratch for the dropped-out probabilities the P.V product reads; P keeps the softmax output
-static int attn_fwd(const float* qkv, int B, int T, int H, int d, float* P, float* out, hipStream_t s, float attn_p = 0.f,
-                    DropKey key = DropKey{0, 0, 0, 0}, unsigned site = 0, unsigned long long pbase = 0, float* Pdrop = nullptr) {
+// P [B*H, T, ld] = causal softmax(Q . K^T / sqrt(hd)): the forward's two launches (recompute mode runs them again in the backward)
+static int attn_probs(const float* qkv, int B, int T, int H, int d, float* P, hipStream_t s) {
     const int hd = d / H, ld = tpad128(T);
     GemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -186,9 +199,18 @@ static int attn_fwd(const float* qkv, int B, int T, int H, int d, float* P, floa
     g.sA0 = (long long)T * 3 * d; g.sA1 = hd; g.sB0 = g.sA0; g.sB1 = hd;
     g.sC0 = (long long)H * T * ld; g.sC1 = (long long)T * ld;
     g.epilogue = EPI_SCALE_DIV; g.scale_div = (float)sqrt((double)hd); g.causal = CAUSAL_QK;
-    int rc = launch_gemm_f32(g, s);
+    const int rc = launch_gemm_f32(g, s);
     if (rc) return rc;
-    if ((rc = launch_causal_softmax(P, B * H, T, ld, ld, s))) return rc;          // row_tile = ld: zero-fill the whole row
+    return launch_causal_softmax(P, B * H, T, ld, ld, s);                         // row_tile = ld: zero-fill the whole row
+}
+
+// `Pdrop` (with attn_p > 0): scratch for the dropped-out probabilities the P.V product reads; P keeps the softmax output
+static int attn_fwd(const float* qkv, int B, int T, int H, int d, float* P, float* out, hipStream_t s, float attn_p = 0.f,
+                    DropKey key = DropKey{0, 0, 0, 0}, unsigned site = 0, unsigned long long pbase = 0, float* Pdrop = nullptr) {
+    const int hd = d / H, ld = tpad128(T);
+    GemmArgs g;
+    int rc = attn_probs(qkv, B, T, H, d, P, s);
+    if (rc) return rc;
     const float* Pv = P;
     if (attn_p > 0.f) {                                                            // attn_dropout(w), modeling_gpt2.py:153
         if ((rc = launch_dropout(P, nullptr, (long long)B * H * T * ld, Pdrop, attn_p, key, site, pbase, s))) return rc;
@@ -258,6 +280,47 @@ static int attn_bwd(const float* qkv, const float* P, const float* dao, int B, i
     return launch_gemm_f32(g, s);
 }
 
+// Recompute mode: the same gradients without a kept P.  A, B, C: three scratch blocks of the batch's [B*H, T, ld] size.  Every
+// GEMM reads the bits it reads in attn_bwd (same launches, same arguments), so every gradient has attn_bwd's bits.
+static int attn_bwd_recompute(const float* qkv, const float* dao, int B, int T, int H, int d, float* dqkv, float* A, float* Bs,
+                              float* C, hipStream_t s, float attn_p, DropKey key, unsigned site, unsigned long long pbase) {
+    const int hd = d / H, ld = tpad128(T), Tp = up4(T);
+    const long long sP0 = (long long)H * T * ld, sP1 = (long long)T * ld;
+    const long long sQ0 = (long long)T * 3 * d, sO0 = (long long)T * d;
+    GemmArgs g;
+    int rc;
+    if ((rc = attn_probs(qkv, B, T, H, d, A, s))) return rc;     // P again, by the forward's two launches
+    // dP = dO . V^T
+    memset(&g, 0, sizeof(g));
+    g.A = dao; g.B = qkv + 2 * d; g.C = Bs;
+    g.M = T; g.N = T; g.K = hd; g.lda = d; g.ldb = 3 * d; g.ldc = ld;
+    g.b_trans = 1; g.b_rows = T; g.nbatch = B * H; g.nb1 = H;
+    g.sA0 = sO0; g.sA1 = hd; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sP0; g.sC1 = sP1;
+    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+    if ((rc = launch_gemm_f32(g, s))) return rc;
+    // dS in place on B (through the dropout mask), dS^T into C
+    if ((rc = launch_softmax_bwd_t(A, Bs, C, B * H, T, ld, (float)sqrt((double)hd), attn_p, key, site, pbase, s))) return rc;
+    // dQ = dS . K,  dK = dS^T . Q
+    for (int which = 0; which < 2; ++which) {
+        memset(&g, 0, sizeof(g));
+        g.A = which ? C : Bs; g.B = which ? qkv : qkv + d; g.C = which ? dqkv + d : dqkv;
+        g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = 3 * d; g.ldc = 3 * d;
+        g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
+        g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
+        g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+        if ((rc = launch_gemm_f32(g, s))) return rc;
+    }
+    // dV = Pd^T . dO  (C is free once the dK GEMM ahead of this launch in the stream has read it)
+    if ((rc = launch_dropout_transpose(A, C, B * H, T, ld, attn_p, key, site, pbase, s))) return rc;
+    memset(&g, 0, sizeof(g));
+    g.A = C; g.B = dao; g.C = dqkv + 2 * d;
+    g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = d; g.ldc = 3 * d;
+    g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
+    g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sO0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
+    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+    return launch_gemm_f32(g, s);
+}
+
 static RowGroups row_groups_of(const std::vector<TrainGroup>& gs) {
     RowGroups R;
     R.n = (int)gs.size();
@@ -289,6 +352,13 @@ int r4d_weight_grad_f32(const float* x_d, const float* dy_d, int32_t rows, int32
     float* red = skp + (gemm_tn_scratch_floats(in_features, out_features, rows) + 63) / 64 * 64;
     return bwd_weight(x_d, dy_d, rows, in_features, out_features, dw_d, db_d, skp, red, (hipStream_t)stream);
 }
+
+int r4d_set_train_attention(int32_t mode) {
+    R4D_REQUIRE(mode == 0 || mode == 1, "set_train_attention: mode %d is neither 0 (stored) nor 1 (recompute)", (int)mode);
+    g_train_attention = mode;
+    return R4D_OK;
+}
+int r4d_get_train_attention(void) { return g_train_attention; }
 
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts) {
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
@@ -343,6 +413,7 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
         return R4D_ERR_WORKSPACE;
     }
     float* ws = (float*)workspace_d;
+    g_last_fwd_ws = workspace_d; g_last_fwd_mode = g_train_attention;
     const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M;
     const RowGroups R = row_groups_of(gs);
     for (int l = 0; l < cfg->n_layer; ++l) {
@@ -364,8 +435,8 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
         }
         if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2))) return rc;
         for (const TrainGroup& G : gs)
-            if ((rc = attn_fwd(qkv + G.row0 * 3 * d, G.B, G.T, H, d, ws + t.P[l] + G.p0, att + G.row0 * d, s, dc.attn_p, dc.key,
-                               4u * l + 0u, G.p0, ws + t.dP))) return rc;
+            if ((rc = attn_fwd(qkv + G.row0 * 3 * d, G.B, G.T, H, d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0, att + G.row0 * d, s,
+                               dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
         float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
         if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
             if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
@@ -403,6 +474,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(w && w->layers && (d_meanpool_d || d_hidden_d) && (!sp || n_groups == 1) && (!d_fused || sp) &&
                 (gr ? gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b : d_fused != nullptr),
                 "gpt2 train backward: null pointer");
+    R4D_REQUIRE(workspace_d != g_last_fwd_ws || g_train_attention == g_last_fwd_mode,
+                "gpt2 train backward: this workspace was filled by a forward in train-attention mode %d, the current mode is %d",
+                g_last_fwd_mode, g_train_attention);
     const TrainLayout t = layout(cfg, gs.data(), n_groups);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -453,9 +527,13 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         }
         if (!frozen && (rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dbr, Lw.attn_proj_w, M, d, d, dy, s, Lw.attn_proj_w3t))) return rc;                              // d(att), merged heads
-        for (const TrainGroup& G : gs)
-            if ((rc = attn_bwd(qkv + G.row0 * 3 * d, ws + t.P[l] + G.p0, dy + G.row0 * d, G.B, G.T, H, d, dqkv + G.row0 * 3 * d,
-                               ws + t.dP, ws + t.PT, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
+        for (const TrainGroup& G : gs) {
+            rc = t.recompute ? attn_bwd_recompute(qkv + G.row0 * 3 * d, dy + G.row0 * d, G.B, G.T, H, d, dqkv + G.row0 * 3 * d, ws + t.pA,
+                                                  ws + t.dP, ws + t.PT, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0)
+                             : attn_bwd(qkv + G.row0 * 3 * d, ws + t.P[l] + G.p0, dy + G.row0 * d, G.B, G.T, H, d, dqkv + G.row0 * 3 * d,
+                                        ws + t.dP, ws + t.PT, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0);
+            if (rc) return rc;
+        }
         if (!frozen && (rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dqkv, Lw.c_attn_w, M, d, 3 * d, dy, s, Lw.c_attn_w3t))) return rc;                            // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)

@@ -338,6 +338,167 @@ int launch_dropout(const float* x, const float* resid, long long n, float* out, 
     return R4D_OK;
 }
 
+// ------------------------------------------------------------------------------------ recompute-mode attention backward
+// The two row kernels of r4d_set_train_attention(1) (train.hip: attn_bwd_recompute).  They replace dropout + softmax_bwd +
+// transpose (dS, dS^T) and dropout + transpose (Pd^T) of the stored path and must leave ITS bits: the GEMMs behind them read
+// what they read there.  Masks: element idx = pbase + (bh * T + i) * ld + j -> Philox block idx / 4, word idx % 4 (pbase, ld
+// multiples of 4, so a block is four consecutive columns of one row and the word is j % 4), threshold / scale as launch_dropout.
+__device__ __forceinline__ uint4 attn_philox(unsigned long long c, DropKey key, unsigned site) {
+    return philox4x32_10(make_uint4((unsigned)c, site + ((unsigned)(c >> 32) << 16), key.step_lo, key.step_hi),
+                         make_uint2(key.seed_lo, key.seed_hi));
+}
+
+// (a) g = mask * dP / (1 - p);  dS_ij = P_ij (g_ij - sum_k P_ik g_ik) / scale_div, IN PLACE on dP with zeros right of the diagonal
+// up to ld, and dst[bh][j][i] = dS_ij for i < T, zero for i in [T, ld) (j < T: the rows the dK GEMM reads).
+// A workgroup owns 32 rows of one (batch, head).  Phase 1: one wave per row in softmax_bwd_kernel's order (lane owns j = lane +
+// 64 c, c ascending, then wave_sum_t) -> the same sum bits.  The four lanes of a column quad share a Philox block per chunk: each
+// generates the block of ONE chunk out of four and hands the others their word (three shuffles), a quarter of the generator work.
+// Phase 2: the workgroup reads its own 32 rows back (L2 / L1 hits, the causal half only) through a padded 32 x 32 LDS tile and
+// writes them transposed, 128 contiguous bytes per destination row; tiles right of the diagonal are zeros without a read.
+template <bool DROP>
+__global__ __launch_bounds__(256) void softmax_bwd_t_kernel(const float* __restrict__ P, float* dP, float* __restrict__ dst, int T,
+                                                            int ld, float scale_div, unsigned threshold, float scale, DropKey key,
+                                                            unsigned site, unsigned long long base4) {
+    __shared__ float tile[32][33];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int i0 = blockIdx.x * 32;
+    const long long zoff = (long long)blockIdx.y * T * ld;
+    for (int r = wid; r < 32; r += 4) {                          // wave-uniform
+        const int i = i0 + r;
+        if (i >= T) break;
+        const long long base = zoff + (long long)i * ld;
+        const int n = i + 1;
+        unsigned keep = 0xffffu;                                 // bit c: column lane + 64 c is kept
+        if (DROP) {
+            keep = 0u;
+            const int q = lane & 3;
+            for (int m = 0; m < 4 && 256 * m < n; ++m) {         // chunks 4m .. 4m + 3; this lane generates chunk 4m + q's block
+                const uint4 rr = attn_philox(base4 + (unsigned long long)((base + 64 * (4 * m + q) + (lane & ~3)) >> 2), key, site);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {                    // lane ^ t owns chunk 4m + (q ^ t) and wants ITS word (q ^ t) of it
+                    const int wsel = q ^ t;
+                    const unsigned send = wsel == 0 ? rr.x : wsel == 1 ? rr.y : wsel == 2 ? rr.z : rr.w;
+                    const unsigned got = t ? (unsigned)__shfl_xor((int)send, t, 64) : send;
+                    keep |= (got >= threshold ? 1u : 0u) << (4 * m + wsel);
+                }
+            }
+        }
+        float p[16], g[16];
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const int j = lane + 64 * c;
+            const bool ok = j < n;
+            p[c] = ok ? P[base + min(j, ld - 1)] : 0.f;
+            g[c] = ok ? dP[base + min(j, ld - 1)] : 0.f;
+            if (DROP) g[c] = ((keep >> c) & 1u) ? g[c] * scale : 0.f;
+            s += p[c] * g[c];
+        }
+        s = wave_sum_t(s);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const int j = lane + 64 * c;
+            if (j < ld) dP[base + j] = (j < n) ? p[c] * (g[c] - s) / scale_div : 0.f;
+        }
+    }
+    __syncthreads();                                             // the rows above: written and visible to the whole workgroup
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const float* in = dP + zoff;
+    float* out = dst + zoff;
+    for (int c0 = 0; c0 < T; c0 += 32) {
+        const bool live = i0 < T && c0 <= i0 + 31;               // workgroup-uniform: something left of / on the diagonal
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < 32; k += 8) {
+                const int i = i0 + ty + k, c = c0 + tx;
+                tile[ty + k][tx] = (i < T && c < T) ? in[(long long)i * ld + c] : 0.f;
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int k = 0; k < 32; k += 8) {
+            const int j = c0 + ty + k;                           // dst row j, column i0 + tx < ld (grid.x = ld / 32)
+            if (j < T) out[(long long)j * ld + i0 + tx] = live ? tile[tx][ty + k] : 0.f;
+        }
+        if (live) __syncthreads();
+    }
+}
+
+// (b) out[bh][j][i] = mask * P_ij / (1 - p) for i, j < T, zero for i in [T, ld).  P is zero right of the diagonal, so the tiles
+// there are written as zeros without a read.  One 32 x 32 tile per workgroup: a thread loads four consecutive columns of a row
+// (16 bytes, ONE Philox block), the tile leaves transposed as in transpose_kernel.
+template <bool DROP>
+__global__ __launch_bounds__(256) void dropout_transpose_kernel(const float* __restrict__ P, float* __restrict__ out, int T, int ld,
+                                                                unsigned threshold, float scale, DropKey key, unsigned site,
+                                                                unsigned long long base4) {
+    __shared__ float tile[32][33];
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;       // P rows i (out columns), P columns j (out rows)
+    const long long zoff = (long long)blockIdx.z * T * ld;
+    const bool live = r0 < T && c0 <= r0 + 31;                   // workgroup-uniform
+    if (live) {
+        const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
+        const int i = r0 + r, j = c0 + c4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < T && j < T) {                                    // j + 3 < up4(T) <= ld: inside the row
+            const long long e = zoff + (long long)i * ld + j;
+            v = *reinterpret_cast<const float4*>(P + e);
+            if (DROP) {
+                const uint4 rr = attn_philox(base4 + (unsigned long long)(e >> 2), key, site);
+                v = make_float4(rr.x >= threshold ? v.x * scale : 0.f, rr.y >= threshold ? v.y * scale : 0.f,
+                                rr.z >= threshold ? v.z * scale : 0.f, rr.w >= threshold ? v.w * scale : 0.f);
+            }
+        }
+        tile[r][c4] = v.x; tile[r][c4 + 1] = v.y; tile[r][c4 + 2] = v.z; tile[r][c4 + 3] = v.w;
+        __syncthreads();
+    }
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) {
+        const int j = c0 + ty + k;
+        if (j < T) out[zoff + (long long)j * ld + r0 + tx] = live ? tile[tx][ty + k] : 0.f;
+    }
+}
+
+static int attn_mask_args(const char* what, int nbh, int T, int ld, float p, unsigned site, unsigned long long pbase, unsigned& threshold,
+                          float& scale) {
+    R4D_REQUIRE(nbh >= 1 && nbh <= 65535 && T >= 1 && T <= 1024 && ld >= T && ld <= 1024 && ld % 32 == 0,
+                "%s: nbh=%d T=%d ld=%d out of range (ld a multiple of 32, <= 1024)", what, nbh, T, ld);
+    R4D_REQUIRE(p >= 0.f && p < 1.f && pbase % 4 == 0 && site < 65536u, "%s: p=%g in [0, 1), pbase=%llu a multiple of 4", what,
+                (double)p, pbase);
+    threshold = (unsigned)((double)p * 4294967296.0);            // launch_dropout's: keep iff u32 >= threshold
+    scale = 1.0f / (1.0f - p);
+    return R4D_OK;
+}
+int launch_softmax_bwd_t(const float* P, float* dP, float* dst, int nbh, int T, int ld, float scale_div, float attn_p, DropKey key,
+                         unsigned site, unsigned long long pbase, hipStream_t s) {
+    unsigned threshold; float scale;
+    const int rc = attn_mask_args("softmax_bwd_t", nbh, T, ld, attn_p, site, pbase, threshold, scale);
+    if (rc) return rc;
+    ProfScope prof(PK_SOFTMAX, 4.0 * nbh * T * (2.5 * (T + 1) + 2.0 * ld), s);    // bytes: P, dP, dS read back (causal half) + two full writes
+    const dim3 grid(ld / 32, nbh);
+    if (attn_p > 0.f)
+        hipLaunchKernelGGL(softmax_bwd_t_kernel<true>, grid, dim3(256), 0, s, P, dP, dst, T, ld, scale_div, threshold, scale, key, site, pbase / 4);
+    else
+        hipLaunchKernelGGL(softmax_bwd_t_kernel<false>, grid, dim3(256), 0, s, P, dP, dst, T, ld, scale_div, threshold, scale, key, site, pbase / 4);
+    R4D_CHECK_LAUNCH("softmax_bwd_t");
+    return R4D_OK;
+}
+int launch_dropout_transpose(const float* P, float* out, int nbh, int T, int ld, float attn_p, DropKey key, unsigned site,
+                             unsigned long long pbase, hipStream_t s) {
+    unsigned threshold; float scale;
+    const int rc = attn_mask_args("dropout_transpose", nbh, T, ld, attn_p, site, pbase, threshold, scale);
+    if (rc) return rc;
+    R4D_REQUIRE(((uintptr_t)P & 15) == 0, "dropout_transpose: P must be 16-byte aligned");
+    ProfScope prof(PK_SOFTMAX, 4.0 * nbh * T * (0.5 * (T + 1) + (double)ld), s);  // bytes: causal half read + one full write
+    const dim3 grid(cdiv(T, 32), ld / 32, nbh);
+    if (attn_p > 0.f)
+        hipLaunchKernelGGL(dropout_transpose_kernel<true>, grid, dim3(256), 0, s, P, out, T, ld, threshold, scale, key, site, pbase / 4);
+    else
+        hipLaunchKernelGGL(dropout_transpose_kernel<false>, grid, dim3(256), 0, s, P, out, T, ld, threshold, scale, key, site, pbase / 4);
+    R4D_CHECK_LAUNCH("dropout_transpose");
+    return R4D_OK;
+}
+
 // ------------------------------------------------------------------------------------ optimizer
 // accum[0] += sum x^2 (the total feeds clip_grad_norm_, train_retriever.py:210).  Two stages, no atomics: the value must be
 // the same bits on every data-parallel rank (same gradients after the all-reduce), or the clip coefficient -- and with it the
@@ -554,6 +715,18 @@ int r4d_dropout_f32(const float* x_d, const float* resid_d, int64_t n, float* ou
     R4D_REQUIRE(x_d && out_d && n >= 0, "dropout: bad arguments");
     const DropKey key{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32)};
     return launch_dropout(x_d, resid_d, n, out_d, p, key, site, index_base, (hipStream_t)stream);
+}
+int r4d_softmax_dropout_bwd_transpose_f32(const float* p_d, float* dp_d, float* dst_d, int32_t nbh, int32_t T, int32_t ld, float scale_div,
+                                          float attn_p, uint64_t seed, uint64_t step, uint32_t site, uint64_t index_base, void* stream) {
+    R4D_REQUIRE(p_d && dp_d && dst_d, "softmax_dropout_bwd_transpose: null pointer");
+    const DropKey key{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32)};
+    return launch_softmax_bwd_t(p_d, dp_d, dst_d, nbh, T, ld, scale_div, attn_p, key, site, index_base, (hipStream_t)stream);
+}
+int r4d_dropout_transpose_f32(const float* p_d, float* out_d, int32_t nbh, int32_t T, int32_t ld, float attn_p, uint64_t seed,
+                              uint64_t step, uint32_t site, uint64_t index_base, void* stream) {
+    R4D_REQUIRE(p_d && out_d, "dropout_transpose: null pointer");
+    const DropKey key{(unsigned)seed, (unsigned)(seed >> 32), (unsigned)step, (unsigned)(step >> 32)};
+    return launch_dropout_transpose(p_d, out_d, nbh, T, ld, attn_p, key, site, index_base, (hipStream_t)stream);
 }
 int r4d_sumsq_accumulate_f32(const float* x_d, int64_t n, float* accum_d, void* stream) {
     R4D_REQUIRE(x_d && accum_d && n >= 0, "sumsq: bad arguments");

@@ -92,7 +92,7 @@ class GeneratorTrainer:
     """One generator training micro-step on the device for a ``GPT2LMHeadModelRAG`` with ``gnn_fusion`` (one layer).  ``grads``
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
-    def __init__(self, model, freeze, dropout=None, seed=0):
+    def __init__(self, model, freeze, dropout=None, seed=0, attention=None):
         gnn = getattr(model, "gnn_fusion", None)
         if gnn is None or gnn.n_layers != 1:
             raise _lib.R4DError("GeneratorTrainer: needs a one-layer gnn_fusion (graph pooling)")
@@ -101,7 +101,7 @@ class GeneratorTrainer:
             raise _lib.R4DError("GeneratorTrainer: --freeze needs the untied head of load_and_freeze_params")
         self.model, self.freeze, self.tied = model, bool(freeze), tied
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
         for n, p in self.params.items():
@@ -202,6 +202,7 @@ class GeneratorTrainer:
         if self.freeze or not backward:
             g = None                                                     # frozen transformer / forward only
         head = self.head.struct()
+        self.enc.set_attention_mode()                                    # before the size query: the step call below reads the same mode
         nbytes = lib.r4d_rag_train_workspace_bytes(ctypes.byref(c), B, Ta, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("rag train step: bad batch shape")
@@ -359,6 +360,7 @@ def train(args, train_dataset, model, tokenizer):
     print("  Num Epochs = {}".format(args.num_train_epochs))
     print("  Trainable parameters = {}".format(", ".join(trainer.params)))
     print("  Total optimization steps = {}".format(t_total))
+    print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

@@ -65,13 +65,13 @@ class LMTrainer:
     the padded LM-head operand ``wte_pad`` [ldV, d] (zero rows past V) and its planes.  Every derived weight is rebuilt when the
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
-    def __init__(self, model, dropout=None, seed=0):
+    def __init__(self, model, dropout=None, seed=0, attention=None):
         head = getattr(model, "lm_head", None)
         if head is None or head.weight is not model.transformer.wte.weight:
             raise _lib.R4DError("SimpleDyG training needs lm_head tied to transformer.wte (the reference's model is always tied); "
                                 "this model's lm_head is a separate tensor")
         self.model = model
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
@@ -127,6 +127,7 @@ class LMTrainer:
         lib = _lib.load()
         c, w, g, keep = self.enc._structs()
         head = self.head.struct()
+        self.enc.set_attention_mode()                              # before the size query: the step call below reads the same mode
         nbytes = lib.r4d_gpt2_lm_train_workspace_bytes(ctypes.byref(c), B, T, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("lm train step: bad batch shape")
@@ -289,6 +290,7 @@ def train(args, train_dataset, model, tokenizer):
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
     print("  Total train batch size (w. parallel, distributed & accumulation) = {}".format(args.train_batch_size * gas * world))
     print("  Gradient Accumulation steps = {}".format(gas))
+    print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

@@ -126,18 +126,35 @@ _LAYER_PARAMS = (("ln_1_w", "ln_1.weight"), ("ln_1_b", "ln_1.bias"), ("c_attn_w"
                  ("mlp_proj_w", "mlp.c_proj.weight"), ("mlp_proj_b", "mlp.c_proj.bias"))
 
 
+TRAIN_ATTENTION_MODES = {"stored": 0, "recompute": 1}
+
+
+def resolve_train_attention(attention=None):
+    """``"stored"`` (the forward keeps the attention probabilities of every layer) or ``"recompute"`` (the backward forms them
+    again: same bits, a smaller workspace; ``r4d_set_train_attention``).  None -> the environment variable
+    ``R4D_TRAIN_ATTENTION``, ``stored`` when it is unset or empty.  Anything else raises."""
+    if attention is None:
+        attention = os.environ.get("R4D_TRAIN_ATTENTION") or "stored"
+    if attention not in TRAIN_ATTENTION_MODES:
+        raise ValueError(f"train attention mode {attention!r}: expected one of {sorted(TRAIN_ATTENTION_MODES)}")
+    return attention
+
+
 class EncoderTrainer:
     """Forward-with-saved-activations and backward of the SimpleDyG encoder on the HIP kernels
     (``r4d_gpt2_train_forward_f32`` / ``r4d_gpt2_train_backward_f32``), for a ``GPT2LMHeadModelRAG`` whose parameters live
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0, want_grads=True):
-        """``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
+    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None):
+        """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``); the
+        trainer sets the library's mode before every size query and step call of its own, so trainers of both modes can share a
+        process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
         (embd_p, attn_p, resid_p).  ``seed`` keys the counter-based mask generator; every forward advances its step."""
         self.model = model
+        self.attention = resolve_train_attention(attention)
         self.dropout, self.seed, self.step = dropout, int(seed), 0
         self._drop_struct = None
         tr = model.transformer
@@ -235,6 +252,10 @@ class EncoderTrainer:
                             self.grads["transformer.ln_f.weight"].data_ptr(), self.grads["transformer.ln_f.bias"].data_ptr(), glayers)
         return c, w, g, (layers, glayers)
 
+    def set_attention_mode(self):
+        """Select this trainer's attention mode in the library (process-wide switch: before every size query and step call)."""
+        _lib.check(_lib.load().r4d_set_train_attention(TRAIN_ATTENTION_MODES[self.attention]), "set_train_attention")
+
     def _dropout_struct(self):
         if self.dropout is not None:
             pe, pa, pr = self.dropout
@@ -257,6 +278,7 @@ class EncoderTrainer:
         Bs = (ctypes.c_int32 * n)(*[int(t.shape[0]) for t in ids])
         Ts = (ctypes.c_int32 * n)(*[int(t.shape[1]) for t in ids])
         ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ids])
+        self.set_attention_mode()
         nbytes = lib.r4d_gpt2_train_workspace_bytes(ctypes.byref(c), n, Bs, Ts)
         if nbytes == 0:
             raise _lib.R4DError("gpt2 train: bad batch shapes")
@@ -281,6 +303,7 @@ class EncoderTrainer:
         lib = _lib.load()
         c, w, g, keep = self._structs()
         de = d_embeddings.to(torch.float32).contiguous()
+        self.set_attention_mode()
         _lib.check(lib.r4d_gpt2_train_backward_f32(ctypes.byref(c), ctypes.byref(w), ctypes.byref(g), n, ptrs, Bs, Ts, de.data_ptr(),
                                                    ctypes.byref(self._drop_struct) if self._drop_struct is not None else None,
                                                    self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream),
@@ -547,6 +570,7 @@ def train(args, train_dataset, model, tokenizer):
     print("  Num examples = {}".format(len(train_dataset)))
     print("  Num Epochs = {}".format(args.num_train_epochs))
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
+    print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.attention))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)
