@@ -486,6 +486,20 @@ int r4d_dropout_f32(const float* x_d, const float* resid_d, int64_t n, float* ou
 int r4d_set_train_attention(int32_t mode);
 int r4d_get_train_attention(void);
 
+/* How the training steps keep the per-layer activations (process-wide; additive ABI v6 entries, independent of the switch above).
+ *   0 stored (default): the forward keeps x_in, ln1, qkv, att, x_mid, ln2, pre, f of every layer (16 * rows * d floats each);
+ *   1 recompute:        the forward keeps each layer's input x_in (and layer 0's ln1); ln1 .. f -- and, under stored attention,
+ *                       ONE P block -- are a single set that all layers share.  The backward walks the layers downwards and,
+ *                       ahead of each layer's backward, runs that layer's forward launches from ln_1 to c_fc (+ GELU) again on
+ *                       x_in with the forward's arguments and dropout sites.  The same launches on the same bits: every output
+ *                       and gradient is bit-identical to mode 0.  The weights, the token ids and the dropout descriptor must be
+ *                       those of the forward until the backward has been issued (the three step calls guarantee it).
+ * Any other value is R4D_ERR_INVALID and changes nothing.  Read like the attention mode: set it BEFORE the size query and keep it
+ * until the step's backward has been issued; a backward on the workspace of the most recent training forward under a different
+ * mode is refused (R4D_ERR_INVALID). */
+int r4d_set_train_activations(int32_t mode);
+int r4d_get_train_activations(void);
+
 /* Scratch of one step: the activations the backward pass needs (16 * rows * d floats per layer + the attention
  * probabilities in stored mode) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts);

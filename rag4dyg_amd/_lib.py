@@ -162,6 +162,8 @@ PROTOTYPES = {
     "r4d_dropout_transpose_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_float, c_uint64, c_uint64, c_uint32, c_uint64, _P]),
     "r4d_set_train_attention": (c_int32, [c_int32]),
     "r4d_get_train_attention": (c_int32, []),
+    "r4d_set_train_activations": (c_int32, [c_int32]),
+    "r4d_get_train_activations": (c_int32, []),
     "r4d_sumsq_accumulate_f32": (c_int32, [_P, c_int64, _P, _P]),
     "r4d_adamw_step_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int32, _P, c_float, _P]),
     "r4d_dispatch_num_branches": (c_int32, []),

@@ -48,8 +48,13 @@ int launch_meanpool_bwd(const float* d_pool, long long rows, int T, int d, float
 // r4d_set_train_attention: 0 stored (the forward keeps P of every layer), 1 recompute (the backward forms P again with the
 // forward's two launches; no per-layer P blocks).  Read by layout(), so the size queries, the forward and the backward follow it.
 static int g_train_attention = 0;
-static const void* g_last_fwd_ws = nullptr;   // workspace and mode of the most recent training forward: a backward on that
+// r4d_set_train_activations: 0 stored (the forward keeps ln1 .. f of every layer), 1 recompute (it keeps each layer's input; the
+// backward forms one layer's activations at a time again, with the forward's launches, in ONE set all layers share).  Read by layout().
+static int g_train_activations = 0;
+static const void* g_last_fwd_ws = nullptr;   // workspace and modes of the most recent training forward: a backward on that
 static int g_last_fwd_mode = 0;               // workspace under another mode would read the wrong layout -> refused
+static int g_last_fwd_act = 0;
+static int g_shared_layer = -1;               // activations recompute: the layer whose activations that workspace's shared set holds
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -64,6 +69,7 @@ struct TrainLayout {
     std::vector<size_t> x_in, ln1, qkv, att, x_mid, ln2, pre, f, P;
     size_t x_out, pool_scratch;
     bool recompute;                                     // no P blocks; scratch pA holds the P of the batch at hand
+    bool act_recompute;                                 // ln1 .. f (and P) of every layer are ONE shared set; x_in stays per layer
     // backward temporaries (pA: recompute mode only; dP / PT are its scratch blocks B / C)
     size_t dx, dy, dbig, dqkv, xT, pA, dP, PT, red;
     size_t emb_acc;                                     // [vocab, d] 64-bit fixed-point token-gradient table (two floats per entry)
@@ -74,6 +80,7 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
     TrainLayout t;
     t.L = cfg->n_layer; t.d = cfg->n_embd;
     t.recompute = g_train_attention == 1;
+    t.act_recompute = g_train_activations == 1;
     const size_t d = t.d;
     t.M = 0; t.Ptot = 0; t.pmax = 0;
     size_t pool = 0;
@@ -87,6 +94,14 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
     size_t off = 0;
     auto take = [&](size_t nfloat) { const size_t o = off; off += (nfloat + 63) / 64 * 64; return o; };
     for (int l = 0; l < t.L; ++l) {
+        if (t.act_recompute && l >= 1) {
+            // layer 0 owns its ln1 (it left the fused embedding kernel; launch_layernorm is not promised to give its bits);
+            // layers 1 .. L-1 share one ln1, and every layer shares the blocks behind it
+            t.x_in.push_back(take(t.M * d)); t.ln1.push_back(l == 1 ? take(t.M * d) : t.ln1[1]); t.qkv.push_back(t.qkv[0]);
+            t.att.push_back(t.att[0]); t.x_mid.push_back(t.x_mid[0]); t.ln2.push_back(t.ln2[0]);
+            t.pre.push_back(t.pre[0]); t.f.push_back(t.f[0]); t.P.push_back(t.P[0]);
+            continue;
+        }
         t.x_in.push_back(take(t.M * d)); t.ln1.push_back(take(t.M * d)); t.qkv.push_back(take(t.M * 3 * d));
         t.att.push_back(take(t.M * d)); t.x_mid.push_back(take(t.M * d)); t.ln2.push_back(take(t.M * d));
         t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take(t.M * 4 * d)); t.P.push_back(t.recompute ? 0 : take(t.Ptot));
@@ -360,6 +375,13 @@ int r4d_set_train_attention(int32_t mode) {
 }
 int r4d_get_train_attention(void) { return g_train_attention; }
 
+int r4d_set_train_activations(int32_t mode) {
+    R4D_REQUIRE(mode == 0 || mode == 1, "set_train_activations: mode %d is neither 0 (stored) nor 1 (recompute)", (int)mode);
+    g_train_activations = mode;
+    return R4D_OK;
+}
+int r4d_get_train_activations(void) { return g_train_activations; }
+
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts) {
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
     std::vector<TrainGroup> gs((size_t)n_groups);
@@ -395,6 +417,60 @@ size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, con
     return layout(cfg, gs.data(), n_groups).total;
 }
 
+// One block of the training forward: x_in[l] -> x_in[l + 1] (x_out behind the last one), layer 0 from the token ids.
+// `again` (activations recompute mode, called by the backward): x_in[l] is there; the launches from ln_1 to c_fc (+ GELU) run on
+// it once more with the forward's arguments and dropout sites, into the set all layers share, and the MLP projection is left out.
+// It borrows the backward temporaries dy (branch of the residual dropout) and dP / pA (attention scratch) like the forward.
+static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int l, const TrainLayout& t,
+                         const std::vector<TrainGroup>& gs, const RowGroups& R, const DropCtx& dc, float* ws,
+                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const SpliceIn* sp, bool again,
+                         hipStream_t s) {
+    const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M;
+    const r4d_gpt2_layer& Lw = w->layers[l];
+    R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
+    float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
+    float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
+    int rc = R4D_OK;
+    if (l == 0 && again)                                         // x_in (after its dropout) and its ln1 are layer 0's own blocks:
+        rc = R4D_OK;                                             // kept, not formed again (the fused kernels below made them)
+    else if (l == 0 && sp)                                       // cat(wte[tok[:, :2]], fused, wte[tok[:, 2:]]) + wpe
+        rc = launch_splice_embed_ln(ids_d[0], sp->fused, sp->r, w->wte, w->wpe, cfg->vocab, Bs[0], Ts[0], d, Lw.ln_1_w, Lw.ln_1_b,
+                                    cfg->ln_eps, x_in, ln1, s);
+    else if (l == 0)
+        rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, Lw.ln_1_w, Lw.ln_1_b, cfg->ln_eps, x_in, ln1, s);
+    else
+        rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s);
+    if (rc) return rc;
+    if (l == 0 && !again && dc.embd_p > 0.f) {                   // self.drop(inputs_embeds + position_embeds), :427
+        if ((rc = launch_dropout(x_in, nullptr, (long long)M * d, x_in, dc.embd_p, dc.key, R4D_DROPOUT_SITE_EMBD, 0, s))) return rc;
+        if ((rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s))) return rc;
+    }
+    if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2))) return rc;
+    for (const TrainGroup& G : gs)
+        if ((rc = attn_fwd(qkv + G.row0 * 3 * d, G.B, G.T, H, d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0, att + G.row0 * d, s,
+                           dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
+    float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
+    if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
+        if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
+        if ((rc = launch_dropout(branch, x_in, (long long)M * d, x_mid, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
+    } else if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, x_in, M, d, d, EPI_RESIDUAL, x_mid, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
+    if ((rc = launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
+    if (g_train_fuse_gelu && Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
+        // one launch: f = gelu_new(v) and the pre-activation v (kept for the backward pass) both leave the GEMM's epilogue
+        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, pre, M, d, 4 * d, EPI_GELU_KEEP, f, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
+    } else {
+        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, nullptr, M, d, 4 * d, EPI_NONE, pre, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
+        if ((rc = launch_gelu_fwd(pre, (long long)M * 4 * d, f, s))) return rc;
+    }
+    if (again) return R4D_OK;                                    // the MLP projection's output, x_in[l + 1], is there already
+    float* x_next = l + 1 < cfg->n_layer ? ws + t.x_in[l + 1] : ws + t.x_out;
+    if (dc.resid_p > 0.f) {                                      // x + dropout(c_proj(act(c_fc(x)))), :212,233
+        if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, nullptr, M, 4 * d, d, EPI_NONE, branch, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
+        if ((rc = launch_dropout(branch, x_mid, (long long)M * d, x_next, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
+    } else if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, x_mid, M, 4 * d, d, EPI_RESIDUAL, x_next, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
+    return R4D_OK;
+}
+
 // The training forward; its output is EITHER the mean pool per sequence (retriever) OR the ln_f output per row (LM head)
 int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
@@ -413,49 +489,12 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
         return R4D_ERR_WORKSPACE;
     }
     float* ws = (float*)workspace_d;
-    g_last_fwd_ws = workspace_d; g_last_fwd_mode = g_train_attention;
-    const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M;
+    g_last_fwd_ws = workspace_d; g_last_fwd_mode = g_train_attention; g_last_fwd_act = g_train_activations;
+    g_shared_layer = cfg->n_layer - 1;
+    const int d = cfg->n_embd;
     const RowGroups R = row_groups_of(gs);
-    for (int l = 0; l < cfg->n_layer; ++l) {
-        const r4d_gpt2_layer& Lw = w->layers[l];
-        R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
-        float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
-        float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
-        if (l == 0 && sp)                                            // cat(wte[tok[:, :2]], fused, wte[tok[:, 2:]]) + wpe
-            rc = launch_splice_embed_ln(ids_d[0], sp->fused, sp->r, w->wte, w->wpe, cfg->vocab, Bs[0], Ts[0], d, Lw.ln_1_w, Lw.ln_1_b,
-                                        cfg->ln_eps, x_in, ln1, s);
-        else if (l == 0)
-            rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, Lw.ln_1_w, Lw.ln_1_b, cfg->ln_eps, x_in, ln1, s);
-        else
-            rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s);
-        if (rc) return rc;
-        if (l == 0 && dc.embd_p > 0.f) {                             // self.drop(inputs_embeds + position_embeds), :427
-            if ((rc = launch_dropout(x_in, nullptr, (long long)M * d, x_in, dc.embd_p, dc.key, R4D_DROPOUT_SITE_EMBD, 0, s))) return rc;
-            if ((rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s))) return rc;
-        }
-        if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2))) return rc;
-        for (const TrainGroup& G : gs)
-            if ((rc = attn_fwd(qkv + G.row0 * 3 * d, G.B, G.T, H, d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0, att + G.row0 * d, s,
-                               dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
-        float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
-        if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
-            if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
-            if ((rc = launch_dropout(branch, x_in, (long long)M * d, x_mid, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
-        } else if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, x_in, M, d, d, EPI_RESIDUAL, x_mid, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
-        if ((rc = launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
-        if (g_train_fuse_gelu && Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
-            // one launch: f = gelu_new(v) and the pre-activation v (kept for the backward pass) both leave the GEMM's epilogue
-            if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, pre, M, d, 4 * d, EPI_GELU_KEEP, f, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
-        } else {
-            if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, nullptr, M, d, 4 * d, EPI_NONE, pre, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
-            if ((rc = launch_gelu_fwd(pre, (long long)M * 4 * d, f, s))) return rc;
-        }
-        float* x_next = l + 1 < cfg->n_layer ? ws + t.x_in[l + 1] : ws + t.x_out;
-        if (dc.resid_p > 0.f) {                                      // x + dropout(c_proj(act(c_fc(x)))), :212,233
-            if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, nullptr, M, 4 * d, d, EPI_NONE, branch, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
-            if ((rc = launch_dropout(branch, x_mid, (long long)M * d, x_next, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
-        } else if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, x_mid, M, 4 * d, d, EPI_RESIDUAL, x_next, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
-    }
+    for (int l = 0; l < cfg->n_layer; ++l)
+        if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, false, s))) return rc;
     return launch_lnf_meanpool_groups(R, ws + t.x_out, w->ln_f_w, w->ln_f_b, d, cfg->ln_eps, out_hidden_d, out_meanpool_d,
                                       ws + t.pool_scratch, s);
 }
@@ -477,6 +516,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(workspace_d != g_last_fwd_ws || g_train_attention == g_last_fwd_mode,
                 "gpt2 train backward: this workspace was filled by a forward in train-attention mode %d, the current mode is %d",
                 g_last_fwd_mode, g_train_attention);
+    R4D_REQUIRE(workspace_d != g_last_fwd_ws || g_train_activations == g_last_fwd_act,
+                "gpt2 train backward: this workspace was filled by a forward in train-activations mode %d, the current mode is %d",
+                g_last_fwd_act, g_train_activations);
     const TrainLayout t = layout(cfg, gs.data(), n_groups);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -485,6 +527,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     float* ws = (float*)workspace_d;
     const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M, L = cfg->n_layer;
     float *dx = ws + t.dx, *dy = ws + t.dy, *dbig = ws + t.dbig, *dqkv = ws + t.dqkv, *xT = ws + t.xT, *red = ws + t.red;
+    const RowGroups R = row_groups_of(gs);
     // mean over T -> ln_f (or the caller's per-row gradient of the ln_f output)
     if (d_meanpool_d) {
         for (const TrainGroup& G : gs)
@@ -502,6 +545,14 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                     Lg.ln_2_b && Lg.c_fc_w && Lg.c_fc_b && Lg.mlp_proj_w && Lg.mlp_proj_b, "gpt2 train backward: null gradient in layer %d", l);
         float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
         float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
+        // activations recompute: this layer's ln1 .. f (and P) into the shared set again, by the forward's launches on x_in[l].
+        // dx holds the live d(x_out) and is not touched; dy, dP and pA, which the launches borrow, are dead here.  The set still
+        // holds the last layer's activations when this backward follows its forward directly: nothing to run again then.
+        if (t.act_recompute && !(workspace_d == g_last_fwd_ws && g_shared_layer == l)) {
+            if (workspace_d == g_last_fwd_ws) g_shared_layer = -1;
+            if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, true, s))) return rc;
+            if (workspace_d == g_last_fwd_ws) g_shared_layer = l;
+        }
         // ---- MLP: x_out = x_mid + gelu(ln_2(x_mid) Wfc + bfc) Wp + bp ;  dx holds d(x_out)
         const float* dbr = dx;                                       // gradient of the branch output: through its dropout mask
         if (dc.resid_p > 0.f) {

@@ -92,7 +92,7 @@ class GeneratorTrainer:
     """One generator training micro-step on the device for a ``GPT2LMHeadModelRAG`` with ``gnn_fusion`` (one layer).  ``grads``
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
-    def __init__(self, model, freeze, dropout=None, seed=0, attention=None):
+    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None):
         gnn = getattr(model, "gnn_fusion", None)
         if gnn is None or gnn.n_layers != 1:
             raise _lib.R4DError("GeneratorTrainer: needs a one-layer gnn_fusion (graph pooling)")
@@ -101,7 +101,7 @@ class GeneratorTrainer:
             raise _lib.R4DError("GeneratorTrainer: --freeze needs the untied head of load_and_freeze_params")
         self.model, self.freeze, self.tied = model, bool(freeze), tied
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
         for n, p in self.params.items():
@@ -328,7 +328,7 @@ def evaluate(args, trainer, loader, bags):
     return float(total) / n if n else float("nan")
 
 
-def train(args, train_dataset, model, tokenizer):
+def train(args, train_dataset, model, tokenizer, activations=None):
     """Drop-in for ``train_generator.train`` (:141-248).  Returns (global_step, tr_loss / global_step)."""
     from .generator import get_eval_metrics_generator, load_and_cache_examples
     check_supported(args)
@@ -345,7 +345,7 @@ def train(args, train_dataset, model, tokenizer):
     else:
         t_total = len(loader) // gas * args.num_train_epochs
     trainer = GeneratorTrainer(model, freeze=bool(getattr(args, "freeze", False)),
-                               seed=int(getattr(args, "seed", 0)) + 7919 * rank)
+                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations)
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():
@@ -361,6 +361,7 @@ def train(args, train_dataset, model, tokenizer):
     print("  Trainable parameters = {}".format(", ".join(trainer.params)))
     print("  Total optimization steps = {}".format(t_total))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
+    print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

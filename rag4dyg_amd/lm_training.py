@@ -65,13 +65,13 @@ class LMTrainer:
     the padded LM-head operand ``wte_pad`` [ldV, d] (zero rows past V) and its planes.  Every derived weight is rebuilt when the
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
-    def __init__(self, model, dropout=None, seed=0, attention=None):
+    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None):
         head = getattr(model, "lm_head", None)
         if head is None or head.weight is not model.transformer.wte.weight:
             raise _lib.R4DError("SimpleDyG training needs lm_head tied to transformer.wte (the reference's model is always tied); "
                                 "this model's lm_head is a separate tensor")
         self.model = model
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
@@ -261,7 +261,7 @@ def train_epoch(model, trainer, optimizer, scheduler, train_dataloader, tr_loss,
     return global_step, tr_loss
 
 
-def train(args, train_dataset, model, tokenizer):
+def train(args, train_dataset, model, tokenizer, activations=None):
     """Drop-in for ``main_SimpleDyG.train`` (:200-343).  Returns (global_step, tr_loss / global_step)."""
     from .evaluation import get_eval_metrics
     if getattr(args, "fp16", False):
@@ -274,7 +274,7 @@ def train(args, train_dataset, model, tokenizer):
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
     else:
         t_total = len(train_dataloader) // gas * args.num_train_epochs
-    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank)      # every rank its own dropout masks
+    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations)      # every rank its own dropout masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -291,6 +291,7 @@ def train(args, train_dataset, model, tokenizer):
     print("  Total train batch size (w. parallel, distributed & accumulation) = {}".format(args.train_batch_size * gas * world))
     print("  Gradient Accumulation steps = {}".format(gas))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
+    print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

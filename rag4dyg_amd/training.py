@@ -140,21 +140,38 @@ def resolve_train_attention(attention=None):
     return attention
 
 
+TRAIN_ACTIVATION_MODES = {"stored": 0, "recompute": 1}
+
+
+def resolve_train_activations(activations=None):
+    """``"stored"`` (the forward keeps ln1 .. f of every layer) or ``"recompute"`` (it keeps each layer's input; the backward
+    forms one layer's activations at a time again: same bits, a workspace that no longer grows with 16 * rows * d per layer;
+    ``r4d_set_train_activations``).  None -> the environment variable ``R4D_TRAIN_ACTIVATIONS``, ``stored`` when it is unset or
+    empty.  Anything else raises."""
+    if activations is None:
+        activations = os.environ.get("R4D_TRAIN_ACTIVATIONS") or "stored"
+    if activations not in TRAIN_ACTIVATION_MODES:
+        raise ValueError(f"train activations mode {activations!r}: expected one of {sorted(TRAIN_ACTIVATION_MODES)}")
+    return activations
+
+
 class EncoderTrainer:
     """Forward-with-saved-activations and backward of the SimpleDyG encoder on the HIP kernels
     (``r4d_gpt2_train_forward_f32`` / ``r4d_gpt2_train_backward_f32``), for a ``GPT2LMHeadModelRAG`` whose parameters live
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None):
-        """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``); the
-        trainer sets the library's mode before every size query and step call of its own, so trainers of both modes can share a
-        process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
+    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None):
+        """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``);
+        ``activations``: the same two words for the per-layer activations (:func:`resolve_train_activations`; None ->
+        ``R4D_TRAIN_ACTIVATIONS``).  The trainer sets both library switches before every size query and step call of its own, so
+        trainers of different modes can share a process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
         (embd_p, attn_p, resid_p).  ``seed`` keys the counter-based mask generator; every forward advances its step."""
         self.model = model
         self.attention = resolve_train_attention(attention)
+        self.activations = resolve_train_activations(activations)
         self.dropout, self.seed, self.step = dropout, int(seed), 0
         self._drop_struct = None
         tr = model.transformer
@@ -253,8 +270,10 @@ class EncoderTrainer:
         return c, w, g, (layers, glayers)
 
     def set_attention_mode(self):
-        """Select this trainer's attention mode in the library (process-wide switch: before every size query and step call)."""
+        """Select this trainer's attention and activations modes in the library (process-wide switches: before every size query
+        and step call)."""
         _lib.check(_lib.load().r4d_set_train_attention(TRAIN_ATTENTION_MODES[self.attention]), "set_train_attention")
+        _lib.check(_lib.load().r4d_set_train_activations(TRAIN_ACTIVATION_MODES[self.activations]), "set_train_activations")
 
     def _dropout_struct(self):
         if self.dropout is not None:
@@ -539,7 +558,7 @@ def distributed_setup(args):
     return dist.get_world_size(), dist.get_rank()
 
 
-def train(args, train_dataset, model, tokenizer):
+def train(args, train_dataset, model, tokenizer, activations=None):
     """Drop-in for ``train/train_retriever.train`` (``:230-354``): AdamW on the time-decayed contrastive + InfoNCE loss, validation
     hit@3 after every epoch, best checkpoint as ``checkpoint-0`` (only once ``epoch > warmup_steps``, as upstream), last as
     ``checkpoint-1``, early stopping after ``--patience`` epochs without improvement, then the test / validation passes on
@@ -559,7 +578,7 @@ def train(args, train_dataset, model, tokenizer):
     gas = max(1, int(getattr(args, "gradient_accumulation_steps", 1)))
     if args.max_steps > 0:
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
-    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank)      # every rank its own masks
+    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations)      # every rank its own masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -571,6 +590,7 @@ def train(args, train_dataset, model, tokenizer):
     print("  Num Epochs = {}".format(args.num_train_epochs))
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.attention))
+    print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.activations))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

@@ -301,9 +301,10 @@ print(json.dumps({"rows": rows, "cols": len(lists), "seconds": el}))
 """
 
 
-def training(attention=None):
-    """(``--attention stored|recompute``: how the step keeps the attention probabilities, ``EncoderTrainer(attention=)``; the
-    line reports the mode and the trainer's workspace bytes.)  SURVEY 8f-4: one retriever training iteration (five forwards with saved activations, losses, encoder backward, clip,
+def training(attention=None, activations=None):
+    """(``--attention stored|recompute``: how the step keeps the attention probabilities, ``EncoderTrainer(attention=)``;
+    ``--activations stored|recompute``: the same for the per-layer activations; the line reports both modes, the trainer's
+    workspace bytes and torch's peak allocated bytes.)  SURVEY 8f-4: one retriever training iteration (five forwards with saved activations, losses, encoder backward, clip,
     AdamW) at the UCI_13 script's shape (L4 H2 d512, batch 64: scripts/train_retriever/train_retriever_UCI_13.sh:8-12) on
     synthetic UCI_13-length sequences.  flop = 3 x the forward's algorithmic encoder flop (forward + dX + dW) of the five
     padded batches; wall clock includes the host side of the step (aug, loss autograd over [5, B, d], ~40 optimizer launches)."""
@@ -330,9 +331,10 @@ def training(attention=None):
     flop = sum(3.0 * (f_enc(shape, B, b[0].shape[1]) * 3 + f_enc(shape, B, b[1].shape[1]) + f_enc(shape, B, b[2].shape[1]))
                for b in batches[2:])
     wall = {}
+    torch.cuda.reset_peak_memory_stats()
     for mode in ("warm", "eval", "train"):               # "train": model.train(), dropout 0.1 at the four sites like the reference
         m.train(mode == "train")
-        trainer = tr.EncoderTrainer(m, seed=42, attention=attention)
+        trainer = tr.EncoderTrainer(m, seed=42, attention=attention, activations=activations)
         opt = tr.AdamW(trainer.params, trainer.grads, lr=1e-5, eps=1e-8, weight_decay=0.0, flat_grads=trainer.flat_grads)
         random.seed(0)
         for b in batches[:2]:
@@ -362,7 +364,8 @@ def training(attention=None):
          ms_per_step_dropout_off=round(1e3 * wall["eval"] / n, 3),
          forward_ms=round(ev[0].elapsed_time(ev[1]), 3), backward_ms=round(ev[1].elapsed_time(ev[2]), 3),
          optimizer_ms=round(ev[2].elapsed_time(ev[3]), 3), padded_T=[int(x.shape[1]) for x in b[:3]],
-         attention=trainer.attention, workspace_bytes=int(trainer._ws.numel()))
+         attention=trainer.attention, activations=trainer.activations, workspace_bytes=int(trainer._ws.numel()),
+         max_memory_allocated=int(torch.cuda.max_memory_allocated()))
 
 
 def training_cpu():
@@ -413,10 +416,13 @@ def jaccard_cpu_all_cores():
 
 
 if __name__ == "__main__":
-    if "--attention" in sys.argv:                              # training entry only
-        i = sys.argv.index("--attention")
-        training = functools.partial(training, attention=sys.argv[i + 1])
-        del sys.argv[i:i + 2]
+    for flag in ("--attention", "--activations"):              # training entry only
+        if flag in sys.argv:
+            i = sys.argv.index(flag)
+            if sys.argv[i + 1] not in ("stored", "recompute"):
+                sys.exit(f"{flag}: stored or recompute")
+            training = functools.partial(training, **{flag[2:]: sys.argv[i + 1]})
+            del sys.argv[i:i + 2]
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):
         {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "generator": generator,
          "generator_reddit": generator_reddit, "simpledyg": simpledyg_eval, "training": training, "training_cpu": training_cpu}[part]()

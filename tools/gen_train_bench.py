@@ -5,7 +5,7 @@ configuration) and unfrozen (tied); the per-class breakdown of ``r4d_profile_*``
 frozen step in torch autograd, fp32 on the GPU (a plain-torch GPT-2 with fused causal attention, ``oracle.generator_ref``'s GCN).  Eval mode: no
 dropout launches in either.
 
-    python tools/gen_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,reddit] [--one-step uci13] [--attention stored|recompute]
+    python tools/gen_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,reddit] [--one-step uci13] [--attention stored|recompute] [--activations stored|recompute]
 """
 import argparse
 import ctypes
@@ -121,12 +121,14 @@ def main():
                     help="one warm-up and ONE timed frozen step at SHAPE, print nothing else (for a kernel trace)")
     ap.add_argument("--attention", default=None, choices=("stored", "recompute"),
                     help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
+    ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
+                    help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
     if a.one_step:
         m, src, idx, tok = _setup(SHAPES[a.one_step], dev, freeze=True)
-        tr = GeneratorTrainer(m, freeze=True, attention=a.attention)
+        tr = GeneratorTrainer(m, freeze=True, attention=a.attention, activations=a.activations)
         bags = PreparedBags(idx, src, 7).batch(range(len(idx)), dev)
         for _ in range(2):
             tr.step(tok, bags)
@@ -138,14 +140,16 @@ def main():
         tokens = s["B"] * (s["T"] + 1)
         for freeze in (True, False):
             m, src, idx, tok = _setup(s, dev, freeze)
-            tr = GeneratorTrainer(m, freeze=freeze, attention=a.attention)
+            torch.cuda.reset_peak_memory_stats()
+            tr = GeneratorTrainer(m, freeze=freeze, attention=a.attention, activations=a.activations)
             bags = PreparedBags(idx, src, 7).batch(range(len(idx)), dev)
             ms = _time(lambda: tr.step(tok, bags), a.steps, a.warmup)
             key = "frozen" if freeze else "unfrozen"
             rec[key + "_ms_per_step"] = round(ms, 4)
             rec[key + "_tokens_per_s"] = round(tokens / (ms / 1e3), 1)
             rec[key + "_workspace_bytes"] = int(tr._ws.numel())
-            rec["attention"] = tr.enc.attention
+            rec[key + "_max_memory_allocated"] = int(torch.cuda.max_memory_allocated())      # model, trainer and the timed steps
+            rec["attention"], rec["activations"] = tr.enc.attention, tr.enc.activations
             if freeze:
                 lib.r4d_profile_enable(1)
                 tr.step(tok, bags)

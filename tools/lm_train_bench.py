@@ -3,7 +3,7 @@
 shapes: ms per step and tokens/s, the per-class breakdown of ``r4d_profile_*``, the CE kernel's bytes / time against the 8 TB/s HBM
 spec, the head's share of the step (step minus forward_hidden + backward_hidden timed alone; eval mode, no dropout), and as a yardstick the same head (h . wte^T, F.cross_entropy, backward) in torch autograd.
 
-    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute]
+    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute]
 """
 import argparse
 import ctypes
@@ -56,6 +56,8 @@ def main():
                     help="run one warm-up and ONE timed step at T of the first shape, print nothing else (for a kernel trace)")
     ap.add_argument("--attention", default=None, choices=("stored", "recompute"),
                     help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
+    ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
+                    help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -69,7 +71,8 @@ def main():
         m.tie_weights()
         # eval mode: no dropout launches, so that the step and its body (timed alone below) differ by the head only
         m = m.to(dev).eval()
-        tr = LMTrainer(m, attention=a.attention)
+        torch.cuda.reset_peak_memory_stats()
+        tr = LMTrainer(m, attention=a.attention, activations=a.activations)
         if a.one_step:
             ids = torch.randint(0, s["V"], (s["B"], a.one_step), device=dev)
             tr.step(ids)
@@ -82,6 +85,7 @@ def main():
             ids = torch.randint(0, V, (B, T), device=dev)
             ms = _time(lambda: tr.step(ids), a.steps, a.warmup)
             ws_bytes = int(tr._ws.numel())                         # (the buffer only grows: shapes run in ascending T)
+            peak = int(torch.cuda.max_memory_allocated())          # model, trainer and the timed steps up to this T
             lib.r4d_profile_enable(1)
             tr.step(ids)
             torch.cuda.synchronize()
@@ -122,7 +126,8 @@ def main():
             lib.r4d_profile_enable(0)
             total_prof = sum(v["ms"] for v in prof2.values())
             head_like = {k: v for k, v in prof2.items() if v["work"] > 0}
-            rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, workspace_bytes=ws_bytes, L=s["L"], H=s["H"], d=d, V=V,
+            rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, activations=tr.enc.activations,
+                       workspace_bytes=ws_bytes, max_memory_allocated=peak, L=s["L"], H=s["H"], d=d, V=V,
                        ldV=ldV, B=B, T=T, ms_per_step=ms,
                        tokens_per_s=N / (ms / 1e3), ce_ms=ce.get("ms"), ce_bytes=ce_bytes,
                        ce_hbm_fraction=(ce_bytes / (ce["ms"] / 1e3) / HBM_BPS) if ce else None,
