@@ -116,6 +116,23 @@ typedef struct r4d_gpt2_weights {
                                       * generator checkpoints carry two different tensors.  Read by the greedy step only. */
 } r4d_gpt2_weights;
 
+/*
+ * WHAT A BUFFER MAY HOLD ON ENTRY (every entry point of this header).
+ * Workspace (workspace_d / *_ws_d), output (out_*_d, loss_d, perm_d, ...) and gradient memory (r4d_gpt2_grads, head_grad_d,
+ * d_fused_d, dw_d / db_d / dx_d) may hold ANYTHING when a call is made -- stale values of another shape or another entry point,
+ * NaN, huge values, non-zero counters: the library never needs such memory zeroed, writes every byte it later reads (padding of
+ * contraction ranges, split-K and top-k ticket counters, fixed-point accumulation tables included: each call clears or
+ * overwrites its own), and one workspace may be shared, grow-only, by any sequence of calls on one stream.  Gradients are
+ * OVERWRITTEN, never accumulated into.  tests/test_gpu_workspace_poison.py runs every entry point on memory filled with NaN
+ * bytes, 0x7F bytes and the word 1 and asserts the bits of a run on zeroed memory.
+ * The exceptions are caller STATE, which a call reads as documented at its entry:
+ *   - the key/value cache rows BELOW pos (r4d_gpt2_decode_step_f32, the greedy entries); rows at and past pos are never read;
+ *   - the optimizer's m / v and sumsq[0] (r4d_adamw_step_f32, r4d_sumsq_accumulate_f32; sumsq[1..] is scratch);
+ *   - a training workspace BETWEEN r4d_gpt2_train_forward*_f32 and the backward of the same step (the saved activations);
+ *   - operands described as zero-padded by their entry (the rows of r4d_lm_head.wte_pad past vocab);
+ *   - the sticky range-guard word (r4d_set_range_flag) and the greedy loop state (r4d_greedy_state).
+ */
+
 /* Scratch bytes r4d_gpt2_encode_f32 needs for a [B,T] batch. */
 size_t r4d_gpt2_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t T);
 
