@@ -555,18 +555,28 @@ int r4d_gpt2_train_backward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt
                                        int32_t n_groups, const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts,
                                        const float* d_hidden_d, const r4d_train_dropout* dropout,
                                        void* workspace_d, size_t workspace_bytes, void* stream);
-/* Fused shifted cross entropy over logits_d f32 [N, ldV] (N = B*T rows, columns [V, ldV) padding, ldV % 4 == 0, V <= ldV <= 15872).
+/* Fused shifted cross entropy over logits_d f32 [N, ldV] (N = B*T rows, columns [V, ldV) padding, ldV % 4 == 0, V <= ldV).
  * Label of row (b, t): src[b, t + 1] with src = labels_d when given (int64 [B, T]) else ids_d (int64 [B, T]); row t = T - 1 has
  * none; a label outside [0, V) (ignore_index -100) is not counted; any other such label also raises R4D_RANGE_BAD_LABEL.  loss_d f32[1] <- mean over the counted rows (the count is
  * taken on the device: NaN when no row counts, as torch); logits_d is OVERWRITTEN with grad_scale * (softmax - onehot) / n_counted,
- * exact zeros in uncounted rows and pad columns.  Fixed-order sums: the same bits on every launch. */
+ * exact zeros in uncounted rows and pad columns.  Fixed-order sums: the same bits on every launch.
+ * ldV <= 15872: one launch, the row staged in LDS.  Larger ldV: the row is walked in column ranges of r4d_lm_head_chunk_rows(ldV)
+ * columns -- one launch per range folds its max and sum of exponentials into the row's running pair (an online softmax), one
+ * launch per range writes the gradient; the workspace (the same query, whatever ldV) carries the rows' (max, sum, label logit). */
 size_t r4d_lm_ce_workspace_bytes(int32_t N);
 int r4d_lm_ce_f32(float* logits_d, int32_t N, int32_t V, int32_t ldV, const int64_t* ids_d, const int64_t* labels_d, int32_t T,
                   float grad_scale, float* loss_d, void* workspace_d, size_t workspace_bytes, void* stream);
 /* The tied LM head operand: wte_pad_d f32 [ldV, d] = wte in rows [0, V), ZERO rows up to ldV (ldV = V rounded up to 128); the
  * optional planes of it (r4d_split3_planes_bf16 / r4d_split2_planes_f16 of wte_pad_d): w3_d [3][ldV][d] (transposed = 1) and
  * h2_d [ldV][d/32][2][32] for the logits GEMM, w3t_d [3][d][ldV] (wte_pad_d as a [K = ldV, N = d] weight, transposed = 0) for
- * dh = dlogits . wte.  Refresh them with the layer planes after every optimizer step. */
+ * dh = dlogits . wte.  Refresh them with the layer planes after every optimizer step.
+ * ldV > 15872 (the chunked head): with C = r4d_lm_head_chunk_rows(ldV), chunk k holds the rows [k C, k C + Ck) of wte_pad_d,
+ * Ck = min(C, ldV - k C) (the last chunk may be shorter; still a multiple of 128).  wte_pad_d and h2_d are row-major over the
+ * vocabulary rows and stay as above; w3_d and w3t_d are laid CHUNK BY CHUNK, chunk k at element offset 3 * k C * d:
+ *   w3_d  chunk k: [3][Ck][d] = r4d_split3_planes_bf16(wte_pad_d + k C d, K = d,  N = Ck, transposed = 1)
+ *   w3t_d chunk k: [3][d][Ck] = r4d_split3_planes_bf16(wte_pad_d + k C d, K = Ck, N = d,  transposed = 0)
+ * so the total sizes are unchanged.  ldV <= 15872 is the one-chunk case of the same rule (C = ldV). */
+int32_t r4d_lm_head_chunk_rows(int32_t ldV);       /* ldV when ldV <= 15872, else the library's chunk rows C (C % 128 == 0, C <= 15872) */
 typedef struct {
     const float* wte_pad;
     int32_t ldV;
@@ -578,7 +588,10 @@ typedef struct {
  * forward GEMM family of the current r4d_set_gemm_split3 mode) -> r4d_lm_ce_f32 -> dh = dlogits . wte (bf16x3 like every data
  * gradient) and dwte_head = dlogits^T . h (the weight-gradient GEMM) -> backward_hidden.  grads->wte = embedding scatter +
  * dwte_head, added in that fixed order.  loss_d f32[1] stays on the device.  grad_scale scales every gradient (1 / accumulation
- * steps), not the loss. */
+ * steps), not the loss.
+ * ldV > 15872: the logits exist one vocabulary chunk [B*T, C] at a time (r4d_lm_head above): a first sweep over the chunks forms
+ * the loss, a second forms each chunk's logits again and feeds dh and dwte_head.  The workspace holds one chunk of logits, so
+ * beyond dwte_head [ldV, d] it does not grow with V.  B*T * C and ldV * d must stay below 2^31 (R4D_ERR_INVALID otherwise). */
 size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t T, int32_t ldV);
 int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                                const r4d_lm_head* head, const int64_t* ids_d, int32_t B, int32_t T, float grad_scale, float* loss_d,

@@ -137,6 +137,7 @@ PROTOTYPES = {
                                                      POINTER(_P), POINTER(c_int32), POINTER(c_int32), _P, POINTER(TrainDropoutC), _P,
                                                      c_size_t, _P]),
     "r4d_lm_ce_workspace_bytes": (c_size_t, [c_int32]),
+    "r4d_lm_head_chunk_rows": (c_int32, [c_int32]),
     "r4d_lm_ce_f32": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P, c_int32, c_float, _P, _P, c_size_t, _P]),
     "r4d_gpt2_lm_train_workspace_bytes": (c_size_t, [POINTER(GPT2ConfigC), c_int32, c_int32, c_int32]),
     "r4d_gpt2_lm_train_step_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(GPT2GradsC), POINTER(LMHeadC), _P,

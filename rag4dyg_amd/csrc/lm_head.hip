@@ -12,6 +12,12 @@
 // planes of dh, I % 128 for gemm_s3tn) and the pad columns of the logits are exact zeros that the CE kernel also writes as
 // zero gradient, so the pad contributes nothing anywhere.  Every sum runs in a fixed order (wave butterflies, then sequential
 // over waves / threads; no float atomics): the same bits on every launch and rank, like losses.hip.
+//
+// ldV > CE_MAX_LDV (a vocabulary beyond what one LDS row holds): the CHUNKED head (lm_head_train_chunked below).  The rows of
+// wte_pad are cut into chunks of CE_CHUNK; the logits exist one chunk [N, Ck] at a time, a first sweep folds every chunk into the
+// row's running (max, sum of exponentials, label logit) -- an online softmax -- and a second sweep forms each chunk's logits again
+// (the same launch on the same bits), turns them into their gradient and feeds the two gradient GEMMs.  Scratch does not grow
+// with V; one extra logits GEMM is the price.
 #include <math.h>
 #include <string.h>
 #include "common.h"
@@ -20,6 +26,9 @@ namespace r4d {
 
 constexpr int CE_THREADS = 512;
 constexpr int CE_MAX_LDV = 15872;          // the row lives in LDS: 62 KB (+ the reduction words) of the 64 KB a workgroup gets
+constexpr int CE_CHUNK = 15872;            // vocabulary rows per chunk of the chunked head (a multiple of 128, <= CE_MAX_LDV); 8192 measured 2 % slower: DESIGN.md 7.1
+static_assert(CE_CHUNK % 128 == 0 && CE_CHUNK <= CE_MAX_LDV, "a chunk row is staged in LDS like a whole row");
+static inline int ce_chunk_rows(int ldV) { return ldV <= CE_MAX_LDV ? ldV : CE_CHUNK; }
 
 __device__ __forceinline__ float ce_wave_sum(float v) {
 #pragma unroll
@@ -125,6 +134,98 @@ __global__ __launch_bounds__(CE_THREADS) void lm_ce_kernel(float* __restrict__ l
     if (tid == 0) terms[r] = logf(se) - (reinterpret_cast<const float*>(row4)[lab] - mx);
 }
 
+// ---- the chunked form (ldV > CE_MAX_LDV): the same row, one column range [c0, c0 + cn) at a time
+// One workgroup per row.  The range is read ONCE into LDS; its max mc and sum of exponentials sc are folded into the row's running
+// pair as m' = max(m, mc), s = s exp(m - m') + sc exp(mc - m') (the range at c0 == 0 starts the pair); the label's logit is kept
+// when the label lies in the range.  `last`: terms[r] = log s - (x_label - m) (0 for an uncounted row).  Columns >= V are never
+// read as classes; a row without a counted label reads nothing.  x: column c0 of row 0 (the range's first element), ld: row stride.
+__global__ __launch_bounds__(CE_THREADS) void lm_ce_stats_kernel(const float* __restrict__ x, size_t ld, int c0, int cn, int V,
+                                                                 const int64_t* __restrict__ src, int T, float* __restrict__ m_run,
+                                                                 float* __restrict__ s_run, float* __restrict__ x_lab, int last,
+                                                                 float* __restrict__ terms) {
+    extern __shared__ float4 row4[];
+    __shared__ float red[CE_THREADS / 64];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lab = ce_label(src, r, T, V);
+    if (lab < 0) {
+        if (last && tid == 0) terms[r] = 0.f;
+        return;
+    }
+    const float4* g4 = reinterpret_cast<const float4*>(x + (size_t)r * ld);
+    const int n4 = cn >> 2;
+    float mx = -INFINITY;
+    for (int i = tid; i < n4; i += CE_THREADS) {
+        const float4 v = g4[i];
+        row4[i] = v;
+        const int c = c0 + 4 * i;
+        if (c < V) mx = fmaxf(mx, v.x);
+        if (c + 1 < V) mx = fmaxf(mx, v.y);
+        if (c + 2 < V) mx = fmaxf(mx, v.z);
+        if (c + 3 < V) mx = fmaxf(mx, v.w);
+    }
+    mx = ce_wave_max(mx);
+    if (lane == 0) red[wv] = mx;
+    __syncthreads();
+    mx = red[0];
+    for (int w = 1; w < CE_THREADS / 64; ++w) mx = fmaxf(mx, red[w]);
+    __syncthreads();                                                // red is reused below
+    float se = 0.f;
+    for (int i = tid; i < n4; i += CE_THREADS) {
+        const float4 v = row4[i];
+        const int c = c0 + 4 * i;
+        if (c < V) se += expf(v.x - mx);
+        if (c + 1 < V) se += expf(v.y - mx);
+        if (c + 2 < V) se += expf(v.z - mx);
+        if (c + 3 < V) se += expf(v.w - mx);
+    }
+    se = ce_wave_sum(se);
+    if (lane == 0) red[wv] = se;
+    __syncthreads();
+    if (tid != 0) return;
+    se = red[0];
+    for (int w = 1; w < CE_THREADS / 64; ++w) se += red[w];
+    float m = mx, sum = se;
+    if (c0 > 0) {                                                   // fold into the ranges before this one
+        const float m0 = m_run[r];
+        m = fmaxf(m0, mx);
+        sum = s_run[r] * expf(m0 - m) + se * expf(mx - m);
+    }
+    m_run[r] = m;
+    s_run[r] = sum;
+    float xl;
+    if (lab >= c0 && lab < c0 + cn) xl = reinterpret_cast<const float*>(row4)[lab - c0];
+    else xl = c0 > 0 ? x_lab[r] : 0.f;
+    x_lab[r] = xl;
+    if (last) terms[r] = logf(sum) - (xl - m);
+}
+
+// One workgroup per row: the range's logits are OVERWRITTEN with gscale * (exp(x - m) / s - onehot) / n_counted from the row's
+// final (m, s); exact zeros in the columns >= V and in rows without a counted label.
+__global__ __launch_bounds__(CE_THREADS) void lm_ce_grad_kernel(float* __restrict__ x, size_t ld, int c0, int cn, int V,
+                                                                const int64_t* __restrict__ src, int T, float gscale,
+                                                                const int* __restrict__ count, const float* __restrict__ m_run,
+                                                                const float* __restrict__ s_run) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    float4* g4 = reinterpret_cast<float4*>(x + (size_t)r * ld);
+    const int n4 = cn >> 2;
+    const int lab = ce_label(src, r, T, V);
+    if (lab < 0) {
+        for (int i = tid; i < n4; i += CE_THREADS) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float mx = m_run[r], inv_se = 1.f / s_run[r], scale = gscale / (float)(*count);
+    for (int i = tid; i < n4; i += CE_THREADS) {
+        const float4 v = g4[i];
+        const int c = c0 + 4 * i;
+        float4 o;
+        o.x = c < V ? (expf(v.x - mx) * inv_se - (c == lab ? 1.f : 0.f)) * scale : 0.f;
+        o.y = c + 1 < V ? (expf(v.y - mx) * inv_se - (c + 1 == lab ? 1.f : 0.f)) * scale : 0.f;
+        o.z = c + 2 < V ? (expf(v.z - mx) * inv_se - (c + 2 == lab ? 1.f : 0.f)) * scale : 0.f;
+        o.w = c + 3 < V ? (expf(v.w - mx) * inv_se - (c + 3 == lab ? 1.f : 0.f)) * scale : 0.f;
+        g4[i] = o;
+    }
+}
+
 // second stage: thread t sums rows t, t + 1024, ... in order, then a fixed tree over the threads; loss = sum / count
 __global__ __launch_bounds__(1024) void lm_ce_reduce_kernel(const float* __restrict__ terms, int N, const int* __restrict__ count,
                                                             float* __restrict__ loss) {
@@ -153,7 +254,13 @@ __global__ __launch_bounds__(256) void add_inplace_kernel(float4* __restrict__ y
 }
 
 static inline size_t up64(size_t n) { return (n + 63) / 64 * 64; }
-static size_t ce_ws_floats(int N) { return up64((size_t)N) + 64; }
+// terms [N], the count word; the chunked form adds the rows' running (m, s, x_label)
+static size_t ce_ws_floats(int N, bool chunked) { return up64((size_t)N) * (chunked ? 4 : 1) + 64; }
+struct CeWs { float* terms; int* count; float* m; float* s; float* xl; };
+static CeWs ce_ws(float* ws, int N) {
+    const size_t n = up64((size_t)N);
+    return {ws, reinterpret_cast<int*>(ws + n), ws + n + 64, ws + 2 * n + 64, ws + 3 * n + 64};
+}
 
 static int lm_ce(float* logits, int N, int V, int ldV, const int64_t* src, int T, float gscale, float* loss, float* ws, hipStream_t s) {
     int* count = reinterpret_cast<int*>(ws + up64((size_t)N));
@@ -170,10 +277,57 @@ static int lm_ce(float* logits, int N, int V, int ldV, const int64_t* src, int T
     return R4D_OK;
 }
 
+// the pieces of the chunked form, in the order the callers issue them: count; stats per range (ascending, the range that
+// holds column V - 1 with last = true); reduce; grad per range
+static int launch_ce_count(const int64_t* src, int N, int T, int V, const CeWs& w, hipStream_t s) {
+    hipLaunchKernelGGL(lm_ce_count_kernel, dim3(1), dim3(1024), 0, s, src, N, T, V, w.count, g_range_flag);
+    R4D_CHECK_LAUNCH("lm_ce_count");
+    return R4D_OK;
+}
+static int launch_ce_stats(const float* x, size_t ld, int c0, int cn, int N, int V, const int64_t* src, int T, const CeWs& w, bool last,
+                           hipStream_t s) {
+    const int real = (V - c0 < cn ? V - c0 : cn);
+    ProfScope prof(PK_LM_CE, (double)N * real * 4.0, s);
+    hipLaunchKernelGGL(lm_ce_stats_kernel, dim3(N), dim3(CE_THREADS), (size_t)cn * sizeof(float), s, x, ld, c0, cn, V, src, T, w.m, w.s,
+                       w.xl, last ? 1 : 0, w.terms);
+    R4D_CHECK_LAUNCH("lm_ce_stats");
+    return R4D_OK;
+}
+static int launch_ce_reduce(int N, const CeWs& w, float* loss, hipStream_t s) {
+    hipLaunchKernelGGL(lm_ce_reduce_kernel, dim3(1), dim3(1024), 0, s, w.terms, N, w.count, loss);
+    R4D_CHECK_LAUNCH("lm_ce_reduce");
+    return R4D_OK;
+}
+static int launch_ce_grad(float* x, size_t ld, int c0, int cn, int N, int V, const int64_t* src, int T, float gscale, const CeWs& w,
+                          hipStream_t s) {
+    ProfScope prof(PK_LM_CE, 2.0 * N * (double)cn * 4.0, s);
+    hipLaunchKernelGGL(lm_ce_grad_kernel, dim3(N), dim3(CE_THREADS), 0, s, x, ld, c0, cn, V, src, T, gscale, w.count, w.m, w.s);
+    R4D_CHECK_LAUNCH("lm_ce_grad");
+    return R4D_OK;
+}
+
+// r4d_lm_ce_f32 on a materialised [N, ldV] matrix with ldV > CE_MAX_LDV: the two kernels over the column ranges, row stride ldV
+static int lm_ce_chunked(float* logits, int N, int V, int ldV, const int64_t* src, int T, float gscale, float* loss, float* ws,
+                         hipStream_t s) {
+    const CeWs w = ce_ws(ws, N);
+    const int C = CE_CHUNK;
+    int rc;
+    if ((rc = launch_ce_count(src, N, T, V, w, s))) return rc;
+    for (int c0 = 0; c0 < V; c0 += C) {                      // ranges past V hold no class
+        const int cn = ldV - c0 < C ? ldV - c0 : C;
+        if ((rc = launch_ce_stats(logits + c0, (size_t)ldV, c0, cn, N, V, src, T, w, c0 + C >= V, s))) return rc;
+    }
+    if ((rc = launch_ce_reduce(N, w, loss, s))) return rc;
+    for (int c0 = 0; c0 < ldV; c0 += C) {
+        const int cn = ldV - c0 < C ? ldV - c0 : C;
+        if ((rc = launch_ce_grad(logits + c0, (size_t)ldV, c0, cn, N, V, src, T, gscale, w, s))) return rc;
+    }
+    return R4D_OK;
+}
+
 int check_ce(int N, int V, int ldV, int T) {
     R4D_REQUIRE(N >= 1 && T >= 1 && N % T == 0, "lm_ce: N=%d is not a multiple of T=%d", N, T);
-    R4D_REQUIRE(V >= 1 && ldV >= V && ldV % 4 == 0 && ldV <= CE_MAX_LDV, "lm_ce: V=%d ldV=%d (V <= ldV <= %d, ldV %% 4 == 0)", V, ldV,
-                CE_MAX_LDV);
+    R4D_REQUIRE(V >= 1 && ldV >= V && ldV % 4 == 0, "lm_ce: V=%d ldV=%d (V <= ldV, ldV %% 4 == 0)", V, ldV);
     return R4D_OK;
 }
 
@@ -183,8 +337,12 @@ LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
     size_t off = 0;
     auto take = [&](size_t n) { const size_t o = off; off += up64(n); return o; };
     t.train = take(gpt2_train_workspace_floats(cfg, 1, &B, &T));
-    t.h = take(N * d); t.logits = take(N * ldV); t.dh = take(N * d); t.dwte = take((size_t)ldV * d);
-    t.tn = take(gemm_tn_scratch_floats(ldV, (int)d, (int)N)); t.ce = take(ce_ws_floats((int)N));
+    // ldV > CE_MAX_LDV: the logits slot and the weight-gradient scratch hold ONE chunk (the full one or the shorter last one)
+    const int C = ce_chunk_rows(ldV), tail = ldV % C;
+    size_t tn = gemm_tn_scratch_floats(C, (int)d, (int)N);
+    if (tail) { const size_t tn2 = gemm_tn_scratch_floats(tail, (int)d, (int)N); tn = tn2 > tn ? tn2 : tn; }
+    t.h = take(N * d); t.logits = take(N * C); t.dh = take(N * d); t.dwte = take((size_t)ldV * d);
+    t.tn = take(tn); t.ce = take(ce_ws_floats((int)N, ldV > CE_MAX_LDV));
     t.total = off;
     return t;
 }
@@ -197,11 +355,64 @@ int launch_add_inplace(float* y, const float* x, long long n, hipStream_t s) {
     return R4D_OK;
 }
 
+// The chunked head (ldV > CE_MAX_LDV).  Chunk k covers the rows [k C, k C + Ck) of wte_pad; `logits` holds ONE chunk [N, Ck].
+//   sweep 1, k ascending:  logits_k = h . wte_k^T (the forward GEMM family of the mode), lm_ce_stats
+//   loss = reduce(terms);  dh == dwte == NULL (the evaluation loss): done
+//   sweep 2, k ascending:  the same GEMM again (deterministic kernels: the same bits), lm_ce_grad, dh (+)= dlogits_k . wte_k through
+//                          the residual epilogue (k == 0 has none), dwte[k C : k C + Ck] = dlogits_k^T . h
+// The planes are laid chunk by chunk (include/r4d.h: r4d_lm_head), so every GEMM is an ordinary aligned one on a contiguous
+// operand; the chunk order is fixed, so dh carries the same bits on every launch.
+static int lm_head_train_chunked(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale,
+                                 float* loss, float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws_, hipStream_t s) {
+    const int ldV = head->ldV, C = CE_CHUNK;
+    R4D_REQUIRE((long long)N * C < (1ll << 31) && (long long)ldV * d < (1ll << 31),
+                "lm head: N=%d rows x %d chunk columns or ldV=%d x d=%d reaches 2^31 elements (32-bit index arithmetic)", N, C, ldV, d);
+    const CeWs w = ce_ws(ce_ws_, N);
+    int rc;
+    auto chunk_logits = [&](int c0, int cn) {
+        const size_t o = (size_t)c0 * d;
+        return conv1d(h, nullptr, head->wte_pad + o, nullptr, nullptr, N, d, cn, EPI_NONE, logits, s, nullptr, false,
+                      head->w3 ? head->w3 + 3 * o : nullptr, head->h2 ? head->h2 + 2 * o : nullptr);
+    };
+    if ((rc = launch_ce_count(src, N, T, V, w, s))) return rc;
+    for (int c0 = 0; c0 < ldV; c0 += C) {
+        const int cn = ldV - c0 < C ? ldV - c0 : C;
+        if ((rc = chunk_logits(c0, cn))) return rc;
+        if ((rc = launch_ce_stats(logits, (size_t)cn, c0, cn, N, V, src, T, w, c0 + C >= ldV, s))) return rc;
+    }
+    if ((rc = launch_ce_reduce(N, w, loss, s))) return rc;
+    if (!dh && !dwte) return R4D_OK;
+    for (int c0 = 0; c0 < ldV; c0 += C) {
+        const int cn = ldV - c0 < C ? ldV - c0 : C;
+        const size_t o = (size_t)c0 * d;
+        if ((rc = chunk_logits(c0, cn))) return rc;
+        if ((rc = launch_ce_grad(logits, (size_t)cn, c0, cn, N, V, src, T, gscale, w, s))) return rc;
+        const int epi = c0 ? EPI_RESIDUAL : EPI_NONE;
+        if (dh && head->w3t && g_gemm_split3 && gemm_s3_supported(N, cn, d)) {
+            S3Args a;
+            memset(&a, 0, sizeof(a));
+            a.A = logits; a.planes = head->w3t + 3 * o; a.C = dh; a.resid = c0 ? dh : nullptr;
+            a.M = N; a.N = d; a.K = cn; a.lda = cn; a.ldc = d; a.ldr = d; a.epilogue = epi;
+            if ((rc = launch_gemm_s3(a, s))) return rc;
+        } else if (dh) {
+            GemmArgs g;
+            memset(&g, 0, sizeof(g));
+            g.A = logits; g.B = head->wte_pad + o; g.C = dh; g.resid = c0 ? dh : nullptr;
+            g.M = N; g.N = d; g.K = cn; g.lda = cn; g.ldb = d; g.ldc = d; g.ldr = d;
+            g.b_trans = 0; g.b_rows = cn; g.nbatch = 1; g.nb1 = 1; g.epilogue = epi; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+            if ((rc = launch_gemm_f32(g, s))) return rc;
+        }
+        if (dwte && (rc = launch_gemm_f32_tn(logits, h, dwte + o, cn, d, N, cn, d, tn_scratch, s))) return rc;
+    }
+    return R4D_OK;
+}
+
 // The head of both training steps (the LM step below, the RAG step of rag_train.hip): logits on the mode's forward GEMM family,
 // the cross entropy, then dh = dlogits . wte_pad (bf16x3 like every data gradient) and dwte = dlogits^T . h
 int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale, float* loss,
                   float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s) {
     const int ldV = head->ldV;
+    if (ldV > CE_MAX_LDV) return lm_head_train_chunked(h, N, V, d, head, src, T, gscale, loss, logits, dh, dwte, tn_scratch, ce_ws, s);
     int rc;
     // logits = h . wte_pad^T: wte_pad [ldV, d] IS the k-contiguous [N, K] operand (planes when the mode has them)
     if ((rc = conv1d(h, nullptr, head->wte_pad, nullptr, nullptr, N, d, ldV, EPI_NONE, logits, s, nullptr, false, head->w3, head->h2)))
@@ -249,7 +460,9 @@ int r4d_gpt2_train_backward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt
                                (hipStream_t)stream);
 }
 
-size_t r4d_lm_ce_workspace_bytes(int32_t N) { return N > 0 ? ce_ws_floats(N) * sizeof(float) : 0; }
+size_t r4d_lm_ce_workspace_bytes(int32_t N) { return N > 0 ? ce_ws_floats(N, true) * sizeof(float) : 0; }
+
+int32_t r4d_lm_head_chunk_rows(int32_t ldV) { return ldV > 0 ? ce_chunk_rows(ldV) : 0; }
 
 int r4d_lm_ce_f32(float* logits_d, int32_t N, int32_t V, int32_t ldV, const int64_t* ids_d, const int64_t* labels_d, int32_t T,
                   float grad_scale, float* loss_d, void* workspace_d, size_t workspace_bytes, void* stream) {
@@ -261,6 +474,7 @@ int r4d_lm_ce_f32(float* logits_d, int32_t N, int32_t V, int32_t ldV, const int6
         set_error("lm_ce: workspace too small");
         return R4D_ERR_WORKSPACE;
     }
+    if (ldV > CE_MAX_LDV) return lm_ce_chunked(logits_d, N, V, ldV, src, T, grad_scale, loss_d, (float*)workspace_d, (hipStream_t)stream);
     return lm_ce(logits_d, N, V, ldV, src, T, grad_scale, loss_d, (float*)workspace_d, (hipStream_t)stream);
 }
 

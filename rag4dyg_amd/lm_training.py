@@ -26,17 +26,29 @@ def padded_vocab(V):
     return (int(V) + 127) // 128 * 128
 
 
+def head_chunks(ldV, chunk_rows):
+    """The vocabulary chunks of the LM head as (first row, rows): ``[k C, min((k + 1) C, ldV))`` for ``C = chunk_rows`` (the
+    library's ``r4d_lm_head_chunk_rows(ldV)``: ldV itself up to 15,872 rows, a fixed multiple of 128 beyond).  The last chunk may
+    be shorter; with ldV a multiple of 128 every chunk is one."""
+    ldV, C = int(ldV), int(chunk_rows)
+    if ldV < 1 or C < 1 or ldV % 128 or (C % 128 and C != ldV):
+        raise ValueError(f"head_chunks: ldV={ldV} chunk_rows={C} (multiples of 128 wanted)")
+    return [(c0, min(C, ldV - c0)) for c0 in range(0, ldV, C)]
+
+
 class HeadOperand:
     """The padded LM-head operand ``pad`` [ldV, d] (the head weight in rows [0, V), zero rows up to ldV) and its GEMM planes, as
-    ``r4d_lm_head`` describes them: bf16x3 planes when the split modes are on, f16x2 planes in f16x2 mode.  Shared by the
-    SimpleDyG and the RAG-generator training steps; ``refresh(weight)`` after every change of the head weight."""
+    ``r4d_lm_head`` describes them: bf16x3 planes when the split modes are on, f16x2 planes in f16x2 mode.  Beyond 15,872 rows the
+    bf16x3 planes are laid chunk by chunk (``head_chunks``: the chunked head of ``csrc/lm_head.hip``); the buffers keep their
+    sizes.  Shared by the SimpleDyG and the RAG-generator training steps; ``refresh(weight)`` after every change of the head
+    weight."""
 
     def __init__(self, V, d, device, use_s3, use_h2):
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
         self.pad = torch.zeros(self.ldV, self.d, dtype=torch.float32, device=device)
         self._w3 = self._w3t = self._h2 = None
         if use_s3 and self.d % 32 == 0:
-            self._w3 = torch.empty(3, self.ldV, self.d, dtype=torch.int16, device=device)
+            self._w3 = torch.empty(3, self.ldV, self.d, dtype=torch.int16, device=device)       # one chunk: this shape; else per chunk
             self._w3t = torch.empty(3, self.d, self.ldV, dtype=torch.int16, device=device)
             if use_h2:
                 self._h2 = torch.empty(self.ldV, self.d // 32, 2, 32, dtype=torch.int16, device=device)
@@ -48,8 +60,10 @@ class HeadOperand:
             lib = _lib.load()
             stream = torch.cuda.current_stream().cuda_stream
             p = self.pad.data_ptr()
-            _lib.check(lib.r4d_split3_planes_bf16(p, self.d, self.ldV, 1, self._w3.data_ptr(), stream), "split3_planes")
-            _lib.check(lib.r4d_split3_planes_bf16(p, self.ldV, self.d, 0, self._w3t.data_ptr(), stream), "split3_planes")
+            for c0, cn in head_chunks(self.ldV, lib.r4d_lm_head_chunk_rows(self.ldV)):
+                w, planes = p + 4 * c0 * self.d, 2 * 3 * c0 * self.d          # byte offsets of the chunk's rows / its planes
+                _lib.check(lib.r4d_split3_planes_bf16(w, self.d, cn, 1, self._w3.data_ptr() + planes, stream), "split3_planes")
+                _lib.check(lib.r4d_split3_planes_bf16(w, cn, self.d, 0, self._w3t.data_ptr() + planes, stream), "split3_planes")
             if self._h2 is not None:
                 _lib.check(lib.r4d_split2_planes_f16(p, self.d, self.ldV, 1, self._h2.data_ptr(), stream), "split2_planes")
 

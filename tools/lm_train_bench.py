@@ -2,6 +2,9 @@
 """SimpleDyG LM-training step (``LMTrainer.step``: forward, LM head, shifted cross entropy, backward) at the reference's script
 shapes: ms per step and tokens/s, the per-class breakdown of ``r4d_profile_*``, the CE kernel's bytes / time against the 8 TB/s HBM
 spec, the head's share of the step (step minus forward_hidden + backward_hidden timed alone; eval mode, no dropout), and as a yardstick the same head (h . wte^T, F.cross_entropy, backward) in torch autograd.
+``wikiv2_v50k`` is the wikiv2 model on a 50,000-token vocabulary: the chunked head (``csrc/lm_head.hip``, ldV > 15,872).  Its record
+adds the chunk rows, the bytes the materialised logits alone would take next to the step's workspace, and the time of ONE sweep of
+logits GEMMs over the chunks (the GEMM the chunked head runs twice) with its share of the step.
 
     python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute]
 """
@@ -16,7 +19,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = {"uci13": dict(L=6, H=8, d=768, V=1800, B=32, Ts=(128, 340)),
-          "wikiv2": dict(L=2, H=6, d=768, V=8814, B=32, Ts=(128, 512))}
+          "wikiv2": dict(L=2, H=6, d=768, V=8814, B=32, Ts=(128, 512)),
+          "wikiv2_v50k": dict(L=2, H=6, d=768, V=50000, B=32, Ts=(128,))}
 HBM_BPS = 8e12
 
 
@@ -41,6 +45,24 @@ def _time(fn, steps, warmup):
     b.record()
     b.synchronize()
     return a.elapsed_time(b) / steps
+
+
+def _logits_sweep(tr, h):
+    """One sweep of the chunked head's logits GEMMs (``h . wte_k^T`` per chunk, the arithmetic of the current mode) as a callable."""
+    from rag4dyg_amd import _lib, ops
+    from rag4dyg_amd.lm_training import head_chunks
+    head, d = tr.head, tr.d
+    chunks = head_chunks(head.ldV, _lib.load().r4d_lm_head_chunk_rows(head.ldV))
+    mode = ops.gemm_mode()
+    if mode == "f16x2" and head._h2 is not None:
+        parts = [head._h2[c0:c0 + cn] for c0, cn in chunks]
+        return lambda: [ops.conv1d_h2(h, p, None) for p in parts]
+    if mode != "f32" and head._w3 is not None:
+        flat = head._w3.view(-1)
+        parts = [flat[3 * c0 * d:3 * (c0 + cn) * d].view(3, cn, d) for c0, cn in chunks]
+        return lambda: [ops.conv1d_s3(h, p, None) for p in parts]
+    parts = [(head.pad[c0:c0 + cn].t().contiguous(), head.pad[c0:c0 + cn]) for c0, cn in chunks]
+    return lambda: [ops.conv1d(h, w, None, "none", None, wt) for w, wt in parts]
 
 
 def main():
@@ -93,7 +115,8 @@ def main():
             lib.r4d_profile_enable(0)
             N, ldV = B * T, tr.ldV
             ce = prof.get("lm_ce", {})
-            ce_bytes = 2.0 * N * V * 4
+            chunked = ldV > 15872                                  # two kernels per chunk: the logits are read twice, written once
+            ce_bytes = (3.0 if chunked else 2.0) * N * V * 4
             head_flop = 3 * 2.0 * N * ldV * d
             # the step without its head: forward_hidden + backward_hidden alone (same workspace layout); head = step - body
             c, w, g, keep = tr.enc._structs()
@@ -134,6 +157,10 @@ def main():
                        head_flop=head_flop, body_ms=body_ms, head_ms=ms - body_ms, head_share=(ms - body_ms) / ms,
                        head_tflops=head_flop / ((ms - body_ms) / 1e3) / 1e12, torch_head_ms=torch_ms, profiled_ms=total_prof,
                        classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"]) for k, v in sorted(head_like.items(), key=lambda kv: -kv[1]["ms"])})
+            if chunked:
+                sweep_ms = _time(_logits_sweep(tr, h), a.steps, a.warmup)
+                rec.update(chunk_rows=int(lib.r4d_lm_head_chunk_rows(ldV)), materialised_logits_bytes=N * ldV * 4,
+                           logits_sweep_ms=sweep_ms, extra_gemm_share=sweep_ms / ms)
             print(json.dumps(rec))
             del h, dh, hr, wr
 
