@@ -217,18 +217,22 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
                         hipStream_t s, const SpliceIn* sp = nullptr, float* d_fused = nullptr);
+// The data-gradient GEMM (Conv1D dx = dy . W^T with b_trans = 1, head dh = dlogits . wte_pad with b_trans = 0): on the bf16x3
+// planes `w3t` when the mode and the shape allow, else exact f32 on `w`; optional residual, optional fused gelu_new' (train.hip)
+int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, int b_trans, int M, int n_out, int k, float* C,
+                   const float* resid, const float* gelu_pre, hipStream_t s);
 int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, const float* wte, const float* wpe, int vocab, int B,
                            int T, int d, const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s);
 
 // ------------------------------------------------------------------ lm_head.hip (the LM head of the training steps)
 struct LMLayout { size_t train, h, logits, dh, dwte, tn, ce, total; };
 LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV);
-int check_ce(int N, int V, int ldV, int T);
-// logits = h . wte_pad^T, loss and dlogits (in place; label of row r: src[r + 1] within a sequence of T rows), then -- when `dh`
-// is given -- dh = dlogits . wte_pad and -- when `dwte` is given -- dwte [ldV, d] = dlogits^T . h
-int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale, float* loss,
-                  float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s);
-int launch_add_inplace(float* y, const float* x, long long n, hipStream_t s);      // y += x (n % 4 == 0, 16-byte aligned)
+// One training step through the LM head (the bodies of r4d_gpt2_lm_train_step_f32 and r4d_rag_train_step_f32 behind their
+// argument checks): forward -> head (loss, dh, dwte) -> backward -> head gradient per `head_mode` (R4D_HEAD_GRAD_*)
+int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
+                    const r4d_lm_head* head, int head_mode, float* head_grad, const int64_t* ids_d, const SpliceIn* sp, int B, int T,
+                    float gscale, float* loss, float* d_fused, float* hidden_out, const r4d_train_dropout* dropout, void* workspace_d,
+                    size_t workspace_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------ topk.hip
 // rows x n values -> rows x k best (value, global index), canonical order; `counters_zeroed`: the caller already cleared

@@ -4,7 +4,7 @@
 //
 //   logits   [N, ldV] = h_lnf . wte_pad^T          the forward GEMM family of the mode (f16x2 / bf16x3 / exact f32), conv1d
 //   loss, dlogits (in place)                       lm_ce_kernel: one workgroup per row, the row read once into LDS, written once
-//   dh       [N, d]   = dlogits . wte_pad          bf16x3 like every data gradient (train.hip: bwd_data)
+//   dh       [N, d]   = dlogits . wte_pad          bf16x3 like every data gradient (train.hip: data_grad_gemm)
 //   dwte_head [ldV, d] = dlogits^T . h_lnf         the weight-gradient GEMM (launch_gemm_f32_tn: gemm_s3tn in the split modes)
 //   grads->wte = embedding scatter (fixed point, train_ops.hip) + dwte_head[0:V]    in that order
 //
@@ -325,7 +325,7 @@ static int lm_ce_chunked(float* logits, int N, int V, int ldV, const int64_t* sr
     return R4D_OK;
 }
 
-int check_ce(int N, int V, int ldV, int T) {
+static int check_ce(int N, int V, int ldV, int T) {
     R4D_REQUIRE(N >= 1 && T >= 1 && N % T == 0, "lm_ce: N=%d is not a multiple of T=%d", N, T);
     R4D_REQUIRE(V >= 1 && ldV >= V && ldV % 4 == 0, "lm_ce: V=%d ldV=%d (V <= ldV, ldV %% 4 == 0)", V, ldV);
     return R4D_OK;
@@ -347,7 +347,8 @@ LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
     return t;
 }
 
-int launch_add_inplace(float* y, const float* x, long long n, hipStream_t s) {
+// y += x (n % 4 == 0, 16-byte aligned)
+static int launch_add_inplace(float* y, const float* x, long long n, hipStream_t s) {
     const long long n4 = n / 4;
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(y),
                        reinterpret_cast<const float4*>(x), n4);
@@ -387,30 +388,18 @@ static int lm_head_train_chunked(const float* h, int N, int V, int d, const r4d_
         const size_t o = (size_t)c0 * d;
         if ((rc = chunk_logits(c0, cn))) return rc;
         if ((rc = launch_ce_grad(logits, (size_t)cn, c0, cn, N, V, src, T, gscale, w, s))) return rc;
-        const int epi = c0 ? EPI_RESIDUAL : EPI_NONE;
-        if (dh && head->w3t && g_gemm_split3 && gemm_s3_supported(N, cn, d)) {
-            S3Args a;
-            memset(&a, 0, sizeof(a));
-            a.A = logits; a.planes = head->w3t + 3 * o; a.C = dh; a.resid = c0 ? dh : nullptr;
-            a.M = N; a.N = d; a.K = cn; a.lda = cn; a.ldc = d; a.ldr = d; a.epilogue = epi;
-            if ((rc = launch_gemm_s3(a, s))) return rc;
-        } else if (dh) {
-            GemmArgs g;
-            memset(&g, 0, sizeof(g));
-            g.A = logits; g.B = head->wte_pad + o; g.C = dh; g.resid = c0 ? dh : nullptr;
-            g.M = N; g.N = d; g.K = cn; g.lda = cn; g.ldb = d; g.ldc = d; g.ldr = d;
-            g.b_trans = 0; g.b_rows = cn; g.nbatch = 1; g.nb1 = 1; g.epilogue = epi; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-            if ((rc = launch_gemm_f32(g, s))) return rc;
-        }
+        if (dh && (rc = data_grad_gemm(logits, head->wte_pad + o, head->w3t ? head->w3t + 3 * o : nullptr, 0, N, d, cn, dh,
+                                       c0 ? dh : nullptr, nullptr, s))) return rc;
         if (dwte && (rc = launch_gemm_f32_tn(logits, h, dwte + o, cn, d, N, cn, d, tn_scratch, s))) return rc;
     }
     return R4D_OK;
 }
 
-// The head of both training steps (the LM step below, the RAG step of rag_train.hip): logits on the mode's forward GEMM family,
-// the cross entropy, then dh = dlogits . wte_pad (bf16x3 like every data gradient) and dwte = dlogits^T . h
-int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale, float* loss,
-                  float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s) {
+// The head of the training step: logits = h . wte_pad^T on the mode's forward GEMM family, loss and dlogits (in place; label of
+// row r: src[r + 1] within a sequence of T rows), then -- when `dh` is given -- dh = dlogits . wte_pad (bf16x3 like every data
+// gradient) and -- when `dwte` is given -- dwte [ldV, d] = dlogits^T . h
+static int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale,
+                         float* loss, float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s) {
     const int ldV = head->ldV;
     if (ldV > CE_MAX_LDV) return lm_head_train_chunked(h, N, V, d, head, src, T, gscale, loss, logits, dh, dwte, tn_scratch, ce_ws, s);
     int rc;
@@ -419,22 +408,45 @@ int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, 
         return rc;
     if ((rc = lm_ce(logits, N, V, ldV, src, T, gscale, loss, ce_ws, s))) return rc;
     // dh = dlogits . wte_pad  (K = ldV: the pad columns of dlogits are zero)
-    if (dh && head->w3t && g_gemm_split3 && gemm_s3_supported(N, ldV, d)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = logits; a.planes = head->w3t; a.C = dh; a.M = N; a.N = d; a.K = ldV; a.lda = ldV; a.ldc = d; a.ldr = d;
-        a.epilogue = EPI_NONE;
-        if ((rc = launch_gemm_s3(a, s))) return rc;
-    } else if (dh) {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = logits; g.B = head->wte_pad; g.C = dh;
-        g.M = N; g.N = d; g.K = ldV; g.lda = ldV; g.ldb = d; g.ldc = d;
-        g.b_trans = 0; g.b_rows = ldV; g.nbatch = 1; g.nb1 = 1; g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-        if ((rc = launch_gemm_f32(g, s))) return rc;
-    }
+    if (dh && (rc = data_grad_gemm(logits, head->wte_pad, head->w3t, 0, N, d, ldV, dh, nullptr, nullptr, s))) return rc;
     // dwte [ldV, d] = dlogits^T . h
     return dwte ? launch_gemm_f32_tn(logits, h, dwte, ldV, d, N, ldV, d, tn_scratch, s) : R4D_OK;
+}
+
+// One training step through the head, behind the argument checks of its two exports (`who`: the export's name in a message):
+// training forward (train.hip) -> lm_head_train on `ids` -> backward -> the head's weight gradient to its place.  The LM step is
+// the RAG step without a splice (`sp` == nullptr), with a tied head and no optional output.  No gradient output at all (`grads`
+// and `d_fused` NULL): forward and loss only.
+int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
+                    const r4d_lm_head* head, int head_mode, float* head_grad, const int64_t* ids_d, const SpliceIn* sp, int B, int T,
+                    float gscale, float* loss, float* d_fused, float* hidden_out, const r4d_train_dropout* dropout, void* workspace_d,
+                    size_t workspace_bytes, hipStream_t s) {
+    const int V = cfg->vocab, ldV = head->ldV, d = cfg->n_embd, N = B * T;
+    int rc = check_ce(N, V, ldV, T);
+    if (rc) return rc;
+    const LMLayout t = lm_layout(cfg, B, T, ldV);
+    if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
+        set_error("%s: workspace %zu bytes < required %zu", who, workspace_bytes, t.total * sizeof(float));
+        return R4D_ERR_WORKSPACE;
+    }
+    float* ws = (float*)workspace_d;
+    float *h = ws + t.h, *logits = ws + t.logits, *dh = ws + t.dh, *dwte = ws + t.dwte;
+    const size_t train_bytes = (t.h - t.train) * sizeof(float);
+    const int64_t* const ids[1] = {ids_d};
+    const bool backward = grads || d_fused;
+    const bool head_w = backward && head_mode != R4D_HEAD_GRAD_NONE;
+    if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &T, nullptr, h, dropout, ws + t.train, train_bytes, s, sp))) return rc;
+    if (hidden_out) R4D_HIP(hipMemcpyAsync(hidden_out, h, (size_t)N * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = lm_head_train(h, N, V, d, head, ids_d, T, gscale, loss, logits, backward ? dh : nullptr, head_w ? dwte : nullptr,
+                            ws + t.tn, ws + t.ce, s))) return rc;
+    if (!backward) return R4D_OK;
+    if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &T, nullptr, dh, dropout, ws + t.train, train_bytes, s, sp, d_fused)))
+        return rc;
+    if (head_mode == R4D_HEAD_GRAD_UNTIED)
+        R4D_HIP(hipMemcpyAsync(head_grad, dwte, (size_t)V * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else if (head_mode == R4D_HEAD_GRAD_TIED)                       // tied weight: the token scatter (written by the backward) + the
+        return launch_add_inplace(grads->wte, dwte, (long long)V * d, s);   // head's part, in this fixed order
+    return R4D_OK;
 }
 
 }  // namespace r4d
@@ -486,28 +498,11 @@ size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, 
 int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                                const r4d_lm_head* head, const int64_t* ids_d, int32_t B, int32_t T, float grad_scale, float* loss_d,
                                const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
     R4D_REQUIRE(cfg && w && grads && grads->wte && head && head->wte_pad && ids_d && loss_d, "lm train step: null pointer");
-    const int V = cfg->vocab, ldV = head->ldV, d = cfg->n_embd;
-    R4D_REQUIRE(B >= 1 && T >= 1 && ldV % 128 == 0 && ldV >= V, "lm train step: B=%d T=%d ldV=%d (a multiple of 128 >= V=%d)", B, T,
-                ldV, V);
-    int rc = check_ce(B * T, V, ldV, T);
-    if (rc) return rc;
-    const LMLayout t = lm_layout(cfg, B, T, ldV);
-    if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
-        set_error("lm train step: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
-        return R4D_ERR_WORKSPACE;
-    }
-    float* ws = (float*)workspace_d;
-    const int N = B * T;
-    float *h = ws + t.h, *logits = ws + t.logits, *dh = ws + t.dh, *dwte = ws + t.dwte;
-    const size_t train_bytes = (t.h - t.train) * sizeof(float);
-    const int64_t* const ids[1] = {ids_d};
-    if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &T, nullptr, h, dropout, ws + t.train, train_bytes, s))) return rc;
-    if ((rc = lm_head_train(h, N, V, d, head, ids_d, T, grad_scale, loss_d, logits, dh, dwte, ws + t.tn, ws + t.ce, s))) return rc;
-    if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &T, nullptr, dh, dropout, ws + t.train, train_bytes, s))) return rc;
-    // tied weight: the embedding scatter (written by the backward) + the head's part, in this fixed order
-    return launch_add_inplace(grads->wte, dwte, (long long)V * d, s);
+    R4D_REQUIRE(B >= 1 && T >= 1 && head->ldV % 128 == 0 && head->ldV >= cfg->vocab,
+                "lm train step: B=%d T=%d ldV=%d (a multiple of 128 >= V=%d)", B, T, head->ldV, cfg->vocab);
+    return head_train_step("lm train step", cfg, w, grads, head, R4D_HEAD_GRAD_TIED, nullptr, ids_d, nullptr, B, T, grad_scale, loss_d,
+                           nullptr, nullptr, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // the one-layer graph-pooling fusion.
 //
 //   splice_embed_ln4_kernel   x_in[b, t] = (aug_ids[b, t] == -100 ? fused[b, t - 2] : wte[aug_ids[b, t]]) + wpe[t]; ln_1 of it
-//   r4d_rag_train_step_f32    training forward (train.hip) -> LM head, CE on aug_ids, dh, dW_head (lm_head.hip: lm_head_train)
+//   r4d_rag_train_step_f32    training forward (train.hip) -> LM head, CE on aug_ids, dh, dW_head (lm_head.hip: head_train_step)
 //                             -> backward (frozen: data gradients only) -> d_fused = gradient of the spliced rows
 //   weighted_bag_kernel       P[q] = sum_{j in span q} c_j wte[nodes_j]   (mean over nodes of A_norm X = c^T X per query)
 //   scatter_fix_kernel        out[ids[k]] = sum_k w_k src[row_of[k]]      (64-bit fixed point, as the embedding backward)
@@ -185,7 +185,6 @@ int r4d_rag_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w
                            int32_t head_mode, float* head_grad_d, const int64_t* aug_ids_d, const float* fused_d, int32_t B, int32_t Ta,
                            int32_t r, float grad_scale, float* loss_d, float* d_fused_d, float* hidden_out_d,
                            const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
     R4D_REQUIRE(cfg && w && head && head->wte_pad && aug_ids_d && fused_d && loss_d, "rag train step: null pointer");
     R4D_REQUIRE(head_mode == R4D_HEAD_GRAD_UNTIED || head_mode == R4D_HEAD_GRAD_TIED || head_mode == R4D_HEAD_GRAD_NONE,
                 "rag train step: head_mode %d", head_mode);
@@ -193,35 +192,11 @@ int r4d_rag_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w
     R4D_REQUIRE(!backward || head_mode != R4D_HEAD_GRAD_UNTIED || head_grad_d, "rag train step: the untied head needs head_grad_d");
     R4D_REQUIRE(!backward || head_mode != R4D_HEAD_GRAD_TIED || (grads && grads->wte), "rag train step: the tied head adds into grads->wte");
     R4D_REQUIRE(!grads || (grads->wte && grads->wpe && grads->ln_f_w && grads->ln_f_b && grads->layers), "rag train step: null gradient");
-    const int V = cfg->vocab, ldV = head->ldV, d = cfg->n_embd;
-    R4D_REQUIRE(B >= 1 && r >= 1 && Ta >= r + 3 && ldV % 128 == 0 && ldV >= V, "rag train step: B=%d Ta=%d r=%d ldV=%d (V=%d)", B, Ta,
-                r, ldV, V);
-    int rc = check_ce(B * Ta, V, ldV, Ta);
-    if (rc) return rc;
-    const LMLayout t = lm_layout(cfg, B, Ta, ldV);
-    if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
-        set_error("rag train step: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
-        return R4D_ERR_WORKSPACE;
-    }
-    float* ws = (float*)workspace_d;
-    const int N = B * Ta;
-    float *h = ws + t.h, *logits = ws + t.logits, *dh = ws + t.dh, *dwte = ws + t.dwte;
-    const size_t train_bytes = (t.h - t.train) * sizeof(float);
-    const int64_t* const ids[1] = {aug_ids_d};
+    R4D_REQUIRE(B >= 1 && r >= 1 && Ta >= r + 3 && head->ldV % 128 == 0 && head->ldV >= cfg->vocab,
+                "rag train step: B=%d Ta=%d r=%d ldV=%d (V=%d)", B, Ta, r, head->ldV, cfg->vocab);
     const SpliceIn sp{fused_d, r};
-    const bool head_w = backward && head_mode != R4D_HEAD_GRAD_NONE;
-    if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &Ta, nullptr, h, dropout, ws + t.train, train_bytes, s, &sp))) return rc;
-    if (hidden_out_d) R4D_HIP(hipMemcpyAsync(hidden_out_d, h, (size_t)N * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if ((rc = lm_head_train(h, N, V, d, head, aug_ids_d, Ta, grad_scale, loss_d, logits, backward ? dh : nullptr, head_w ? dwte : nullptr,
-                            ws + t.tn, ws + t.ce, s))) return rc;
-    if (!backward) return R4D_OK;
-    if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &Ta, nullptr, dh, dropout, ws + t.train, train_bytes, s, &sp, d_fused_d)))
-        return rc;
-    if (head_mode == R4D_HEAD_GRAD_UNTIED)
-        R4D_HIP(hipMemcpyAsync(head_grad_d, dwte, (size_t)V * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-    else if (head_mode == R4D_HEAD_GRAD_TIED)                       // the token scatter (written by the backward) + the head's part
-        return launch_add_inplace(grads->wte, dwte, (long long)V * d, s);
-    return R4D_OK;
+    return head_train_step("rag train step", cfg, w, grads, head, head_mode, head_grad_d, aug_ids_d, &sp, B, Ta, grad_scale, loss_d,
+                           d_fused_d, hidden_out_d, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
 }
 
 int r4d_weighted_bag_f32(const float* table_d, int32_t vocab, int32_t d, const int64_t* ids_d, const float* weights_d,

@@ -29,12 +29,11 @@ int launch_ln_bwd(const float* x, const float* w, const float* dy, const float* 
 size_t colsum_scratch_floats(long long rows, int n);
 int launch_colsum(const float* x, long long rows, int n, int ld, float* out, float* scratch, int accumulate, hipStream_t s);
 int launch_gelu_fwd(const float* pre, long long n, float* y, hipStream_t s);
-static int g_train_fuse_gelu = -1;    // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once, below)
 int launch_gelu_bwd(const float* pre, const float* dy, long long n, float* dx, hipStream_t s);
 int launch_softmax_bwd(const float* P, float* dP, int nbh, int T, int ld, float scale_div, hipStream_t s);
 int launch_transpose(const float* in, int rows, int cols, long long ld_in, long long stride_in, float* out, long long ld_out,
                      long long stride_out, int nbatch, hipStream_t s);
-// recompute mode only: dropout backward + softmax backward in place on dP and its transpose into dst; dropout + transpose of P
+// recompute mode: dropout backward + softmax backward in place on dP and its transpose into dst; dropout + transpose of P
 int launch_softmax_bwd_t(const float* P, float* dP, float* dst, int nbh, int T, int ld, float scale_div, float attn_p, DropKey key,
                          unsigned site, unsigned long long pbase, hipStream_t s);
 int launch_dropout_transpose(const float* P, float* out, int nbh, int T, int ld, float attn_p, DropKey key, unsigned site,
@@ -46,15 +45,24 @@ int launch_embedding_absmax(const float* dx, long long n, unsigned long long* ac
 int launch_meanpool_bwd(const float* d_pool, long long rows, int T, int d, float* dh, hipStream_t s);
 
 // r4d_set_train_attention: 0 stored (the forward keeps P of every layer), 1 recompute (the backward forms P again with the
-// forward's two launches; no per-layer P blocks).  Read by layout(), so the size queries, the forward and the backward follow it.
+// forward's two launches; no per-layer P blocks).
 static int g_train_attention = 0;
 // r4d_set_train_activations: 0 stored (the forward keeps ln1 .. f of every layer), 1 recompute (it keeps each layer's input; the
-// backward forms one layer's activations at a time again, with the forward's launches, in ONE set all layers share).  Read by layout().
+// backward forms one layer's activations at a time again, with the forward's launches, in ONE set all layers share).
 static int g_train_activations = 0;
-static const void* g_last_fwd_ws = nullptr;   // workspace and modes of the most recent training forward: a backward on that
-static int g_last_fwd_mode = 0;               // workspace under another mode would read the wrong layout -> refused
-static int g_last_fwd_act = 0;
-static int g_shared_layer = -1;               // activations recompute: the layer whose activations that workspace's shared set holds
+// The two modes as a value: every entry point (size queries, forward, backward) reads the globals ONCE, here, and hands the
+// value down; nothing below an entry point looks at a global.
+struct TrainModes { int attention, activations; };
+static TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations}; }
+// tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
+static bool train_fuse_gelu() {
+    static const int v = [] { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); return e ? atoi(e) : 1; }();
+    return v != 0;
+}
+// The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
+// activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
+// would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -70,17 +78,17 @@ struct TrainLayout {
     size_t x_out, pool_scratch;
     bool recompute;                                     // no P blocks; scratch pA holds the P of the batch at hand
     bool act_recompute;                                 // ln1 .. f (and P) of every layer are ONE shared set; x_in stays per layer
-    // backward temporaries (pA: recompute mode only; dP / PT are its scratch blocks B / C)
+    // backward temporaries (pA, dP, PT: attn_bwd's scratch blocks A, B, C; pA in recompute mode only)
     size_t dx, dy, dbig, dqkv, xT, pA, dP, PT, red;
     size_t emb_acc;                                     // [vocab, d] 64-bit fixed-point token-gradient table (two floats per entry)
     size_t total;
 };
 
-static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int n) {
+static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int n, TrainModes md) {
     TrainLayout t;
     t.L = cfg->n_layer; t.d = cfg->n_embd;
-    t.recompute = g_train_attention == 1;
-    t.act_recompute = g_train_activations == 1;
+    t.recompute = md.attention == 1;
+    t.act_recompute = md.activations == 1;
     const size_t d = t.d;
     t.M = 0; t.Ptot = 0; t.pmax = 0;
     size_t pool = 0;
@@ -153,29 +161,40 @@ static int fwd_linear(const float* x, const float* w, const float* wT, const flo
                       int epi, float* y, hipStream_t s, const unsigned short* w3 = nullptr, const unsigned short* w2h = nullptr) {
     return conv1d(x, w, wT, bias, resid, M, K, N, epi, y, s, nullptr, false, w3, w2h);     // f16x2 planes (mode 2) > bf16x3 planes > [N,K] copy > reference layout
 }
-// dx[M,K] = dy[M,N] . W[K,N]^T : W's rows are k(N)-contiguous, i.e. W IS the [N' = K, K' = N] operand of the fast kernel;
-// `w3t` (nullable): its bf16x3 planes [3][K][N] -> the bf16 matrix cores at fp32 accuracy
-// `gelu_pre` (bf16x3 path only): dx = (dy . W^T) * gelu_new'(gelu_pre), gelu_pre [M,K]
+// The data-gradient GEMM of the training steps: C[M, n_out] = epilogue(A[M, k] . W), A a GRADIENT, W one of
+//   b_trans = 1   w [n_out, k]: Conv1D, dx = dy . W^T -- the weight [in, out] IS the k-contiguous operand of the fast kernel
+//   b_trans = 0   w [k, n_out]: the LM head, dh = dlogits . wte_pad
+// `w3t` (nullable): W's bf16x3 planes [3][n_out][k] -> the bf16 matrix cores at fp32 accuracy, when the mode and the shape allow;
+// else the exact-f32 kernel on `w`.  `resid` (nullable): C = resid + A . W.  `gelu_pre` [M, n_out] (bf16x3 path only):
+// C = (A . W) * gelu_new'(gelu_pre).
 // (The data gradients stay on bf16x3 in EVERY split mode: their A operand is a GRADIENT -- 1e-5 .. 1e-8 per element in a real run -- and
 //  the f16x2 form has fp16's exponent range: below 2.4e-4 an element's absolute error stops shrinking (6e-11), i.e. 1e-4 relative at
 //  1e-6.  Built and measured in round 5 (46.9 instead of 50.6 ms per step, G8 green at its max-norm bounds), then taken out: a
 //  per-tensor power-of-two scale from an absmax pass would be needed to make it safe, and that pass costs what the kernel saves.)
-static int bwd_data(const float* dy, const float* w, int M, int K, int N, float* dx, hipStream_t s, const unsigned short* w3t = nullptr,
-                    const float* gelu_pre = nullptr) {
-    if (w3t && g_gemm_split3 && gemm_s3_supported(M, N, K)) {
+int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, int b_trans, int M, int n_out, int k, float* C,
+                   const float* resid, const float* gelu_pre, hipStream_t s) {
+    const int epi = gelu_pre ? EPI_GELU_GRAD : resid ? EPI_RESIDUAL : EPI_NONE;
+    if (w3t && g_gemm_split3 && gemm_s3_supported(M, k, n_out)) {
         S3Args a;
         memset(&a, 0, sizeof(a));
-        a.A = dy; a.planes = w3t; a.C = dx; a.M = M; a.N = K; a.K = N; a.lda = N; a.ldc = K; a.ldr = K;
-        a.epilogue = gelu_pre ? EPI_GELU_GRAD : EPI_NONE; a.resid = gelu_pre;
+        a.A = A; a.planes = w3t; a.C = C; a.resid = gelu_pre ? gelu_pre : resid;
+        a.M = M; a.N = n_out; a.K = k; a.lda = k; a.ldc = n_out; a.ldr = n_out; a.epilogue = epi;
         return launch_gemm_s3(a, s);
     }
     R4D_REQUIRE(!gelu_pre, "bwd_data: the fused GELU derivative needs the bf16x3 planes");
     GemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.A = dy; g.B = w; g.C = dx;
-    g.M = M; g.N = K; g.K = N; g.lda = N; g.ldb = N; g.ldc = K;
-    g.b_trans = 1; g.b_rows = K; g.nbatch = 1; g.nb1 = 1; g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+    g.A = A; g.B = w; g.C = C; g.resid = resid;
+    g.M = M; g.N = n_out; g.K = k; g.lda = k; g.ldb = b_trans ? k : n_out; g.ldc = n_out;
+    g.ldr = n_out;                                                // read under EPI_RESIDUAL / a non-null resid only (gemm_f32.hip)
+    g.b_trans = b_trans; g.b_rows = b_trans ? n_out : k; g.nbatch = 1; g.nb1 = 1; g.epilogue = epi; g.scale_div = 1.f;
+    g.causal = CAUSAL_NONE;
     return launch_gemm_f32(g, s);
+}
+// dx[M,K] = dy[M,N] . W[K,N]^T (Conv1D backward); `w3t`: W's planes [3][K][N]
+static int bwd_data(const float* dy, const float* w, int M, int K, int N, float* dx, hipStream_t s,
+                    const unsigned short* w3t = nullptr, const float* gelu_pre = nullptr) {
+    return data_grad_gemm(dy, w, w3t, 1, M, K, N, dx, nullptr, gelu_pre, s);
 }
 // dW[K,N] = x[M,K]^T . dy[M,N]: both operands read row by row over the contracted token index (split-K partials in `skp`);
 // db[N] = column sums of dy
@@ -187,7 +206,6 @@ static int bwd_weight(const float* x, const float* dy, int M, int K, int N, floa
     return (db && !db_done) ? launch_colsum(dy, M, N, N, db, red, 0, s) : R4D_OK;
 }
 
-// Attention._attn forward over one batch, probabilities kept in P [B*H, T, ld] with EVERY column right of the diagonal zero
 struct DropCtx {                                                  // dropout of one step; p == 0 everywhere -> identity
     float embd_p, attn_p, resid_p;
     DropKey key;
@@ -203,137 +221,90 @@ static int drop_ctx(const r4d_train_dropout* dp, DropCtx& c) {
     return R4D_OK;
 }
 
-// P [B*H, T, ld] = causal softmax(Q . K^T / sqrt(hd)): the forward's two launches (recompute mode runs them again in the backward)
-static int attn_probs(const float* qkv, int B, int T, int H, int d, float* P, hipStream_t s) {
-    const int hd = d / H, ld = tpad128(T);
+// The per-head batched GEMMs of one batch [B, T]: T rows per (sequence, head), hd = d / H columns per head.  An operand is
+// a pointer and a HeadLd: its leading dimension and its strides per sequence and per head.  Three kinds occur:
+struct HeadLd { int ld; long long s0, s1; };
+struct HeadDims {
+    int B, T, H, d, hd, ld, Tp;                                   // ld = tpad128(T): row stride of a P-shaped block; Tp = up4(T)
+    HeadLd qkv, merged, probs;                                    // a Q / K / V slice of [B, T, 3d]; [B, T, d]; [B*H, T, ld]
+    HeadDims(int B_, int T_, int H_, int d_)
+        : B(B_), T(T_), H(H_), d(d_), hd(d_ / H_), ld(tpad128(T_)), Tp(up4(T_)), qkv{3 * d_, (long long)T_ * 3 * d_, d_ / H_},
+          merged{d_, (long long)T_ * d_, d_ / H_}, probs{ld, (long long)H_ * T_ * ld, (long long)T_ * ld} {}
+};
+// C[T, N] = epilogue(A[T, K] . B) per (sequence, head); B is [N, K] (b_trans) or [K, N], T valid rows either way
+static GemmArgs head_gemm(const HeadDims& D, const float* A, HeadLd a, const float* Bm, HeadLd b, float* C, HeadLd c, int N, int K,
+                          int b_trans, int a_cols, int epilogue = EPI_NONE, float scale_div = 1.f, int causal = CAUSAL_NONE) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.A = qkv; g.B = qkv + d; g.C = P;
-    g.M = T; g.N = T; g.K = hd; g.lda = 3 * d; g.ldb = 3 * d; g.ldc = ld;
-    g.b_trans = 1; g.b_rows = T; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = (long long)T * 3 * d; g.sA1 = hd; g.sB0 = g.sA0; g.sB1 = hd;
-    g.sC0 = (long long)H * T * ld; g.sC1 = (long long)T * ld;
-    g.epilogue = EPI_SCALE_DIV; g.scale_div = (float)sqrt((double)hd); g.causal = CAUSAL_QK;
-    const int rc = launch_gemm_f32(g, s);
-    if (rc) return rc;
-    return launch_causal_softmax(P, B * H, T, ld, ld, s);                         // row_tile = ld: zero-fill the whole row
+    g.A = A; g.B = Bm; g.C = C;
+    g.M = D.T; g.N = N; g.K = K; g.lda = a.ld; g.ldb = b.ld; g.ldc = c.ld;
+    g.b_trans = b_trans; g.b_rows = D.T; g.a_cols = a_cols; g.nbatch = D.B * D.H; g.nb1 = D.H;
+    g.sA0 = a.s0; g.sA1 = a.s1; g.sB0 = b.s0; g.sB1 = b.s1; g.sC0 = c.s0; g.sC1 = c.s1;
+    g.epilogue = epilogue; g.scale_div = scale_div; g.causal = causal;
+    return g;
 }
 
+// P [B*H, T, ld] = causal softmax(Q . K^T / sqrt(hd)): the forward's two launches (recompute mode runs them again in the backward)
+static int attn_probs(const HeadDims& D, const float* qkv, float* P, hipStream_t s) {
+    const int rc = launch_gemm_f32(head_gemm(D, qkv, D.qkv, qkv + D.d, D.qkv, P, D.probs, D.T, D.hd, 1, 0, EPI_SCALE_DIV,
+                                             (float)sqrt((double)D.hd), CAUSAL_QK), s);
+    if (rc) return rc;
+    return launch_causal_softmax(P, D.B * D.H, D.T, D.ld, D.ld, s);                // row_tile = ld: zero-fill the whole row
+}
+
+// Attention._attn forward over one batch, probabilities kept in P [B*H, T, ld] with EVERY column right of the diagonal zero
 // `Pdrop` (with attn_p > 0): scratch for the dropped-out probabilities the P.V product reads; P keeps the softmax output
-static int attn_fwd(const float* qkv, int B, int T, int H, int d, float* P, float* out, hipStream_t s, float attn_p = 0.f,
-                    DropKey key = DropKey{0, 0, 0, 0}, unsigned site = 0, unsigned long long pbase = 0, float* Pdrop = nullptr) {
-    const int hd = d / H, ld = tpad128(T);
-    GemmArgs g;
-    int rc = attn_probs(qkv, B, T, H, d, P, s);
+static int attn_fwd(const HeadDims& D, const float* qkv, float* P, float* out, hipStream_t s, float attn_p, DropKey key,
+                    unsigned site, unsigned long long pbase, float* Pdrop) {
+    int rc = attn_probs(D, qkv, P, s);
     if (rc) return rc;
     const float* Pv = P;
     if (attn_p > 0.f) {                                                            // attn_dropout(w), modeling_gpt2.py:153
-        if ((rc = launch_dropout(P, nullptr, (long long)B * H * T * ld, Pdrop, attn_p, key, site, pbase, s))) return rc;
+        if ((rc = launch_dropout(P, nullptr, (long long)D.B * D.H * D.T * D.ld, Pdrop, attn_p, key, site, pbase, s))) return rc;
         Pv = Pdrop;
     }
-    memset(&g, 0, sizeof(g));
-    g.A = Pv; g.B = qkv + 2 * d; g.C = out;
-    g.M = T; g.N = hd; g.K = T; g.lda = ld; g.ldb = 3 * d; g.ldc = d;
-    g.b_trans = 0; g.b_rows = T; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = (long long)H * T * ld; g.sA1 = (long long)T * ld;
-    g.sB0 = (long long)T * 3 * d; g.sB1 = hd; g.sC0 = (long long)T * d; g.sC1 = hd;
-    g.a_cols = ld; g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_PV;
-    return launch_gemm_f32(g, s);
+    return launch_gemm_f32(head_gemm(D, Pv, D.probs, qkv + 2 * D.d, D.qkv, out, D.merged, D.hd, D.T, 0, D.ld, EPI_NONE, 1.f,
+                                     CAUSAL_PV), s);
 }
 
-// Attention backward over one batch: dao [B,T,d] (merged heads) -> dqkv [B,T,3d]
-static int attn_bwd(const float* qkv, const float* P, const float* dao, int B, int T, int H, int d, float* dqkv, float* dP,
-                    float* PT, hipStream_t s, float attn_p = 0.f, DropKey key = DropKey{0, 0, 0, 0}, unsigned site = 0,
-                    unsigned long long pbase = 0) {
-    const int hd = d / H, ld = tpad128(T), Tp = up4(T);
-    const long long sP0 = (long long)H * T * ld, sP1 = (long long)T * ld;
-    const long long sQ0 = (long long)T * 3 * d, sO0 = (long long)T * d;
-    GemmArgs g;
+// Attention backward over one batch: dao [B,T,d] (merged heads) -> dqkv [B,T,3d].  `P`: the probabilities the forward kept, or
+// nullptr (recompute mode): they are formed again into A by the forward's two launches, the same bits.  A (recompute mode
+// only), Bs, C: scratch blocks of the batch's [B*H, T, ld] size.  The four GEMMs are the same launches in both modes; the
+// element-wise steps between them are separate launches in stored mode and the two fused row kernels, written to leave those
+// launches' bits, in recompute mode (stored mode can take the fused kernels over once they have been timed against it).
+static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const float* dao, float* dqkv, float* A, float* Bs, float* C,
+                    hipStream_t s, float attn_p, DropKey key, unsigned site, unsigned long long pbase) {
+    const int d = D.d, BH = D.B * D.H;
+    const long long n = (long long)BH * D.T * D.ld;
+    const float sd = (float)sqrt((double)D.hd);                  // the logits were divided by sqrt(hd) before the softmax
+    const bool fused = P == nullptr;
     int rc;
-    // dP = dO . V^T
-    memset(&g, 0, sizeof(g));
-    g.A = dao; g.B = qkv + 2 * d; g.C = dP;
-    g.M = T; g.N = T; g.K = hd; g.lda = d; g.ldb = 3 * d; g.ldc = ld;
-    g.b_trans = 1; g.b_rows = T; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = sO0; g.sA1 = hd; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sP0; g.sC1 = sP1;
-    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    if ((rc = launch_gemm_f32(g, s))) return rc;
-    if (attn_p > 0.f &&                                          // through attn_dropout: d(softmax out) = mask * dP / (1 - p)
-        (rc = launch_dropout(dP, nullptr, (long long)B * H * T * ld, dP, attn_p, key, site, pbase, s))) return rc;
-    // dS (in place), logits were divided by sqrt(hd) before the softmax
-    if ((rc = launch_softmax_bwd(P, dP, B * H, T, ld, (float)sqrt((double)hd), s))) return rc;
-    // dQ = dS . K
-    memset(&g, 0, sizeof(g));
-    g.A = dP; g.B = qkv + d; g.C = dqkv;
-    g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = 3 * d; g.ldc = 3 * d;
-    g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
-    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    if ((rc = launch_gemm_f32(g, s))) return rc;
-    // dK = dS^T . Q
-    if ((rc = launch_transpose(dP, T, T, ld, sP1, PT, ld, sP1, B * H, s))) return rc;
-    memset(&g, 0, sizeof(g));
-    g.A = PT; g.B = qkv; g.C = dqkv + d;
-    g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = 3 * d; g.ldc = 3 * d;
-    g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
-    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    if ((rc = launch_gemm_f32(g, s))) return rc;
-    // dV = P^T . dO  (the probabilities the forward multiplied V with: after dropout; dP's buffer is free by now)
-    const float* Pv = P;
-    if (attn_p > 0.f) {
-        if ((rc = launch_dropout(P, nullptr, (long long)B * H * T * ld, dP, attn_p, key, site, pbase, s))) return rc;
-        Pv = dP;
+    if (!P) {
+        if ((rc = attn_probs(D, qkv, A, s))) return rc;
+        P = A;
     }
-    if ((rc = launch_transpose(Pv, T, T, ld, sP1, PT, ld, sP1, B * H, s))) return rc;
-    memset(&g, 0, sizeof(g));
-    g.A = PT; g.B = dao; g.C = dqkv + 2 * d;
-    g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = d; g.ldc = 3 * d;
-    g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sO0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
-    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    return launch_gemm_f32(g, s);
-}
-
-// Recompute mode: the same gradients without a kept P.  A, B, C: three scratch blocks of the batch's [B*H, T, ld] size.  Every
-// GEMM reads the bits it reads in attn_bwd (same launches, same arguments), so every gradient has attn_bwd's bits.
-static int attn_bwd_recompute(const float* qkv, const float* dao, int B, int T, int H, int d, float* dqkv, float* A, float* Bs,
-                              float* C, hipStream_t s, float attn_p, DropKey key, unsigned site, unsigned long long pbase) {
-    const int hd = d / H, ld = tpad128(T), Tp = up4(T);
-    const long long sP0 = (long long)H * T * ld, sP1 = (long long)T * ld;
-    const long long sQ0 = (long long)T * 3 * d, sO0 = (long long)T * d;
-    GemmArgs g;
-    int rc;
-    if ((rc = attn_probs(qkv, B, T, H, d, A, s))) return rc;     // P again, by the forward's two launches
     // dP = dO . V^T
-    memset(&g, 0, sizeof(g));
-    g.A = dao; g.B = qkv + 2 * d; g.C = Bs;
-    g.M = T; g.N = T; g.K = hd; g.lda = d; g.ldb = 3 * d; g.ldc = ld;
-    g.b_trans = 1; g.b_rows = T; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = sO0; g.sA1 = hd; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sP0; g.sC1 = sP1;
-    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    if ((rc = launch_gemm_f32(g, s))) return rc;
-    // dS in place on B (through the dropout mask), dS^T into C
-    if ((rc = launch_softmax_bwd_t(A, Bs, C, B * H, T, ld, (float)sqrt((double)hd), attn_p, key, site, pbase, s))) return rc;
+    if ((rc = launch_gemm_f32(head_gemm(D, dao, D.merged, qkv + 2 * d, D.qkv, Bs, D.probs, D.T, D.hd, 1, 0), s))) return rc;
+    // dS in place on Bs (through the dropout mask: d(softmax out) = mask * dP / (1 - p)), dS^T into C
+    if (fused) {
+        if ((rc = launch_softmax_bwd_t(P, Bs, C, BH, D.T, D.ld, sd, attn_p, key, site, pbase, s))) return rc;
+    } else {
+        if (attn_p > 0.f && (rc = launch_dropout(Bs, nullptr, n, Bs, attn_p, key, site, pbase, s))) return rc;
+        if ((rc = launch_softmax_bwd(P, Bs, BH, D.T, D.ld, sd, s))) return rc;
+    }
     // dQ = dS . K,  dK = dS^T . Q
-    for (int which = 0; which < 2; ++which) {
-        memset(&g, 0, sizeof(g));
-        g.A = which ? C : Bs; g.B = which ? qkv : qkv + d; g.C = which ? dqkv + d : dqkv;
-        g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = 3 * d; g.ldc = 3 * d;
-        g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
-        g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sQ0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
-        g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-        if ((rc = launch_gemm_f32(g, s))) return rc;
+    if ((rc = launch_gemm_f32(head_gemm(D, Bs, D.probs, qkv + d, D.qkv, dqkv, D.qkv, D.hd, D.Tp, 0, D.Tp), s))) return rc;
+    if (!fused && (rc = launch_transpose(Bs, D.T, D.T, D.ld, D.probs.s1, C, D.ld, D.probs.s1, BH, s))) return rc;
+    if ((rc = launch_gemm_f32(head_gemm(D, C, D.probs, qkv, D.qkv, dqkv + d, D.qkv, D.hd, D.Tp, 0, D.Tp), s))) return rc;
+    // dV = Pd^T . dO: the probabilities the forward multiplied V with, after dropout, transposed into C (free once the dK GEMM
+    // ahead in the stream has read it; Bs is free by now)
+    if (fused) {
+        if ((rc = launch_dropout_transpose(P, C, BH, D.T, D.ld, attn_p, key, site, pbase, s))) return rc;
+    } else {
+        if (attn_p > 0.f && (rc = launch_dropout(P, nullptr, n, Bs, attn_p, key, site, pbase, s))) return rc;
+        if ((rc = launch_transpose(attn_p > 0.f ? Bs : P, D.T, D.T, D.ld, D.probs.s1, C, D.ld, D.probs.s1, BH, s))) return rc;
     }
-    // dV = Pd^T . dO  (C is free once the dK GEMM ahead of this launch in the stream has read it)
-    if ((rc = launch_dropout_transpose(A, C, B * H, T, ld, attn_p, key, site, pbase, s))) return rc;
-    memset(&g, 0, sizeof(g));
-    g.A = C; g.B = dao; g.C = dqkv + 2 * d;
-    g.M = T; g.N = hd; g.K = Tp; g.lda = ld; g.ldb = d; g.ldc = 3 * d;
-    g.b_trans = 0; g.b_rows = T; g.a_cols = Tp; g.nbatch = B * H; g.nb1 = H;
-    g.sA0 = sP0; g.sA1 = sP1; g.sB0 = sO0; g.sB1 = hd; g.sC0 = sQ0; g.sC1 = hd;
-    g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    return launch_gemm_f32(g, s);
+    return launch_gemm_f32(head_gemm(D, C, D.probs, dao, D.merged, dqkv + 2 * d, D.qkv, D.hd, D.Tp, 0, D.Tp), s);
 }
 
 static RowGroups row_groups_of(const std::vector<TrainGroup>& gs) {
@@ -384,12 +355,9 @@ int r4d_get_train_activations(void) { return g_train_activations; }
 
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts) {
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
-    std::vector<TrainGroup> gs((size_t)n_groups);
-    for (int g = 0; g < n_groups; ++g) {
+    for (int g = 0; g < n_groups; ++g)
         if (Bs[g] <= 0 || Ts[g] <= 0) return 0;
-        gs[g] = TrainGroup{nullptr, Bs[g], Ts[g], 0, 0, 0};
-    }
-    return layout(cfg, gs.data(), n_groups).total * sizeof(float) + 256;
+    return gpt2_train_workspace_floats(cfg, n_groups, Bs, Ts) * sizeof(float) + 256;
 }
 
 int r4d_gpt2_train_forward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int32_t n_groups,
@@ -414,7 +382,7 @@ namespace r4d {
 size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts) {
     std::vector<TrainGroup> gs((size_t)n_groups);
     for (int g = 0; g < n_groups; ++g) gs[g] = TrainGroup{nullptr, Bs[g], Ts[g], 0, 0, 0};
-    return layout(cfg, gs.data(), n_groups).total;
+    return layout(cfg, gs.data(), n_groups, train_modes()).total;
 }
 
 // One block of the training forward: x_in[l] -> x_in[l + 1] (x_out behind the last one), layer 0 from the token ids.
@@ -447,15 +415,15 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
     }
     if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2))) return rc;
     for (const TrainGroup& G : gs)
-        if ((rc = attn_fwd(qkv + G.row0 * 3 * d, G.B, G.T, H, d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0, att + G.row0 * d, s,
-                           dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
+        if ((rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
+                           att + G.row0 * d, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
     float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
     if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
         if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
         if ((rc = launch_dropout(branch, x_in, (long long)M * d, x_mid, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
     } else if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, x_in, M, d, d, EPI_RESIDUAL, x_mid, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
     if ((rc = launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
-    if (g_train_fuse_gelu && Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
+    if (train_fuse_gelu() && Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
         // one launch: f = gelu_new(v) and the pre-activation v (kept for the backward pass) both leave the GEMM's epilogue
         if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, pre, M, d, 4 * d, EPI_GELU_KEEP, f, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
     } else {
@@ -475,7 +443,7 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
 int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
                        const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s, const SpliceIn* sp) {
-    if (g_train_fuse_gelu < 0) { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); g_train_fuse_gelu = e ? atoi(e) : 1; }
+    const TrainModes md = train_modes();
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
@@ -483,14 +451,13 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
     DropCtx dc;
     if ((rc = drop_ctx(dropout, dc))) return rc;
     R4D_REQUIRE(w && w->wte && w->wpe && w->ln_f_w && w->ln_f_b && w->layers && (out_meanpool_d || out_hidden_d), "gpt2 train: null pointer");
-    const TrainLayout t = layout(cfg, gs.data(), n_groups);
+    const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
         return R4D_ERR_WORKSPACE;
     }
     float* ws = (float*)workspace_d;
-    g_last_fwd_ws = workspace_d; g_last_fwd_mode = g_train_attention; g_last_fwd_act = g_train_activations;
-    g_shared_layer = cfg->n_layer - 1;
+    g_last_fwd.ws = workspace_d; g_last_fwd.modes = md; g_last_fwd.shared_layer = cfg->n_layer - 1;
     const int d = cfg->n_embd;
     const RowGroups R = row_groups_of(gs);
     for (int l = 0; l < cfg->n_layer; ++l)
@@ -504,7 +471,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
                         hipStream_t s, const SpliceIn* sp, float* d_fused) {
-    if (g_train_fuse_gelu < 0) { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); g_train_fuse_gelu = e ? atoi(e) : 1; }
+    const TrainModes md = train_modes();
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
@@ -513,13 +480,14 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(w && w->layers && (d_meanpool_d || d_hidden_d) && (!sp || n_groups == 1) && (!d_fused || sp) &&
                 (gr ? gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b : d_fused != nullptr),
                 "gpt2 train backward: null pointer");
-    R4D_REQUIRE(workspace_d != g_last_fwd_ws || g_train_attention == g_last_fwd_mode,
+    const bool after_fwd = workspace_d == g_last_fwd.ws;             // the workspace of the most recent forward
+    R4D_REQUIRE(!after_fwd || md.attention == g_last_fwd.modes.attention,
                 "gpt2 train backward: this workspace was filled by a forward in train-attention mode %d, the current mode is %d",
-                g_last_fwd_mode, g_train_attention);
-    R4D_REQUIRE(workspace_d != g_last_fwd_ws || g_train_activations == g_last_fwd_act,
+                g_last_fwd.modes.attention, md.attention);
+    R4D_REQUIRE(!after_fwd || md.activations == g_last_fwd.modes.activations,
                 "gpt2 train backward: this workspace was filled by a forward in train-activations mode %d, the current mode is %d",
-                g_last_fwd_act, g_train_activations);
-    const TrainLayout t = layout(cfg, gs.data(), n_groups);
+                g_last_fwd.modes.activations, md.activations);
+    const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
         return R4D_ERR_WORKSPACE;
@@ -548,10 +516,10 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         // activations recompute: this layer's ln1 .. f (and P) into the shared set again, by the forward's launches on x_in[l].
         // dx holds the live d(x_out) and is not touched; dy, dP and pA, which the launches borrow, are dead here.  The set still
         // holds the last layer's activations when this backward follows its forward directly: nothing to run again then.
-        if (t.act_recompute && !(workspace_d == g_last_fwd_ws && g_shared_layer == l)) {
-            if (workspace_d == g_last_fwd_ws) g_shared_layer = -1;
+        if (t.act_recompute && !(after_fwd && g_last_fwd.shared_layer == l)) {
+            if (after_fwd) g_last_fwd.shared_layer = -1;
             if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, true, s))) return rc;
-            if (workspace_d == g_last_fwd_ws) g_shared_layer = l;
+            if (after_fwd) g_last_fwd.shared_layer = l;
         }
         // ---- MLP: x_out = x_mid + gelu(ln_2(x_mid) Wfc + bfc) Wp + bp ;  dx holds d(x_out)
         const float* dbr = dx;                                       // gradient of the branch output: through its dropout mask
@@ -560,7 +528,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             dbr = dy;
         }
         if (!frozen && (rc = bwd_weight(f, dbr, M, 4 * d, d, Lg.mlp_proj_w, Lg.mlp_proj_b, xT, red, s))) return rc;
-        if (g_train_fuse_gelu && Lw.mlp_proj_w3t && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
+        if (train_fuse_gelu() && Lw.mlp_proj_w3t && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
             // d(pre) = (d(branch) . Wp^T) * gelu_new'(pre): the derivative is applied in the GEMM's epilogue
             if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, pre))) return rc;
         } else {
@@ -578,13 +546,10 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         }
         if (!frozen && (rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dbr, Lw.attn_proj_w, M, d, d, dy, s, Lw.attn_proj_w3t))) return rc;                              // d(att), merged heads
-        for (const TrainGroup& G : gs) {
-            rc = t.recompute ? attn_bwd_recompute(qkv + G.row0 * 3 * d, dy + G.row0 * d, G.B, G.T, H, d, dqkv + G.row0 * 3 * d, ws + t.pA,
-                                                  ws + t.dP, ws + t.PT, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0)
-                             : attn_bwd(qkv + G.row0 * 3 * d, ws + t.P[l] + G.p0, dy + G.row0 * d, G.B, G.T, H, d, dqkv + G.row0 * 3 * d,
-                                        ws + t.dP, ws + t.PT, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0);
-            if (rc) return rc;
-        }
+        for (const TrainGroup& G : gs)                               // stored mode: the kept P, and no block A (pA does not exist)
+            if ((rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
+                               dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, s,
+                               dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
         if (!frozen && (rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s))) return rc;
         if ((rc = bwd_data(dqkv, Lw.c_attn_w, M, d, 3 * d, dy, s, Lw.c_attn_w3t))) return rc;                            // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)

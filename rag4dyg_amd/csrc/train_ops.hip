@@ -339,7 +339,7 @@ int launch_dropout(const float* x, const float* resid, long long n, float* out, 
 }
 
 // ------------------------------------------------------------------------------------ recompute-mode attention backward
-// The two row kernels of r4d_set_train_attention(1) (train.hip: attn_bwd_recompute).  They replace dropout + softmax_bwd +
+// The two row kernels of r4d_set_train_attention(1) (train.hip: attn_bwd without a kept P).  They replace dropout + softmax_bwd +
 // transpose (dS, dS^T) and dropout + transpose (Pd^T) of the stored path and must leave ITS bits: the GEMMs behind them read
 // what they read there.  Masks: element idx = pbase + (bh * T + i) * ld + j -> Philox block idx / 4, word idx % 4 (pbase, ld
 // multiples of 4, so a block is four consecutive columns of one row and the word is j % 4), threshold / scale as launch_dropout.
