@@ -17,22 +17,9 @@
 // k-tile).  Tile shape is picked per launch by a wave-quantisation cost model (launch_gemm_f32).
 #include <stdlib.h>
 #include <string.h>
-#include "common.h"
+#include "gemm_common.h"
 
 namespace r4d {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-
-__device__ __forceinline__ float gelu_new_f(float x) {
-    // gelu_new(x) = 0.5x(1+tanh(u)), u = sqrt(2/pi)(x+0.044715x^3)  -- modeling_gpt2.py:25,206.
-    // Algebraically 0.5(1+tanh(u)) = 1/(1+exp(-2u)) = 1/(1+exp2(x*(k0 + k1*x^2))) with k0 = -2 sqrt(2/pi) log2(e),
-    // k1 = 0.044715 k0: mul, fma, mul, v_exp_f32, add, v_rcp_f32, mul -- every epilogue VALU instruction is taken from
-    // the MFMA issue slots of the co-resident workgroup, the ocml tanhf form (~40) cost 15 % of a c_fc tile.
-    // |error| < 3e-7 |x| (checked against the oracle at 1e-5 relative in tests/test_gpu_ops.py).
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, k1, k0)));
-}
 
 template <int N>
 struct FragLoad;
@@ -84,21 +71,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 8) ? 4 : 1) void gemm
     __shared__ __attribute__((aligned(16))) float As[2][BK * LDA];
     __shared__ __attribute__((aligned(16))) float Bs[2][BK * LDB];
 
-    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (bid % 8 = XCD group), each with
-    // its own 4 MB L2.  Remap so that an XCD walks a CONTIGUOUS range of tiles (n fastest): the workgroups
-    // that share one A row-panel then hit the same L2 instead of fetching it 8 times.  Bijective for any grid.
-    const int nblk = gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = blockIdx.x & 7;
-    const int bid = xcd * xq + min(xcd, xr) + (blockIdx.x >> 3);
-    // Inside an XCD's range the tiles are walked in groups of GROUP_M row-panels (m fastest inside a group): the
-    // ~64 tiles resident on an XCD then span ~8 row-panels x ~8 column-panels, i.e. ~2 MB of A + ~2 MB of B in its
-    // 4 MB L2, instead of 4 row-panels x every column-panel of B.
-    constexpr int GROUP_M = 8;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = bid / per_group, first_m = grp * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tile_m = first_m + (bid % per_group) % gsz, tile_n = (bid % per_group) / gsz;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    int m0, n0;
+    grouped_tile<BM, BN>(g.M, g.N, m0, n0);                          // XCD-aware grouped tile order
     if (g.causal == CAUSAL_QK && n0 > m0 + BM - 1) return;           // tile strictly above the diagonal
 
     const int z0 = blockIdx.z / g.nb1, z1 = blockIdx.z % g.nb1;
@@ -283,7 +257,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 8) ? 4 : 1) void gemm
             for (int j = 0; j < TN; ++j) v[j] = acc[i][j][r] + bias[j];
             if (g.epilogue == EPI_GELU) {
 #pragma unroll
-                for (int j = 0; j < TN; ++j) v[j] = gelu_new_f(v[j]);
+                for (int j = 0; j < TN; ++j) v[j] = gelu_new1(v[j]);
             } else if (g.epilogue == EPI_RESIDUAL) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) v[j] += res[r][j];

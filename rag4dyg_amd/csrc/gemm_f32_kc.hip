@@ -18,10 +18,10 @@
 //     loads in flight for a whole iteration (see the pipeline comment in the kernel).
 // Per wave and BK = 16 k-tile that leaves 16 MFMAs + 6 ds_read + 2 ds_write + 2 buffer_load and NO VALU.
 // Measured (MI355X, 157.3 TF peak): 8192^3 148 TF (vendor hipBLASLt 154.6); M=35456 K=512 N=1536 137 TF (the
-// previous kernel 102; vendor 141).  XCD-aware grouped tile order and fused bias / gelu_new / residual / scale
-// epilogues as in gemm_f32.hip.
+// previous kernel 102; vendor 141).  XCD-aware grouped tile order (gemm_common.h) and fused bias / gelu_new / residual /
+// scale epilogues (gemm_epilogue_rowmajor.h).
 #include <stdlib.h>
-#include "common.h"
+#include "gemm_common.h"
 
 #ifndef KC_DBG
 #define KC_DBG 0   // tuning aid (tools/kc_ablate.sh): bit 0 drops the fragment reads, bit 1 the staging, bit 2 the barrier, bit 3 only the global loads, bit 4 the C stores, bit 5 the whole epilogue
@@ -46,34 +46,6 @@
 
 namespace r4d {
 
-typedef float f32x16k __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4k __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float gelu_new_kc(float x) {
-    // gelu_new(x) = 0.5x(1+tanh(u)), u = sqrt(2/pi)(x+0.044715x^3)  -- modeling_gpt2.py:25,206.
-    // Algebraically 0.5(1+tanh(u)) = 1/(1+exp(-2u)) = 1/(1+exp2(x*(k0 + k1*x^2))) with k0 = -2 sqrt(2/pi) log2(e),
-    // k1 = 0.044715 k0: mul, fma, mul, v_exp_f32, add, v_rcp_f32, mul -- every epilogue VALU instruction is taken from
-    // the MFMA issue slots of the co-resident workgroup, the ocml tanhf form (~40) cost 15 % of a c_fc tile.
-    // |error| < 3e-7 |x| (checked against the oracle at 1e-5 relative in tests/test_gpu_ops.py).
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, k1, k0)));
-}
-
-typedef float f32x2k __attribute__((ext_vector_type(2)));
-// two outputs at a time: the polynomial part as packed fp32 (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 on gfx950),
-// only exp2 and rcp stay scalar -- 4.5 instead of 7 instructions per element
-__device__ __forceinline__ f32x2k gelu_new_kc2(f32x2k x) {
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    const f32x2k a = x * x * k1 + k0;
-    const f32x2k w = x * a;
-    f32x2k e;
-    e.x = __builtin_amdgcn_exp2f(w.x); e.y = __builtin_amdgcn_exp2f(w.y);
-    e = e + 1.0f;
-    f32x2k r;
-    r.x = __builtin_amdgcn_rcpf(e.x); r.y = __builtin_amdgcn_rcpf(e.y);
-    return x * r;
-}
-
 struct KcShape {
     int M, N, K, lda, ldb, ldc, ldr, nb1, epilogue, causal;
     long long sA0, sA1, sB0, sB1, sC0, sC1;
@@ -95,16 +67,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_f32_kc_kernel(
     static_assert(NLA >= 1 && NLB >= 1 && TM >= 1 && TN >= 1 && (NS == 2 || NS == 4), "tile");
     __shared__ __attribute__((aligned(16))) float lds[NBUF * STAGE];   // stage b: A image at b*STAGE, B image after it
 
-    // XCD-aware grouped tile order (see gemm_f32.hip)
-    const int nblk = gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = blockIdx.x & 7;
-    const int bid = xcd * xq + min(xcd, xr) + (blockIdx.x >> 3);
-    constexpr int GROUP_M = 8;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = bid / per_group, first_m = grp * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tile_m = first_m + (bid % per_group) % gsz, tile_n = (bid % per_group) / gsz;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    int m0, n0;
+    grouped_tile<BM, BN>(g.M, g.N, m0, n0);                          // XCD-aware grouped tile order
     if (g.causal == CAUSAL_QK && n0 > m0 + BM - 1) return;           // tile strictly above the diagonal
 
     const int z0 = blockIdx.z / g.nb1, z1 = blockIdx.z % g.nb1;
@@ -153,7 +117,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_f32_kc_kernel(
         const_cast<float*>(A), 0, (int)(((long long)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(B), 0, (int)(((long long)(g.N - 1) * g.ldb + g.K) * 4), 0x00020000);
-    u32x4k ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
+    u32x4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
 #define KC_LD_(RSRC, OFF, SOFF) __builtin_amdgcn_raw_buffer_load_b128(RSRC, OFF, SOFF, 0)
 #define KC_LOAD_INTO(A0, A1, A2, A3, B0, B1, B2, B3, SOFF)                                         \
     {                                                                                              \
@@ -166,7 +130,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_f32_kc_kernel(
         if (NLB > 2) B2 = KC_LD_(b_rsrc, b_off[NLB > 2 ? 2 : 0], SOFF);                            \
         if (NLB > 3) B3 = KC_LD_(b_rsrc, b_off[NLB > 3 ? 3 : 0], SOFF);                            \
     }
-#define KC_ST_(PTR, V) *reinterpret_cast<u32x4k*>(PTR) = V
+#define KC_ST_(PTR, V) *reinterpret_cast<u32x4*>(PTR) = V
 #define KC_STORE_FROM(A0, A1, A2, A3, B0, B1, B2, B3, STG)                                         \
     {                                                                                              \
         float* sa_ = lds + (STG) * STAGE + st_dst;                                                 \
@@ -203,7 +167,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_f32_kc_kernel(
     const int frag_a = (wm * WM + li) * LDS_ROW + 4 * lh;
     const int frag_b = (wn * WN + li) * LDS_ROW + 4 * lh;
     float4 fa[2][TM], fb[2][TN];
-    f32x16k acc[TM][TN];
+    f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -214,7 +178,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_f32_kc_kernel(
     // prologue: the loads of k-tiles 0, 1, 2 go out back-to-back (ONE exposed memory latency, not three): tiles 0 and 1
     // land in temporaries that die here, tile 2 in the loop's staging registers
     {
-        u32x4k p0, p1, p2, p3, p4, p5, p6, p7, q0, q1, q2, q3, q4, q5, q6, q7;
+        u32x4 p0, p1, p2, p3, p4, p5, p6, p7, q0, q1, q2, q3, q4, q5, q6, q7;
         KC_LOAD_INTO(p0, p1, p2, p3, p4, p5, p6, p7, 0)
         KC_LOAD_INTO(q0, q1, q2, q3, q4, q5, q6, q7, min(1, nkt - 1) * (BK * 4))
         KC_LOAD(2)
@@ -284,87 +248,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void gemm_f32_kc_kernel(
         return;
     }
 #endif
-    // epilogue.  C/D layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) inside each 32x32 tile.
-    // The epilogue kind is a TEMPLATE parameter and interior tiles take a path without bounds checks: with a runtime
-    // switch and per-element guards the 32 outputs of a lane cost ~2,800 instructions (ten branches each) -- at K = 512
-    // that, not the stores themselves, was the 8 % between a launch (130 TF) and the k-loop asymptote (143).
-    // (Measured and dropped earlier: float4 stores through swapped MFMA operands; two-iteration load prefetch.)
-    const bool interior = (m0 + BM <= g.M) & (n0 + BN <= g.N);       // wave-uniform
-    if (interior) {
-        // buffer stores / loads from the tile's origin: the lane's byte offset is computed once (voffset), the
-        // (compile-time row) * ld part lives on the scalar unit (soffset) -- one VALU instruction per element (the bias add)
-        const int lane_c = ((wm * WM + 4 * lh) * g.ldc + wn * WN + li) * 4;
-        const int lane_r = ((wm * WM + 4 * lh) * g.ldr + wn * WN + li) * 4;
-        const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            C + (long long)m0 * g.ldc + n0, 0, ((BM - 1) * g.ldc + BN) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(EPI == EPI_RESIDUAL ? residg + (long long)m0 * g.ldr + n0 : Ag), 0,
-            EPI == EPI_RESIDUAL ? ((BM - 1) * g.ldr + BN) * 4 : 0, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float bias = biasg ? biasg[n0 + wn * WN + j * 32 + li] : 0.f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                float res[16];
-                if (EPI == EPI_RESIDUAL) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        res[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                            r_rsrc, lane_r, ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0));
-                }
-#pragma unroll
-                for (int r2 = 0; r2 < 16; r2 += 2) {
-                    f32x2k v2 = {acc[i][j][r2] + bias, acc[i][j][r2 + 1] + bias};
-                    if (EPI == EPI_GELU) v2 = gelu_new_kc2(v2);
-                    else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
-                    else if (EPI == EPI_SCALE_DIV) { v2.x = v2.x / g.scale_div; v2.y = v2.y / g.scale_div; }
-                    else if (EPI == EPI_HALF_PLUS) { v2.x = (v2.x + 1.0f) / 2.0f; v2.y = (v2.y + 1.0f) / 2.0f; }
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int r = r2 + h2;
-                        const float v = h2 ? v2.y : v2.x;
-#if KC_DBG & 16
-                        if (v == 12345.678f)                             // ablation: (almost) never true, keeps v alive
-#endif
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), c_rsrc, lane_c,
-                                                              ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc + j * 32) * 4, 0);
-                    }
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {                                   // edge tiles: clamped reads, guarded stores
-        const int col = n0 + wn * WN + j * 32 + li;
-        const bool col_ok = col < g.N;
-        const int colc = min(col, g.N - 1);
-        const float bias = biasg ? biasg[colc] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            float res[16];
-            if (EPI == EPI_RESIDUAL) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, g.M - 1);
-                    res[r] = residg[(long long)row * g.ldr + colc];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                float v = acc[i][j][r] + bias;
-                if (EPI == EPI_GELU) v = gelu_new_kc(v);
-                else if (EPI == EPI_RESIDUAL) v += res[r];
-                else if (EPI == EPI_SCALE_DIV) v = v / g.scale_div;
-                else if (EPI == EPI_HALF_PLUS) v = (v + 1.0f) / 2.0f;
-#if KC_DBG & 16
-                if (v == 12345.678f)
-#endif
-                if (row < g.M && col_ok) C[(long long)row * g.ldc + col] = v;
-            }
-        }
-    }
+    // epilogue: the shared row-major one
+#define EPILOGUE_VALUE(i, j, r) acc[i][j][r]
+#define EPILOGUE_SCALE_DIVISOR g.scale_div
+#define EPILOGUE_EDGE_PRELOAD 1
+#define EPILOGUE_DBG_NO_STORES ((KC_DBG & 16) != 0)
+#include "gemm_epilogue_rowmajor.h"
 }
 
 struct KcTile { int bm, bn, cls, blocks_per_cu, waves_per_block; double eff; };
@@ -395,14 +284,9 @@ static int launch_kc(const GemmArgs& g, int cls, hipStream_t stream) {
 #define KC_LAUNCH_(E)                                                                              \
     hipLaunchKernelGGL((gemm_f32_kc_kernel<BM, BN, BK, WGM, WGN, MINW, E>), dim3(tiles, 1, g.nbatch), dim3(NTHREADS), 0, \
                        stream, g.A, g.B, g.C, g.bias, g.resid, sh)
-    switch (g.epilogue) {
-        case EPI_NONE: KC_LAUNCH_(EPI_NONE); break;
-        case EPI_GELU: KC_LAUNCH_(EPI_GELU); break;
-        case EPI_RESIDUAL: KC_LAUNCH_(EPI_RESIDUAL); break;
-        case EPI_SCALE_DIV: KC_LAUNCH_(EPI_SCALE_DIV); break;
-        case EPI_HALF_PLUS: KC_LAUNCH_(EPI_HALF_PLUS); break;
-        default: set_error("gemm_f32_kc: unknown epilogue %d", g.epilogue); return R4D_ERR_INVALID;
-    }
+#define KC_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_SCALE_DIV) X(L, EPI_HALF_PLUS)
+    R4D_EPI_DISPATCH(g.epilogue, KC_KINDS, KC_LAUNCH_, set_error("gemm_f32_kc: unknown epilogue %d", g.epilogue); return R4D_ERR_INVALID;)
+#undef KC_KINDS
 #undef KC_LAUNCH_
     R4D_CHECK_LAUNCH("gemm_f32_kc");
     return R4D_OK;

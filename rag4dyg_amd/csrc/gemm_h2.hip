@@ -26,8 +26,7 @@
 // stages fit (144 KB) where bf16x3 had room for two.
 #include <stdlib.h>
 #include <string.h>
-#include "common.h"
-#include "h2.h"
+#include "gemm_common.h"
 
 #ifndef H2_DBG
 #define H2_DBG 0   // tuning aid (tools/kc_ablate.sh gemm_h2.hip H2_DBG n): bit 0 drops the fragment reads, bit 1 the LDS staging stores (and the split), bit 2 the barrier, bit 3 the global loads, bit 5 the epilogue, bit 6 the MFMAs
@@ -35,29 +34,7 @@
 
 namespace r4d {
 
-typedef float f32x16h __attribute__((ext_vector_type(16)));
-typedef float f32x2h __attribute__((ext_vector_type(2)));
-typedef float f32x4h __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4h __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2h __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2h __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x2h gelu_new_h2(f32x2h x) {            // the epilogue of gemm_s3.hip / gemm_f32_kc.hip, same instructions
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    const f32x2h a = x * x * k1 + k0;
-    const f32x2h w = x * a;
-    f32x2h e;
-    e.x = __builtin_amdgcn_exp2f(w.x); e.y = __builtin_amdgcn_exp2f(w.y);
-    e = e + 1.0f;
-    f32x2h r;
-    r.x = __builtin_amdgcn_rcpf(e.x); r.y = __builtin_amdgcn_rcpf(e.y);
-    return x * r;
-}
-__device__ __forceinline__ float gelu_new_h2_1(float x) {
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, k1, k0)));
-}
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct H2Shape {
     int M, N, K, lda, ldc, ldr;
@@ -109,18 +86,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
     constexpr int STAGE = 2 * (A_PLANE + B_PLANE) + B_SKEW;
     constexpr int NBUF = 3;                                           // LDS stages (48 KB each at 128 x 256)
     static_assert(NLA >= 1 && NLB >= 1 && NLA <= 4 && NLB <= 8 && TM >= 1 && TN >= 1, "tile");
-    __shared__ u32x4h lds[NBUF * STAGE];
+    __shared__ u32x4 lds[NBUF * STAGE];
 
-    // XCD-aware grouped tile order (gemm_f32_kc.hip)
-    const int nblk = gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = blockIdx.x & 7;
-    const int bid = xcd * xq + min(xcd, xr) + (blockIdx.x >> 3);
-    constexpr int GROUP_M = 8;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = bid / per_group, first_m = grp * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tile_m = first_m + (bid % per_group) % gsz, tile_n = (bid % per_group) / gsz;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    int m0, n0;
+    grouped_tile<BM, BN>(g.M, g.N, m0, n0);                          // XCD-aware grouped tile order
     const int nkt = g.K / BK;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned short*>(Bp), 0, 2 * g.plane_bytes, 0x00020000);
 
-    u32x4h ra[NLA], rb[NLB];
+    u32x4 ra[NLA], rb[NLB];
 #define H2_LOAD(KT)                                                                                \
     {                                                                                              \
         const int kt_ = min((KT), nkt - 1);                                                        \
@@ -156,14 +125,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
     }
 #define H2_STORE(STG)                                                                              \
     {                                                                                              \
-        u32x4h* sa_ = lds + (STG) * STAGE;                                                         \
-        u32x2h* sa2_ = reinterpret_cast<u32x2h*>(sa_);                                             \
-        u32x4h* sb_ = sa_ + 2 * A_PLANE;                                                           \
+        u32x4* sa_ = lds + (STG) * STAGE;                                                         \
+        u32x2* sa2_ = reinterpret_cast<u32x2*>(sa_);                                             \
+        u32x4* sb_ = sa_ + 2 * A_PLANE;                                                           \
         _Pragma("unroll") for (int i = 0; i < NLB; ++i) sb_[b_dst[i]] = rb[i];                     \
         _Pragma("unroll") for (int i = 0; i < NLA; ++i) {                                          \
             /* (cast the WHOLE vector: __builtin_bit_cast on an ext-vector element reads element 0) */ \
-            const f32x4h src_ = __builtin_bit_cast(f32x4h, ra[i]);                                 \
-            u32x2h h_, l_;                                                                         \
+            const f32x4 src_ = __builtin_bit_cast(f32x4, ra[i]);                                 \
+            u32x2 h_, l_;                                                                         \
             unsigned hh_, ll_;                                                                     \
             split2_pair<true>(src_[0], src_[1], hh_, ll_);                                         \
             h_[0] = hh_; l_[0] = ll_;                                                              \
@@ -178,7 +147,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
     const int f_off0 = li * 4 + ((0 + lh) ^ fq), f_off1 = li * 4 + ((2 + lh) ^ fq);
     const int fa_base = wm * WM * 4, fb_base = 2 * A_PLANE + wn * WN * 4;
 
-    f32x16h acc0[TM][TN], acc1[TM][TN];                  // hi.hi  /  the two cross terms (factor 2^11)
+    f32x16 acc0[TM][TN], acc1[TM][TN];                  // hi.hi  /  the two cross terms (factor 2^11)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -187,12 +156,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
             for (int r = 0; r < 16; ++r) { acc0[i][j][r] = 0.f; acc1[i][j][r] = 0.f; }
 
 #define H2_MFMA(ACC, A_, B_, I_, J_) \
-    if (!(H2_DBG & 64)) ACC[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8h, A_), __builtin_bit_cast(f16x8h, B_), ACC[I_][J_], 0, 0, 0); \
+    if (!(H2_DBG & 64)) ACC[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A_), __builtin_bit_cast(f16x8, B_), ACC[I_][J_], 0, 0, 0); \
     else { asm volatile("" :: "v"(A_), "v"(B_)); }
-    u32x4h fa[2][TM][2], fb[2][TN][2];                   // two fragment sets: the reads of k-step s+1 travel under the MFMAs of k-step s
+    u32x4 fa[2][TM][2], fb[2][TN][2];                   // two fragment sets: the reads of k-step s+1 travel under the MFMAs of k-step s
 #define H2_FRAGS(SET, STG, S)                                                                      \
     {                                                                                              \
-        const u32x4h* st_ = lds + (STG) * STAGE;                                                   \
+        const u32x4* st_ = lds + (STG) * STAGE;                                                   \
         const int fo_ = (S) ? f_off1 : f_off0;                                                     \
         /* in the order the MFMAs want them: lo(A) . hi(B) first */                                \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) fa[SET][i][1] = (H2_DBG & 1) ? dbg_frag : st_[fa_base + 1 * A_PLANE + i * 128 + fo_]; \
@@ -208,7 +177,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
         _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) H2_MFMA(acc1, fa[SET][i][0], fb[SET][j][1], i, j); \
     }
 
-    u32x4h dbg_frag = {(unsigned)tid, 0x3c003c00u, 0x3c003c00u, (unsigned)lane};   // (ablation builds only)
+    u32x4 dbg_frag = {(unsigned)tid, 0x3c003c00u, 0x3c003c00u, (unsigned)lane};   // (ablation builds only)
     if (H2_DBG & 1) asm volatile("" : "+v"(dbg_frag));
     // prologue: k-tiles 0 and 1 into stages 0 and 1, k-tile 2 into the staging registers, k-step 0 of k-tile 0 into fragment set 0
     H2_LOAD(0)
@@ -295,85 +264,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2_kerne
         return;
     }
 #endif
-    // epilogue: gemm_s3.hip's (C/D layout: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)), instruction for instruction, on
-    // value = (acc0 + 2^-11 acc1) * unscale.  A form with the operands of the MFMA swapped -- the accumulator then holds C^T and a
-    // lane stores 16 bytes per instruction, a quarter of the store instructions -- was built in round 4 and REMOVED: no faster
-    // (c_attn 442 vs 430 us) and its GELU variant gave run-to-run different values in lanes 12-15 / 28-31 of each half-wave at some
-    // shapes (scalar or packed arithmetic, with or without wait states; tools/h2_check.py now repeats every launch three times).
-    constexpr float UNS = H2_A_UNSCALE;
-    constexpr bool USES_R = EPI == EPI_RESIDUAL || EPI == EPI_GELU_KEEP;      // the second buffer is read (residual) or written (training forward: the pre-activation)
+    // epilogue: the shared row-major one, on value = (acc0 + 2^-11 acc1) * unscale.  A form with the operands of the MFMA swapped -- the
+    // accumulator then holds C^T and a lane stores 16 bytes per instruction, a quarter of the store instructions -- was built in round 4
+    // and REMOVED: no faster (c_attn 442 vs 430 us) and its GELU variant gave run-to-run different values in lanes 12-15 / 28-31 of each
+    // half-wave at some shapes (scalar or packed arithmetic, with or without wait states; tools/h2_check.py now repeats every launch
+    // three times).
     float* __restrict__ C = Cg;
-    const bool interior = (m0 + BM <= g.M) & (n0 + BN <= g.N);       // wave-uniform
-    if (interior) {
-        const int lane_c = ((wm * WM + 4 * lh) * g.ldc + wn * WN + li) * 4;
-        const int lane_r = ((wm * WM + 4 * lh) * g.ldr + wn * WN + li) * 4;
-        const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            C + (long long)m0 * g.ldc + n0, 0, ((BM - 1) * g.ldc + BN) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(USES_R ? residg + (long long)m0 * g.ldr + n0 : Ag), 0,
-            USES_R ? ((BM - 1) * g.ldr + BN) * 4 : 0, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float bias = biasg ? biasg[n0 + wn * WN + j * 32 + li] : 0.f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                float res[16];
-                if (EPI == EPI_RESIDUAL) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        res[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                            r_rsrc, lane_r, ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0));
-                }
-#pragma unroll
-                for (int r2 = 0; r2 < 16; r2 += 2) {
-                    f32x2h v2 = {__builtin_fmaf(acc1[i][j][r2], H2_LO_UNSCALE, acc0[i][j][r2]) * UNS + bias,
-                                 __builtin_fmaf(acc1[i][j][r2 + 1], H2_LO_UNSCALE, acc0[i][j][r2 + 1]) * UNS + bias};
-                    if (EPI == EPI_GELU_KEEP) {                       // training forward: the pre-activation goes to the second buffer
-#pragma unroll
-                        for (int h2 = 0; h2 < 2; ++h2) {
-                            const int r = r2 + h2;
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, h2 ? v2.y : v2.x), r_rsrc, lane_r,
-                                                                  ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0);
-                        }
-                    }
-                    if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v2 = gelu_new_h2(v2);
-                    else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
-                    else if (EPI == EPI_HALF_PLUS) { v2.x = (v2.x + 1.0f) / 2.0f; v2.y = (v2.y + 1.0f) / 2.0f; }     // train_retriever.py:438
-                    const float vx = v2.x, vy = v2.y;     // (copies first: __builtin_bit_cast on an ext-vector ELEMENT reads element 0)
-                    unsigned o2[2] = {__builtin_bit_cast(unsigned int, vx), __builtin_bit_cast(unsigned int, vy)};
-                    if (EPI == EPI_H2WORDS) h2_words<true>(v2.x, v2.y, o2[0], o2[1]);     // C is the uint32 word image of the result (attention_h2.hip)
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int r = r2 + h2;
-                        __builtin_amdgcn_raw_buffer_store_b32(o2[h2], c_rsrc, lane_c,
-                                                              ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc + j * 32) * 4, 0);
-                    }
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {                                   // edge tiles: clamped reads, guarded stores
-        const int col = n0 + wn * WN + j * 32 + li;
-        const bool col_ok = col < g.N;
-        const int colc = min(col, g.N - 1);
-        const float bias = biasg ? biasg[colc] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                float v = __builtin_fmaf(acc1[i][j][r], H2_LO_UNSCALE, acc0[i][j][r]) * UNS + bias;
-                if (EPI == EPI_GELU_KEEP && row < g.M && col_ok) const_cast<float*>(residg)[(long long)row * g.ldr + col] = v;
-                if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v = gelu_new_h2_1(v);
-                else if (EPI == EPI_RESIDUAL) v += residg[(long long)min(row, g.M - 1) * g.ldr + colc];
-                else if (EPI == EPI_HALF_PLUS) v = (v + 1.0f) / 2.0f;
-                else if (EPI == EPI_H2WORDS) { unsigned w0, w1; h2_words<true>(v, 0.f, w0, w1); v = __builtin_bit_cast(float, w0); }
-                if (row < g.M && col_ok) C[(long long)row * g.ldc + col] = v;
-            }
-        }
-    }
+#define EPILOGUE_VALUE(i, j, r) (__builtin_fmaf(acc1[i][j][r], H2_LO_UNSCALE, acc0[i][j][r]) * H2_A_UNSCALE)
+#define EPILOGUE_PAIR_WORDS 1
+#include "gemm_epilogue_rowmajor.h"
 }
 
 // ---------------------------------------------------------------------------------------------- host side
@@ -386,14 +285,9 @@ static int launch_h2(const S3Args& a, int cls, hipStream_t stream) {
 #define H2_LAUNCH_(E)                                                                              \
     hipLaunchKernelGGL((gemm_h2_kernel<BM, BN, WGM, WGN, E>), dim3(tiles), dim3(64 * WGM * WGN), 0, stream, a.A, \
                        a.planes, a.C, a.bias, a.resid, sh)
-    switch (a.epilogue) {
-        case EPI_NONE: H2_LAUNCH_(EPI_NONE); break;
-        case EPI_GELU: H2_LAUNCH_(EPI_GELU); break;
-        case EPI_RESIDUAL: H2_LAUNCH_(EPI_RESIDUAL); break;
-        case EPI_H2WORDS: H2_LAUNCH_(EPI_H2WORDS); break;
-        case EPI_GELU_KEEP: H2_LAUNCH_(EPI_GELU_KEEP); break;
-        default: set_error("gemm_h2: epilogue %d has no instantiation", a.epilogue); return R4D_ERR_INVALID;
-    }
+#define H2_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_H2WORDS) X(L, EPI_GELU_KEEP)
+    R4D_EPI_DISPATCH(a.epilogue, H2_KINDS, H2_LAUNCH_, set_error("gemm_h2: epilogue %d has no instantiation", a.epilogue); return R4D_ERR_INVALID;)
+#undef H2_KINDS
 #undef H2_LAUNCH_
     R4D_CHECK_LAUNCH("gemm_h2");
     return R4D_OK;
@@ -413,11 +307,7 @@ int launch_gemm_h2(const S3Args& a, hipStream_t stream) {
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("R4D_GEMM_H2_TILE"); forced = e ? atoi(e) : -1; }
     int t = forced;
-    if (t < 0 || t > 1) {                                             // fewest tile waves; the wide tile wins ties
-        const long long b0 = (long long)cdiv(a.M, 128) * cdiv(a.N, 256), b1 = (long long)cdiv(a.M, 128) * cdiv(a.N, 128);
-        const double c0 = (double)((b0 + 255) / 256) * 128 * 256, c1 = (double)((b1 + 255) / 256) * 128 * 128 / 0.9;
-        t = c1 < c0 ? 1 : 0;
-    }
+    if (t < 0 || t > 1) t = pick_tile_128(a.M, a.N);
     if (t == 0) { R4D_BRANCH(H2_128x256); return launch_h2<128, 256, 2, 4>(a, PK_GEMM_H2_128x256, stream); }
     R4D_BRANCH(H2_128x128);
     return launch_h2<128, 128, 2, 4>(a, PK_GEMM_H2_128x128, stream);

@@ -1,5 +1,5 @@
 // "f16x2" GEMM with BOTH operands pre-split (round 5): C[M,N] = epilogue(A . W^T + bias), the arithmetic of
-// gemm_h2.hip instruction for instruction -- same fragments, same three products per 16 k, same two accumulator sets, same epilogues --
+// gemm_h2.hip -- same fragments, same three products per 16 k, same two accumulator sets, the epilogue arithmetic of gemm_epilogue_rowmajor.h --
 // but the A operand arrives ALREADY as f16x2 lines, written by its producer (LayerNorm: encoder_ops.hip; the c_fc GELU epilogue:
 // this file) in the layout r4d_split2_planes_f16 gives the weights:
 //     [rows][K/32][2][32] fp16 -- per row and 32 consecutive k ONE 128-byte line of 32 hi = RN16(x/4) then 32 lo' = RN16((x/4 - hi) 2^11)
@@ -17,33 +17,13 @@
 // front of the first fragment read of that k-tile.
 #include <stdlib.h>
 #include <string.h>
-#include "common.h"
-#include "h2.h"
+#include "gemm_common.h"
 
 namespace r4d {
 
-typedef float f32x16p __attribute__((ext_vector_type(16)));
-typedef float f32x2p __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4p __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8p __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 int g_gemm_h2p = 1;               // r4d_set_gemm_h2p: 0 keeps the register-staged gemm_h2 kernels and fp32 activations everywhere
-
-__device__ __forceinline__ f32x2p gelu_new_h2p(f32x2p x) {           // gemm_h2.hip's, same instructions
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    const f32x2p a = x * x * k1 + k0;
-    const f32x2p w = x * a;
-    f32x2p e;
-    e.x = __builtin_amdgcn_exp2f(w.x); e.y = __builtin_amdgcn_exp2f(w.y);
-    e = e + 1.0f;
-    f32x2p r;
-    r.x = __builtin_amdgcn_rcpf(e.x); r.y = __builtin_amdgcn_rcpf(e.y);
-    return x * r;
-}
-__device__ __forceinline__ float gelu_new_h2p_1(float x) {
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, k1, k0)));
-}
 
 struct H2PShape {
     int M, N, K, ldc, ldr;
@@ -89,18 +69,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
     constexpr int NGA = BM / 8 / NW, NGB = BN / 8 / NW;               // 8-row groups per wavefront and k-tile: 2 of A, 4 (2) of W with 8 wavefronts
     constexpr int NDMA = NGA + NGB;
     static_assert(BM == 128 && (BN == 256 || BN == 128) && TM >= 1 && TN >= 1 && (NGA == 2 || NGA == 4) && (NGB == 2 || NGB == 4 || NGB == 8), "tile");
-    __shared__ u32x4p lds[NBUF * STAGE];
+    __shared__ u32x4 lds[NBUF * STAGE];
 
-    // XCD-aware grouped tile order (gemm_h2.hip)
-    const int nblk = gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = blockIdx.x & 7;
-    const int bid = xcd * xq + min(xcd, xr) + (blockIdx.x >> 3);
-    constexpr int GROUP_M = 8;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = bid / per_group, first_m = grp * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tile_m = first_m + (bid % per_group) % gsz, tile_n = (bid % per_group) / gsz;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    int m0, n0;
+    grouped_tile<BM, BN>(g.M, g.N, m0, n0);                          // XCD-aware grouped tile order
     const int nkt = g.K / 32;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -146,7 +118,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
         for (int p = 0; p < 2; ++p) f_off[s_][p] = li * 8 + ((4 * p + 2 * s_ + lh) ^ fsw);
     const int fa_base = wm * WM * 8, fb_base = BM * 8 + wn * WN * 8;
 
-    f32x16p acc0[TM][TN], acc1[TM][TN];                  // hi.hi  /  the two cross terms (factor 2^11)
+    f32x16 acc0[TM][TN], acc1[TM][TN];                  // hi.hi  /  the two cross terms (factor 2^11)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -155,11 +127,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
             for (int r = 0; r < 16; ++r) { acc0[i][j][r] = 0.f; acc1[i][j][r] = 0.f; }
 
 #define H2P_MFMA(ACC, A_, B_, I_, J_) \
-    ACC[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8p, A_), __builtin_bit_cast(f16x8p, B_), ACC[I_][J_], 0, 0, 0);
-    u32x4p fa[2][TM][2], fb[2][TN][2];                   // two fragment sets: the reads of k-step s+1 travel under the MFMAs of k-step s
+    ACC[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A_), __builtin_bit_cast(f16x8, B_), ACC[I_][J_], 0, 0, 0);
+    u32x4 fa[2][TM][2], fb[2][TN][2];                   // two fragment sets: the reads of k-step s+1 travel under the MFMAs of k-step s
 #define H2P_FRAGS(SET, STG, S)                                                                     \
     {                                                                                              \
-        const u32x4p* st_ = lds + (STG) * STAGE;                                                   \
+        const u32x4* st_ = lds + (STG) * STAGE;                                                   \
         /* in the order the MFMAs want them: lo(A) . hi(B) first */                                \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) fa[SET][i][1] = st_[fa_base + i * 256 + f_off[S][1]]; \
         _Pragma("unroll") for (int j = 0; j < TN; ++j) fb[SET][j][0] = st_[fb_base + j * 256 + f_off[S][0]]; \
@@ -228,7 +200,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
 #undef H2P_MFMA
 #undef H2P_ISSUE
 
-    // epilogue: gemm_h2.hip's, instruction for instruction, on value = (acc0 + 2^-11 acc1) * unscale
+    // epilogue on value = (acc0 + 2^-11 acc1) * unscale.  Beside its f16x2-line output this file keeps its OWN copy of the row-major
+    // epilogue (the arithmetic of gemm_epilogue_rowmajor.h as gemm_h2.hip uses it; helpers from gemm_common.h): it gathers the 16 words of
+    // an accumulator tile ahead of their stores, so that the K third of the h2-word output can go to the key-blocked image 16 bytes at
+    // a time.  Through the shared text the six row-major kernels without h2 words get another instruction order, and with a
+    // gathered-stores switch in that text the 128 x 256 residual kernel still gets another SGPR assignment (DESIGN_LOG 12.15): unshared.
     constexpr float UNS = H2_A_UNSCALE;
     float* __restrict__ C = Cg;
     const bool interior = (m0 + BM <= g.M) & (n0 + BN <= g.N);       // wave-uniform
@@ -250,9 +226,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
             for (int i = 0; i < TM; ++i) {
 #pragma unroll
                 for (int r2 = 0; r2 < 16; r2 += 2) {
-                    f32x2p v2 = {__builtin_fmaf(acc1[i][j][r2], H2_LO_UNSCALE, acc0[i][j][r2]) * UNS + bias,
-                                 __builtin_fmaf(acc1[i][j][r2 + 1], H2_LO_UNSCALE, acc0[i][j][r2 + 1]) * UNS + bias};
-                    v2 = gelu_new_h2p(v2);
+                    f32x2 v2 = {__builtin_fmaf(acc1[i][j][r2], H2_LO_UNSCALE, acc0[i][j][r2]) * UNS + bias,
+                                __builtin_fmaf(acc1[i][j][r2 + 1], H2_LO_UNSCALE, acc0[i][j][r2 + 1]) * UNS + bias};
+                    v2 = gelu_new2(v2);
                     const float vx = v2.x, vy = v2.y;                 // rows r2 and r2 + 1 of this lane's column
                     const float send = odd ? vx : vy;
                     const float recv = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
@@ -306,9 +282,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
                     unsigned o[16];
 #pragma unroll
                     for (int r2 = 0; r2 < 16; r2 += 2) {
-                        f32x2p v2 = {__builtin_fmaf(acc1[i][j][r2], H2_LO_UNSCALE, acc0[i][j][r2]) * UNS + bias,
+                        f32x2 v2 = {__builtin_fmaf(acc1[i][j][r2], H2_LO_UNSCALE, acc0[i][j][r2]) * UNS + bias,
                                      __builtin_fmaf(acc1[i][j][r2 + 1], H2_LO_UNSCALE, acc0[i][j][r2 + 1]) * UNS + bias};
-                        if (EPI == EPI_GELU) v2 = gelu_new_h2p(v2);
+                        if (EPI == EPI_GELU) v2 = gelu_new2(v2);
                         else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
                         const float vx = v2.x, vy = v2.y;     // (copies first: __builtin_bit_cast on an ext-vector ELEMENT reads element 0)
                         o[r2] = __builtin_bit_cast(unsigned int, vx); o[r2 + 1] = __builtin_bit_cast(unsigned int, vy);
@@ -337,7 +313,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
                                 const unsigned r13 = (unsigned)__builtin_amdgcn_mov_dpp((int)s13, 0x4E, 0xF, 0xF, true);
                                 if (o2) { x0 = r02; x1 = r13; } else { x2 = r02; x3 = r13; }
                             }
-                            const u32x4p slot = {x0, x1, x2, x3};
+                            const u32x4 slot = {x0, x1, x2, x3};
                             __builtin_amdgcn_raw_buffer_store_b128(slot, kb_rsrc, lane_kb, kb_soff + 2 * a4 * 16, 0);      // rows 8 (a4 / 4) ..
                         }
                     } else {
@@ -361,7 +337,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_h2p_kern
                 for (int r = 0; r < 16; ++r) {
                     const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     float v = __builtin_fmaf(acc1[i][j][r], H2_LO_UNSCALE, acc0[i][j][r]) * UNS + bias;
-                    if (EPI == EPI_GELU) v = gelu_new_h2p_1(v);
+                    if (EPI == EPI_GELU) v = gelu_new1(v);
                     else if (EPI == EPI_RESIDUAL) v += residg[(long long)min(row, g.M - 1) * g.ldr + colc];
                     else if (EPI == EPI_H2WORDS) { unsigned w0, w1; h2_words<true>(v, 0.f, w0, w1); v = __builtin_bit_cast(float, w0); }
                     if (EPI == EPI_H2WORDS && g.kb_hd && col >= g.N / 3 && col < 2 * (g.N / 3)) {      // the K third: key-blocked image
@@ -411,13 +387,11 @@ static int launch_h2p(const S3Args& a, const unsigned short* a_lines, bool out_l
         if (a.epilogue != EPI_GELU) { set_error("gemm_h2p: line output exists for the GELU epilogue only"); return R4D_ERR_INVALID; }
         H2P_LAUNCH_(EPI_GELU, true);
     } else {
-        switch (a.epilogue) {
-            case EPI_NONE: H2P_LAUNCH_(EPI_NONE, false); break;
-            case EPI_GELU: H2P_LAUNCH_(EPI_GELU, false); break;
-            case EPI_RESIDUAL: H2P_LAUNCH_(EPI_RESIDUAL, false); break;
-            case EPI_H2WORDS: H2P_LAUNCH_(EPI_H2WORDS, false); break;
-            default: set_error("gemm_h2p: epilogue %d has no instantiation", a.epilogue); return R4D_ERR_INVALID;
-        }
+#define H2P_LAUNCH_ROWMAJOR_(E) H2P_LAUNCH_(E, false)
+#define H2P_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_H2WORDS)
+        R4D_EPI_DISPATCH(a.epilogue, H2P_KINDS, H2P_LAUNCH_ROWMAJOR_, set_error("gemm_h2p: epilogue %d has no instantiation", a.epilogue); return R4D_ERR_INVALID;)
+#undef H2P_KINDS
+#undef H2P_LAUNCH_ROWMAJOR_
     }
 #undef H2P_LAUNCH_
     R4D_CHECK_LAUNCH("gemm_h2p");
@@ -433,10 +407,7 @@ int launch_gemm_h2p(const S3Args& a, const unsigned short* a_lines, bool out_lin
     R4D_REQUIRE(a.epilogue != EPI_RESIDUAL || a.resid, "gemm_h2p: the residual epilogue needs the second buffer");
     R4D_REQUIRE(!a.kblk || (a.epilogue == EPI_H2WORDS && a.N % 3 == 0 && a.kb_hd >= 32 && a.kb_hd % 32 == 0 && (a.N / 3) % a.kb_hd == 0),
                 "gemm_h2p: the key-blocked K image goes with the h2-word epilogue, N = 3 d and a head_dim that is a multiple of 32");
-    // fewest tile waves; the wide tile wins ties (gemm_h2.hip's rule: a row's result never depends on the tile either way)
-    const long long b0 = (long long)cdiv(a.M, 128) * cdiv(a.N, 256), b1 = (long long)cdiv(a.M, 128) * cdiv(a.N, 128);
-    const double c0 = (double)((b0 + 255) / 256) * 128 * 256, c1 = (double)((b1 + 255) / 256) * 128 * 128 / 0.9;
-    if (c1 < c0) { R4D_BRANCH(H2P_128x128); return launch_h2p<128>(a, a_lines, out_lines, PK_GEMM_H2_128x128, stream); }
+    if (pick_tile_128(a.M, a.N)) { R4D_BRANCH(H2P_128x128); return launch_h2p<128>(a, a_lines, out_lines, PK_GEMM_H2_128x128, stream); }
     R4D_BRANCH(H2P_128x256);
     return launch_h2p<256>(a, a_lines, out_lines, PK_GEMM_H2_128x256, stream);
 }

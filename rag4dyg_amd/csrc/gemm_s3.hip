@@ -23,7 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
-#include "common.h"
+#include "gemm_common.h"
 
 #ifndef S3_NRS
 #define S3_NRS 1   // register stages of the 128 x 256 tile; 2 measured no faster (K = 512: 157-166 vs 163-168 TFLOP/s, 240 vs 206 VGPRs): the k-tile loads are not latency-bound
@@ -34,16 +34,12 @@
 
 namespace r4d {
 
-typedef float f32x16s __attribute__((ext_vector_type(16)));
-typedef float f32x2s __attribute__((ext_vector_type(2)));
-typedef float f32x4s __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2s __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32: low half = bf16(a), RNE
-    const f32x2s v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2s));
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 // two fp32 -> packed (hi, hi), (mid, mid), (lo, lo)
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
@@ -54,30 +50,6 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, uns
     l = cvt_pk_bf16(s0, s1);
 }
 
-__device__ __forceinline__ f32x2s gelu_new_s3(f32x2s x) {            // the epilogue of gemm_f32_kc.hip, same instructions
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    const f32x2s a = x * x * k1 + k0;
-    const f32x2s w = x * a;
-    f32x2s e;
-    e.x = __builtin_amdgcn_exp2f(w.x); e.y = __builtin_amdgcn_exp2f(w.y);
-    e = e + 1.0f;
-    f32x2s r;
-    r.x = __builtin_amdgcn_rcpf(e.x); r.y = __builtin_amdgcn_rcpf(e.y);
-    return x * r;
-}
-__device__ __forceinline__ float gelu_new_s3_1(float x) {
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, k1, k0)));
-}
-
-// d gelu_new / dx with the exponential of gelu_new_s3: tanh(u) = 1 - 2 / (1 + e^(2u))
-__device__ __forceinline__ float gelu_new_grad_s3(float x) {
-    const float c = 0.7978845608028654f;
-    const float x2 = x * x;
-    const float u2 = 2.0f * c * 1.4426950408889634f * x * __builtin_fmaf(x2, 0.044715f, 1.0f);     // 2u log2(e)
-    const float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u2));
-    return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * c * __builtin_fmaf(x2, 3.0f * 0.044715f, 1.0f);
-}
 
 struct S3Shape {
     int M, N, K, lda, ldc, ldr;
@@ -138,18 +110,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
     constexpr int D = NBUF - 1;                                       // k-tiles between the LDS store and its use
     static_assert(NIA >= 1 && NIB >= 1 && NIA <= 2 && NIB <= 2 && TM >= 1 && TN >= 1 && (NBUF == 2 || NBUF == 3), "tile");
     static_assert(NRS == 1 || (NRS == 2 && NBUF == 2), "two register stages: with the two-stage LDS ring only");
-    __shared__ u32x4s lds[NBUF * STAGE];
+    __shared__ u32x4 lds[NBUF * STAGE];
 
-    // XCD-aware grouped tile order (gemm_f32_kc.hip)
-    const int nblk = gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = blockIdx.x & 7;
-    const int bid = xcd * xq + min(xcd, xr) + (blockIdx.x >> 3);
-    constexpr int GROUP_M = 8;
-    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = bid / per_group, first_m = grp * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tile_m = first_m + (bid % per_group) % gsz, tile_n = (bid % per_group) / gsz;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    int m0, n0;
+    grouped_tile<BM, BN>(g.M, g.N, m0, n0);                          // XCD-aware grouped tile order
     const int nkt = g.K / BK;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -178,7 +142,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
     // staging registers (fully unrolled indices only).  NRS = 2: two register stages -- a k-tile's loads are requested TWO
     // iterations before they are split and stored (at K = 512 the A rows of a tile come from beyond the XCD's L2, one
     // iteration of flight time does not cover that latency)
-    u32x4s ra[NRS][NIA][2], rb[NRS][NIB][3];            // BF32: rb[..][0..1] = the 8 fp32 of the item, split at the LDS store
+    u32x4 ra[NRS][NIA][2], rb[NRS][NIB][3];            // BF32: rb[..][0..1] = the 8 fp32 of the item, split at the LDS store
     static_assert(SCAN == 0 || BF32, "scan order: with the fp32 second operand only");
     constexpr int P2 = SCAN ? 32 : 16;                                // byte distance of an item's two 16-byte pieces
     const int scan_kw = SCAN ? nkt / (SCAN ? SCAN : 1) : 1;           // wavefronts the scan kernels split this K over
@@ -202,13 +166,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
     }
 #define S3_STORE(RS, STG)                                                                          \
     {                                                                                              \
-        u32x4s* sa_ = lds + (STG) * STAGE;                                                         \
-        u32x4s* sb_ = sa_ + 3 * A_PLANE;                                                           \
+        u32x4* sa_ = lds + (STG) * STAGE;                                                         \
+        u32x4* sb_ = sa_ + 3 * A_PLANE;                                                           \
         _Pragma("unroll") for (int i = 0; i < NIA; ++i) {                                          \
-            u32x4s h_, m_, l_;                                                                     \
+            u32x4 h_, m_, l_;                                                                     \
             _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                        \
                 /* (cast the WHOLE vector: __builtin_bit_cast on an ext-vector element reads element 0) */ \
-                const f32x4s src_ = __builtin_bit_cast(f32x4s, ra[RS][i][q >> 1]);                 \
+                const f32x4 src_ = __builtin_bit_cast(f32x4, ra[RS][i][q >> 1]);                 \
                 const float x0_ = src_[(q & 1) * 2], x1_ = src_[(q & 1) * 2 + 1];                  \
                 unsigned hh_, mm_, ll_;                                                            \
                 if (S3_DBG & 16) { hh_ = __builtin_bit_cast(unsigned, x0_); mm_ = __builtin_bit_cast(unsigned, x1_); ll_ = hh_ ^ mm_; } \
@@ -219,9 +183,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
         }                                                                                          \
         _Pragma("unroll") for (int i = 0; i < NIB; ++i) {                                          \
             if (BF32) {                                                                            \
-                u32x4s h_, m_, l_;                                                                 \
+                u32x4 h_, m_, l_;                                                                 \
                 _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                    \
-                    const f32x4s src_ = __builtin_bit_cast(f32x4s, rb[RS][i][q >> 1]);            \
+                    const f32x4 src_ = __builtin_bit_cast(f32x4, rb[RS][i][q >> 1]);            \
                     unsigned hh_, mm_, ll_;                                                        \
                     split3_pair(src_[(q & 1) * 2], src_[(q & 1) * 2 + 1], hh_, mm_, ll_);          \
                     h_[q] = hh_; m_[q] = mm_; l_[q] = ll_;                                         \
@@ -238,14 +202,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
     const int f_off0 = li * 4 + ((0 + lh) ^ fq), f_off1 = li * 4 + ((2 + lh) ^ fq);
     const int fa_base = wm * WM * 4, fb_base = 3 * A_PLANE + wn * WN * 4;
 
-    f32x16s acc[TM][TN];
+    f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    f32x16s fin[SCAN ? TM : 1][SCAN ? TN : 1];                       // SCAN: the sum of the finished slices' partial sums
+    f32x16 fin[SCAN ? TM : 1][SCAN ? TN : 1];                       // SCAN: the sum of the finished slices' partial sums
     if constexpr (SCAN != 0) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -256,15 +220,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
     }
 
 #define S3_MFMA(A_, B_, I_, J_) \
-    acc[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8s, A_), __builtin_bit_cast(bf16x8s, B_), acc[I_][J_], 0, 0, 0)
+    acc[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, B_), acc[I_][J_], 0, 0, 0)
     // fragment registers, two sets: the reads of k-step s+1 travel under the MFMAs of k-step s
     // (SCAN: ONE set -- the second accumulator takes the registers -- a fragment is re-read as soon as the last MFMA that uses it has
     //  issued: program order and the register dependences give the progressive refill, the other wavefront of the SIMD covers the rest)
-    u32x4s fa[SCAN ? 1 : 2][TM][3], fb[SCAN ? 1 : 2][TN][3];
+    u32x4 fa[SCAN ? 1 : 2][TM][3], fb[SCAN ? 1 : 2][TN][3];
 #define S3_FRAGS(SET_, STG, S)                                                                     \
     {                                                                                              \
         constexpr int SET = SCAN ? 0 : (SET_);                                                     \
-        const u32x4s* st_ = lds + (STG) * STAGE;                                                   \
+        const u32x4* st_ = lds + (STG) * STAGE;                                                   \
         const int fo_ = (S) ? f_off1 : f_off0;                                                     \
         /* in the order the MFMAs want them: lo(A) . hi(B) first */                                \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) fa[SET][i][2] = (S3_DBG & 1) ? dbg_frag : st_[fa_base + 2 * A_PLANE + i * 128 + fo_]; \
@@ -286,7 +250,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
         _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) S3_MFMA(fa[SET][i][0], fb[SET][j][0], i, j); \
     }
 
-    u32x4s dbg_frag = {(unsigned)tid, 0x3f803f80u, 0x3f803f80u, (unsigned)lane};   // (ablation builds only)
+    u32x4 dbg_frag = {(unsigned)tid, 0x3f803f80u, 0x3f803f80u, (unsigned)lane};   // (ablation builds only)
     if (S3_DBG & 1) asm volatile("" : "+v"(dbg_frag));
     // prologue: k-tiles 0 .. D-1 into their stages, k-tile D (and D+1 with two register stages) into the staging registers
     if constexpr (NRS == 2) {
@@ -393,85 +357,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kerne
         return;
     }
 #endif
-    // epilogue: the one of gemm_f32_kc.hip (C/D layout is dtype-independent: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5))
+    // epilogue: the shared row-major one
     float* __restrict__ C = Cg;
-    const bool interior = (m0 + BM <= g.M) & (n0 + BN <= g.N);       // wave-uniform
-    if (interior) {
-        const int lane_c = ((wm * WM + 4 * lh) * g.ldc + wn * WN + li) * 4;
-        const int lane_r = ((wm * WM + 4 * lh) * g.ldr + wn * WN + li) * 4;
-        const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            C + (long long)m0 * g.ldc + n0, 0, ((BM - 1) * g.ldc + BN) * 4, 0x00020000);
-        const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>((EPI == EPI_RESIDUAL || EPI >= EPI_GELU_KEEP) ? residg + (long long)m0 * g.ldr + n0 : Ag), 0,
-            (EPI == EPI_RESIDUAL || EPI >= EPI_GELU_KEEP) ? ((BM - 1) * g.ldr + BN) * 4 : 0, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const float bias = biasg ? biasg[n0 + wn * WN + j * 32 + li] : 0.f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                float res[16];
-                if (EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        res[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                            r_rsrc, lane_r, ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0));
-                }
-#pragma unroll
-                for (int r2 = 0; r2 < 16; r2 += 2) {
-                    f32x2s v2 = {acc[i][j][r2] + bias, acc[i][j][r2 + 1] + bias};
-                    if (EPI == EPI_GELU_KEEP) {                       // the pre-activation, for the backward pass
-#pragma unroll
-                        for (int h2 = 0; h2 < 2; ++h2) {
-                            const int r = r2 + h2;
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, h2 ? v2.y : v2.x), r_rsrc, lane_r,
-                                                                  ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0);
-                        }
-                    }
-                    if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v2 = gelu_new_s3(v2);
-                    else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
-                    else if (EPI == EPI_GELU_GRAD) { v2.x *= gelu_new_grad_s3(res[r2]); v2.y *= gelu_new_grad_s3(res[r2 + 1]); }
-                    else if (EPI == EPI_HALF_PLUS) { v2.x = (v2.x + 1.0f) / 2.0f; v2.y = (v2.y + 1.0f) / 2.0f; }     // train_retriever.py:438
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const int r = r2 + h2;
-                        const float v = h2 ? v2.y : v2.x;
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), c_rsrc, lane_c,
-                                                              ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc + j * 32) * 4, 0);
-                    }
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {                                   // edge tiles: clamped reads, guarded stores
-        const int col = n0 + wn * WN + j * 32 + li;
-        const bool col_ok = col < g.N;
-        const int colc = min(col, g.N - 1);
-        const float bias = biasg ? biasg[colc] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            float res[16];
-            if (EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, g.M - 1);
-                    res[r] = residg[(long long)row * g.ldr + colc];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                float v = acc[i][j][r] + bias;
-                if (EPI == EPI_GELU_KEEP && row < g.M && col_ok) const_cast<float*>(residg)[(long long)row * g.ldr + col] = v;
-                if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v = gelu_new_s3_1(v);
-                else if (EPI == EPI_RESIDUAL) v += res[r];
-                else if (EPI == EPI_GELU_GRAD) v *= gelu_new_grad_s3(res[r]);
-                else if (EPI == EPI_HALF_PLUS) v = (v + 1.0f) / 2.0f;
-                if (row < g.M && col_ok) C[(long long)row * g.ldc + col] = v;
-            }
-        }
-    }
+#define EPILOGUE_VALUE(i, j, r) acc[i][j][r]
+#define EPILOGUE_EDGE_PRELOAD 1
+#include "gemm_epilogue_rowmajor.h"
 }
 
 // ---------------------------------------------------------------------------------------------- persistent form of the 128 x 256 tile
@@ -496,7 +386,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
     constexpr int BM = 128, BN = 256, BK = 32, WGN = 4, WM = 64, WN = 64, TM = 2, TN = 2;
     constexpr int NIB = 2;                                            // (row, chunk) items of the W tile per thread (A: one)
     constexpr int A_PLANE = BM * 4, B_PLANE = BN * 4, STAGE = 3 * (A_PLANE + B_PLANE);
-    __shared__ u32x4s lds[2 * STAGE];
+    __shared__ u32x4 lds[2 * STAGE];
     __shared__ int s_next;                                            // virtual index of the tile AFTER the current one
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WGN, wn = wid % WGN;
@@ -505,17 +395,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
     const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
     unsigned* const tickets = g_s3p_slots[slot];
     const int cls = blockIdx.x & 7, G = (int)gridDim.x;
-    // XCD-aware grouped tile order over the VIRTUAL block index v (v & 7 == blockIdx.x & 7 for every tile of this workgroup)
-    auto origin = [&](int v, int& m0, int& n0) {
-        const int xq = ntiles >> 3, xr = ntiles & 7, xcd = v & 7;
-        const int bid = xcd * xq + min(xcd, xr) + (v >> 3);
-        constexpr int GROUP_M = 8;
-        const int per_group = GROUP_M * tiles_n;
-        const int grp = bid / per_group, first_m = grp * GROUP_M;
-        const int gsz = min(tiles_m - first_m, GROUP_M);
-        m0 = (first_m + (bid % per_group) % gsz) * BM;
-        n0 = ((bid % per_group) / gsz) * BN;
-    };
+    // the XCD-aware grouped tile order runs over the VIRTUAL block index v (v & 7 == blockIdx.x & 7 for every tile of this workgroup)
     const int st_row = tid >> 2, st_c = tid & 3;                      // staging item: row, 8-k chunk (A: rows 0..127; W: + 128)
     const int st_dst = st_row * 4 + (st_c ^ ((st_row >> 2) & 3));
     auto offsets = [&](int m0, int n0, int& ao, int (&bo)[NIB]) {
@@ -527,7 +407,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
         const_cast<float*>(Ag), 0, (int)(((long long)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned short*>(Bp), 0, 3 * g.plane_bytes, 0x00020000);
-    u32x4s ra[2], rb[NIB][3];
+    u32x4 ra[2], rb[NIB][3];
 #define P_LOAD(AO, BO, KT)                                                                         \
     {                                                                                              \
         ra[0] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, AO, (KT) * (BK * 4), 0);             \
@@ -538,10 +418,10 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
     }
 #define P_STORE(STG)                                                                               \
     {                                                                                              \
-        u32x4s* sa_ = lds + (STG) * STAGE + st_dst;                                                \
-        u32x4s h_, m_, l_;                                                                         \
+        u32x4* sa_ = lds + (STG) * STAGE + st_dst;                                                \
+        u32x4 h_, m_, l_;                                                                         \
         _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                            \
-            const f32x4s src_ = __builtin_bit_cast(f32x4s, ra[q >> 1]);                            \
+            const f32x4 src_ = __builtin_bit_cast(f32x4, ra[q >> 1]);                            \
             unsigned hh_, mm_, ll_;                                                                \
             split3_pair(src_[(q & 1) * 2], src_[(q & 1) * 2 + 1], hh_, mm_, ll_);                  \
             h_[q] = hh_; m_[q] = mm_; l_[q] = ll_;                                                 \
@@ -553,11 +433,11 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
     const int fq = (li >> 2) & 3;
     const int f_off0 = li * 4 + ((0 + lh) ^ fq), f_off1 = li * 4 + ((2 + lh) ^ fq);
     const int fa_base = wm * WM * 4, fb_base = 3 * A_PLANE + wn * WN * 4;
-    u32x4s fa[2][TM][3], fb[2][TN][3];
-    f32x16s acc[TM][TN];
+    u32x4 fa[2][TM][3], fb[2][TN][3];
+    f32x16 acc[TM][TN];
 #define P_FRAGS(SET, STG, S)                                                                       \
     {                                                                                              \
-        const u32x4s* st_ = lds + (STG) * STAGE;                                                   \
+        const u32x4* st_ = lds + (STG) * STAGE;                                                   \
         const int fo_ = (S) ? f_off1 : f_off0;                                                     \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) fa[SET][i][2] = st_[fa_base + 2 * A_PLANE + i * 128 + fo_]; \
         _Pragma("unroll") for (int j = 0; j < TN; ++j) fb[SET][j][0] = st_[fb_base + 0 * B_PLANE + j * 128 + fo_]; \
@@ -567,7 +447,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
         _Pragma("unroll") for (int j = 0; j < TN; ++j) fb[SET][j][1] = st_[fb_base + 1 * B_PLANE + j * 128 + fo_]; \
     }
 #define P_MFMA(A_, B_, I_, J_) \
-    acc[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8s, A_), __builtin_bit_cast(bf16x8s, B_), acc[I_][J_], 0, 0, 0)
+    acc[I_][J_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, B_), acc[I_][J_], 0, 0, 0)
 #define P_MFMAS(SET)                                                                               \
     {                                                                                              \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) P_MFMA(fa[SET][i][2], fb[SET][j][0], i, j); \
@@ -605,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
     }
 
     int m0, n0;
-    origin((int)blockIdx.x, m0, n0);
+    grouped_tile<BM, BN>(tiles_m, tiles_n, (int)blockIdx.x, ntiles, m0, n0);
     int ao, bo[NIB], aon, bon[NIB];
     offsets(m0, n0, ao, bo);
     P_LOAD(ao, bo, 0)
@@ -619,7 +499,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
         unsigned tk = 0;
         if (tid == 0 && has_next) tk = __hip_atomic_fetch_add(&tickets[cls], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         int m0n, n0n;
-        origin(has_next ? vn : (int)blockIdx.x, m0n, n0n);
+        grouped_tile<BM, BN>(tiles_m, tiles_n, has_next ? vn : (int)blockIdx.x, ntiles, m0n, n0n);
         offsets(m0n, n0n, aon, bon);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -637,73 +517,10 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
         if (tid == 0) s_next = has_next ? G + 8 * (int)tk + cls : ntiles;      // behind >= 1 barrier of this tile, published by the next
         P_ITER(1, 0, aon, bon, 1)
 
-        // epilogue (accumulator layout: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) per 32 x 32 tile)
-        const bool interior = (m0 + BM <= g.M) & (n0 + BN <= g.N);
-        if (interior) {
-            const int lane_c = ((wm * WM + 4 * lh) * g.ldc + wn * WN + li) * 4;
-            const int lane_r = ((wm * WM + 4 * lh) * g.ldr + wn * WN + li) * 4;
-            const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                Cg + (long long)m0 * g.ldc + n0, 0, ((BM - 1) * g.ldc + BN) * 4, 0x00020000);
-            const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float*>((EPI == EPI_RESIDUAL || EPI >= EPI_GELU_KEEP) ? residg + (long long)m0 * g.ldr + n0 : Ag), 0,
-                (EPI == EPI_RESIDUAL || EPI >= EPI_GELU_KEEP) ? ((BM - 1) * g.ldr + BN) * 4 : 0, 0x00020000);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const float bias = biasg ? biasg[n0 + wn * WN + j * 32 + li] : 0.f;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    float res[16];
-                    if (EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            res[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                r_rsrc, lane_r, ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0));
-                    }
-#pragma unroll
-                    for (int r2 = 0; r2 < 16; r2 += 2) {
-                        f32x2s v2 = {acc[i][j][r2] + bias, acc[i][j][r2 + 1] + bias};
-                        if (EPI == EPI_GELU_KEEP) {
-#pragma unroll
-                            for (int h2 = 0; h2 < 2; ++h2) {
-                                const int r = r2 + h2;
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, h2 ? v2.y : v2.x), r_rsrc, lane_r,
-                                                                      ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0);
-                            }
-                        }
-                        if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v2 = gelu_new_s3(v2);
-                        else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
-                        else if (EPI == EPI_GELU_GRAD) { v2.x *= gelu_new_grad_s3(res[r2]); v2.y *= gelu_new_grad_s3(res[r2 + 1]); }
-#pragma unroll
-                        for (int h2 = 0; h2 < 2; ++h2) {
-                            const int r = r2 + h2;
-                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, h2 ? v2.y : v2.x), c_rsrc, lane_c,
-                                                                  ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc + j * 32) * 4, 0);
-                        }
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {                           // edge tiles: clamped reads, guarded stores
-                const int col = n0 + wn * WN + j * 32 + li;
-                const bool col_ok = col < g.N;
-                const int colc = min(col, g.N - 1);
-                const float bias = biasg ? biasg[colc] : 0.f;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        float vv = acc[i][j][r] + bias;
-                        if (EPI == EPI_GELU_KEEP && row < g.M && col_ok) const_cast<float*>(residg)[(long long)row * g.ldr + col] = vv;
-                        if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) vv = gelu_new_s3_1(vv);
-                        else if (EPI == EPI_RESIDUAL) vv += residg[(long long)min(row, g.M - 1) * g.ldr + colc];
-                        else if (EPI == EPI_GELU_GRAD) vv *= gelu_new_grad_s3(residg[(long long)min(row, g.M - 1) * g.ldr + colc]);
-                        if (row < g.M && col_ok) Cg[(long long)row * g.ldc + col] = vv;
-                    }
-                }
-            }
-        }
+        // epilogue: the shared row-major one (it falls through to the next tile)
+        float* __restrict__ C = Cg;
+#define EPILOGUE_VALUE(i, j, r) acc[i][j][r]
+#include "gemm_epilogue_rowmajor.h"
         if (!has_next) break;
         m0 = m0n; n0 = n0n; ao = aon;
 #pragma unroll
@@ -724,13 +541,7 @@ __global__ __launch_bounds__(512, 2) void gemm_s3p_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-struct S3Tile { int bm, bn, cls; double eff; };
-static const S3Tile kS3[] = {
-    {128, 256, PK_GEMM_S3_128x256, 1.0},
-    {128, 128, PK_GEMM_S3_128x128, 0.9},
-};
-constexpr int kNumS3 = 2;
-
+#define S3_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_GRAD)   // both kernels
 template <int BM, int BN, int WGM, int WGN, int NBUF, int NRS>
 static int launch_s3(const S3Args& a, int cls, hipStream_t stream) {
     const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
@@ -740,14 +551,7 @@ static int launch_s3(const S3Args& a, int cls, hipStream_t stream) {
 #define S3_LAUNCH_(E)                                                                              \
     hipLaunchKernelGGL((gemm_s3_kernel<BM, BN, WGM, WGN, NBUF, NRS, E>), dim3(tiles), dim3(64 * WGM * WGN), 0, stream, a.A, \
                        a.planes, a.C, a.bias, a.resid, sh)
-    switch (a.epilogue) {
-        case EPI_NONE: S3_LAUNCH_(EPI_NONE); break;
-        case EPI_GELU: S3_LAUNCH_(EPI_GELU); break;
-        case EPI_RESIDUAL: S3_LAUNCH_(EPI_RESIDUAL); break;
-        case EPI_GELU_KEEP: S3_LAUNCH_(EPI_GELU_KEEP); break;
-        case EPI_GELU_GRAD: S3_LAUNCH_(EPI_GELU_GRAD); break;
-        default: set_error("gemm_s3: unknown epilogue %d", a.epilogue); return R4D_ERR_INVALID;
-    }
+    R4D_EPI_DISPATCH(a.epilogue, S3_KINDS, S3_LAUNCH_, set_error("gemm_s3: unknown epilogue %d", a.epilogue); return R4D_ERR_INVALID;)
 #undef S3_LAUNCH_
     R4D_CHECK_LAUNCH("gemm_s3");
     return R4D_OK;
@@ -762,14 +566,7 @@ static int launch_s3p(const S3Args& a, hipStream_t stream) {
     static std::atomic<unsigned> seq{0};
     const int slot = (int)(seq.fetch_add(1) % 64u);
 #define SP_LAUNCH_(E) hipLaunchKernelGGL((gemm_s3p_kernel<E>), dim3(grid), dim3(512), 0, stream, a.A, a.planes, a.C, a.bias, a.resid, sh, ntiles, slot)
-    switch (a.epilogue) {
-        case EPI_NONE: SP_LAUNCH_(EPI_NONE); break;
-        case EPI_GELU: SP_LAUNCH_(EPI_GELU); break;
-        case EPI_RESIDUAL: SP_LAUNCH_(EPI_RESIDUAL); break;
-        case EPI_GELU_KEEP: SP_LAUNCH_(EPI_GELU_KEEP); break;
-        case EPI_GELU_GRAD: SP_LAUNCH_(EPI_GELU_GRAD); break;
-        default: set_error("gemm_s3: unknown epilogue %d", a.epilogue); return R4D_ERR_INVALID;
-    }
+    R4D_EPI_DISPATCH(a.epilogue, S3_KINDS, SP_LAUNCH_, set_error("gemm_s3: unknown epilogue %d", a.epilogue); return R4D_ERR_INVALID;)
 #undef SP_LAUNCH_
     R4D_CHECK_LAUNCH("gemm_s3p");
     return R4D_OK;
@@ -797,11 +594,9 @@ static int s3_launch_tile(const S3Args& a, int t, hipStream_t stream) {
         R4D_BRANCH(S3_PERSISTENT);
         return launch_s3p(a, stream);
     }
-    if (t == 0) R4D_BRANCH(S3_128x256); else R4D_BRANCH(S3_128x128);
-    switch (t) {
-        case 0: return launch_s3<128, 256, 2, 4, 2, S3_NRS>(a, kS3[0].cls, stream);
-        default: return launch_s3<128, 128, 2, 4, 3, 1>(a, kS3[1].cls, stream);
-    }
+    if (t == 0) { R4D_BRANCH(S3_128x256); return launch_s3<128, 256, 2, 4, 2, S3_NRS>(a, PK_GEMM_S3_128x256, stream); }
+    R4D_BRANCH(S3_128x128);
+    return launch_s3<128, 128, 2, 4, 3, 1>(a, PK_GEMM_S3_128x128, stream);
 }
 
 bool gemm_s3_supported(int M, int K, int N) {
@@ -817,16 +612,8 @@ int launch_gemm_s3(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.epilogue != EPI_SCALE_DIV && a.epilogue != EPI_HALF_PLUS, "gemm_s3: epilogue %d has no instantiation", a.epilogue);
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("R4D_GEMM_S3_TILE"); forced = e ? atoi(e) : -1; }
-    if (forced >= 0 && forced < kNumS3) return s3_launch_tile(a, forced, stream);
-    int best = 0;
-    double best_cost = 1e300;
-    for (int t = 0; t < kNumS3; ++t) {
-        if (kS3[t].eff <= 0.0) continue;
-        const long long blocks = (long long)cdiv(a.M, kS3[t].bm) * cdiv(a.N, kS3[t].bn);
-        const double cost = (double)((blocks + 255) / 256) * kS3[t].bm * kS3[t].bn / kS3[t].eff;
-        if (cost < best_cost) { best_cost = cost; best = t; }
-    }
-    return s3_launch_tile(a, best, stream);
+    if (forced >= 0 && forced < 2) return s3_launch_tile(a, forced, stream);
+    return s3_launch_tile(a, pick_tile_128(a.M, a.N), stream);
 }
 
 // C[M,N] = epilogue(A[M,K] . B[N,K]^T) with BOTH operands fp32 and split on the fly (the retrieval scoring GEMM at Q > 64:

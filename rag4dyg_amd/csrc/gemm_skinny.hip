@@ -19,18 +19,12 @@
 // per workgroup from the L2-resident x, applied to the fragments) run in the same launch.  K = 4d (mlp c_proj) still
 // splits over gridDim.y and keeps the epilogue kernel.
 #include <stdlib.h>
-#include "common.h"
+#include "gemm_common.h"
 
 namespace r4d {
 
-typedef float f32x16g __attribute__((ext_vector_type(16)));
 constexpr int SK_KC = 256;                              // k-slice per workgroup
 constexpr int SK_LDX = SK_KC + 4;                       // Xs row stride (floats): conflict-free b128 reads
-
-__device__ __forceinline__ float gelu_new_sk(float x) {   // same form as gemm_f32_kc.hip
-    const float k0 = -2.0f * 0.7978845608028654f * 1.4426950408889634f, k1 = 0.044715f * k0;
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * __builtin_fmaf(x * x, k1, k0)));
-}
 
 // partial[ks][m][n] = sum over k in slice ks of x[m,k] * wT[n,k]        (m < 32 padded with zero rows)
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restrict__ x, const float* __restrict__ wT, int M,
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const float* __restric
     // k order as in pool_scan_kernel: lane half h of row j owns the 64-byte halves [32g + 16h, +16) of each 128-byte line
     const float4* __restrict__ wrow =
         reinterpret_cast<const float4*>(wT + (long long)min(row, N - 1) * K + k0) + 4 * lh;     // clamped: always valid
-    f32x16g acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     constexpr int NG = SK_KC / 32;                     // 8 groups of 32 k
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_epilogue_kernel(const float* 
     float v = 0.f;
     for (int ks = 0; ks < KS; ++ks) v += partial[((long long)ks * 32 + m) * N + n];
     v += bias ? bias[n] : 0.f;
-    if (epilogue == EPI_GELU) v = gelu_new_sk(v);
+    if (epilogue == EPI_GELU) v = gelu_new1(v);
     else if (epilogue == EPI_RESIDUAL) v += resid[idx];
     y[idx] = v;
 }
@@ -214,7 +208,7 @@ __global__ __launch_bounds__(64 * S8_NW) void gemm_skinny8_kernel(const float* _
             }
         __syncthreads();                               // red is reused for the partial tiles
     }
-    f32x16g acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -248,7 +242,7 @@ __global__ __launch_bounds__(64 * S8_NW) void gemm_skinny8_kernel(const float* _
             partial[((long long)blockIdx.y * 32 + m) * N + n] = v;                  // rows m >= M: written, never read
         } else if (m < M) {
             v += bias_n;
-            if (epilogue == EPI_GELU) v = gelu_new_sk(v);
+            if (epilogue == EPI_GELU) v = gelu_new1(v);
             else if (epilogue == EPI_RESIDUAL) v += pass ? res1 : res0;
             y[(long long)m * N + n] = v;
         }
@@ -277,7 +271,6 @@ __device__ __forceinline__ float consume_sk(const float* p) {
     return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const uint32_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-typedef float f32x4g __attribute__((ext_vector_type(4)));
 
 // grid (ceil(N/16), KS), 512 threads.  KS == 1: y = epilogue(x' . wT^T + bias), x' = LN ? LayerNorm(x) : x.
 // KS > 1 (never with LN): partial[ks][32][N] + counters[tile]; the last arriver writes y.
@@ -338,9 +331,9 @@ __global__ __launch_bounds__(64 * S8_NW) void gemm_skinny16_kernel(const float* 
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) a[t][j] = *reinterpret_cast<const float4*>(xs + (16 * t + n16) * LDX + 16 * j + 4 * q);
-    f32x4g acc[2];
+    f32x4 acc[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t] = f32x4g{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 2; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -416,7 +409,7 @@ __global__ __launch_bounds__(64 * S8_NW) void gemm_skinny16_kernel(const float* 
     if (fused) {
         if (en < N && em < M) {
             v += bias_n;
-            if (epilogue == EPI_GELU) v = gelu_new_sk(v);
+            if (epilogue == EPI_GELU) v = gelu_new1(v);
             else if (epilogue == EPI_RESIDUAL) v += res;
             y[(long long)em * N + en] = v;
         }
@@ -439,7 +432,7 @@ __global__ __launch_bounds__(64 * S8_NW) void gemm_skinny16_kernel(const float* 
         float o = 0.f;
         for (int ks = 0; ks < KS; ++ks) o += consume_sk(partial + ((long long)ks * 32 + em) * N + en);
         o += bias_n;
-        if (epilogue == EPI_GELU) o = gelu_new_sk(o);
+        if (epilogue == EPI_GELU) o = gelu_new1(o);
         else if (epilogue == EPI_RESIDUAL) o += resid[(long long)em * N + en];
         y[(long long)em * N + en] = o;
     }

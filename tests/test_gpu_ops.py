@@ -99,6 +99,35 @@ def test_conv1d_f16x2_all_epilogues_tiles_and_range(dev, M, K, N):
     assert not torch.isfinite(ops.conv1d_h2(xd * 1e7, p2, bd)).all() or M * K < 64     # beyond 2^18: inf / NaN, never a quiet wrong number
 
 
+def test_conv1d_bf16x3_persistent_edge_tiles(dev):
+    """The PERSISTENT bf16x3 kernel (``gemm_s3p_kernel``: one workgroup per CU walks the tiles) on edge tiles in M and in N, no
+    epilogue and GELU, against the float64 product of the same fp32 inputs at the bound of test_conv1d_all_epilogues; the branch
+    table says which kernel ran.  Two shapes, both with 5 rows in the last row-panel, 40 columns in the last column-panel and two
+    k-tiles: (4229, 64, 2088) is 34 x 9 = 306 tiles of 128 x 256 -- but the tile rule gives it to the 128 x 128 tile (three
+    rounds of 128 x 128 at 0.9 cost less than two of 128 x 256: 54,613 < 65,536), so it covers that kernel's edges;
+    (4229, 64, 2856) is 34 x 12 = 408 tiles against 34 x 23 = 782 (four rounds), which the rule leaves to the 128 x 256 tile and
+    thereby to the persistent form."""
+    from rag4dyg_amd import ops, _lib
+    from oracle import gpt2_ref
+    lib = _lib.load()
+    names = {lib.r4d_dispatch_branch_name(i).decode(): i for i in range(lib.r4d_dispatch_num_branches())}
+    for (M, K, N), branch in (((4229, 64, 2088), "gemm_s3:128x128x32"),
+                              ((4229, 64, 2856), "gemm_s3:128x256x32 persistent (pipeline across tiles)")):
+        g = torch.Generator().manual_seed(M + K + N)
+        x = torch.randn(M, K, generator=g)
+        w = torch.randn(K, N, generator=g) * 0.05
+        b = torch.randn(N, generator=g) * 0.1
+        ref64 = x.double() @ w.double() + b.double()
+        xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
+        p3 = ops.split3_planes(wd)
+        before = int(lib.r4d_dispatch_branch_hits(names[branch]))
+        err_none = rel_err(ops.conv1d_s3(xd, p3, bd).cpu().numpy(), ref64.numpy())
+        err_gelu = rel_err(ops.conv1d_s3(xd, p3, bd, "gelu").cpu().numpy(), gpt2_ref.gelu_new(ref64).numpy())
+        print(f"bf16x3 edge tiles {(M, K, N)} [{branch}]: rel_err none {err_none:.3e} gelu {err_gelu:.3e}")
+        assert int(lib.r4d_dispatch_branch_hits(names[branch])) - before == 2, (M, K, N, branch)
+        assert err_none < 1e-5 and err_gelu < 1e-5, (M, K, N, err_none, err_gelu)
+
+
 def test_conv1d_k_contiguous_tiles(dev):
     """Every auto-selectable tile of the k-contiguous GEMM is exercised (checked through the launch profiler) and
     agrees with the oracle on ragged M / N."""
