@@ -362,6 +362,26 @@ int r4d_fold_layernorm_f32(const float* wT_d, const float* ln_w_d, const float* 
                            float* lnc_d, void* stream);
 int r4d_set_gemm_split3(int32_t mode);
 int r4d_get_gemm_split3(void);
+/*
+ * Plain bf16 arithmetic for the encoder FORWARD GEMMs (additive ABI v6 entries; csrc/gemm_b1.hip).  NOT fp32-accurate: both
+ * operands are rounded to bf16 (8 significant bits, round to nearest even) and multiplied ONCE on v_mfma_f32_32x32x16_bf16 with
+ * fp32 accumulation -- a sixth of the matrix-pipe work of bf16x3, a third of f16x2's.  bf16 has fp32's exponent range.
+ * r4d_conv1d_bf16_f32: y = epilogue(RN_bf16(x)[M,K] @ RN_bf16(W) + bias) with W given as ONE k-contiguous bf16 plane
+ * w_bf16_d [N][K] = plane 0 of r4d_split3_planes_bf16 (2 * N * K bytes); x stays fp32 and is rounded while it is staged.
+ * K % 32 == 0, x_d and w_bf16_d 16-byte aligned (R4D_ERR_INVALID otherwise, nothing is launched); epilogue as r4d_conv1d_f32.
+ * A row's result does not depend on M or on the other rows of the call.
+ * r4d_set_encode_bf16(on != 0): while on, the four Conv1D GEMMs of a block run on that kernel in r4d_gpt2_encode_f32,
+ * r4d_gpt2_encode_groups_f32 and r4d_gpt2_encode_groups_ex_f32 -- wherever the layer carries *_w3 planes and the shape qualifies,
+ * WHATEVER r4d_set_gemm_split3 says -- with the structure of the bf16x3 path: fp32 activations, the exact-f32 attention kernels,
+ * no f16x2 lines or h2 words.  Only plane 0 of *_w3 is read in this mode: a caller may pass a buffer that holds just that plane.
+ * No other entry reads the switch (training forwards and steps, the cached decode step at any batch size, the greedy step and
+ * graph, r4d_lm_logits_f32, r4d_conv1d_*, the scoring kernels: the same bits on as off).  Returns the previous setting; default 0;
+ * process-wide like r4d_set_gemm_split3: ranks must agree.  r4d_get_encode_bf16 reads it.
+ */
+int r4d_conv1d_bf16_f32(const float* x_d, const uint16_t* w_bf16_d /* [N][K] */, const float* bias_d, const float* residual_d,
+                        int32_t M, int32_t K, int32_t N, int32_t epilogue, float* y_d, void* stream);
+int r4d_set_encode_bf16(int32_t on);
+int r4d_get_encode_bf16(void);
 /* Causal multi-head attention on packed c_attn output qkv_d [B,T,3d] -> a_d [B,T,d] (heads merged).
  * Attention._attn + split/merge_heads, modeling_gpt2.py:140-175; scale = division by sqrt(hd) (:143).
  * scores_ws_d: device scratch of r4d_attention_workspace_bytes(B,H,T). */

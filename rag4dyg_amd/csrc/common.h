@@ -44,7 +44,7 @@ enum ProfClass {
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
-    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_COUNT
+    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -83,7 +83,8 @@ struct ProfScope {
     X(DEC_ATT_32, "decode_attention:<32>") X(DEC_ATT_64, "decode_attention:<64>")                                         \
     X(JAC_LDS, "jaccard:LDS table") X(JAC_MERGE, "jaccard:merge walk (vocab too large for LDS)")                          \
     X(JAC_PREP_DENSE_LDS, "jaccard_prep:dense tokens, LDS histogram") X(JAC_PREP_DENSE_GLOBAL, "jaccard_prep:dense tokens, global histogram") X(JAC_PREP_ORDER, "jaccard_prep:rows longest first") \
-    X(ARGSORT_ONE, "argsort:one chunk") X(ARGSORT_MULTI, "argsort:chunk sort + rank scatter")
+    X(ARGSORT_ONE, "argsort:one chunk") X(ARGSORT_MULTI, "argsort:chunk sort + rank scatter")                              \
+    X(B1_128x256, "tuning:encode_bf16:128x256x32") X(B1_128x128, "tuning:encode_bf16:128x128x32")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -168,6 +169,11 @@ extern int g_gemm_h2p;
 bool gemm_h2p_supported(int M, int K, int N);
 int launch_gemm_h2p(const S3Args& a, const unsigned short* a_lines, bool out_lines, hipStream_t stream);
 int launch_split2_lines(const float* x, long long rows, int K, unsigned short* lines, hipStream_t s);
+// gemm_b1.hip: C = epilogue(RN_bf16(A) . RN_bf16(W)^T + bias), one bf16 MFMA per k-step (NOT fp32-accurate); a.planes = ONE bf16
+// plane [N][K] (plane 0 of the bf16x3 planes); the bf16x3 kernel's shape contract; epilogues none / GELU / residual
+bool gemm_b1_supported(int M, int K, int N);
+int launch_gemm_b1(const S3Args& a, hipStream_t stream);
+extern int g_encode_bf16;             // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs on gemm_b1 wherever a layer carries *_w3
 extern int g_gemm_split3;             // Conv1D arithmetic (r4d_set_gemm_split3): 0 exact-f32 MFMA, 1 bf16x3 planes, 2 f16x2 planes (bf16x3 where a layer carries no f16 planes)
 // Conv1D dispatch shared by the encoder and the training forward (encoder.hip): skinny weight stream (decode), bf16x3 planes,
 // k-contiguous copy, reference layout -- in that order of preference

@@ -17,6 +17,7 @@ void set_error(const char* fmt, ...) {
 }
 
 int g_gemm_split3 = 1;                // r4d_set_gemm_split3: 0 exact f32, 1 bf16x3, 2 f16x2
+int g_encode_bf16 = 0;                // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs in plain bf16 (gemm_b1.hip), whatever the mode above
 
 int conv1d(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K,
            int N, int epilogue, float* y, hipStream_t s, float* skinny_scratch, bool sk_counters_zeroed,
@@ -52,6 +53,20 @@ int conv1d(const float* x, const float* w, const float* wT, const float* bias, c
     g.nbatch = 1; g.nb1 = 1;
     g.epilogue = epilogue; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
     return launch_gemm_f32(g, s);
+}
+
+// The encoder calls' Conv1D (encode_impl only): under r4d_set_encode_bf16(1), on ONE bf16 MFMA per k-step wherever the layer
+// carries planes and the shape qualifies (only plane 0 of `w3` is read); every other case is conv1d above, unchanged
+static int conv1d_encode(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K, int N,
+                         int epilogue, float* y, hipStream_t s, const unsigned short* w3, const unsigned short* w2h) {
+    if (g_encode_bf16 && w3 && epilogue <= EPI_RESIDUAL && gemm_b1_supported(M, K, N)) {
+        S3Args a;
+        memset(&a, 0, sizeof(a));
+        a.A = x; a.planes = w3; a.C = y; a.bias = bias; a.resid = resid;
+        a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
+        return launch_gemm_b1(a, s);
+    }
+    return conv1d(x, w, wT, bias, resid, M, K, N, epilogue, y, s, nullptr, false, w3, w2h);
 }
 
 // Conv1D whose input rows are f16x2 LINES written by their producer (gemm_h2p.hip): f16x2 mode only; out_lines: the GELU epilogue
@@ -176,6 +191,12 @@ int r4d_fold_layernorm_f32(const float* wT_d, const float* ln_w_d, const float* 
 
 int r4d_set_gemm_split3(int32_t mode) { g_gemm_split3 = mode == 2 ? 2 : (mode != 0); return R4D_OK; }
 int r4d_get_gemm_split3(void) { return g_gemm_split3; }
+int r4d_set_encode_bf16(int32_t on) {
+    const int prev = g_encode_bf16;
+    g_encode_bf16 = on != 0;
+    return prev;
+}
+int r4d_get_encode_bf16(void) { return g_encode_bf16; }
 int r4d_set_range_flag(uint32_t* flag_d) { g_range_flag = flag_d; return R4D_OK; }
 int r4d_set_attention_kblk(int32_t on) {
     const int prev = g_attention_kblk < 0 ? 1 : g_attention_kblk;
@@ -258,7 +279,8 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         // f16x2 mode, round 5: the LayerNorms write their rows as f16x2 LINES, the c_fc GELU epilogue too, and c_attn / c_fc /
         // mlp.c_proj take them through LDS-DMA (gemm_h2p.hip) -- the values of the register-staged gemm_h2 path, bit for bit
         // (r4d_set_gemm_h2p(0) keeps that one); the buffers keep their size (4 bytes per element either way)
-        const bool lines = g_gemm_split3 == 2 && g_gemm_h2p && L.c_attn_h2 && L.c_fc_h2 && L.mlp_proj_h2 && layernorm_lines_supported(d) &&
+        // (bf16 precision takes the structure of the bf16x3 path: fp32 activations, exact-f32 attention, no lines or h2 words)
+        const bool lines = !g_encode_bf16 && g_gemm_split3 == 2 && g_gemm_h2p && L.c_attn_h2 && L.c_fc_h2 && L.mlp_proj_h2 && layernorm_lines_supported(d) &&
                            gemm_h2p_supported(M, d, 3 * d) && gemm_h2p_supported(M, d, 4 * d) && gemm_h2p_supported(M, 4 * d, d);
         unsigned short* ln_lines = reinterpret_cast<unsigned short*>(ws.ln);
         unsigned short* fc_lines = reinterpret_cast<unsigned short*>(ws.fc);
@@ -283,7 +305,7 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         float* qkv = out_qkv_d ? out_qkv_d + (size_t)l * M * 3 * d : ws.qkv;
         // f16x2 mode, head_dim 128 / 256, qkv not handed out: c_attn writes h2 words (csrc/h2.h) and the attention runs on
         // the fp16 matrix cores (attention_h2.hip); every other case: fp32 qkv and the exact-f32 kernels below
-        bool words = !out_qkv_d && g_attention_h2 && g_attention_fused != 0 && g_gemm_split3 == 2 && L.c_attn_h2 &&
+        bool words = !g_encode_bf16 && !out_qkv_d && g_attention_h2 && g_attention_fused != 0 && g_gemm_split3 == 2 && L.c_attn_h2 &&
                      attention_h2_supported(H, d) && gemm_h2_supported(M, d, 3 * d);
         for (int g0 = 0; g0 < n_groups && words; g0 += ATT_MAXG) {
             int nseq = 0;
@@ -300,7 +322,7 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         }
         if (lines) rc = conv1d_lines(ln_lines, L.c_attn_h2, L.c_attn_b, nullptr, M, d, 3 * d, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s,
                                      kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
-        else rc = conv1d(ws.ln, L.c_attn_w, L.c_attn_wT, L.c_attn_b, nullptr, M, d, 3 * d, words ? EPI_H2WORDS : EPI_NONE, qkv, s, nullptr, false, L.c_attn_w3, L.c_attn_h2);
+        else rc = conv1d_encode(ws.ln, L.c_attn_w, L.c_attn_wT, L.c_attn_b, nullptr, M, d, 3 * d, words ? EPI_H2WORDS : EPI_NONE, qkv, s, L.c_attn_w3, L.c_attn_h2);
         if (rc) return rc;
         // ... and with them the attention output: attn_h2_kernel writes its merged-head rows as lines for attn.c_proj
         const bool att_lines = words && lines && L.attn_proj_h2 && gemm_h2p_supported(M, d, d);
@@ -339,7 +361,7 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             }
         }
         if (att_lines) rc = conv1d_lines(reinterpret_cast<const unsigned short*>(ws.att), L.attn_proj_h2, L.attn_proj_b, ws.x, M, d, d, EPI_RESIDUAL, ws.x, false, s);
-        else rc = conv1d(ws.att, L.attn_proj_w, L.attn_proj_wT, L.attn_proj_b, ws.x, M, d, d, EPI_RESIDUAL, ws.x, s, nullptr, false, L.attn_proj_w3, L.attn_proj_h2);
+        else rc = conv1d_encode(ws.att, L.attn_proj_w, L.attn_proj_wT, L.attn_proj_b, ws.x, M, d, d, EPI_RESIDUAL, ws.x, s, L.attn_proj_w3, L.attn_proj_h2);
         if (rc) return rc;
         if (lines) {
             if ((rc = launch_layernorm_lines(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ln_lines, s))) return rc;
@@ -348,8 +370,8 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             continue;
         }
         if ((rc = launch_layernorm(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ws.ln, s))) return rc;
-        if ((rc = conv1d(ws.ln, L.c_fc_w, L.c_fc_wT, L.c_fc_b, nullptr, M, d, 4 * d, EPI_GELU, ws.fc, s, nullptr, false, L.c_fc_w3, L.c_fc_h2))) return rc;
-        if ((rc = conv1d(ws.fc, L.mlp_proj_w, L.mlp_proj_wT, L.mlp_proj_b, ws.x, M, 4 * d, d, EPI_RESIDUAL, ws.x, s, nullptr, false, L.mlp_proj_w3, L.mlp_proj_h2))) return rc;
+        if ((rc = conv1d_encode(ws.ln, L.c_fc_w, L.c_fc_wT, L.c_fc_b, nullptr, M, d, 4 * d, EPI_GELU, ws.fc, s, L.c_fc_w3, L.c_fc_h2))) return rc;
+        if ((rc = conv1d_encode(ws.fc, L.mlp_proj_w, L.mlp_proj_wT, L.mlp_proj_b, ws.x, M, 4 * d, d, EPI_RESIDUAL, ws.x, s, L.mlp_proj_w3, L.mlp_proj_h2))) return rc;
     }
     size_t part0 = 0;                                                   // scratch offset of the launch's first batch
     for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {

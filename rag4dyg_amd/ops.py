@@ -229,6 +229,67 @@ def conv1d_s3(x, planes, bias, epilogue="none", residual=None):
     return y
 
 
+_ENCODE_PRECISIONS = {"fp32": 0, "bf16": 1}
+_ENCODE_PRECISION = None
+
+
+def resolve_encode_precision(precision=None):
+    """``"fp32"`` or ``"bf16"``.  None -> the environment variable ``R4D_ENCODE_PRECISION``, ``fp32`` when it is unset or empty.
+    Anything else raises."""
+    if precision is None:
+        import os
+        precision = os.environ.get("R4D_ENCODE_PRECISION") or "fp32"
+    if precision not in _ENCODE_PRECISIONS:
+        raise ValueError(f"encode precision {precision!r}: expected one of {sorted(_ENCODE_PRECISIONS)}")
+    return precision
+
+
+def encode_precision():
+    """Arithmetic of the encoder FORWARD GEMMs (``encode``, ``encode_groups*``, ``prefill``, ``prefill_last``, ``forward()``,
+    ``retrieval.encode_batches``): ``"fp32"`` (default) -- the fp32-accurate arithmetic :func:`gemm_mode` names; ``"bf16"`` -- both
+    operands rounded to bf16, one matrix-core product per fp32 product (``csrc/gemm_b1.hip``).  "bf16" is NOT fp32-accurate
+    (DESIGN.md 7): retrieval under it is approximate, and greedy decoding prefills in bf16 while the cached step stays fp32.
+    ``R4D_ENCODE_PRECISION=bf16`` (read once, at the first call) or :func:`set_encode_precision` select it.  Process-wide: the
+    ranks of a sharded job must agree."""
+    if _ENCODE_PRECISION is None:
+        set_encode_precision(resolve_encode_precision())
+    return _ENCODE_PRECISION
+
+
+def set_encode_precision(precision):
+    """Select :func:`encode_precision` ("fp32" | "bf16"; anything else raises ValueError and changes nothing).  Returns the
+    previous setting."""
+    global _ENCODE_PRECISION
+    if precision not in _ENCODE_PRECISIONS:
+        raise ValueError(f"encode precision {precision!r}: expected one of {sorted(_ENCODE_PRECISIONS)}")
+    prev = _ENCODE_PRECISION if _ENCODE_PRECISION is not None else resolve_encode_precision()
+    _lib.load().r4d_set_encode_bf16(_ENCODE_PRECISIONS[precision])
+    _ENCODE_PRECISION = precision
+    return prev
+
+
+def bf16_plane(w, transposed=False):
+    """Static Conv1D weight [K,N] (``transposed``: an [N,K] copy) -> its round-to-nearest-even bf16 image as ONE k-contiguous
+    plane, an int16 tensor [N,K] (torch's bfloat16 bit patterns of ``w.t()``): plane 0 of :func:`split3_planes`, the weight
+    operand of :func:`conv1d_bf16`."""
+    return split3_planes(w, transposed)[0].clone()
+
+
+def conv1d_bf16(x, w_bf16, bias, epilogue="none", residual=None):
+    """y = epilogue(bf16(x) @ bf16(W) + bias) with ONE bf16 matrix-core product per fp32 product and fp32 accumulation: NOT
+    fp32-accurate (8 significant bits per operand).  ``w_bf16`` from :func:`bf16_plane`; K % 32 == 0.  The kernel the encoder
+    runs under ``encode_precision() == "bf16"``."""
+    N, K = w_bf16.shape
+    M = x.numel() // K
+    y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
+    epi = {"none": 0, "gelu": 1, "residual": 2}[epilogue]
+    rp = _dev(residual, torch.float32, "residual") if residual is not None else None
+    bp = _dev(bias, torch.float32, "bias") if bias is not None else None
+    check(_lib.load().r4d_conv1d_bf16_f32(_dev(x, torch.float32, "x"), _dev(w_bf16, torch.int16, "w_bf16"), bp, rp, M, K, N, epi,
+                                          y.data_ptr(), _stream()), "conv1d_bf16")
+    return y
+
+
 def set_attention_fused(mode):
     """-1 / None: auto by head_dim (default); True: fused flash-style kernel; False: three-launch GEMM form."""
     _lib.load().r4d_set_attention_fused(-1 if mode is None or mode == -1 else (2 if mode == 2 else int(bool(mode))))

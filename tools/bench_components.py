@@ -4,6 +4,8 @@
   scan      (S+1)/2 cosine scan at the reference query batch (32) over N pool rows + top-10
   jaccard   f64 Jaccard matrices: real hepth/11 sets (golden fixture) and a synthetic 20k x 20k scale-up
   pool      pool-encode sequences/s (reference batching, fused groups)
+  encode_precision   the bench step's encode, val-mode greedy decode and the real-data top-10 lists under
+            ops.set_encode_precision("bf16") beside the f16x2 and bf16x3 arithmetics (alternated in one process)
 Each line: achieved = algorithmic bytes / HIP-event time of the kernel class (r4d_profile_* hooks), peak 8 TB/s.
 CPU baselines: oracle single-thread python-set Jaccard (as retrieval_data_annotation.py:36-41) on a bounded sample.
 """
@@ -162,6 +164,111 @@ def pool():
         el = time.perf_counter() - t0
         emit(component="pool_encode", shape=name, sequences=12500, padded_tokens=int(sum(x.numel() for x in b)),
              seqs_per_s=round(12500 / el, 1))
+
+
+def _alternate(arms, run, rounds=5):
+    """``arms``: name -> (encode precision, gemm mode); ``run()`` -> (seconds of device time, units of work).  Every arm in every
+    round, round after round; -> name -> list of rates."""
+    out = {n: [] for n in arms}
+    for _ in range(rounds):
+        for n, (prec, mode) in arms.items():
+            ops.set_encode_precision(prec); ops.set_gemm_mode(mode)
+            el, work = run()
+            out[n].append(work / el)
+    return out
+
+
+def encode_precision():
+    """The opt-in bf16 precision of the encoder forward (ops.set_encode_precision) beside the default f16x2 and bf16x3:
+    (a) bench.py's encode step -- ``encode_groups_meanpool`` of 8 query batches of 32 -- on the UCI_13 and wikiv2 shapes, device
+    events around 10 steps behind 2 warm-up steps, the arms alternated over 5 rounds; with the per-class launch times of one arm;
+    (b) val-mode greedy decode (SimpleDyG loop, 11 tokens per prompt, batches of 32) at the UCI_13 generator model L6 H8 d768:
+    tokens/s, wall clock around a synchronised batch loop;
+    (c) recorded, not gated: the bf16 top-10 lists on the real UCI_13 (G4) and wikiv2 (G12) fixtures against the golden lists."""
+    import statistics
+    from bench import build_model
+    from oracle import gpt2_ref
+    from rag4dyg_amd.evaluation import greedy_decode_batch
+    from rag4dyg_amd.gpt2 import GPT2Config, GPT2LMHeadModel, GPT2LMHeadModelRAG
+    from rag4dyg_amd.retrieval import PoolIndex, encode_batches, right_pad_batches
+    was = (ops.encode_precision(), ops.gemm_mode())
+    arms = {"bf16": ("bf16", "f16x2"), "f16x2": ("fp32", "f16x2"), "bf16x3": ("fp32", "bf16x3")}
+    med = lambda v: statistics.median(v)
+    try:
+        for name in ("UCI_13", "wikiv2"):
+            shape = synth.SHAPES[name]
+            m = build_model(shape, dev)
+            qb = right_pad_batches(synth.sequences(shape, 32 * 96, "query", seed=9000), 32, shape.pad_id, dev)
+            groups = [qb[i:i + 8] for i in range(0, len(qb), 8)]
+            rows = sum(b.numel() for g_ in groups[2:] for b in g_) / 10.0
+
+            def run():
+                for g_ in groups[:2]:
+                    m.encode_groups_meanpool(g_)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for g_ in groups[2:]:
+                    m.encode_groups_meanpool(g_)
+                b.record(); torch.cuda.synchronize()
+                return a.elapsed_time(b) * 1e-3, 10.0
+            rates = _alternate(arms, run)
+            ms = {n: [1e3 / r for r in v] for n, v in rates.items()}
+            ops.set_encode_precision("bf16"); ops.set_gemm_mode("f16x2")
+            _wall, classes = profile(lambda: m.encode_groups_meanpool(groups[2]), 5)
+            emit(component="encode_step", shape=name, batches_per_step=8, mean_token_rows_per_step=round(rows),
+                 ms_per_step={n: round(med(v), 3) for n, v in ms.items()}, ms_min_max={n: [round(min(v), 3), round(max(v), 3)] for n, v in ms.items()},
+                 bf16_over_f16x2=round(med(ms["bf16"]) / med(ms["f16x2"]), 3), bf16_over_bf16x3=round(med(ms["bf16"]) / med(ms["bf16x3"]), 3),
+                 bf16_arm_classes={k: dict(us=round(v["us"], 1), launches=v["launches"]) for k, v in classes.items()})
+        # (b) val-mode decode
+        shape = synth.SHAPES["UCI_13"]
+        L, H, d, V = 6, 8, 768, shape.vocab
+        sd = gpt2_ref.make_state_dict(L, d, V, n_positions=1024, seed=4, random_affine=True)
+        model = GPT2LMHeadModel(GPT2Config(vocab_size=V, n_positions=1024, n_ctx=1024, n_embd=d, n_layer=L, n_head=H))
+        model.load_state_dict(sd, strict=False); model.tie_weights()
+        model = model.to(dev).eval()
+        import types
+        tok = types.SimpleNamespace(encode=lambda s_: [shape.v0])
+        prompts = [s_.tolist() for s_ in synth.sequences(shape, 256, "query", seed=2)]
+
+        def run_decode():
+            greedy_decode_batch(model, tok, prompts[:32], "val", 1024, 12, dev); torch.cuda.synchronize()
+            t0, n = time.perf_counter(), 0
+            for b0 in range(0, len(prompts), 32):
+                outs = greedy_decode_batch(model, tok, prompts[b0:b0 + 32], "val", 1024, 12, dev)
+                n += sum(len(o) - len(p) for o, p in zip(outs, prompts[b0:b0 + 32]))
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, float(n)
+        tps = _alternate(arms, run_decode, rounds=3)
+        emit(component="val_decode", shape="UCI_13", model=f"L{L} H{H} d{d} V{V}", prompts=len(prompts), batch=32,
+             mean_prompt_len=round(float(np.mean([len(p) for p in prompts])), 1),
+             tokens_per_s={n: round(med(v), 1) for n, v in tps.items()}, tokens_per_s_min_max={n: [round(min(v), 1), round(max(v), 1)] for n, v in tps.items()})
+        # (c) real-data retrieval under bf16 against the golden top-10 lists
+        gold = os.path.join(REPO, "tests", "golden")
+        unrag = lambda flat, off: [flat[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)]
+        for fixture, tokens in (("g4_uci_retrieval", "g6_uci_tokens"), ("g12_wikiv2_retrieval", "g6_wikiv2_tokens")):
+            g, k = np.load(os.path.join(gold, fixture + ".npz")), np.load(os.path.join(gold, tokens + ".npz"))
+            if fixture.startswith("g4"):
+                L, H, d, V, ref10 = 4, 2, 512, 1801, g["top10_stable"]
+            else:
+                (L, H, d, V), ref10 = (int(x) for x in g["cfg"]), g["top32_idx"][:, :10]
+            sd = gpt2_ref.make_state_dict(L, d, V, seed=int(g["seed"]), random_affine=True)
+            m = GPT2LMHeadModelRAG(GPT2Config(vocab_size=V, n_positions=1024, n_ctx=1024, n_embd=d, n_layer=L, n_head=H))
+            m.load_state_dict(sd, strict=False); m.tie_weights()
+            m = m.to(dev).eval()
+            pad = int(k["pad_id"])
+            res = {}
+            for n, (prec, mode) in arms.items():
+                ops.set_encode_precision(prec); ops.set_gemm_mode(mode)
+                pool = encode_batches(m, right_pad_batches(unrag(k["pool_flat"], k["pool_off"]), 32, pad, dev))
+                q = encode_batches(m, right_pad_batches(unrag(k["test_flat"], k["test_off"]), 32, pad, dev))
+                idx = PoolIndex(pool).search(q, 10)[1].cpu().numpy()
+                inter = [len(set(a.tolist()) & set(b.tolist())) for a, b in zip(idx, ref10)]
+                res[n] = dict(mean_overlap_of_10=round(float(np.mean(inter)), 3), min_overlap=int(min(inter)),
+                              lists_identical=round(float((idx == ref10).all(axis=1).mean()), 4), top1_identical=round(float((idx[:, 0] == ref10[:, 0]).mean()), 4))
+            emit(component="retrieval_top10_vs_golden", fixture=fixture, queries=int(ref10.shape[0]), pool=int(len(k["pool_off"]) - 1), **res)
+    finally:
+        ops.set_encode_precision(was[0]); ops.set_gemm_mode(was[1])
 
 
 def generator(shape_name="UCI_13", L=6, H=8, d=768, topk=7, pool_n=512):
@@ -424,5 +531,5 @@ if __name__ == "__main__":
             training = functools.partial(training, **{flag[2:]: sys.argv[i + 1]})
             del sys.argv[i:i + 2]
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):
-        {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "generator": generator,
+        {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "generator": generator,
          "generator_reddit": generator_reddit, "simpledyg": simpledyg_eval, "training": training, "training_cpu": training_cpu}[part]()

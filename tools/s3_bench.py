@@ -4,6 +4,7 @@ k-contiguous weight copy) on the encoder's shapes -- time per launch, effective 
 float64 product (max-norm and element-wise).  Each forced tile (R4D_GEMM_S3_TILE) runs in a fresh process.
 
     python tools/s3_bench.py [tile ...]        # default: 0 1 auto
+    python tools/s3_bench.py bf16 [tile ...]   # the plain-bf16 kernel (r4d_conv1d_bf16_f32, R4D_GEMM_B1_TILE) against f16x2 and bf16x3
 """
 import json
 import os
@@ -96,8 +97,60 @@ def child():
         print(json.dumps({"tile": tile, "M": M, "K": K, "N": N, "epi": epi, **out}), flush=True)
 
 
+def bf16_child():
+    """The four Conv1D launches of the UCI_13 bench step at that step's row count: the plain-bf16 kernel, the f16x2 launch as the
+    encoder makes it (A as lines, LDS-DMA; the default arithmetic) and bf16x3, ALTERNATED round by round in one process, each
+    round warmed up and timed with device events.  One JSON line per shape: median / min / max per arm, bf16's share of f16x2."""
+    import statistics
+    import torch
+    sys.path.insert(0, REPO)
+    from rag4dyg_amd import ops
+    dev = torch.device("cuda:0")
+    tile = os.environ.get("R4D_GEMM_B1_TILE", "auto")
+    g = torch.Generator(device=dev).manual_seed(1)
+    for M, K, N, epi in SHAPES[:4]:
+        x = torch.randn(M, K, device=dev, generator=g)
+        w = torch.randn(K, N, device=dev, generator=g) * 0.02
+        b = torch.randn(N, device=dev, generator=g)
+        r = torch.randn(M, N, device=dev, generator=g) if epi == "residual" else None
+        plane, planes3, planes2, lines = ops.bf16_plane(w), ops.split3_planes(w), ops.split2_planes(w), ops.split2_lines(x)
+        arms = {"bf16": lambda: ops.conv1d_bf16(x, plane, b, epi, r),
+                "f16x2": lambda: ops.conv1d_h2p(lines, planes2, b, epi, r, out_lines=(epi == "gelu")),
+                "bf16x3": lambda: ops.conv1d_s3(x, planes3, b, epi, r)}
+        us = {n: [] for n in arms}
+        for _round in range(7):
+            for name, fn in arms.items():
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                us[name].append(e0.elapsed_time(e1) / 20 * 1e3)
+        out = {"bench": "bf16_launch", "b1_tile": tile, "M": M, "K": K, "N": N, "epi": epi}
+        for name, v in us.items():
+            out[name + "_us"] = round(statistics.median(v), 1)
+            out[name + "_us_min_max"] = [round(min(v), 1), round(max(v), 1)]
+        out["bf16_TF"] = round(2.0 * M * K * N / statistics.median(us["bf16"]) / 1e6, 1)
+        out["bf16_over_f16x2"] = round(statistics.median(us["bf16"]) / statistics.median(us["f16x2"]), 3)
+        print(json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "child":
+    if len(sys.argv) > 1 and sys.argv[1] == "bf16_child":
+        bf16_child()
+    elif len(sys.argv) > 1 and sys.argv[1] == "bf16":
+        for t in (sys.argv[2:] or ["auto"]):
+            env = dict(os.environ)
+            if t != "auto":
+                env["R4D_GEMM_B1_TILE"] = t
+            else:
+                env.pop("R4D_GEMM_B1_TILE", None)
+            subprocess.run([sys.executable, __file__, "bf16_child"], env=env, check=True)
+    elif len(sys.argv) > 1 and sys.argv[1] == "child":
         child()
     else:
         for t in (sys.argv[1:] or ["0", "1", "auto"]):
