@@ -537,6 +537,40 @@ int r4d_get_train_attention(void);
 int r4d_set_train_activations(int32_t mode);
 int r4d_get_train_activations(void);
 
+/* Mixed-precision training: plain bf16 operands for the twelve Conv1D GEMMs of every transformer block (process-wide; additive
+ * ABI v6 entries; csrc/gemm_b1.hip, csrc/gemm_b1tn.hip).  NOT fp32-accurate: each operand of those GEMMs is rounded to bf16 (8
+ * significant bits, round to nearest even) and multiplied ONCE on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
+ *   forward        y  = epilogue(RN(x) . RN(W) + b)          plane 0 of *_w3  (RN(W) as [out][in])
+ *   data gradient  dx = RN(dy) . RN(W)^T                     plane 0 of *_w3t (RN(W) as [in][out])
+ *   weight grad.   dW = RN(x)^T . RN(dy),  db = column sums of the UNROUNDED dy
+ * Master weights, gradients, the optimizer, LayerNorm, softmax, GELU, the losses, the embedding scatter and every accumulator stay
+ * fp32; the attention GEMMs stay exact f32; the LM head's three GEMMs, r4d_weight_grad_f32, the GCN projection of the RAG step
+ * and every encoder / decode entry do not read the switch.  A layer GEMM is switched in EVERY gemm mode (f32 included) whenever
+ * the layer carries the plane and the shape is supported (K % 32 == 0; weight gradient: in % 128 == 0, out % 256 == 0, rows >=
+ * 32); anything else keeps the gemm mode's kernel.  Only plane 0 of the plane sets is read by the switched GEMMs.
+ * r4d_set_train_bf16(on != 0) returns the previous setting; default 0.  Read once by the three workspace queries and by every
+ * training forward / backward / step call: set it BEFORE the size query and keep it until the step's backward has been issued.  A
+ * backward on the workspace of the most recent training forward under the other setting is refused (R4D_ERR_INVALID): under
+ * activation recompute its re-forward would differ from the forward. */
+int r4d_set_train_bf16(int32_t on);
+int r4d_get_train_bf16(void);
+/* The single ops of that mode, exported for per-op tests and tools (the kernels the step launches; not read by the switch).
+ * r4d_conv1d_bf16_keep_f32: the c_fc forward: pre_d [M,N] = RN(x) . W + b (the kept pre-activation), y_d [M,N] = gelu_new(pre).
+ * r4d_conv1d_bf16_dgrad_f32: dx_d [M,in] = RN(dy_d [M,out]) . wt_bf16_d^T with wt_bf16_d [in][out] = plane 0 of the layer's *_w3t;
+ *   kind 0 none, 1 dx = second_d + ..., 2 dx = (...) * gelu_new'(second_d) (second_d [M,in]).  out % 32 == 0.
+ * r4d_weight_grad_bf16_f32: dw_d [in,out] = RN(x)^T . RN(dy), db_d [out] (nullable, 16-byte aligned) = column sums of dy, for
+ *   x_d [rows, in] with row stride ldx and dy_d [rows, out] with row stride ldy (floats, multiples of 4, >= in / out).  in % 128
+ *   == 0, out % 256 == 0, rows >= 32, else R4D_ERR_INVALID and nothing is launched (the size query returns 0).  The contraction
+ *   is split over slices whose fp32 partials the workspace holds; they are written before they are summed, in slice order: the
+ *   same bits on every run, whatever the workspace held. */
+int r4d_conv1d_bf16_keep_f32(const float* x_d, const uint16_t* w_bf16_d /* [N][K] */, const float* bias_d, int32_t M, int32_t K,
+                             int32_t N, float* pre_d, float* y_d, void* stream);
+int r4d_conv1d_bf16_dgrad_f32(const float* dy_d, const uint16_t* wt_bf16_d /* [in][out] */, int32_t M, int32_t in_features,
+                              int32_t out_features, int32_t kind, const float* second_d, float* dx_d, void* stream);
+size_t r4d_weight_grad_bf16_workspace_bytes(int32_t rows, int32_t in_features, int32_t out_features);
+int r4d_weight_grad_bf16_f32(const float* x_d, int32_t ldx, const float* dy_d, int32_t ldy, int32_t rows, int32_t in_features,
+                             int32_t out_features, float* dw_d, float* db_d, void* workspace_d, size_t workspace_bytes, void* stream);
+
 /* Scratch of one step: the activations the backward pass needs (16 * rows * d floats per layer + the attention
  * probabilities in stored mode) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts);

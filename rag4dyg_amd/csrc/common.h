@@ -44,7 +44,7 @@ enum ProfClass {
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
-    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_COUNT
+    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -84,7 +84,8 @@ struct ProfScope {
     X(JAC_LDS, "jaccard:LDS table") X(JAC_MERGE, "jaccard:merge walk (vocab too large for LDS)")                          \
     X(JAC_PREP_DENSE_LDS, "jaccard_prep:dense tokens, LDS histogram") X(JAC_PREP_DENSE_GLOBAL, "jaccard_prep:dense tokens, global histogram") X(JAC_PREP_ORDER, "jaccard_prep:rows longest first") \
     X(ARGSORT_ONE, "argsort:one chunk") X(ARGSORT_MULTI, "argsort:chunk sort + rank scatter")                              \
-    X(B1_128x256, "tuning:encode_bf16:128x256x32") X(B1_128x128, "tuning:encode_bf16:128x128x32")
+    X(B1_128x256, "tuning:encode_bf16:128x256x32") X(B1_128x128, "tuning:encode_bf16:128x128x32")                           \
+    X(TB_FWD, "tuning:train_bf16:fwd") X(TB_DGRAD, "tuning:train_bf16:dgrad") X(TB_WGRAD, "tuning:train_bf16:wgrad") X(TB_WGRAD_FALLBACK, "tuning:train_bf16:wgrad_fallback")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -102,7 +103,7 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ------------------------------------------------------------------ fp32 MFMA GEMM (gemm_f32.hip)
 enum GemmEpilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_SCALE_DIV = 3, EPI_HALF_PLUS = 4,
-                    // gemm_s3 only (training): GELU_KEEP writes gelu(v) to C and the pre-activation v to the `resid` buffer;
+                    // gemm_s3 and gemm_b1 only (training): GELU_KEEP writes gelu(v) to C and the pre-activation v to the `resid` buffer;
                     // GELU_GRAD writes v * gelu'(u) with u read from the `resid` buffer
                     EPI_GELU_KEEP = 5, EPI_GELU_GRAD = 6,
                     // gemm_h2 only: C receives the result as uint32 "h2 words" (fp16 hi | fp16 lo' << 16 of value / 4: csrc/h2.h), the
@@ -171,8 +172,17 @@ int launch_gemm_h2p(const S3Args& a, const unsigned short* a_lines, bool out_lin
 int launch_split2_lines(const float* x, long long rows, int K, unsigned short* lines, hipStream_t s);
 // gemm_b1.hip: C = epilogue(RN_bf16(A) . RN_bf16(W)^T + bias), one bf16 MFMA per k-step (NOT fp32-accurate); a.planes = ONE bf16
 // plane [N][K] (plane 0 of the bf16x3 planes); the bf16x3 kernel's shape contract; epilogues none / GELU / residual
+// (training, r4d_set_train_bf16: also GELU_KEEP and GELU_GRAD)
 bool gemm_b1_supported(int M, int K, int N);
 int launch_gemm_b1(const S3Args& a, hipStream_t stream);
+// gemm_b1tn.hip: dW[I,J] = RN_bf16(X[M,I])^T . RN_bf16(dY[M,J]), db = column sums of the unrounded dY; gemm_s3tn's shape contract;
+// slices' partials in `part` / `db_part` (their room bounds the slice count), summed in slice order
+bool gemm_b1tn_supported(int I, int J, int M, int lda, int ldb);
+int gemm_b1tn_slices(int I, int J, int M, int max_slices);
+int launch_gemm_b1tn(const float* X, const float* dY, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part,
+                     size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t stream);
+// gemm_f32.hip: C[4 n4] = part[0] + part[1] + ... + part[S-1] (slices of 4 n4 floats), added in that order
+int launch_splitk_reduce(const float* part, long long n4, int S, float* C, hipStream_t stream);
 extern int g_encode_bf16;             // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs on gemm_b1 wherever a layer carries *_w3
 extern int g_gemm_split3;             // Conv1D arithmetic (r4d_set_gemm_split3): 0 exact-f32 MFMA, 1 bf16x3 planes, 2 f16x2 planes (bf16x3 where a layer carries no f16 planes)
 // Conv1D dispatch shared by the encoder and the training forward (encoder.hip): skinny weight stream (decode), bf16x3 planes,
@@ -226,7 +236,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
 // The data-gradient GEMM (Conv1D dx = dy . W^T with b_trans = 1, head dh = dlogits . wte_pad with b_trans = 0): on the bf16x3
 // planes `w3t` when the mode and the shape allow, else exact f32 on `w`; optional residual, optional fused gelu_new' (train.hip)
 int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, int b_trans, int M, int n_out, int k, float* C,
-                   const float* resid, const float* gelu_pre, hipStream_t s);
+                   const float* resid, const float* gelu_pre, hipStream_t s, int bf16 = 0);
 int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, const float* wte, const float* wpe, int vocab, int B,
                            int T, int d, const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s);
 

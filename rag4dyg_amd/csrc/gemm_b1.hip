@@ -33,10 +33,11 @@ __device__ __forceinline__ unsigned cvt_pk_bf16_b1(float a, float b) {   // v_cv
 
 struct B1Shape { int M, N, K, lda, ldc, ldr; };
 
-// Registers: two workgroups per CU (<= 128 VGPRs) -- except the 128 x 256 tile with the residual epilogue, whose 64 accumulators
-// and prefetched residual values do not fit 128 without scratch: that one keeps the whole file (one workgroup per CU)
+// Registers: two workgroups per CU (<= 128 VGPRs) -- except the 128 x 256 tile with an epilogue that READS the second buffer
+// (residual; training: the GELU derivative), whose 64 accumulators and prefetched second-buffer values do not fit 128 without
+// scratch: those keep the whole file (one workgroup per CU)
 template <int BM, int BN, int WGM, int WGN, int EPI>
-__global__ __launch_bounds__(64 * WGM * WGN, (EPI == EPI_RESIDUAL && BN == 256) ? 2 : 4) void gemm_b1_kernel(
+__global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD) && BN == 256) ? 2 : 4) void gemm_b1_kernel(
     const float* __restrict__ Ag, const unsigned short* __restrict__ Bp, float* __restrict__ Cg,
     const float* __restrict__ biasg, const float* __restrict__ residg, const B1Shape g) {
     constexpr int BK = 32, NBUF = 3, D = NBUF - 1;                    // D k-tiles between an LDS store and its use
@@ -197,7 +198,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (EPI == EPI_RESIDUAL && BN == 256) 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-#define B1_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL)      // what the encoder forward uses
+// what the encoder forward uses, and the two kinds of the training step (c_fc forward with the kept pre-activation; the mlp
+// c_proj data gradient times gelu_new'(pre))
+#define B1_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_GRAD)
 template <int BM, int BN, int WGM, int WGN>
 static int launch_b1(const S3Args& a, hipStream_t stream) {
     const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
@@ -223,7 +226,7 @@ int launch_gemm_b1(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.A && a.planes && a.C, "gemm_b1: null pointer");
     R4D_REQUIRE(gemm_b1_supported(a.M, a.K, a.N), "gemm_b1: unsupported shape M=%d K=%d N=%d (K %% 32 == 0 wanted)", a.M, a.K, a.N);
     R4D_REQUIRE(a.lda % 4 == 0 && ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.planes % 16) == 0, "gemm_b1: alignment");
-    R4D_REQUIRE(a.epilogue != EPI_RESIDUAL || a.resid, "gemm_b1: the residual epilogue needs the second buffer");
+    R4D_REQUIRE((a.epilogue != EPI_RESIDUAL && a.epilogue != EPI_GELU_KEEP && a.epilogue != EPI_GELU_GRAD) || a.resid, "gemm_b1: epilogue %d needs the second buffer", a.epilogue);
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("R4D_GEMM_B1_TILE"); forced = e ? atoi(e) : -1; }   // tuning aid: 0 / 1 forces a tile
     const int t = (forced == 0 || forced == 1) ? forced : pick_tile_128(a.M, a.N);

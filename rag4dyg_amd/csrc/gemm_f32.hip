@@ -371,6 +371,11 @@ static int tn_splits(int M, int N, int Kt) {
     if (S > 64) S = 64;
     return S < 1 ? 1 : S;
 }
+int launch_splitk_reduce(const float* part, long long n4, int S, float* C, hipStream_t stream) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, n4, S, C);
+    R4D_CHECK_LAUNCH("splitk_reduce");
+    return R4D_OK;
+}
 size_t gemm_tn_scratch_floats(int M, int N, int Kt) {
     const int S = tn_splits(M, N, Kt);
     return S > 1 ? (size_t)S * M * N : 0;

@@ -50,10 +50,13 @@ static int g_train_attention = 0;
 // r4d_set_train_activations: 0 stored (the forward keeps ln1 .. f of every layer), 1 recompute (it keeps each layer's input; the
 // backward forms one layer's activations at a time again, with the forward's launches, in ONE set all layers share).
 static int g_train_activations = 0;
-// The two modes as a value: every entry point (size queries, forward, backward) reads the globals ONCE, here, and hands the
+// r4d_set_train_bf16: 0 the gemm mode's arithmetic (default), 1 the twelve Conv1D GEMMs of a block on plain bf16 operands
+// (gemm_b1.hip, gemm_b1tn.hip) wherever the layer carries the plane and the shape is supported.  NOT fp32-accurate.
+static int g_train_bf16 = 0;
+// The three modes as a value: every entry point (size queries, forward, backward) reads the globals ONCE, here, and hands the
 // value down; nothing below an entry point looks at a global.
-struct TrainModes { int attention, activations; };
-static TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations}; }
+struct TrainModes { int attention, activations, bf16; };
+static TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations, g_train_bf16}; }
 // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
 static bool train_fuse_gelu() {
     static const int v = [] { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); return e ? atoi(e) : 1; }();
@@ -62,7 +65,7 @@ static bool train_fuse_gelu() {
 // The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
 // activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
 // would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
-static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0}, -1};
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -157,8 +160,18 @@ static int check_groups(const r4d_gpt2_config* cfg, int n_groups, const int64_t*
 
 // y[M,N] = epilogue(x[M,K] . W[K,N] + bias)   (Conv1D.forward, modeling_utils.py:1267-1271).  `wT` (nullable): the caller's
 // CURRENT [N,K] copy of the weight (refreshed after every optimizer step) -> the k-contiguous kernel; else the reference layout
+// `bf16` (r4d_set_train_bf16, decided HERE and not in conv1d, which the encoder shares): plane 0 of `w3` on the plain-bf16 kernel
+static bool fwd_linear_bf16(int bf16, const unsigned short* w3, int M, int K, int N) { return bf16 && w3 && gemm_b1_supported(M, K, N); }
 static int fwd_linear(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K, int N,
-                      int epi, float* y, hipStream_t s, const unsigned short* w3 = nullptr, const unsigned short* w2h = nullptr) {
+                      int epi, float* y, hipStream_t s, const unsigned short* w3, const unsigned short* w2h, int bf16) {
+    if (fwd_linear_bf16(bf16, w3, M, K, N)) {
+        S3Args a;
+        memset(&a, 0, sizeof(a));
+        a.A = x; a.planes = w3; a.C = y; a.bias = bias; a.resid = resid;
+        a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epi;
+        R4D_BRANCH(TB_FWD);
+        return launch_gemm_b1(a, s);
+    }
     return conv1d(x, w, wT, bias, resid, M, K, N, epi, y, s, nullptr, false, w3, w2h);     // f16x2 planes (mode 2) > bf16x3 planes > [N,K] copy > reference layout
 }
 // The data-gradient GEMM of the training steps: C[M, n_out] = epilogue(A[M, k] . W), A a GRADIENT, W one of
@@ -171,9 +184,21 @@ static int fwd_linear(const float* x, const float* w, const float* wT, const flo
 //  the f16x2 form has fp16's exponent range: below 2.4e-4 an element's absolute error stops shrinking (6e-11), i.e. 1e-4 relative at
 //  1e-6.  Built and measured in round 5 (46.9 instead of 50.6 ms per step, G8 green at its max-norm bounds), then taken out: a
 //  per-tensor power-of-two scale from an absmax pass would be needed to make it safe, and that pass costs what the kernel saves.)
+// `bf16` (r4d_set_train_bf16; the Conv1D form only): RN_bf16(A) . plane 0 of `w3t` on the plain-bf16 kernel, in every gemm mode.
+static bool data_grad_bf16(int bf16, const unsigned short* w3t, int b_trans, int M, int n_out, int k) {
+    return bf16 && b_trans == 1 && w3t && gemm_b1_supported(M, k, n_out);
+}
 int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, int b_trans, int M, int n_out, int k, float* C,
-                   const float* resid, const float* gelu_pre, hipStream_t s) {
+                   const float* resid, const float* gelu_pre, hipStream_t s, int bf16) {
     const int epi = gelu_pre ? EPI_GELU_GRAD : resid ? EPI_RESIDUAL : EPI_NONE;
+    if (data_grad_bf16(bf16, w3t, b_trans, M, n_out, k)) {
+        S3Args a;
+        memset(&a, 0, sizeof(a));
+        a.A = A; a.planes = w3t; a.C = C; a.resid = gelu_pre ? gelu_pre : resid;
+        a.M = M; a.N = n_out; a.K = k; a.lda = k; a.ldc = n_out; a.ldr = n_out; a.epilogue = epi;
+        R4D_BRANCH(TB_DGRAD);
+        return launch_gemm_b1(a, s);
+    }
     if (w3t && g_gemm_split3 && gemm_s3_supported(M, k, n_out)) {
         S3Args a;
         memset(&a, 0, sizeof(a));
@@ -192,15 +217,27 @@ int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, in
     return launch_gemm_f32(g, s);
 }
 // dx[M,K] = dy[M,N] . W[K,N]^T (Conv1D backward); `w3t`: W's planes [3][K][N]
-static int bwd_data(const float* dy, const float* w, int M, int K, int N, float* dx, hipStream_t s,
-                    const unsigned short* w3t = nullptr, const float* gelu_pre = nullptr) {
-    return data_grad_gemm(dy, w, w3t, 1, M, K, N, dx, nullptr, gelu_pre, s);
+static int bwd_data(const float* dy, const float* w, int M, int K, int N, float* dx, hipStream_t s, const unsigned short* w3t,
+                    const float* gelu_pre, int bf16) {
+    return data_grad_gemm(dy, w, w3t, 1, M, K, N, dx, nullptr, gelu_pre, s, bf16);
 }
 // dW[K,N] = x[M,K]^T . dy[M,N]: both operands read row by row over the contracted token index (split-K partials in `skp`);
 // db[N] = column sums of dy
+// `bf16` (r4d_set_train_bf16): RN_bf16(x)^T . RN_bf16(dy) on gemm_b1tn where its shape contract holds (db stays the fp32 sum of
+// the unrounded dy); `skp` holds gemm_tn_scratch_floats(K, N, M) floats, which bounds that kernel's slices.  Else today's kernel.
 static int bwd_weight(const float* x, const float* dy, int M, int K, int N, float* dW, float* db, float* skp, float* red,
-                      hipStream_t s) {
+                      hipStream_t s, int bf16) {
     bool db_done = false;                                             // the bf16x3 kernel sums dy's columns while it stages them
+    if (bf16) {
+        if (gemm_b1tn_supported(K, N, M, K, N)) {
+            R4D_BRANCH(TB_WGRAD);
+            const int rc = launch_gemm_b1tn(x, dy, dW, db, K, N, M, K, N, skp, gemm_tn_scratch_floats(K, N, M), red,
+                                            colsum_scratch_floats(M, N), &db_done, s);
+            if (rc) return rc;
+            return (db && !db_done) ? launch_colsum(dy, M, N, N, db, red, 0, s) : R4D_OK;
+        }
+        R4D_BRANCH(TB_WGRAD_FALLBACK);
+    }
     const int rc = launch_gemm_f32_tn(x, dy, dW, K, N, M, K, N, skp, s, db, red, colsum_scratch_floats(M, N), &db_done);
     if (rc) return rc;
     return (db && !db_done) ? launch_colsum(dy, M, N, N, db, red, 0, s) : R4D_OK;
@@ -336,7 +373,7 @@ int r4d_weight_grad_f32(const float* x_d, const float* dy_d, int32_t rows, int32
                 "weight_grad: workspace too small");
     float* skp = (float*)workspace_d;
     float* red = skp + (gemm_tn_scratch_floats(in_features, out_features, rows) + 63) / 64 * 64;
-    return bwd_weight(x_d, dy_d, rows, in_features, out_features, dw_d, db_d, skp, red, (hipStream_t)stream);
+    return bwd_weight(x_d, dy_d, rows, in_features, out_features, dw_d, db_d, skp, red, (hipStream_t)stream, 0);
 }
 
 int r4d_set_train_attention(int32_t mode) {
@@ -352,6 +389,67 @@ int r4d_set_train_activations(int32_t mode) {
     return R4D_OK;
 }
 int r4d_get_train_activations(void) { return g_train_activations; }
+
+int r4d_set_train_bf16(int32_t on) {
+    const int prev = g_train_bf16;
+    g_train_bf16 = on != 0;
+    return prev;
+}
+int r4d_get_train_bf16(void) { return g_train_bf16; }
+
+int r4d_conv1d_bf16_keep_f32(const float* x_d, const uint16_t* w_bf16_d, const float* bias_d, int32_t M, int32_t K, int32_t N,
+                             float* pre_d, float* y_d, void* stream) {
+    R4D_REQUIRE(pre_d && y_d && pre_d != y_d, "conv1d_bf16_keep: two output buffers wanted");
+    S3Args a;
+    memset(&a, 0, sizeof(a));
+    a.A = x_d; a.planes = w_bf16_d; a.C = y_d; a.bias = bias_d; a.resid = pre_d;
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = EPI_GELU_KEEP;
+    return launch_gemm_b1(a, (hipStream_t)stream);
+}
+
+int r4d_conv1d_bf16_dgrad_f32(const float* dy_d, const uint16_t* wt_bf16_d, int32_t M, int32_t in_features, int32_t out_features,
+                              int32_t kind, const float* second_d, float* dx_d, void* stream) {
+    R4D_REQUIRE(kind >= 0 && kind <= 2, "conv1d_bf16_dgrad: kind %d not in {0 none, 1 residual, 2 gelu derivative}", kind);
+    R4D_REQUIRE(kind == 0 || second_d, "conv1d_bf16_dgrad: kind %d needs the second buffer", kind);
+    S3Args a;
+    memset(&a, 0, sizeof(a));
+    a.A = dy_d; a.planes = wt_bf16_d; a.C = dx_d; a.resid = kind ? second_d : nullptr;
+    a.M = M; a.N = in_features; a.K = out_features; a.lda = out_features; a.ldc = in_features; a.ldr = in_features;
+    a.epilogue = kind == 2 ? EPI_GELU_GRAD : kind == 1 ? EPI_RESIDUAL : EPI_NONE;
+    return launch_gemm_b1(a, (hipStream_t)stream);
+}
+
+// workspace of the single op: the slices' dW partials (64-float aligned), behind them their db partials
+static size_t wgrad_bf16_part_floats(int rows, int I, int J, int* S) {
+    *S = gemm_b1tn_slices(I, J, rows, 64);
+    return *S > 1 ? ((size_t)*S * I * J + 63) / 64 * 64 : 0;
+}
+size_t r4d_weight_grad_bf16_workspace_bytes(int32_t rows, int32_t in_features, int32_t out_features) {
+    if (!gemm_b1tn_supported(in_features, out_features, rows, in_features, out_features)) return 0;
+    int S;
+    const size_t part = wgrad_bf16_part_floats(rows, in_features, out_features, &S);
+    return (part + (S > 1 ? (size_t)S * out_features : 0) + 64) * sizeof(float);
+}
+
+int r4d_weight_grad_bf16_f32(const float* x_d, int32_t ldx, const float* dy_d, int32_t ldy, int32_t rows, int32_t in_features,
+                             int32_t out_features, float* dw_d, float* db_d, void* workspace_d, size_t workspace_bytes, void* stream) {
+    R4D_REQUIRE(x_d && dy_d && dw_d, "weight_grad_bf16: null pointer");
+    R4D_REQUIRE(gemm_b1tn_supported(in_features, out_features, rows, ldx, ldy),
+                "weight_grad_bf16: unsupported shape rows=%d in=%d out=%d ldx=%d ldy=%d (in %% 128 == 0, out %% 256 == 0, rows >= 32 wanted)",
+                rows, in_features, out_features, ldx, ldy);
+    R4D_REQUIRE(workspace_d && ((uintptr_t)workspace_d % 16) == 0 &&
+                workspace_bytes >= r4d_weight_grad_bf16_workspace_bytes(rows, in_features, out_features), "weight_grad_bf16: workspace too small");
+    R4D_REQUIRE(!db_d || ((uintptr_t)db_d % 16) == 0, "weight_grad_bf16: db must be 16-byte aligned");
+    int S;
+    const size_t part = wgrad_bf16_part_floats(rows, in_features, out_features, &S);
+    float* ws = (float*)workspace_d;
+    bool db_done = false;
+    const int rc = launch_gemm_b1tn(x_d, dy_d, dw_d, db_d, in_features, out_features, rows, ldx, ldy, ws, part, ws + part,
+                                    S > 1 ? (size_t)S * out_features : 0, &db_done, (hipStream_t)stream);
+    if (rc) return rc;
+    R4D_REQUIRE(!db_d || db_done, "weight_grad_bf16: the bias gradient was not formed");
+    return R4D_OK;
+}
 
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts) {
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
@@ -392,7 +490,7 @@ size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, con
 static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int l, const TrainLayout& t,
                          const std::vector<TrainGroup>& gs, const RowGroups& R, const DropCtx& dc, float* ws,
                          const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const SpliceIn* sp, bool again,
-                         hipStream_t s) {
+                         int bf16, hipStream_t s) {
     const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M;
     const r4d_gpt2_layer& Lw = w->layers[l];
     R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
@@ -413,29 +511,29 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
         if ((rc = launch_dropout(x_in, nullptr, (long long)M * d, x_in, dc.embd_p, dc.key, R4D_DROPOUT_SITE_EMBD, 0, s))) return rc;
         if ((rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s))) return rc;
     }
-    if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2))) return rc;
+    if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2, bf16))) return rc;
     for (const TrainGroup& G : gs)
         if ((rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
                            att + G.row0 * d, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
     float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
     if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
-        if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
+        if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2, bf16))) return rc;
         if ((rc = launch_dropout(branch, x_in, (long long)M * d, x_mid, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
-    } else if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, x_in, M, d, d, EPI_RESIDUAL, x_mid, s, Lw.attn_proj_w3, Lw.attn_proj_h2))) return rc;
+    } else if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, x_in, M, d, d, EPI_RESIDUAL, x_mid, s, Lw.attn_proj_w3, Lw.attn_proj_h2, bf16))) return rc;
     if ((rc = launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
-    if (train_fuse_gelu() && Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
+    if (train_fuse_gelu() && (fwd_linear_bf16(bf16, Lw.c_fc_w3, M, d, 4 * d) || (Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)))) {
         // one launch: f = gelu_new(v) and the pre-activation v (kept for the backward pass) both leave the GEMM's epilogue
-        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, pre, M, d, 4 * d, EPI_GELU_KEEP, f, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
+        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, pre, M, d, 4 * d, EPI_GELU_KEEP, f, s, Lw.c_fc_w3, Lw.c_fc_h2, bf16))) return rc;
     } else {
-        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, nullptr, M, d, 4 * d, EPI_NONE, pre, s, Lw.c_fc_w3, Lw.c_fc_h2))) return rc;
+        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, nullptr, M, d, 4 * d, EPI_NONE, pre, s, Lw.c_fc_w3, Lw.c_fc_h2, bf16))) return rc;
         if ((rc = launch_gelu_fwd(pre, (long long)M * 4 * d, f, s))) return rc;
     }
     if (again) return R4D_OK;                                    // the MLP projection's output, x_in[l + 1], is there already
     float* x_next = l + 1 < cfg->n_layer ? ws + t.x_in[l + 1] : ws + t.x_out;
     if (dc.resid_p > 0.f) {                                      // x + dropout(c_proj(act(c_fc(x)))), :212,233
-        if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, nullptr, M, 4 * d, d, EPI_NONE, branch, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
+        if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, nullptr, M, 4 * d, d, EPI_NONE, branch, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2, bf16))) return rc;
         if ((rc = launch_dropout(branch, x_mid, (long long)M * d, x_next, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
-    } else if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, x_mid, M, 4 * d, d, EPI_RESIDUAL, x_next, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2))) return rc;
+    } else if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, x_mid, M, 4 * d, d, EPI_RESIDUAL, x_next, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2, bf16))) return rc;
     return R4D_OK;
 }
 
@@ -461,7 +559,7 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
     const int d = cfg->n_embd;
     const RowGroups R = row_groups_of(gs);
     for (int l = 0; l < cfg->n_layer; ++l)
-        if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, false, s))) return rc;
+        if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, false, md.bf16, s))) return rc;
     return launch_lnf_meanpool_groups(R, ws + t.x_out, w->ln_f_w, w->ln_f_b, d, cfg->ln_eps, out_hidden_d, out_meanpool_d,
                                       ws + t.pool_scratch, s);
 }
@@ -487,6 +585,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(!after_fwd || md.activations == g_last_fwd.modes.activations,
                 "gpt2 train backward: this workspace was filled by a forward in train-activations mode %d, the current mode is %d",
                 g_last_fwd.modes.activations, md.activations);
+    R4D_REQUIRE(!after_fwd || md.bf16 == g_last_fwd.modes.bf16,
+                "gpt2 train backward: this workspace was filled by a forward with train-bf16 %d, the current setting is %d",
+                g_last_fwd.modes.bf16, md.bf16);
     const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -518,7 +619,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         // holds the last layer's activations when this backward follows its forward directly: nothing to run again then.
         if (t.act_recompute && !(after_fwd && g_last_fwd.shared_layer == l)) {
             if (after_fwd) g_last_fwd.shared_layer = -1;
-            if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, true, s))) return rc;
+            if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, true, md.bf16, s))) return rc;
             if (after_fwd) g_last_fwd.shared_layer = l;
         }
         // ---- MLP: x_out = x_mid + gelu(ln_2(x_mid) Wfc + bfc) Wp + bp ;  dx holds d(x_out)
@@ -527,16 +628,17 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dy, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
             dbr = dy;
         }
-        if (!frozen && (rc = bwd_weight(f, dbr, M, 4 * d, d, Lg.mlp_proj_w, Lg.mlp_proj_b, xT, red, s))) return rc;
-        if (train_fuse_gelu() && Lw.mlp_proj_w3t && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)) {
+        if (!frozen && (rc = bwd_weight(f, dbr, M, 4 * d, d, Lg.mlp_proj_w, Lg.mlp_proj_b, xT, red, s, md.bf16))) return rc;
+        if (train_fuse_gelu() && (data_grad_bf16(md.bf16, Lw.mlp_proj_w3t, 1, M, 4 * d, d) ||
+                                  (Lw.mlp_proj_w3t && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)))) {
             // d(pre) = (d(branch) . Wp^T) * gelu_new'(pre): the derivative is applied in the GEMM's epilogue
-            if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, pre))) return rc;
+            if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, pre, md.bf16))) return rc;
         } else {
-            if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t))) return rc;                    // d(f)
+            if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, nullptr, md.bf16))) return rc;                    // d(f)
             if ((rc = launch_gelu_bwd(pre, dbig, (long long)M * 4 * d, dbig, s))) return rc;              // d(pre), in place
         }
-        if (!frozen && (rc = bwd_weight(ln2, dbig, M, d, 4 * d, Lg.c_fc_w, Lg.c_fc_b, xT, red, s))) return rc;
-        if ((rc = bwd_data(dbig, Lw.c_fc_w, M, d, 4 * d, dy, s, Lw.c_fc_w3t))) return rc;                              // d(ln_2 out)
+        if (!frozen && (rc = bwd_weight(ln2, dbig, M, d, 4 * d, Lg.c_fc_w, Lg.c_fc_b, xT, red, s, md.bf16))) return rc;
+        if ((rc = bwd_data(dbig, Lw.c_fc_w, M, d, 4 * d, dy, s, Lw.c_fc_w3t, nullptr, md.bf16))) return rc;                              // d(ln_2 out)
         if ((rc = launch_ln_bwd(x_mid, Lw.ln_2_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_2_w, Lg.ln_2_b, red, 0, s))) return rc;   // dx = d(x_mid)
         // ---- attention: x_mid = x_in + attn(ln_1(x_in)) Wo + bo
         dbr = dx;
@@ -544,14 +646,14 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dbig, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
             dbr = dbig;
         }
-        if (!frozen && (rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s))) return rc;
-        if ((rc = bwd_data(dbr, Lw.attn_proj_w, M, d, d, dy, s, Lw.attn_proj_w3t))) return rc;                              // d(att), merged heads
+        if (!frozen && (rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s, md.bf16))) return rc;
+        if ((rc = bwd_data(dbr, Lw.attn_proj_w, M, d, d, dy, s, Lw.attn_proj_w3t, nullptr, md.bf16))) return rc;                              // d(att), merged heads
         for (const TrainGroup& G : gs)                               // stored mode: the kept P, and no block A (pA does not exist)
             if ((rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
                                dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, s,
                                dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
-        if (!frozen && (rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s))) return rc;
-        if ((rc = bwd_data(dqkv, Lw.c_attn_w, M, d, 3 * d, dy, s, Lw.c_attn_w3t))) return rc;                            // d(ln_1 out)
+        if (!frozen && (rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s, md.bf16))) return rc;
+        if ((rc = bwd_data(dqkv, Lw.c_attn_w, M, d, 3 * d, dy, s, Lw.c_attn_w3t, nullptr, md.bf16))) return rc;                            // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)
     }
     // embeddings: x_in[0] = drop(wte[ids] + wpe[0..T-1])

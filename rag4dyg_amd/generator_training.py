@@ -47,7 +47,8 @@ def augmented_ids(tokens, r):
 def check_supported(args):
     """The configurations this build trains; every other one raises here, before any work."""
     if getattr(args, "fp16", False):
-        raise NotImplementedError("generator training: --fp16 (apex mixed precision) is not built; the path is fp32")
+        raise NotImplementedError("generator training: --fp16 (apex mixed precision) is not built; the path is fp32 "
+                                  "(R4D_TRAIN_PRECISION=bf16 selects this project's own mixed precision)")
     if getattr(args, "should_continue", False):
         raise NotImplementedError("generator training: --should_continue (resume) is not built")
     if args.fusion != "graphpooling":
@@ -92,7 +93,7 @@ class GeneratorTrainer:
     """One generator training micro-step on the device for a ``GPT2LMHeadModelRAG`` with ``gnn_fusion`` (one layer).  ``grads``
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
-    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None):
+    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None):
         gnn = getattr(model, "gnn_fusion", None)
         if gnn is None or gnn.n_layers != 1:
             raise _lib.R4DError("GeneratorTrainer: needs a one-layer gnn_fusion (graph pooling)")
@@ -101,7 +102,8 @@ class GeneratorTrainer:
             raise _lib.R4DError("GeneratorTrainer: --freeze needs the untied head of load_and_freeze_params")
         self.model, self.freeze, self.tied = model, bool(freeze), tied
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations,
+                                  precision=precision)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
         for n, p in self.params.items():
@@ -328,7 +330,7 @@ def evaluate(args, trainer, loader, bags):
     return float(total) / n if n else float("nan")
 
 
-def train(args, train_dataset, model, tokenizer, activations=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None):
     """Drop-in for ``train_generator.train`` (:141-248).  Returns (global_step, tr_loss / global_step)."""
     from .generator import get_eval_metrics_generator, load_and_cache_examples
     check_supported(args)
@@ -345,7 +347,7 @@ def train(args, train_dataset, model, tokenizer, activations=None):
     else:
         t_total = len(loader) // gas * args.num_train_epochs
     trainer = GeneratorTrainer(model, freeze=bool(getattr(args, "freeze", False)),
-                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations)
+                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision)
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():
@@ -362,6 +364,7 @@ def train(args, train_dataset, model, tokenizer, activations=None):
     print("  Total optimization steps = {}".format(t_total))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION)".format(trainer.enc.precision))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

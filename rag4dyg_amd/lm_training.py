@@ -79,13 +79,13 @@ class LMTrainer:
     the padded LM-head operand ``wte_pad`` [ldV, d] (zero rows past V) and its planes.  Every derived weight is rebuilt when the
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
-    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None):
+    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None):
         head = getattr(model, "lm_head", None)
         if head is None or head.weight is not model.transformer.wte.weight:
             raise _lib.R4DError("SimpleDyG training needs lm_head tied to transformer.wte (the reference's model is always tied); "
                                 "this model's lm_head is a separate tensor")
         self.model = model
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations, precision=precision)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
@@ -275,11 +275,12 @@ def train_epoch(model, trainer, optimizer, scheduler, train_dataloader, tr_loss,
     return global_step, tr_loss
 
 
-def train(args, train_dataset, model, tokenizer, activations=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None):
     """Drop-in for ``main_SimpleDyG.train`` (:200-343).  Returns (global_step, tr_loss / global_step)."""
     from .evaluation import get_eval_metrics
     if getattr(args, "fp16", False):
-        raise NotImplementedError("SimpleDyG training: --fp16 (apex mixed precision) is not built; the path is fp32")
+        raise NotImplementedError("SimpleDyG training: --fp16 (apex mixed precision) is not built; the path is fp32 "
+                                  "(R4D_TRAIN_PRECISION=bf16 selects this project's own mixed precision)")
     world, rank = distributed_setup(args)
     train_dataloader, args = get_train_dataloader(train_dataset, tokenizer, args)
     gas = max(1, int(getattr(args, "gradient_accumulation_steps", 1)))
@@ -288,7 +289,7 @@ def train(args, train_dataset, model, tokenizer, activations=None):
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
     else:
         t_total = len(train_dataloader) // gas * args.num_train_epochs
-    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations)      # every rank its own dropout masks
+    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision)      # every rank its own dropout masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -306,6 +307,7 @@ def train(args, train_dataset, model, tokenizer, activations=None):
     print("  Gradient Accumulation steps = {}".format(gas))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION)".format(trainer.enc.precision))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

@@ -290,6 +290,57 @@ def conv1d_bf16(x, w_bf16, bias, epilogue="none", residual=None):
     return y
 
 
+def conv1d_bf16_keep(x, w_bf16, bias):
+    """The c_fc forward of the training steps' "bf16" precision (``training.resolve_train_precision``): -> (pre, y) with pre =
+    bf16(x) @ bf16(W) + bias (the pre-activation the backward keeps) and y = gelu_new(pre), one launch.  NOT fp32-accurate."""
+    N, K = w_bf16.shape
+    M = x.numel() // K
+    pre = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
+    y = torch.empty_like(pre)
+    bp = _dev(bias, torch.float32, "bias") if bias is not None else None
+    check(_lib.load().r4d_conv1d_bf16_keep_f32(_dev(x, torch.float32, "x"), _dev(w_bf16, torch.int16, "w_bf16"), bp, M, K, N,
+                                               pre.data_ptr(), y.data_ptr(), _stream()), "conv1d_bf16_keep")
+    return pre, y
+
+
+def conv1d_bf16_dgrad(dy, wt_bf16, kind="none", second=None):
+    """The Conv1D data gradient of the "bf16" training precision: dx = bf16(dy) @ bf16(W)^T for a weight W [in, out] given as
+    ``wt_bf16`` = ``bf16_plane(W.t().contiguous())`` ([in, out], out contiguous: plane 0 of the trainers' ``_w3t`` sets).
+    ``kind``: "none"; "residual" (dx = second + ...); "gelu_grad" (dx = (...) * gelu_new'(second)); ``second`` [M, in]."""
+    n_in, n_out = wt_bf16.shape
+    M = dy.numel() // n_out
+    dx = torch.empty(dy.shape[:-1] + (n_in,), dtype=torch.float32, device=dy.device)
+    k = {"none": 0, "residual": 1, "gelu_grad": 2}[kind]
+    sp = _dev(second, torch.float32, "second") if second is not None else None
+    check(_lib.load().r4d_conv1d_bf16_dgrad_f32(_dev(dy, torch.float32, "dy"), _dev(wt_bf16, torch.int16, "wt_bf16"), M, n_in, n_out, k,
+                                                sp, dx.data_ptr(), _stream()), "conv1d_bf16_dgrad")
+    return dx
+
+
+def weight_grad_bf16(x, dy, want_db=True, workspace=None):
+    """The Conv1D weight gradient of the "bf16" training precision: -> (dW [in, out] = bf16(x)^T @ bf16(dy), db [out] = the fp32
+    column sums of the unrounded dy, or None).  ``x`` [rows, in] and ``dy`` [rows, out] may be column blocks of wider buffers
+    (row stride >= width, element stride 1).  in % 128 == 0, out % 256 == 0, rows >= 32, else R4DError.  ``workspace``: a uint8
+    tensor of at least ``r4d_weight_grad_bf16_workspace_bytes`` (default: a fresh one)."""
+    lib = _lib.load()
+    for t, n in ((x, "x"), (dy, "dy")):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+            raise R4DError(f"weight_grad_bf16: {n} must be a 2-D fp32 device tensor with contiguous rows")
+    rows, n_in = x.shape
+    n_out = dy.shape[1]
+    if dy.shape[0] != rows:
+        raise R4DError("weight_grad_bf16: x and dy differ in rows")
+    nbytes = lib.r4d_weight_grad_bf16_workspace_bytes(rows, n_in, n_out)
+    if workspace is None:
+        workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=x.device)
+    dw = torch.empty(n_in, n_out, dtype=torch.float32, device=x.device)
+    db = torch.empty(n_out, dtype=torch.float32, device=x.device) if want_db else None
+    check(lib.r4d_weight_grad_bf16_f32(x.data_ptr(), int(x.stride(0)), dy.data_ptr(), int(dy.stride(0)), rows, n_in, n_out, dw.data_ptr(),
+                                       db.data_ptr() if want_db else None, workspace.data_ptr(), workspace.numel(), _stream()),
+          "weight_grad_bf16")
+    return dw, db
+
+
 def set_attention_fused(mode):
     """-1 / None: auto by head_dim (default); True: fused flash-style kernel; False: three-launch GEMM form."""
     _lib.load().r4d_set_attention_fused(-1 if mode is None or mode == -1 else (2 if mode == 2 else int(bool(mode))))

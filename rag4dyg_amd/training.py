@@ -155,16 +155,32 @@ def resolve_train_activations(activations=None):
     return activations
 
 
+TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}
+
+
+def resolve_train_precision(precision=None):
+    """``"fp32"`` (the gemm mode's fp32-accurate arithmetic) or ``"bf16"`` (mixed precision: the twelve Conv1D GEMMs of every
+    block on bf16 operands with fp32 accumulation -- NOT fp32-accurate; master weights, gradients, AdamW, LayerNorm, softmax,
+    GELU and the losses stay fp32; ``r4d_set_train_bf16``).  None -> the environment variable ``R4D_TRAIN_PRECISION``, ``fp32``
+    when it is unset or empty.  Anything else raises."""
+    if precision is None:
+        precision = os.environ.get("R4D_TRAIN_PRECISION") or "fp32"
+    if precision not in TRAIN_PRECISIONS:
+        raise ValueError(f"train precision {precision!r}: expected one of {sorted(TRAIN_PRECISIONS)}")
+    return precision
+
+
 class EncoderTrainer:
     """Forward-with-saved-activations and backward of the SimpleDyG encoder on the HIP kernels
     (``r4d_gpt2_train_forward_f32`` / ``r4d_gpt2_train_backward_f32``), for a ``GPT2LMHeadModelRAG`` whose parameters live
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None):
+    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None):
         """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``);
         ``activations``: the same two words for the per-layer activations (:func:`resolve_train_activations`; None ->
-        ``R4D_TRAIN_ACTIVATIONS``).  The trainer sets both library switches before every size query and step call of its own, so
+        ``R4D_TRAIN_ACTIVATIONS``); ``precision``: ``"fp32"`` / ``"bf16"`` (:func:`resolve_train_precision`; None ->
+        ``R4D_TRAIN_PRECISION``).  The trainer sets the three library switches before every size query and step call of its own, so
         trainers of different modes can share a process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
@@ -172,6 +188,7 @@ class EncoderTrainer:
         self.model = model
         self.attention = resolve_train_attention(attention)
         self.activations = resolve_train_activations(activations)
+        self.precision = resolve_train_precision(precision)
         self.dropout, self.seed, self.step = dropout, int(seed), 0
         self._drop_struct = None
         tr = model.transformer
@@ -208,13 +225,15 @@ class EncoderTrainer:
         # bf16x3 planes of the same weights: [3,out,in] for the forward GEMMs, [3,in,out] for the data gradients dx = dy . W^T
         # (ops.split3_planes; the bf16 matrix cores at fp32 accuracy); refreshed with the copies above
         self.use_s3 = ops.gemm_split3_enabled() and os.environ.get("R4D_TRAIN_SPLIT3", "1") != "0"
+        # precision "bf16" reads plane 0 of both sets in EVERY gemm mode: the planes are kept then even where use_s3 is false
+        self.use_planes = self.use_s3 or self.precision == "bf16"
         self._w3, self._w3t = {}, {}
         # f16x2 mode (round 5): f16x2 lines [out, in/32, 2, 32] of the same weights for the FORWARD GEMMs -- the fp16 matrix cores with
         # three products per fp32 product (csrc/gemm_h2.hip).  Every gradient GEMM keeps bf16x3: a gradient operand (1e-5 .. 1e-8) needs
         # fp32's exponent range (csrc/train.hip: bwd_data).  R4D_TRAIN_H2=0 keeps bf16x3 in the forward pass too.
         self.use_h2 = self.use_s3 and ops.gemm_mode() == "f16x2" and os.environ.get("R4D_TRAIN_H2", "1") != "0"
         self._h2 = {}
-        if self.use_wt or self.use_s3:
+        if self.use_wt or self.use_planes:
             self.refresh_transposed()
 
     @torch.no_grad()
@@ -222,7 +241,7 @@ class EncoderTrainer:
         """Bring the [out,in] weight copies and the bf16x3 planes up to date (call after every optimizer step / load_state_dict)."""
         for (i, f), wt in self._wt.items():
             wt.copy_(self.params[f"transformer.h.{i}.{dict(_LAYER_PARAMS)[f]}"].t())
-        if self.use_s3:
+        if self.use_planes:
             lib = _lib.load()
             stream = torch.cuda.current_stream().cuda_stream
             for i in range(len(self.model.transformer.h)):
@@ -270,10 +289,11 @@ class EncoderTrainer:
         return c, w, g, (layers, glayers)
 
     def set_attention_mode(self):
-        """Select this trainer's attention and activations modes in the library (process-wide switches: before every size query
-        and step call)."""
+        """Select this trainer's attention and activations modes and its precision in the library (process-wide switches: before
+        every size query and step call)."""
         _lib.check(_lib.load().r4d_set_train_attention(TRAIN_ATTENTION_MODES[self.attention]), "set_train_attention")
         _lib.check(_lib.load().r4d_set_train_activations(TRAIN_ACTIVATION_MODES[self.activations]), "set_train_activations")
+        _lib.load().r4d_set_train_bf16(TRAIN_PRECISIONS[self.precision])                # (returns the previous setting)
 
     def _dropout_struct(self):
         if self.dropout is not None:
@@ -558,7 +578,7 @@ def distributed_setup(args):
     return dist.get_world_size(), dist.get_rank()
 
 
-def train(args, train_dataset, model, tokenizer, activations=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None):
     """Drop-in for ``train/train_retriever.train`` (``:230-354``): AdamW on the time-decayed contrastive + InfoNCE loss, validation
     hit@3 after every epoch, best checkpoint as ``checkpoint-0`` (only once ``epoch > warmup_steps``, as upstream), last as
     ``checkpoint-1``, early stopping after ``--patience`` epochs without improvement, then the test / validation passes on
@@ -572,13 +592,14 @@ def train(args, train_dataset, model, tokenizer, activations=None):
     from .dataloader import get_dataloader
     from .retriever import test
     if getattr(args, "fp16", False):
-        raise NotImplementedError("retriever training: --fp16 (apex mixed precision) is not built; the path is fp32")
+        raise NotImplementedError("retriever training: --fp16 (apex mixed precision) is not built; the path is fp32 "
+                                  "(R4D_TRAIN_PRECISION=bf16 selects this project's own mixed precision)")
     world, rank = distributed_setup(args)
     train_dataloader, args = get_dataloader(train_dataset, tokenizer, args, split="train")
     gas = max(1, int(getattr(args, "gradient_accumulation_steps", 1)))
     if args.max_steps > 0:
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
-    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations)      # every rank its own masks
+    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision)      # every rank its own masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -591,6 +612,7 @@ def train(args, train_dataset, model, tokenizer, activations=None):
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.activations))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION)".format(trainer.precision))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

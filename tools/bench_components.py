@@ -408,9 +408,10 @@ print(json.dumps({"rows": rows, "cols": len(lists), "seconds": el}))
 """
 
 
-def training(attention=None, activations=None):
+def training(attention=None, activations=None, precision=None):
     """(``--attention stored|recompute``: how the step keeps the attention probabilities, ``EncoderTrainer(attention=)``;
-    ``--activations stored|recompute``: the same for the per-layer activations; the line reports both modes, the trainer's
+    ``--activations stored|recompute``: the same for the per-layer activations; ``--precision fp32|bf16``: the arithmetic of the
+    blocks' Conv1D GEMMs, ``EncoderTrainer(precision=)``; the line reports the three modes, the trainer's
     workspace bytes and torch's peak allocated bytes.)  SURVEY 8f-4: one retriever training iteration (five forwards with saved activations, losses, encoder backward, clip,
     AdamW) at the UCI_13 script's shape (L4 H2 d512, batch 64: scripts/train_retriever/train_retriever_UCI_13.sh:8-12) on
     synthetic UCI_13-length sequences.  flop = 3 x the forward's algorithmic encoder flop (forward + dX + dW) of the five
@@ -441,7 +442,7 @@ def training(attention=None, activations=None):
     torch.cuda.reset_peak_memory_stats()
     for mode in ("warm", "eval", "train"):               # "train": model.train(), dropout 0.1 at the four sites like the reference
         m.train(mode == "train")
-        trainer = tr.EncoderTrainer(m, seed=42, attention=attention, activations=activations)
+        trainer = tr.EncoderTrainer(m, seed=42, attention=attention, activations=activations, precision=precision)
         opt = tr.AdamW(trainer.params, trainer.grads, lr=1e-5, eps=1e-8, weight_decay=0.0, flat_grads=trainer.flat_grads)
         random.seed(0)
         for b in batches[:2]:
@@ -471,7 +472,7 @@ def training(attention=None, activations=None):
          ms_per_step_dropout_off=round(1e3 * wall["eval"] / n, 3),
          forward_ms=round(ev[0].elapsed_time(ev[1]), 3), backward_ms=round(ev[1].elapsed_time(ev[2]), 3),
          optimizer_ms=round(ev[2].elapsed_time(ev[3]), 3), padded_T=[int(x.shape[1]) for x in b[:3]],
-         attention=trainer.attention, activations=trainer.activations, workspace_bytes=int(trainer._ws.numel()),
+         attention=trainer.attention, activations=trainer.activations, precision=trainer.precision, workspace_bytes=int(trainer._ws.numel()),
          max_memory_allocated=int(torch.cuda.max_memory_allocated()))
 
 
@@ -523,11 +524,12 @@ def jaccard_cpu_all_cores():
 
 
 if __name__ == "__main__":
-    for flag in ("--attention", "--activations"):              # training entry only
+    for flag, words in (("--attention", ("stored", "recompute")), ("--activations", ("stored", "recompute")),
+                        ("--precision", ("fp32", "bf16"))):      # training entry only
         if flag in sys.argv:
             i = sys.argv.index(flag)
-            if sys.argv[i + 1] not in ("stored", "recompute"):
-                sys.exit(f"{flag}: stored or recompute")
+            if sys.argv[i + 1] not in words:
+                sys.exit(f"{flag}: {' or '.join(words)}")
             training = functools.partial(training, **{flag[2:]: sys.argv[i + 1]})
             del sys.argv[i:i + 2]
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):

@@ -6,7 +6,7 @@ spec, the head's share of the step (step minus forward_hidden + backward_hidden 
 adds the chunk rows, the bytes the materialised logits alone would take next to the step's workspace, and the time of ONE sweep of
 logits GEMMs over the chunks (the GEMM the chunked head runs twice) with its share of the step.
 
-    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute]
+    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16]
 """
 import argparse
 import ctypes
@@ -80,6 +80,8 @@ def main():
                     help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
     ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
                     help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
+    ap.add_argument("--precision", default=None, choices=("fp32", "bf16"),
+                    help="arithmetic of the blocks' Conv1D GEMMs (default: R4D_TRAIN_PRECISION, else fp32)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -94,7 +96,7 @@ def main():
         # eval mode: no dropout launches, so that the step and its body (timed alone below) differ by the head only
         m = m.to(dev).eval()
         torch.cuda.reset_peak_memory_stats()
-        tr = LMTrainer(m, attention=a.attention, activations=a.activations)
+        tr = LMTrainer(m, attention=a.attention, activations=a.activations, precision=a.precision)
         if a.one_step:
             ids = torch.randint(0, s["V"], (s["B"], a.one_step), device=dev)
             tr.step(ids)
@@ -149,7 +151,7 @@ def main():
             lib.r4d_profile_enable(0)
             total_prof = sum(v["ms"] for v in prof2.values())
             head_like = {k: v for k, v in prof2.items() if v["work"] > 0}
-            rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, activations=tr.enc.activations,
+            rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, activations=tr.enc.activations, precision=tr.enc.precision,
                        workspace_bytes=ws_bytes, max_memory_allocated=peak, L=s["L"], H=s["H"], d=d, V=V,
                        ldV=ldV, B=B, T=T, ms_per_step=ms,
                        tokens_per_s=N / (ms / 1e3), ce_ms=ce.get("ms"), ce_bytes=ce_bytes,

@@ -55,6 +55,12 @@ def build_workdir(root):
 
 
 def main():
+    if "--precision" in sys.argv:                               # fp32 | bf16: the trainer reads R4D_TRAIN_PRECISION
+        i = sys.argv.index("--precision")
+        if sys.argv[i + 1] not in ("fp32", "bf16"):
+            sys.exit("--precision: fp32 or bf16")
+        os.environ["R4D_TRAIN_PRECISION"] = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     lr = sys.argv[2] if len(sys.argv) > 2 else "1e-5"
     root = tempfile.mkdtemp(prefix="r4d_uci13_")
@@ -69,7 +75,7 @@ def main():
             f"--test_data_gt_file {ret}/test_score.retrieval --per_gpu_train_batch_size 64 --num_train_epochs {epochs} "
             f"--learning_rate {lr} --n_layer 4 --n_head 2 --n_embed 512 --block_size 512 --seed 42 --patience 50 --topK 5").split()
     print(f"# main_retriever.py {' '.join(a for a in argv if not a.startswith(root))[:0]}--do_train on UCI_13/12 (1,708 training histories, "
-          f"9,578 annotation triples, batch 64, lr {lr}, {epochs} epochs, L4 H2 d512, dropout 0.1, seed 42)", flush=True)
+          f"9,578 annotation triples, batch 64, lr {lr}, {epochs} epochs, L4 H2 d512, dropout 0.1, seed 42, precision {os.environ.get('R4D_TRAIN_PRECISION') or 'fp32'})", flush=True)
     buf = io.StringIO()
     t0 = time.time()
     with redirect_stdout(buf):
