@@ -740,6 +740,17 @@ int r4d_dispatch_num_branches(void);
 const char* r4d_dispatch_branch_name(int32_t i);
 int64_t r4d_dispatch_branch_hits(int32_t i);      /* launches through branch i since load / the last reset */
 int r4d_dispatch_reset(void);
+/* Which kernel a Conv1D GEMM WOULD take (additive, ABI 6; read-only: launches nothing, needs no device, reads the current
+ * r4d_set_gemm_split3 mode and nothing else).  The precedence is csrc/conv1d_route.h (DESIGN.md "Conv1D routing").
+ *   kind   0 encoder call, 1 cached decode step, 2 training forward: y[M, N] = epilogue(x[M, K] . W[K, N] + b);
+ *          3 data gradient of a Conv1D, 4 of the LM head (K = d, N = ldV): dx[M, K] = dy[M, N] . W^T;
+ *          5 weight gradient dW[K, N] = x[M, K]^T . dy[M, N] (dense rows)
+ *   have   what the caller carries of the weight: bit 0 the [N, K] copy wT, 1 the planes w3, 2 the planes w3t, 3 the planes h2,
+ *          4 (kind 1) the decode step's split-K scratch, i.e. batch <= 32
+ *   bf16   the kind's precision switch: r4d_set_encode_bf16 (kind 0), r4d_set_train_bf16 (kinds 2, 3, 5); ignored otherwise
+ * Returns a route id, or -1 for an unknown kind or M, K or N <= 0; r4d_conv1d_route_name gives its name ("unknown" outside the table). */
+int32_t r4d_conv1d_route(int32_t kind, int32_t M, int32_t K, int32_t N, int32_t epilogue, uint32_t have, int32_t bf16);
+const char* r4d_conv1d_route_name(int32_t route);
 
 #ifdef __cplusplus
 }

@@ -180,6 +180,8 @@ PROTOTYPES = {
     "r4d_dispatch_branch_name": (c_char_p, [c_int32]),
     "r4d_dispatch_branch_hits": (c_int64, [c_int32]),
     "r4d_dispatch_reset": (c_int32, []),
+    "r4d_conv1d_route": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_int32]),
+    "r4d_conv1d_route_name": (c_char_p, [c_int32]),
     "r4d_profile_enable": (c_int32, [c_int32]),
     "r4d_profile_num_classes": (c_int32, []),
     "r4d_profile_class_name": (c_char_p, [c_int32]),

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/r4d.h"
+#include "conv1d_route.h"      // GemmEpilogue, the kernels' shape contracts, Conv1DW, the routes (host-only text)
 
 namespace r4d {
 
@@ -99,16 +100,8 @@ extern unsigned long long g_branch_hits[BR_COUNT];
 extern unsigned* g_range_flag;         // bits: R4D_RANGE_NONFINITE_HIDDEN, R4D_RANGE_BAD_NORM, R4D_RANGE_BAD_LABEL
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ------------------------------------------------------------------ fp32 MFMA GEMM (gemm_f32.hip)
-enum GemmEpilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_SCALE_DIV = 3, EPI_HALF_PLUS = 4,
-                    // gemm_s3 and gemm_b1 only (training): GELU_KEEP writes gelu(v) to C and the pre-activation v to the `resid` buffer;
-                    // GELU_GRAD writes v * gelu'(u) with u read from the `resid` buffer
-                    EPI_GELU_KEEP = 5, EPI_GELU_GRAD = 6,
-                    // gemm_h2 only: C receives the result as uint32 "h2 words" (fp16 hi | fp16 lo' << 16 of value / 4: csrc/h2.h), the
-                    // operand format of attention_h2.hip
-                    EPI_H2WORDS = 7 };
 enum GemmCausal { CAUSAL_NONE = 0, CAUSAL_QK = 1, CAUSAL_PV = 2 };
 
 struct GemmArgs {
@@ -125,17 +118,23 @@ struct GemmArgs {
     int epilogue; float scale_div;
     int causal;
 };
+// C[M,N] = epilogue(A[M,K] . B + bias) on dense rows, one batch; B is [N,K] (b_trans) or [K,N]
+static inline GemmArgs gemm_args(const float* A, const float* B, int b_trans, const float* bias, const float* resid, int M, int K, int N,
+                                 int epilogue, float* C) {
+    GemmArgs g{};
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.resid = resid;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = b_trans ? K : N; g.ldc = N; g.ldr = N;
+    g.b_trans = b_trans; g.b_rows = b_trans ? N : K; g.nbatch = 1; g.nb1 = 1;
+    g.epilogue = epilogue; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
+    return g;
+}
 int launch_gemm_f32(const GemmArgs& g, hipStream_t stream);
 int launch_gemm_f32_kc(const GemmArgs& g, hipStream_t stream);      // B given as [N,K]: k-contiguous kernel
 // C[M,N] = A[Kt,M]^T . B[Kt,N] (weight gradients), split-K partials in scratch (gemm_tn_scratch_floats floats)
 size_t gemm_tn_scratch_floats(int M, int N, int Kt);
-// `colsum_out` (nullable, with `colsum_scratch` of `colsum_scratch_floats` floats): ALSO the column sums of B over its Kt rows
-// (the bias gradient), when the bf16x3 kernel takes the call; *colsum_done says whether they were written
-int launch_gemm_f32_tn(const float* A, const float* B, float* C, int M, int N, int Kt, int lda, int ldb, float* scratch,
-                       hipStream_t stream, float* colsum_out = nullptr, float* colsum_scratch = nullptr,
-                       size_t colsum_scratch_floats = 0, bool* colsum_done = nullptr);
+// (the exact-f32 kernel only: weight_grad below chooses between it and the two matrix-core forms)
+int launch_gemm_f32_tn(const float* A, const float* B, float* C, int M, int N, int Kt, int lda, int ldb, float* scratch, hipStream_t stream);
 // gemm_skinny.hip: M <= 32 rows against a k-contiguous weight [N,K], K % 256 == 0 (decode step); split-K partials in scratch
-bool gemm_skinny_supported(int M, int K, int N);
 size_t gemm_skinny_scratch_floats(int K, int N);
 bool gemm_skinny_fuses_ln(int M, int K, int N);       // y = epilogue(LayerNorm(x) . wT^T + bias) in one launch
 // `counters_zeroed`: the caller cleared the split-K ticket counters (gemm_skinny_counters) on this stream since the last
@@ -154,14 +153,20 @@ struct S3Args {
     int M, N, K, lda, ldc, ldr, epilogue;
     unsigned* kblk; int kb_hd;        // gemm_h2p, EPI_H2WORDS, N = 3 d: columns [d, 2d) go to the key-blocked K image instead (kb_hd = head_dim; 0 = off)
 };
-bool gemm_s3_supported(int M, int K, int N);
+// y[M,N] = epilogue(x[M,K] . planes + bias) on dense rows (lda = K, ldc = ldr = N): the arguments of every planes kernel
+static inline S3Args s3_args(const float* x, const unsigned short* planes, const float* bias, const float* resid, int M, int K, int N,
+                             int epilogue, float* y) {
+    S3Args a{};
+    a.A = x; a.planes = planes; a.C = y; a.bias = bias; a.resid = resid;
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
+    return a;
+}
 int launch_gemm_s3(const S3Args& a, hipStream_t stream);
 bool gemm_s3_f32b_supported(int M, int K, int N);
 int launch_gemm_s3_f32b(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldc, int epilogue, hipStream_t stream);
 int launch_gemm_s3_scan_order(const float* q_hat, const float* pool_hat, float* scores, int Q, int N, int d, int ng, hipStream_t stream);
 // w element (n, k) at w[k * ld_k + n * ld_n] -> planes [3][N][K] bf16 (hi, mid, lo)
 // gemm_h2.hip: the same contract on the fp16 matrix cores, two fp16 terms per operand and THREE products (planes [2][N][K])
-bool gemm_h2_supported(int M, int K, int N);
 int launch_gemm_h2(const S3Args& a, hipStream_t stream);
 int launch_split2_planes(const float* w, int N, int K, long long ld_k, long long ld_n, unsigned short* planes, hipStream_t s);
 // gemm_h2p.hip: the same arithmetic with the A operand already split by its producer into f16x2 lines [M][K/32][2][32] fp16 (both
@@ -173,25 +178,26 @@ int launch_split2_lines(const float* x, long long rows, int K, unsigned short* l
 // gemm_b1.hip: C = epilogue(RN_bf16(A) . RN_bf16(W)^T + bias), one bf16 MFMA per k-step (NOT fp32-accurate); a.planes = ONE bf16
 // plane [N][K] (plane 0 of the bf16x3 planes); the bf16x3 kernel's shape contract; epilogues none / GELU / residual
 // (training, r4d_set_train_bf16: also GELU_KEEP and GELU_GRAD)
-bool gemm_b1_supported(int M, int K, int N);
 int launch_gemm_b1(const S3Args& a, hipStream_t stream);
-// gemm_b1tn.hip: dW[I,J] = RN_bf16(X[M,I])^T . RN_bf16(dY[M,J]), db = column sums of the unrounded dY; gemm_s3tn's shape contract;
-// slices' partials in `part` / `db_part` (their room bounds the slice count), summed in slice order
-bool gemm_b1tn_supported(int I, int J, int M, int lda, int ldb);
+// gemm_b1tn.hip: out[I,J] (one slice) or partials [S][I][J] <- RN_bf16(X[M,I])^T . RN_bf16(dY[M,J]) over S slices of the M rows,
+// db_out (nullable) [J] or [S][J] <- column sums of the unrounded dY; gemm_s3tn's shape contract
 int gemm_b1tn_slices(int I, int J, int M, int max_slices);
-int launch_gemm_b1tn(const float* X, const float* dY, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part,
-                     size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t stream);
+int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out, int I, int J, int M, int lda, int ldb, int S,
+                     hipStream_t stream);
+// slices that hold rows when M token rows are cut into S slices of whole 32-row steps (gemm_s3tn / gemm_b1tn)
+static inline int tn_row_slices(int M, int S) { return cdiv(M, cdiv(cdiv(M, S), 32) * 32); }
 // gemm_f32.hip: C[4 n4] = part[0] + part[1] + ... + part[S-1] (slices of 4 n4 floats), added in that order
 int launch_splitk_reduce(const float* part, long long n4, int S, float* C, hipStream_t stream);
 extern int g_encode_bf16;             // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs on gemm_b1 wherever a layer carries *_w3
-extern int g_gemm_split3;             // Conv1D arithmetic (r4d_set_gemm_split3): 0 exact-f32 MFMA, 1 bf16x3 planes, 2 f16x2 planes (bf16x3 where a layer carries no f16 planes)
-// Conv1D dispatch shared by the encoder and the training forward (encoder.hip): skinny weight stream (decode), bf16x3 planes,
-// k-contiguous copy, reference layout -- in that order of preference
-int conv1d(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K, int N,
-           int epilogue, float* y, hipStream_t s, float* skinny_scratch = nullptr, bool sk_counters_zeroed = false,
-           const unsigned short* w3 = nullptr, const unsigned short* w2h = nullptr);
+// y[M, W.out] = epilogue(x[M, W.in] . W + W.b) on the kernel conv1d_route names (encoder.hip): the encoder calls, the decode step,
+// the training forward and the LM head.  `resid`: the second buffer of the residual / GELU_KEEP epilogues
+struct Conv1DOpts {
+    float* skinny_scratch = nullptr;   // decode step: the split-K scratch of the weight-stream kernel (gemm_skinny_scratch_floats)
+    bool counters_zeroed = false;      // ... whose ticket counters the caller cleared on this stream
+    int bf16 = BF16_OFF;               // Bf16Use: who asks for plain bf16
+};
+int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts = {});
 // gemm_s3tn.hip: C[I,J] = X[M,I]^T . dY[M,J] on the bf16 matrix cores at fp32 accuracy, split over the token rows
-bool gemm_s3tn_supported(int I, int J, int M, int lda, int ldb);
 int gemm_s3tn_slices(int I, int J, int M, int max_slices);
 int launch_gemm_s3tn(const float* X, const float* dY, float* out, int I, int J, int M, int lda, int ldb, int S, int* slices_out,
                      hipStream_t stream, float* db_partials = nullptr);
@@ -233,10 +239,13 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
                         hipStream_t s, const SpliceIn* sp = nullptr, float* d_fused = nullptr);
-// The data-gradient GEMM (Conv1D dx = dy . W^T with b_trans = 1, head dh = dlogits . wte_pad with b_trans = 0): on the bf16x3
-// planes `w3t` when the mode and the shape allow, else exact f32 on `w`; optional residual, optional fused gelu_new' (train.hip)
-int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, int b_trans, int M, int n_out, int k, float* C,
-                   const float* resid, const float* gelu_pre, hipStream_t s, int bf16 = 0);
+// dx[M, W.in] = epilogue(dy[M, W.out] . W^T) on the kernel dgrad_route names (train.hip): optional residual (dx = resid + ...),
+// optional fused gelu_new' (dx = (...) * gelu_new'(gelu_pre); the planes routes only)
+int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* resid, const float* gelu_pre, hipStream_t s, int bf16 = 0);
+// dW[I,J] = x[M,I]^T . dy[M,J] on the kernel wgrad_route names, db (nullable) [J] = column sums of dy (train.hip).  `part`: room for
+// the slices' partials (gemm_tn_scratch_floats(I, J, M) floats); `red`: colsum_scratch_floats(M, J) floats (with db only)
+int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part, float* red,
+                hipStream_t s, int bf16 = 0);
 int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, const float* wte, const float* wpe, int vocab, int B,
                            int T, int d, const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s);
 

@@ -19,65 +19,31 @@ void set_error(const char* fmt, ...) {
 int g_gemm_split3 = 1;                // r4d_set_gemm_split3: 0 exact f32, 1 bf16x3, 2 f16x2
 int g_encode_bf16 = 0;                // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs in plain bf16 (gemm_b1.hip), whatever the mode above
 
-int conv1d(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K,
-           int N, int epilogue, float* y, hipStream_t s, float* skinny_scratch, bool sk_counters_zeroed,
-           const unsigned short* w3, const unsigned short* w2h) {
-    if (skinny_scratch && wT && gemm_skinny_supported(M, K, N))        // decode step: a weight stream, not a tiled GEMM
-        return launch_gemm_skinny(x, wT, bias, resid, M, K, N, epilogue, y, skinny_scratch, s, nullptr, nullptr, 0.f,
-                                  sk_counters_zeroed);
-    // f16x2 planes present and selected: fp16 matrix cores, three products per fp32 product, fp32 accuracy (gemm_h2.hip).
-    // NOT gated on M, like the bf16x3 branch below
-    if (w2h && g_gemm_split3 == 2 && (epilogue <= EPI_RESIDUAL || epilogue == EPI_GELU_KEEP || epilogue == EPI_H2WORDS) && gemm_h2_supported(M, K, N)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.planes = w2h; a.C = y; a.bias = bias; a.resid = resid;
-        a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
-        return launch_gemm_h2(a, s);
-    }
-    // bf16x3 planes present: bf16 matrix cores at fp32 accuracy.  NOT gated on M: a row's result must not depend on how many
-    // other rows share the call (fused multi-batch encode == one call per batch, bit for bit)
-    if (w3 && g_gemm_split3 && gemm_s3_supported(M, K, N)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.planes = w3; a.C = y; a.bias = bias; a.resid = resid;
-        a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
-        return launch_gemm_s3(a, s);
+int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts) {
+    const int K = W.in, N = W.out;
+    const GemmRoute route = conv1d_route(W, M, epilogue, opts.skinny_scratch != nullptr, opts.bf16);
+    switch (route) {
+        case ROUTE_B1:
+            if (opts.bf16 == BF16_TRAIN) R4D_BRANCH(TB_FWD);
+            return launch_gemm_b1(s3_args(x, W.w3, W.b, resid, M, K, N, epilogue, y), s);
+        case ROUTE_SKINNY:
+            return launch_gemm_skinny(x, W.wT, W.b, resid, M, K, N, epilogue, y, opts.skinny_scratch, s, nullptr, nullptr, 0.f,
+                                      opts.counters_zeroed);
+        case ROUTE_H2: return launch_gemm_h2(s3_args(x, W.h2, W.b, resid, M, K, N, epilogue, y), s);
+        case ROUTE_S3: return launch_gemm_s3(s3_args(x, W.w3, W.b, resid, M, K, N, epilogue, y), s);
+        default: break;
     }
     R4D_REQUIRE(epilogue != EPI_H2WORDS, "conv1d: the h2-word epilogue exists in the f16x2 GEMM only");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = x; g.C = y; g.bias = bias; g.resid = resid;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N;
-    if (wT) { g.B = wT; g.ldb = K; g.b_trans = 1; g.b_rows = N; }     // k-contiguous copy of the weight: fast kernel
-    else { g.B = w; g.ldb = N; g.b_trans = 0; g.b_rows = K; }         // reference layout [in,out]
-    g.nbatch = 1; g.nb1 = 1;
-    g.epilogue = epilogue; g.scale_div = 1.f; g.causal = CAUSAL_NONE;
-    return launch_gemm_f32(g, s);
+    const bool kcopy = route == ROUTE_F32_KCOPY;
+    return launch_gemm_f32(gemm_args(x, kcopy ? W.wT : W.w, kcopy, W.b, resid, M, K, N, epilogue, y), s);
 }
 
-// The encoder calls' Conv1D (encode_impl only): under r4d_set_encode_bf16(1), on ONE bf16 MFMA per k-step wherever the layer
-// carries planes and the shape qualifies (only plane 0 of `w3` is read); every other case is conv1d above, unchanged
-static int conv1d_encode(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K, int N,
-                         int epilogue, float* y, hipStream_t s, const unsigned short* w3, const unsigned short* w2h) {
-    if (g_encode_bf16 && w3 && epilogue <= EPI_RESIDUAL && gemm_b1_supported(M, K, N)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.planes = w3; a.C = y; a.bias = bias; a.resid = resid;
-        a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
-        return launch_gemm_b1(a, s);
-    }
-    return conv1d(x, w, wT, bias, resid, M, K, N, epilogue, y, s, nullptr, false, w3, w2h);
-}
-
-// Conv1D whose input rows are f16x2 LINES written by their producer (gemm_h2p.hip): f16x2 mode only; out_lines: the GELU epilogue
-// writes the result as lines too (c_fc -> mlp.c_proj)
+// Conv1D whose input rows are f16x2 LINES written by their producer (gemm_h2p.hip): f16x2 mode only, so it is no route of
+// conv1d; out_lines: the GELU epilogue writes the result as lines too (c_fc -> mlp.c_proj)
 // kblk / kb_hd (c_attn with the h2-word epilogue only): the K third goes to the key-blocked image of attention_h2.hip
-static int conv1d_lines(const unsigned short* x_lines, const unsigned short* w2h, const float* bias, const float* resid, int M, int K, int N,
-                        int epilogue, void* y, bool out_lines, hipStream_t s, unsigned* kblk = nullptr, int kb_hd = 0) {
-    S3Args a;
-    memset(&a, 0, sizeof(a));
-    a.planes = w2h; a.C = (float*)y; a.bias = bias; a.resid = resid;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
+static int conv1d_lines(const Conv1DW& W, const unsigned short* x_lines, const float* resid, int M, int epilogue, void* y, bool out_lines,
+                        hipStream_t s, unsigned* kblk = nullptr, int kb_hd = 0) {
+    S3Args a = s3_args(nullptr, W.h2, W.b, resid, M, W.in, W.out, epilogue, (float*)y);
     a.kblk = kblk; a.kb_hd = kb_hd;
     return launch_gemm_h2p(a, x_lines, out_lines, s);
 }
@@ -276,11 +242,13 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         const r4d_gpt2_layer& L = w->layers[l];
         R4D_REQUIRE(L.ln_1_w && L.c_attn_w && L.attn_proj_w && L.ln_2_w && L.c_fc_w && L.mlp_proj_w,
                     "gpt2: null weight in layer %d", l);
+        const Conv1DW Wqkv = conv1d_w(L, C_ATTN, d), Wo = conv1d_w(L, ATTN_PROJ, d), Wfc = conv1d_w(L, C_FC, d), Wp = conv1d_w(L, MLP_PROJ, d);
+        const Conv1DOpts enc{nullptr, false, g_encode_bf16 ? BF16_ENCODE : BF16_OFF};
         // f16x2 mode, round 5: the LayerNorms write their rows as f16x2 LINES, the c_fc GELU epilogue too, and c_attn / c_fc /
         // mlp.c_proj take them through LDS-DMA (gemm_h2p.hip) -- the values of the register-staged gemm_h2 path, bit for bit
         // (r4d_set_gemm_h2p(0) keeps that one); the buffers keep their size (4 bytes per element either way)
         // (bf16 precision takes the structure of the bf16x3 path: fp32 activations, exact-f32 attention, no lines or h2 words)
-        const bool lines = !g_encode_bf16 && g_gemm_split3 == 2 && g_gemm_h2p && L.c_attn_h2 && L.c_fc_h2 && L.mlp_proj_h2 && layernorm_lines_supported(d) &&
+        const bool lines = !g_encode_bf16 && g_gemm_split3 == 2 && g_gemm_h2p && Wqkv.h2 && Wfc.h2 && Wp.h2 && layernorm_lines_supported(d) &&
                            gemm_h2p_supported(M, d, 3 * d) && gemm_h2p_supported(M, d, 4 * d) && gemm_h2p_supported(M, 4 * d, d);
         unsigned short* ln_lines = reinterpret_cast<unsigned short*>(ws.ln);
         unsigned short* fc_lines = reinterpret_cast<unsigned short*>(ws.fc);
@@ -305,7 +273,7 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         float* qkv = out_qkv_d ? out_qkv_d + (size_t)l * M * 3 * d : ws.qkv;
         // f16x2 mode, head_dim 128 / 256, qkv not handed out: c_attn writes h2 words (csrc/h2.h) and the attention runs on
         // the fp16 matrix cores (attention_h2.hip); every other case: fp32 qkv and the exact-f32 kernels below
-        bool words = !g_encode_bf16 && !out_qkv_d && g_attention_h2 && g_attention_fused != 0 && g_gemm_split3 == 2 && L.c_attn_h2 &&
+        bool words = !g_encode_bf16 && !out_qkv_d && g_attention_h2 && g_attention_fused != 0 && g_gemm_split3 == 2 && Wqkv.h2 &&
                      attention_h2_supported(H, d) && gemm_h2_supported(M, d, 3 * d);
         for (int g0 = 0; g0 < n_groups && words; g0 += ATT_MAXG) {
             int nseq = 0;
@@ -320,12 +288,11 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             set_error("gpt2: memset of the key-block tail failed");
             return R4D_ERR_HIP;
         }
-        if (lines) rc = conv1d_lines(ln_lines, L.c_attn_h2, L.c_attn_b, nullptr, M, d, 3 * d, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s,
-                                     kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
-        else rc = conv1d_encode(ws.ln, L.c_attn_w, L.c_attn_wT, L.c_attn_b, nullptr, M, d, 3 * d, words ? EPI_H2WORDS : EPI_NONE, qkv, s, L.c_attn_w3, L.c_attn_h2);
+        if (lines) rc = conv1d_lines(Wqkv, ln_lines, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s, kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
+        else rc = conv1d(Wqkv, ws.ln, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, s, enc);
         if (rc) return rc;
         // ... and with them the attention output: attn_h2_kernel writes its merged-head rows as lines for attn.c_proj
-        const bool att_lines = words && lines && L.attn_proj_h2 && gemm_h2p_supported(M, d, d);
+        const bool att_lines = words && lines && Wo.h2 && gemm_h2p_supported(M, d, d);
         bool fused_done = false;
         if (words) {
             fused_done = true;
@@ -360,18 +327,18 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
                 if ((rc = attention(qkv + G.row0 * 3 * d, G.B, G.T, H, d, ws.att + G.row0 * d, ws.scores, s))) return rc;
             }
         }
-        if (att_lines) rc = conv1d_lines(reinterpret_cast<const unsigned short*>(ws.att), L.attn_proj_h2, L.attn_proj_b, ws.x, M, d, d, EPI_RESIDUAL, ws.x, false, s);
-        else rc = conv1d_encode(ws.att, L.attn_proj_w, L.attn_proj_wT, L.attn_proj_b, ws.x, M, d, d, EPI_RESIDUAL, ws.x, s, L.attn_proj_w3, L.attn_proj_h2);
+        if (att_lines) rc = conv1d_lines(Wo, reinterpret_cast<const unsigned short*>(ws.att), ws.x, M, EPI_RESIDUAL, ws.x, false, s);
+        else rc = conv1d(Wo, ws.att, ws.x, M, EPI_RESIDUAL, ws.x, s, enc);
         if (rc) return rc;
         if (lines) {
             if ((rc = launch_layernorm_lines(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ln_lines, s))) return rc;
-            if ((rc = conv1d_lines(ln_lines, L.c_fc_h2, L.c_fc_b, nullptr, M, d, 4 * d, EPI_GELU, fc_lines, true, s))) return rc;
-            if ((rc = conv1d_lines(fc_lines, L.mlp_proj_h2, L.mlp_proj_b, ws.x, M, 4 * d, d, EPI_RESIDUAL, ws.x, false, s))) return rc;
+            if ((rc = conv1d_lines(Wfc, ln_lines, nullptr, M, EPI_GELU, fc_lines, true, s))) return rc;
+            if ((rc = conv1d_lines(Wp, fc_lines, ws.x, M, EPI_RESIDUAL, ws.x, false, s))) return rc;
             continue;
         }
         if ((rc = launch_layernorm(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ws.ln, s))) return rc;
-        if ((rc = conv1d_encode(ws.ln, L.c_fc_w, L.c_fc_wT, L.c_fc_b, nullptr, M, d, 4 * d, EPI_GELU, ws.fc, s, L.c_fc_w3, L.c_fc_h2))) return rc;
-        if ((rc = conv1d_encode(ws.fc, L.mlp_proj_w, L.mlp_proj_wT, L.mlp_proj_b, ws.x, M, 4 * d, d, EPI_RESIDUAL, ws.x, s, L.mlp_proj_w3, L.mlp_proj_h2))) return rc;
+        if ((rc = conv1d(Wfc, ws.ln, nullptr, M, EPI_GELU, ws.fc, s, enc))) return rc;
+        if ((rc = conv1d(Wp, ws.fc, ws.x, M, EPI_RESIDUAL, ws.x, s, enc))) return rc;
     }
     size_t part0 = 0;                                                   // scratch offset of the launch's first batch
     for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {
@@ -445,6 +412,15 @@ size_t r4d_gpt2_decode_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B) {
     return carve(nullptr, (size_t)B, 0, decode_skinny_floats(cfg->n_embd), cfg->n_embd).bytes;
 }
 
+// y = epilogue(LayerNorm(x) . W + b) in ONE weight-stream launch (gemm_skinny_fuses_ln), the counters clear: on the LayerNorm
+// pre-folded into a decode-only copy of the weight when the layer carries it, else on wT with the gain and shift
+static int skinny_ln(const Conv1DW& W, const float* x, const float* ln_w, const float* ln_b, float eps, int M, int epilogue, float* y,
+                     float* sk, hipStream_t s) {
+    const bool folded = W.wTg && W.lnc;
+    return launch_gemm_skinny(x, folded ? W.wTg : W.wT, W.b, nullptr, M, W.in, W.out, epilogue, y, sk, s, folded ? nullptr : ln_w,
+                              folded ? nullptr : ln_b, eps, true, folded ? W.lnc : nullptr);
+}
+
 // `x_ready`: the un-normalised input rows are already in the workspace's x buffer and the ticket counters are clear (the
 // greedy step's bookkeeping kernel did both): no embedding launch, layer 0 reads its LayerNorm like every other layer
 static int decode_step_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const int64_t* ids_d,
@@ -473,9 +449,12 @@ static int decode_step_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* 
         const r4d_gpt2_layer& L = w->layers[l];
         R4D_REQUIRE(L.ln_1_w && L.c_attn_w && L.attn_proj_w && L.ln_2_w && L.c_fc_w && L.mlp_proj_w,
                     "gpt2 decode: null weight in layer %d", l);
+        const Conv1DW Wqkv = conv1d_w_decode(conv1d_w(L, C_ATTN, d)), Wo = conv1d_w_decode(conv1d_w(L, ATTN_PROJ, d)),
+                      Wfc = conv1d_w_decode(conv1d_w(L, C_FC, d)), Wp = conv1d_w_decode(conv1d_w(L, MLP_PROJ, d));
+        const Conv1DOpts first{sk, false, BF16_OFF}, later{sk, true, BF16_OFF};    // the two residual projections promise clear ticket counters
         // M <= 32 and d in {512, 768}: LayerNorm runs inside the projection that reads it (gemm_skinny8_kernel) -- x stays
         // the un-normalised residual stream and two launches per layer disappear
-        const bool fuse_ln = sk && L.c_attn_wT && L.c_fc_wT && gemm_skinny_fuses_ln(B, d, 3 * d);
+        const bool fuse_ln = sk && Wqkv.wT && Wfc.wT && gemm_skinny_fuses_ln(B, d, 3 * d);
         if (l == 0 && !x_ready)
             rc = launch_embed_pos_layernorm(ids_d, inputs_embeds_d, pos_d, w->wte, w->wpe, cfg->vocab, cfg->n_positions,
                                             t_cap, B, d, L.ln_1_w, L.ln_1_b, cfg->ln_eps, ws.x, ws.ln, s, cnt, cbytes);
@@ -483,29 +462,21 @@ static int decode_step_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* 
             rc = launch_layernorm(ws.x, L.ln_1_w, L.ln_1_b, B, d, cfg->ln_eps, ws.ln, s);
         if (rc) return rc;
         if (fuse_ln && (l > 0 || x_ready))
-            rc = (L.c_attn_wTg && L.c_attn_lnc)            // LayerNorm pre-folded into a decode-only copy of the weight
-                     ? launch_gemm_skinny(ws.x, L.c_attn_wTg, L.c_attn_b, nullptr, B, d, 3 * d, EPI_NONE, ws.qkv, sk, s, nullptr, nullptr,
-                                          cfg->ln_eps, true, L.c_attn_lnc)
-                     : launch_gemm_skinny(ws.x, L.c_attn_wT, L.c_attn_b, nullptr, B, d, 3 * d, EPI_NONE, ws.qkv, sk, s, L.ln_1_w,
-                                          L.ln_1_b, cfg->ln_eps, true);
+            rc = skinny_ln(Wqkv, ws.x, L.ln_1_w, L.ln_1_b, cfg->ln_eps, B, EPI_NONE, ws.qkv, sk, s);
         else
-            rc = conv1d(ws.ln, L.c_attn_w, L.c_attn_wT, L.c_attn_b, nullptr, B, d, 3 * d, EPI_NONE, ws.qkv, s, sk);
+            rc = conv1d(Wqkv, ws.ln, nullptr, B, EPI_NONE, ws.qkv, s, first);
         if (rc) return rc;
         if ((rc = launch_decode_attention(ws.qkv, kv_cache_d + (size_t)l * layer_stride, pos_d, B, t_cap, H, d, ws.att, s)))
             return rc;
-        if ((rc = conv1d(ws.att, L.attn_proj_w, L.attn_proj_wT, L.attn_proj_b, ws.x, B, d, d, EPI_RESIDUAL, ws.x, s, sk, true))) return rc;
+        if ((rc = conv1d(Wo, ws.att, ws.x, B, EPI_RESIDUAL, ws.x, s, later))) return rc;
         if (fuse_ln) {
-            rc = (L.c_fc_wTg && L.c_fc_lnc)
-                     ? launch_gemm_skinny(ws.x, L.c_fc_wTg, L.c_fc_b, nullptr, B, d, 4 * d, EPI_GELU, ws.fc, sk, s, nullptr, nullptr,
-                                          cfg->ln_eps, true, L.c_fc_lnc)
-                     : launch_gemm_skinny(ws.x, L.c_fc_wT, L.c_fc_b, nullptr, B, d, 4 * d, EPI_GELU, ws.fc, sk, s, L.ln_2_w, L.ln_2_b,
-                                          cfg->ln_eps, true);
+            rc = skinny_ln(Wfc, ws.x, L.ln_2_w, L.ln_2_b, cfg->ln_eps, B, EPI_GELU, ws.fc, sk, s);
         } else {
             if ((rc = launch_layernorm(ws.x, L.ln_2_w, L.ln_2_b, B, d, cfg->ln_eps, ws.ln, s))) return rc;
-            rc = conv1d(ws.ln, L.c_fc_w, L.c_fc_wT, L.c_fc_b, nullptr, B, d, 4 * d, EPI_GELU, ws.fc, s, sk);
+            rc = conv1d(Wfc, ws.ln, nullptr, B, EPI_GELU, ws.fc, s, first);
         }
         if (rc) return rc;
-        if ((rc = conv1d(ws.fc, L.mlp_proj_w, L.mlp_proj_wT, L.mlp_proj_b, ws.x, B, 4 * d, d, EPI_RESIDUAL, ws.x, s, sk, true))) return rc;
+        if ((rc = conv1d(Wp, ws.fc, ws.x, B, EPI_RESIDUAL, ws.x, s, later))) return rc;
     }
     return launch_layernorm(ws.x, w->ln_f_w, w->ln_f_b, B, d, cfg->ln_eps, out_hidden_d, s);
 }
@@ -618,12 +589,7 @@ void r4d_decode_graph_destroy(r4d_decode_graph* graph) {
 int r4d_lm_logits_f32(const float* hidden_d, const float* wte_d, int32_t M, int32_t V, int32_t d, float* logits_d,
                       void* stream) {
     R4D_REQUIRE(hidden_d && wte_d && logits_d, "lm_logits: null pointer");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = hidden_d; g.B = wte_d; g.C = logits_d;
-    g.M = M; g.N = V; g.K = d; g.lda = d; g.ldb = d; g.ldc = V;
-    g.b_trans = 1; g.b_rows = V; g.nbatch = 1; g.nb1 = 1; g.epilogue = EPI_NONE; g.scale_div = 1.f;
-    return launch_gemm_f32(g, (hipStream_t)stream);
+    return launch_gemm_f32(gemm_args(hidden_d, wte_d, 1, nullptr, nullptr, M, d, V, EPI_NONE, logits_d), (hipStream_t)stream);
 }
 
 int r4d_layernorm_f32(const float* x_d, const float* w_d, const float* b_d, int32_t rows, int32_t d, float eps,
@@ -643,8 +609,13 @@ int r4d_conv1d_f32(const float* x_d, const float* w_d, const float* w_t_d, const
     R4D_REQUIRE(x_d && w_d && y_d, "conv1d: null pointer");
     R4D_REQUIRE(epilogue >= 0 && epilogue <= 2, "conv1d: epilogue %d not in {0,1,2}", epilogue);
     R4D_REQUIRE(epilogue != EPI_RESIDUAL || residual_d, "conv1d: residual epilogue needs residual_d");
-    return conv1d(x_d, w_d, w_t_d, bias_d, residual_d, M, K, N, epilogue, y_d, (hipStream_t)stream);
+    return conv1d(Conv1DW{w_d, bias_d, w_t_d, nullptr, nullptr, nullptr, nullptr, nullptr, K, N}, x_d, residual_d, M, epilogue, y_d, (hipStream_t)stream);
 }
+
+int32_t r4d_conv1d_route(int32_t kind, int32_t M, int32_t K, int32_t N, int32_t epilogue, uint32_t have, int32_t bf16) {
+    return conv1d_route_query(kind, M, K, N, epilogue, have, bf16);
+}
+const char* r4d_conv1d_route_name(int32_t route) { return gemm_route_name(route); }
 
 size_t r4d_attention_workspace_bytes(int32_t B, int32_t n_head, int32_t T) {
     if (B <= 0 || n_head <= 0 || T <= 0) return 0;

@@ -216,12 +216,6 @@ static int launch_b1(const S3Args& a, hipStream_t stream) {
     return R4D_OK;
 }
 
-// the bf16x3 kernel's shape contract (every shape gemm_s3_supported takes is taken here: one plane is a third of its bytes)
-bool gemm_b1_supported(int M, int K, int N) {
-    return M >= 1 && K >= 32 && K % 32 == 0 && N >= 1 && (long long)N * K * 2 < (1ll << 31) && (long long)M * K < (1ll << 29) &&
-           128ll * N < (1ll << 29);
-}
-
 int launch_gemm_b1(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.A && a.planes && a.C, "gemm_b1: null pointer");
     R4D_REQUIRE(gemm_b1_supported(a.M, a.K, a.N), "gemm_b1: unsupported shape M=%d K=%d N=%d (K %% 32 == 0 wanted)", a.M, a.K, a.N);
@@ -244,11 +238,7 @@ extern "C" {
 int r4d_conv1d_bf16_f32(const float* x_d, const uint16_t* w_bf16_d, const float* bias_d, const float* residual_d, int32_t M,
                         int32_t K, int32_t N, int32_t epilogue, float* y_d, void* stream) {
     R4D_REQUIRE(epilogue >= 0 && epilogue <= 2, "conv1d_bf16: epilogue %d not in {0,1,2}", epilogue);
-    S3Args a;
-    memset(&a, 0, sizeof(a));
-    a.A = x_d; a.planes = w_bf16_d; a.C = y_d; a.bias = bias_d; a.resid = residual_d;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
-    return launch_gemm_b1(a, (hipStream_t)stream);
+    return launch_gemm_b1(s3_args(x_d, w_bf16_d, bias_d, residual_d, M, K, N, epilogue, y_d), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -204,12 +204,6 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
             }
 }
 
-// gemm_s3tn's shape contract; the 64 rows the pipeline requests past the last one stay inside 32-bit byte offsets
-bool gemm_b1tn_supported(int I, int J, int M, int lda, int ldb) {
-    return I >= 128 && I % 128 == 0 && J >= 256 && J % 256 == 0 && M >= 32 && lda >= I && ldb >= J && lda % 4 == 0 && ldb % 4 == 0 &&
-           ((long long)M + 64) * lda < (1ll << 29) && ((long long)M + 64) * ldb < (1ll << 29);
-}
-
 // slices: enough workgroups for one round of the chip at two per CU, at least 8 k-tiles each, never more than `max_slices`
 int gemm_b1tn_slices(int I, int J, int M, int max_slices) {
     const int tiles = (I / 128) * (J / 256);
@@ -221,36 +215,20 @@ int gemm_b1tn_slices(int I, int J, int M, int max_slices) {
     return S < 1 ? 1 : S;
 }
 
-// dW <- RN(X)^T . RN(dY), db (nullable) <- column sums of dY.  `part` / `db_part`: room for the slices' partials (part_floats /
-// db_part_floats floats; the slice count follows the smaller room, one slice needs none).  Every partial that the reduce
-// launches read is written by the kernel launch ahead of them.  *db_done: whether db was written.
-int launch_gemm_b1tn(const float* X, const float* dY, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part,
-                     size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t stream) {
-    if (db_done) *db_done = false;
-    R4D_REQUIRE(X && dY && dW, "gemm_b1tn: null pointer");
+// out (S slices with rows: [S][I][J], else [I][J]) <- RN(X)^T . RN(dY) per slice, db_out (nullable; [S][J] / [J]) <- the slices' column
+// sums of dY.  train.hip (wgrad_b1tn) sizes the slices and sums the partials.
+int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out, int I, int J, int M, int lda, int ldb, int S,
+                     hipStream_t stream) {
+    R4D_REQUIRE(X && dY && out && S >= 1, "gemm_b1tn: null pointer");
     R4D_REQUIRE(gemm_b1tn_supported(I, J, M, lda, ldb), "gemm_b1tn: unsupported shape I=%d J=%d M=%d lda=%d ldb=%d (I %% 128 == 0, J %% 256 == 0, M >= 32 wanted)", I, J, M, lda, ldb);
-    R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)dW % 16) == 0 && ((uintptr_t)part % 16) == 0,
+    R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)db_out % 16) == 0,
                 "gemm_b1tn: 16-byte alignment");
-    const int max_s = part ? (int)(part_floats / ((size_t)I * J) > 64 ? 64 : part_floats / ((size_t)I * J)) : 1;
-    const int S = gemm_b1tn_slices(I, J, M, max_s);
     B1TnShape sh;
     sh.M = M; sh.I = I; sh.J = J; sh.lda = lda; sh.ldb = ldb;
     sh.kper = cdiv(cdiv(M, S), 32) * 32;
-    const int Sx = cdiv(M, sh.kper);                                 // slices that hold rows
-    const bool want_db = db && db_done && ((uintptr_t)db % 16) == 0 &&
-                         (Sx == 1 || (db_part && ((uintptr_t)db_part % 16) == 0 && (size_t)Sx * J <= db_part_floats));
-    {
-        ProfScope prof(PK_GEMM_B1TN, 2.0 * (double)I * J * M, stream);
-        hipLaunchKernelGGL(gemm_b1tn_kernel, dim3((I / 128) * (J / 256), 1, Sx), dim3(512), 0, stream, X, dY, Sx > 1 ? part : dW, sh,
-                           want_db ? (Sx > 1 ? db_part : db) : nullptr);
-        R4D_CHECK_LAUNCH("gemm_b1tn");
-    }
-    if (Sx > 1) {
-        int rc = launch_splitk_reduce(part, (long long)I * J / 4, Sx, dW, stream);
-        if (rc) return rc;
-        if (want_db && (rc = launch_splitk_reduce(db_part, (long long)(J / 4), Sx, db, stream))) return rc;
-    }
-    if (want_db) *db_done = true;
+    ProfScope prof(PK_GEMM_B1TN, 2.0 * (double)I * J * M, stream);
+    hipLaunchKernelGGL(gemm_b1tn_kernel, dim3((I / 128) * (J / 256), 1, cdiv(M, sh.kper)), dim3(512), 0, stream, X, dY, out, sh, db_out);
+    R4D_CHECK_LAUNCH("gemm_b1tn");
     return R4D_OK;
 }
 

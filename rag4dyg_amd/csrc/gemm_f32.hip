@@ -360,17 +360,6 @@ static int pick_tile(const GemmArgs& g) {
     return best;
 }
 
-// C[M,N] = A[Kt,M]^T . B[Kt,N]  (both operands row-major over the contraction index: weight gradients), split over the
-// contraction so that a small [M,N] still fills the chip: S partial products of ceil(Kt/S) rows each in `scratch`
-// (gemm_tn_scratch_floats), summed in a fixed order.  M, N multiples of 4.
-static int tn_splits(int M, int N, int Kt) {
-    const int tiles = cdiv(M, 128) * cdiv(N, 128);
-    int S = cdiv(1024, tiles);                                       // ~4 workgroups per CU
-    const int smax = cdiv(Kt, 256);                                  // at least 8 k-tiles per split
-    if (S > smax) S = smax;
-    if (S > 64) S = 64;
-    return S < 1 ? 1 : S;
-}
 int launch_splitk_reduce(const float* part, long long n4, int S, float* C, hipStream_t stream) {
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, n4, S, C);
     R4D_CHECK_LAUNCH("splitk_reduce");
@@ -380,30 +369,14 @@ size_t gemm_tn_scratch_floats(int M, int N, int Kt) {
     const int S = tn_splits(M, N, Kt);
     return S > 1 ? (size_t)S * M * N : 0;
 }
-int launch_gemm_f32_tn(const float* A, const float* B, float* C, int M, int N, int Kt, int lda, int ldb, float* scratch,
-                       hipStream_t stream, float* colsum_out, float* colsum_scratch, size_t colsum_scratch_floats, bool* colsum_done) {
-    if (colsum_done) *colsum_done = false;
+// C[M,N] = A[Kt,M]^T . B[Kt,N]  (both operands row-major over the contraction index: weight gradients), split over the
+// contraction so that a small [M,N] still fills the chip: S partial products of ceil(Kt/S) rows each in `scratch`
+// (gemm_tn_scratch_floats; tn_splits: conv1d_route.h), summed in a fixed order.  M, N multiples of 4.
+int launch_gemm_f32_tn(const float* A, const float* B, float* C, int M, int N, int Kt, int lda, int ldb, float* scratch, hipStream_t stream) {
     R4D_REQUIRE(M > 0 && N > 0 && Kt > 0 && M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0,
                 "gemm_tn: M=%d N=%d Kt=%d lda=%d ldb=%d (multiples of 4 wanted)", M, N, Kt, lda, ldb);
     R4D_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0, "gemm_tn: 16-byte alignment");
     const int S = tn_splits(M, N, Kt);
-    if (g_gemm_split3 && S > 1 && gemm_s3tn_supported(M, N, Kt, lda, ldb)) {    // bf16x3 form (gemm_s3tn.hip); S == 1: tiny problems stay here
-        int Sx3 = 1;
-        const int S3 = gemm_s3tn_slices(M, N, Kt, S);
-        const bool cs = colsum_out && colsum_scratch && colsum_done && (size_t)S3 * N <= colsum_scratch_floats &&
-                        ((uintptr_t)colsum_scratch % 16) == 0 && ((uintptr_t)colsum_out % 16) == 0;
-        const int rc3 = launch_gemm_s3tn(A, B, scratch, M, N, Kt, lda, ldb, S3, &Sx3, stream, cs ? colsum_scratch : nullptr);
-        if (rc3) return rc3;
-        const long long mn4_ = (long long)M * N / 4;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((mn4_ + 255) / 256)), dim3(256), 0, stream, scratch, mn4_, Sx3, C);
-        R4D_CHECK_LAUNCH("splitk_reduce");
-        if (cs) {                                                    // the slices' column sums, added in slice order
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((N / 4 + 255) / 256)), dim3(256), 0, stream, colsum_scratch, (long long)(N / 4), Sx3, colsum_out);
-            R4D_CHECK_LAUNCH("colsum_reduce");
-            *colsum_done = true;
-        }
-        return R4D_OK;
-    }
     const int kper = cdiv(cdiv(Kt, S), BKT) * BKT;
     const int Sx = cdiv(Kt, kper);                                   // splits that have rows
     R4D_REQUIRE(S == 1 || scratch, "gemm_tn: split-K scratch missing");
@@ -420,12 +393,7 @@ int launch_gemm_f32_tn(const float* A, const float* B, float* C, int M, int N, i
                            stream, A, B, Sx > 1 ? scratch : C, nullptr, nullptr, sh);
         R4D_CHECK_LAUNCH("gemm_f32_tn");
     }
-    if (Sx > 1) {
-        const long long mn4 = (long long)M * N / 4;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((mn4 + 255) / 256)), dim3(256), 0, stream, scratch, mn4, Sx, C);
-        R4D_CHECK_LAUNCH("splitk_reduce");
-    }
-    return R4D_OK;
+    return Sx > 1 ? launch_splitk_reduce(scratch, (long long)M * N / 4, Sx, C, stream) : R4D_OK;
 }
 
 int launch_gemm_f32(const GemmArgs& g0, hipStream_t stream) {

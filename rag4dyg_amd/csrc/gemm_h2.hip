@@ -293,11 +293,6 @@ static int launch_h2(const S3Args& a, int cls, hipStream_t stream) {
     return R4D_OK;
 }
 
-bool gemm_h2_supported(int M, int K, int N) {
-    return M >= 1 && K >= 32 && K % 32 == 0 && N >= 1 && (long long)N * K * 4 < (1ll << 31) && (long long)M * K < (1ll << 29) &&
-           128ll * N < (1ll << 29);
-}
-
 int launch_gemm_h2(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.A && a.planes && a.C, "gemm_h2: null pointer");
     R4D_REQUIRE(gemm_h2_supported(a.M, a.K, a.N), "gemm_h2: unsupported shape M=%d K=%d N=%d (K %% 32 == 0 wanted)", a.M, a.K, a.N);
@@ -338,11 +333,7 @@ int r4d_split2_planes_f16(const float* w_d, int32_t K, int32_t N, int32_t transp
 int r4d_conv1d_h2_f32(const float* x_d, const uint16_t* planes_d, const float* bias_d, const float* residual_d, int32_t M,
                       int32_t K, int32_t N, int32_t epilogue, float* y_d, void* stream) {
     R4D_REQUIRE(epilogue >= 0 && epilogue <= 2, "conv1d_h2: epilogue %d not in {0,1,2}", epilogue);
-    S3Args a;
-    memset(&a, 0, sizeof(a));
-    a.A = x_d; a.planes = planes_d; a.C = y_d; a.bias = bias_d; a.resid = residual_d;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
-    return launch_gemm_h2(a, (hipStream_t)stream);
+    return launch_gemm_h2(s3_args(x_d, planes_d, bias_d, residual_d, M, K, N, epilogue, y_d), (hipStream_t)stream);
 }
 
 }  // extern "C"

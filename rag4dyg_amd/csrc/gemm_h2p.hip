@@ -441,11 +441,7 @@ int r4d_split2_lines_f16(const float* x_d, int64_t rows, int32_t K, uint16_t* li
 int r4d_conv1d_h2p_f32(const uint16_t* x_lines_d, const uint16_t* planes_d, const float* bias_d, const float* residual_d, int32_t M,
                        int32_t K, int32_t N, int32_t epilogue, int32_t out_lines, void* y_d, void* stream) {
     R4D_REQUIRE(epilogue >= 0 && epilogue <= 2, "conv1d_h2p: epilogue %d not in {0,1,2}", epilogue);
-    S3Args a;
-    memset(&a, 0, sizeof(a));
-    a.planes = planes_d; a.C = (float*)y_d; a.bias = bias_d; a.resid = residual_d;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epilogue;
-    return launch_gemm_h2p(a, x_lines_d, out_lines != 0, (hipStream_t)stream);
+    return launch_gemm_h2p(s3_args(nullptr, planes_d, bias_d, residual_d, M, K, N, epilogue, (float*)y_d), x_lines_d, out_lines != 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -238,11 +238,6 @@ __global__ __launch_bounds__(512, 2) void gemm_s3tn_kernel(const float* __restri
             }
 }
 
-bool gemm_s3tn_supported(int I, int J, int M, int lda, int ldb) {
-    return I % 128 == 0 && J % 256 == 0 && M >= 32 && lda % 4 == 0 && ldb % 4 == 0 && (long long)M * lda < (1ll << 29) &&
-           (long long)M * ldb < (1ll << 29);
-}
-
 // slices: enough workgroups for two rounds of the chip, at least 8 k-tiles each, never more than `max_slices` (the caller's
 // scratch was sized for the exact-f32 kernel's split)
 int gemm_s3tn_slices(int I, int J, int M, int max_slices) {

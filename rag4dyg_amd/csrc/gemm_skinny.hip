@@ -468,7 +468,7 @@ bool gemm_skinny_fuses_ln(int M, int K, int N) { return gemm_skinny_supported(M,
 
 size_t gemm_skinny_scratch_floats(int K, int N) { return (size_t)cdiv(K, SK_KC) * 32 * N + S16_MAX_TILES; }   // + ticket counters
 
-bool gemm_skinny_supported(int M, int K, int N) { return M >= 1 && M <= 32 && K % SK_KC == 0 && K >= SK_KC && N >= 1; }
+static_assert(SK_KC == SKINNY_KC, "gemm_skinny_supported (conv1d_route.h) states this kernel's k-slice");
 
 void* gemm_skinny_counters(float* scratch, size_t* bytes) { *bytes = S16_MAX_TILES * sizeof(unsigned); return scratch; }
 

@@ -4,8 +4,8 @@
 //
 //   logits   [N, ldV] = h_lnf . wte_pad^T          the forward GEMM family of the mode (f16x2 / bf16x3 / exact f32), conv1d
 //   loss, dlogits (in place)                       lm_ce_kernel: one workgroup per row, the row read once into LDS, written once
-//   dh       [N, d]   = dlogits . wte_pad          bf16x3 like every data gradient (train.hip: data_grad_gemm)
-//   dwte_head [ldV, d] = dlogits^T . h_lnf         the weight-gradient GEMM (launch_gemm_f32_tn: gemm_s3tn in the split modes)
+//   dh       [N, d]   = dlogits . wte_pad          bf16x3 like every data gradient (train.hip: data_grad)
+//   dwte_head [ldV, d] = dlogits^T . h_lnf         the weight-gradient GEMM (train.hip: weight_grad -- gemm_s3tn in the split modes)
 //   grads->wte = embedding scatter (fixed point, train_ops.hip) + dwte_head[0:V]    in that order
 //
 // V is padded to ldV (a multiple of 128) with ZERO rows of wte_pad: every GEMM family then sees its aligned shape (K % 32 for the
@@ -370,11 +370,7 @@ static int lm_head_train_chunked(const float* h, int N, int V, int d, const r4d_
                 "lm head: N=%d rows x %d chunk columns or ldV=%d x d=%d reaches 2^31 elements (32-bit index arithmetic)", N, C, ldV, d);
     const CeWs w = ce_ws(ce_ws_, N);
     int rc;
-    auto chunk_logits = [&](int c0, int cn) {
-        const size_t o = (size_t)c0 * d;
-        return conv1d(h, nullptr, head->wte_pad + o, nullptr, nullptr, N, d, cn, EPI_NONE, logits, s, nullptr, false,
-                      head->w3 ? head->w3 + 3 * o : nullptr, head->h2 ? head->h2 + 2 * o : nullptr);
-    };
+    auto chunk_logits = [&](int c0, int cn) { return conv1d(conv1d_w(*head, d, c0, cn), h, nullptr, N, EPI_NONE, logits, s); };
     if ((rc = launch_ce_count(src, N, T, V, w, s))) return rc;
     for (int c0 = 0; c0 < ldV; c0 += C) {
         const int cn = ldV - c0 < C ? ldV - c0 : C;
@@ -385,12 +381,10 @@ static int lm_head_train_chunked(const float* h, int N, int V, int d, const r4d_
     if (!dh && !dwte) return R4D_OK;
     for (int c0 = 0; c0 < ldV; c0 += C) {
         const int cn = ldV - c0 < C ? ldV - c0 : C;
-        const size_t o = (size_t)c0 * d;
         if ((rc = chunk_logits(c0, cn))) return rc;
         if ((rc = launch_ce_grad(logits, (size_t)cn, c0, cn, N, V, src, T, gscale, w, s))) return rc;
-        if (dh && (rc = data_grad_gemm(logits, head->wte_pad + o, head->w3t ? head->w3t + 3 * o : nullptr, 0, N, d, cn, dh,
-                                       c0 ? dh : nullptr, nullptr, s))) return rc;
-        if (dwte && (rc = launch_gemm_f32_tn(logits, h, dwte + o, cn, d, N, cn, d, tn_scratch, s))) return rc;
+        if (dh && (rc = data_grad(conv1d_w(*head, d, c0, cn), logits, N, dh, c0 ? dh : nullptr, nullptr, s))) return rc;
+        if (dwte && (rc = weight_grad(logits, h, dwte + (size_t)c0 * d, nullptr, cn, d, N, cn, d, tn_scratch, nullptr, s))) return rc;
     }
     return R4D_OK;
 }
@@ -404,13 +398,13 @@ static int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head*
     if (ldV > CE_MAX_LDV) return lm_head_train_chunked(h, N, V, d, head, src, T, gscale, loss, logits, dh, dwte, tn_scratch, ce_ws, s);
     int rc;
     // logits = h . wte_pad^T: wte_pad [ldV, d] IS the k-contiguous [N, K] operand (planes when the mode has them)
-    if ((rc = conv1d(h, nullptr, head->wte_pad, nullptr, nullptr, N, d, ldV, EPI_NONE, logits, s, nullptr, false, head->w3, head->h2)))
-        return rc;
+    const Conv1DW W = conv1d_w(*head, d, 0, ldV);
+    if ((rc = conv1d(W, h, nullptr, N, EPI_NONE, logits, s))) return rc;
     if ((rc = lm_ce(logits, N, V, ldV, src, T, gscale, loss, ce_ws, s))) return rc;
     // dh = dlogits . wte_pad  (K = ldV: the pad columns of dlogits are zero)
-    if (dh && (rc = data_grad_gemm(logits, head->wte_pad, head->w3t, 0, N, d, ldV, dh, nullptr, nullptr, s))) return rc;
+    if (dh && (rc = data_grad(W, logits, N, dh, nullptr, nullptr, s))) return rc;
     // dwte [ldV, d] = dlogits^T . h
-    return dwte ? launch_gemm_f32_tn(logits, h, dwte, ldV, d, N, ldV, d, tn_scratch, s) : R4D_OK;
+    return dwte ? weight_grad(logits, h, dwte, nullptr, ldV, d, N, ldV, d, tn_scratch, nullptr, s) : R4D_OK;
 }
 
 // One training step through the head, behind the argument checks of its two exports (`who`: the export's name in a message):

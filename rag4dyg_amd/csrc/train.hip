@@ -158,89 +158,71 @@ static int check_groups(const r4d_gpt2_config* cfg, int n_groups, const int64_t*
     return R4D_OK;
 }
 
-// y[M,N] = epilogue(x[M,K] . W[K,N] + bias)   (Conv1D.forward, modeling_utils.py:1267-1271).  `wT` (nullable): the caller's
-// CURRENT [N,K] copy of the weight (refreshed after every optimizer step) -> the k-contiguous kernel; else the reference layout
-// `bf16` (r4d_set_train_bf16, decided HERE and not in conv1d, which the encoder shares): plane 0 of `w3` on the plain-bf16 kernel
-static bool fwd_linear_bf16(int bf16, const unsigned short* w3, int M, int K, int N) { return bf16 && w3 && gemm_b1_supported(M, K, N); }
-static int fwd_linear(const float* x, const float* w, const float* wT, const float* bias, const float* resid, int M, int K, int N,
-                      int epi, float* y, hipStream_t s, const unsigned short* w3, const unsigned short* w2h, int bf16) {
-    if (fwd_linear_bf16(bf16, w3, M, K, N)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = x; a.planes = w3; a.C = y; a.bias = bias; a.resid = resid;
-        a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = epi;
-        R4D_BRANCH(TB_FWD);
-        return launch_gemm_b1(a, s);
-    }
-    return conv1d(x, w, wT, bias, resid, M, K, N, epi, y, s, nullptr, false, w3, w2h);     // f16x2 planes (mode 2) > bf16x3 planes > [N,K] copy > reference layout
-}
-// The data-gradient GEMM of the training steps: C[M, n_out] = epilogue(A[M, k] . W), A a GRADIENT, W one of
-//   b_trans = 1   w [n_out, k]: Conv1D, dx = dy . W^T -- the weight [in, out] IS the k-contiguous operand of the fast kernel
-//   b_trans = 0   w [k, n_out]: the LM head, dh = dlogits . wte_pad
-// `w3t` (nullable): W's bf16x3 planes [3][n_out][k] -> the bf16 matrix cores at fp32 accuracy, when the mode and the shape allow;
-// else the exact-f32 kernel on `w`.  `resid` (nullable): C = resid + A . W.  `gelu_pre` [M, n_out] (bf16x3 path only):
-// C = (A . W) * gelu_new'(gelu_pre).
-// (The data gradients stay on bf16x3 in EVERY split mode: their A operand is a GRADIENT -- 1e-5 .. 1e-8 per element in a real run -- and
-//  the f16x2 form has fp16's exponent range: below 2.4e-4 an element's absolute error stops shrinking (6e-11), i.e. 1e-4 relative at
-//  1e-6.  Built and measured in round 5 (46.9 instead of 50.6 ms per step, G8 green at its max-norm bounds), then taken out: a
-//  per-tensor power-of-two scale from an absmax pass would be needed to make it safe, and that pass costs what the kernel saves.)
-// `bf16` (r4d_set_train_bf16; the Conv1D form only): RN_bf16(A) . plane 0 of `w3t` on the plain-bf16 kernel, in every gemm mode.
-static bool data_grad_bf16(int bf16, const unsigned short* w3t, int b_trans, int M, int n_out, int k) {
-    return bf16 && b_trans == 1 && w3t && gemm_b1_supported(M, k, n_out);
-}
-int data_grad_gemm(const float* A, const float* w, const unsigned short* w3t, int b_trans, int M, int n_out, int k, float* C,
-                   const float* resid, const float* gelu_pre, hipStream_t s, int bf16) {
+// The data-gradient GEMM of the training steps: dx[M, W.in] = epilogue(dy[M, W.out] . W^T), dy a GRADIENT (conv1d_route.h:
+// dgrad_route for the kernel and why no f16x2 form exists).  The exact-f32 kernel reads a Conv1D's w [in, out] as its k-contiguous
+// operand, the LM head's table [out, in] (dh = dlogits . wte_pad) as a row-major one.
+int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* resid, const float* gelu_pre, hipStream_t s, int bf16) {
     const int epi = gelu_pre ? EPI_GELU_GRAD : resid ? EPI_RESIDUAL : EPI_NONE;
-    if (data_grad_bf16(bf16, w3t, b_trans, M, n_out, k)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = A; a.planes = w3t; a.C = C; a.resid = gelu_pre ? gelu_pre : resid;
-        a.M = M; a.N = n_out; a.K = k; a.lda = k; a.ldc = n_out; a.ldr = n_out; a.epilogue = epi;
+    const GemmRoute route = dgrad_route(W, M, bf16);
+    if (route != ROUTE_DGRAD_F32) {
+        const S3Args a = s3_args(dy, W.w3t, nullptr, gelu_pre ? gelu_pre : resid, M, W.out, W.in, epi, dx);
+        if (route == ROUTE_DGRAD_S3) return launch_gemm_s3(a, s);
         R4D_BRANCH(TB_DGRAD);
         return launch_gemm_b1(a, s);
     }
-    if (w3t && g_gemm_split3 && gemm_s3_supported(M, k, n_out)) {
-        S3Args a;
-        memset(&a, 0, sizeof(a));
-        a.A = A; a.planes = w3t; a.C = C; a.resid = gelu_pre ? gelu_pre : resid;
-        a.M = M; a.N = n_out; a.K = k; a.lda = k; a.ldc = n_out; a.ldr = n_out; a.epilogue = epi;
-        return launch_gemm_s3(a, s);
-    }
     R4D_REQUIRE(!gelu_pre, "bwd_data: the fused GELU derivative needs the bf16x3 planes");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.B = w; g.C = C; g.resid = resid;
-    g.M = M; g.N = n_out; g.K = k; g.lda = k; g.ldb = b_trans ? k : n_out; g.ldc = n_out;
-    g.ldr = n_out;                                                // read under EPI_RESIDUAL / a non-null resid only (gemm_f32.hip)
-    g.b_trans = b_trans; g.b_rows = b_trans ? n_out : k; g.nbatch = 1; g.nb1 = 1; g.epilogue = epi; g.scale_div = 1.f;
-    g.causal = CAUSAL_NONE;
-    return launch_gemm_f32(g, s);
+    return launch_gemm_f32(gemm_args(dy, W.w ? W.w : W.wT, W.w != nullptr, nullptr, resid, M, W.out, W.in, epi, dx), s);
 }
-// dx[M,K] = dy[M,N] . W[K,N]^T (Conv1D backward); `w3t`: W's planes [3][K][N]
-static int bwd_data(const float* dy, const float* w, int M, int K, int N, float* dx, hipStream_t s, const unsigned short* w3t,
-                    const float* gelu_pre, int bf16) {
-    return data_grad_gemm(dy, w, w3t, 1, M, K, N, dx, nullptr, gelu_pre, s, bf16);
-}
-// dW[K,N] = x[M,K]^T . dy[M,N]: both operands read row by row over the contracted token index (split-K partials in `skp`);
-// db[N] = column sums of dy
-// `bf16` (r4d_set_train_bf16): RN_bf16(x)^T . RN_bf16(dy) on gemm_b1tn where its shape contract holds (db stays the fp32 sum of
-// the unrounded dy); `skp` holds gemm_tn_scratch_floats(K, N, M) floats, which bounds that kernel's slices.  Else today's kernel.
-static int bwd_weight(const float* x, const float* dy, int M, int K, int N, float* dW, float* db, float* skp, float* red,
-                      hipStream_t s, int bf16) {
-    bool db_done = false;                                             // the bf16x3 kernel sums dy's columns while it stages them
-    if (bf16) {
-        if (gemm_b1tn_supported(K, N, M, K, N)) {
-            R4D_BRANCH(TB_WGRAD);
-            const int rc = launch_gemm_b1tn(x, dy, dW, db, K, N, M, K, N, skp, gemm_tn_scratch_floats(K, N, M), red,
-                                            colsum_scratch_floats(M, N), &db_done, s);
-            if (rc) return rc;
-            return (db && !db_done) ? launch_colsum(dy, M, N, N, db, red, 0, s) : R4D_OK;
-        }
-        R4D_BRANCH(TB_WGRAD_FALLBACK);
-    }
-    const int rc = launch_gemm_f32_tn(x, dy, dW, K, N, M, K, N, skp, s, db, red, colsum_scratch_floats(M, N), &db_done);
+
+// gemm_b1tn and its reduces: dW <- RN(X)^T . RN(dY), db (nullable) <- column sums of dY.  `part` / `db_part`: room for the slices'
+// partials (the slice count follows the smaller room, one slice needs none).  *db_done: whether db was written.
+static int wgrad_b1tn(const float* X, const float* dY, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part,
+                      size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t s) {
+    R4D_REQUIRE(X && dY && dW, "gemm_b1tn: null pointer");
+    R4D_REQUIRE(gemm_b1tn_supported(I, J, M, lda, ldb), "gemm_b1tn: unsupported shape I=%d J=%d M=%d lda=%d ldb=%d (I %% 128 == 0, J %% 256 == 0, M >= 32 wanted)", I, J, M, lda, ldb);
+    R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)dW % 16) == 0 && ((uintptr_t)part % 16) == 0,
+                "gemm_b1tn: 16-byte alignment");
+    const int max_s = part ? (int)(part_floats / ((size_t)I * J) > 64 ? 64 : part_floats / ((size_t)I * J)) : 1;
+    const int S = gemm_b1tn_slices(I, J, M, max_s), Sx = tn_row_slices(M, S);
+    const bool want_db = db && ((uintptr_t)db % 16) == 0 &&
+                         (Sx == 1 || (db_part && ((uintptr_t)db_part % 16) == 0 && (size_t)Sx * J <= db_part_floats));
+    int rc = launch_gemm_b1tn(X, dY, Sx > 1 ? part : dW, want_db ? (Sx > 1 ? db_part : db) : nullptr, I, J, M, lda, ldb, S, s);
     if (rc) return rc;
-    return (db && !db_done) ? launch_colsum(dy, M, N, N, db, red, 0, s) : R4D_OK;
+    if (Sx > 1) {
+        if ((rc = launch_splitk_reduce(part, (long long)I * J / 4, Sx, dW, s))) return rc;
+        if (want_db && (rc = launch_splitk_reduce(db_part, (long long)(J / 4), Sx, db, s))) return rc;
+    }
+    *db_done = want_db;
+    return R4D_OK;
+}
+
+// dW[I,J] = x[M,I]^T . dy[M,J]: both operands read row by row over the contracted token index, split over it into slices whose
+// partials (in `part`) are summed in slice order; db[J] = column sums of dy -- by the matrix-core kernels while they stage dy where
+// `red` has the room for their slices' sums, else by the column-sum kernel.  wgrad_route names the kernel; the slice rules are
+// each kernel's own (the bits of dW depend on them): gemm_b1tn_slices within the room of `part`, gemm_s3tn_slices within tn_splits
+int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part, float* red,
+                hipStream_t s, int bf16) {
+    const GemmRoute route = wgrad_route(I, J, M, lda, ldb, bf16);
+    const size_t red_floats = db ? colsum_scratch_floats(M, J) : 0;
+    bool db_done = false;
+    int rc;
+    if (bf16) { if (route == ROUTE_WGRAD_B1TN) R4D_BRANCH(TB_WGRAD); else R4D_BRANCH(TB_WGRAD_FALLBACK); }
+    if (route == ROUTE_WGRAD_B1TN) {
+        rc = wgrad_b1tn(x, dy, dW, db, I, J, M, lda, ldb, part, gemm_tn_scratch_floats(I, J, M), red, red_floats, &db_done, s);
+    } else if (route == ROUTE_WGRAD_S3TN) {
+        R4D_REQUIRE(I > 0 && J > 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dW % 16) == 0, "gemm_tn: 16-byte alignment");
+        const int S = gemm_s3tn_slices(I, J, M, tn_splits(I, J, M));
+        int Sx = 1;
+        const bool cs = db && red && (size_t)S * J <= red_floats && ((uintptr_t)red % 16) == 0 && ((uintptr_t)db % 16) == 0;
+        if ((rc = launch_gemm_s3tn(x, dy, part, I, J, M, lda, ldb, S, &Sx, s, cs ? red : nullptr))) return rc;
+        rc = launch_splitk_reduce(part, (long long)I * J / 4, Sx, dW, s);
+        if (!rc && cs) rc = launch_splitk_reduce(red, (long long)(J / 4), Sx, db, s);     // the slices' column sums, added in slice order
+        db_done = cs;
+    } else {
+        rc = launch_gemm_f32_tn(x, dy, dW, I, J, M, lda, ldb, part, s);
+    }
+    if (rc) return rc;
+    return (db && !db_done) ? launch_colsum(dy, M, J, ldb, db, red, 0, s) : R4D_OK;
 }
 
 struct DropCtx {                                                  // dropout of one step; p == 0 everywhere -> identity
@@ -373,7 +355,7 @@ int r4d_weight_grad_f32(const float* x_d, const float* dy_d, int32_t rows, int32
                 "weight_grad: workspace too small");
     float* skp = (float*)workspace_d;
     float* red = skp + (gemm_tn_scratch_floats(in_features, out_features, rows) + 63) / 64 * 64;
-    return bwd_weight(x_d, dy_d, rows, in_features, out_features, dw_d, db_d, skp, red, (hipStream_t)stream, 0);
+    return weight_grad(x_d, dy_d, dw_d, db_d, in_features, out_features, rows, in_features, out_features, skp, red, (hipStream_t)stream);
 }
 
 int r4d_set_train_attention(int32_t mode) {
@@ -400,23 +382,15 @@ int r4d_get_train_bf16(void) { return g_train_bf16; }
 int r4d_conv1d_bf16_keep_f32(const float* x_d, const uint16_t* w_bf16_d, const float* bias_d, int32_t M, int32_t K, int32_t N,
                              float* pre_d, float* y_d, void* stream) {
     R4D_REQUIRE(pre_d && y_d && pre_d != y_d, "conv1d_bf16_keep: two output buffers wanted");
-    S3Args a;
-    memset(&a, 0, sizeof(a));
-    a.A = x_d; a.planes = w_bf16_d; a.C = y_d; a.bias = bias_d; a.resid = pre_d;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = N; a.ldr = N; a.epilogue = EPI_GELU_KEEP;
-    return launch_gemm_b1(a, (hipStream_t)stream);
+    return launch_gemm_b1(s3_args(x_d, w_bf16_d, bias_d, pre_d, M, K, N, EPI_GELU_KEEP, y_d), (hipStream_t)stream);
 }
 
 int r4d_conv1d_bf16_dgrad_f32(const float* dy_d, const uint16_t* wt_bf16_d, int32_t M, int32_t in_features, int32_t out_features,
                               int32_t kind, const float* second_d, float* dx_d, void* stream) {
     R4D_REQUIRE(kind >= 0 && kind <= 2, "conv1d_bf16_dgrad: kind %d not in {0 none, 1 residual, 2 gelu derivative}", kind);
     R4D_REQUIRE(kind == 0 || second_d, "conv1d_bf16_dgrad: kind %d needs the second buffer", kind);
-    S3Args a;
-    memset(&a, 0, sizeof(a));
-    a.A = dy_d; a.planes = wt_bf16_d; a.C = dx_d; a.resid = kind ? second_d : nullptr;
-    a.M = M; a.N = in_features; a.K = out_features; a.lda = out_features; a.ldc = in_features; a.ldr = in_features;
-    a.epilogue = kind == 2 ? EPI_GELU_GRAD : kind == 1 ? EPI_RESIDUAL : EPI_NONE;
-    return launch_gemm_b1(a, (hipStream_t)stream);
+    return launch_gemm_b1(s3_args(dy_d, wt_bf16_d, nullptr, kind ? second_d : nullptr, M, out_features, in_features,
+                                  kind == 2 ? EPI_GELU_GRAD : kind == 1 ? EPI_RESIDUAL : EPI_NONE, dx_d), (hipStream_t)stream);
 }
 
 // workspace of the single op: the slices' dW partials (64-float aligned), behind them their db partials
@@ -444,8 +418,8 @@ int r4d_weight_grad_bf16_f32(const float* x_d, int32_t ldx, const float* dy_d, i
     const size_t part = wgrad_bf16_part_floats(rows, in_features, out_features, &S);
     float* ws = (float*)workspace_d;
     bool db_done = false;
-    const int rc = launch_gemm_b1tn(x_d, dy_d, dw_d, db_d, in_features, out_features, rows, ldx, ldy, ws, part, ws + part,
-                                    S > 1 ? (size_t)S * out_features : 0, &db_done, (hipStream_t)stream);
+    const int rc = wgrad_b1tn(x_d, dy_d, dw_d, db_d, in_features, out_features, rows, ldx, ldy, ws, part, ws + part,
+                              S > 1 ? (size_t)S * out_features : 0, &db_done, (hipStream_t)stream);
     if (rc) return rc;
     R4D_REQUIRE(!db_d || db_done, "weight_grad_bf16: the bias gradient was not formed");
     return R4D_OK;
@@ -494,6 +468,8 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
     const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M;
     const r4d_gpt2_layer& Lw = w->layers[l];
     R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
+    const Conv1DW Wqkv = conv1d_w(Lw, C_ATTN, d), Wo = conv1d_w(Lw, ATTN_PROJ, d), Wfc = conv1d_w(Lw, C_FC, d), Wp = conv1d_w(Lw, MLP_PROJ, d);
+    const Conv1DOpts fwd{nullptr, false, bf16 ? BF16_TRAIN : BF16_OFF};
     float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
     float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
     int rc = R4D_OK;
@@ -511,29 +487,29 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
         if ((rc = launch_dropout(x_in, nullptr, (long long)M * d, x_in, dc.embd_p, dc.key, R4D_DROPOUT_SITE_EMBD, 0, s))) return rc;
         if ((rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s))) return rc;
     }
-    if ((rc = fwd_linear(ln1, Lw.c_attn_w, Lw.c_attn_wT, Lw.c_attn_b, nullptr, M, d, 3 * d, EPI_NONE, qkv, s, Lw.c_attn_w3, Lw.c_attn_h2, bf16))) return rc;
+    if ((rc = conv1d(Wqkv, ln1, nullptr, M, EPI_NONE, qkv, s, fwd))) return rc;
     for (const TrainGroup& G : gs)
         if ((rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
                            att + G.row0 * d, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
     float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
     if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
-        if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, nullptr, M, d, d, EPI_NONE, branch, s, Lw.attn_proj_w3, Lw.attn_proj_h2, bf16))) return rc;
+        if ((rc = conv1d(Wo, att, nullptr, M, EPI_NONE, branch, s, fwd))) return rc;
         if ((rc = launch_dropout(branch, x_in, (long long)M * d, x_mid, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
-    } else if ((rc = fwd_linear(att, Lw.attn_proj_w, Lw.attn_proj_wT, Lw.attn_proj_b, x_in, M, d, d, EPI_RESIDUAL, x_mid, s, Lw.attn_proj_w3, Lw.attn_proj_h2, bf16))) return rc;
+    } else if ((rc = conv1d(Wo, att, x_in, M, EPI_RESIDUAL, x_mid, s, fwd))) return rc;
     if ((rc = launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
-    if (train_fuse_gelu() && (fwd_linear_bf16(bf16, Lw.c_fc_w3, M, d, 4 * d) || (Lw.c_fc_w3 && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)))) {
+    if (train_fuse_gelu() && conv1d_fuses_gelu_keep(Wfc, M, fwd.bf16)) {
         // one launch: f = gelu_new(v) and the pre-activation v (kept for the backward pass) both leave the GEMM's epilogue
-        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, pre, M, d, 4 * d, EPI_GELU_KEEP, f, s, Lw.c_fc_w3, Lw.c_fc_h2, bf16))) return rc;
+        if ((rc = conv1d(Wfc, ln2, pre, M, EPI_GELU_KEEP, f, s, fwd))) return rc;
     } else {
-        if ((rc = fwd_linear(ln2, Lw.c_fc_w, Lw.c_fc_wT, Lw.c_fc_b, nullptr, M, d, 4 * d, EPI_NONE, pre, s, Lw.c_fc_w3, Lw.c_fc_h2, bf16))) return rc;
+        if ((rc = conv1d(Wfc, ln2, nullptr, M, EPI_NONE, pre, s, fwd))) return rc;
         if ((rc = launch_gelu_fwd(pre, (long long)M * 4 * d, f, s))) return rc;
     }
     if (again) return R4D_OK;                                    // the MLP projection's output, x_in[l + 1], is there already
     float* x_next = l + 1 < cfg->n_layer ? ws + t.x_in[l + 1] : ws + t.x_out;
     if (dc.resid_p > 0.f) {                                      // x + dropout(c_proj(act(c_fc(x)))), :212,233
-        if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, nullptr, M, 4 * d, d, EPI_NONE, branch, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2, bf16))) return rc;
+        if ((rc = conv1d(Wp, f, nullptr, M, EPI_NONE, branch, s, fwd))) return rc;
         if ((rc = launch_dropout(branch, x_mid, (long long)M * d, x_next, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
-    } else if ((rc = fwd_linear(f, Lw.mlp_proj_w, Lw.mlp_proj_wT, Lw.mlp_proj_b, x_mid, M, 4 * d, d, EPI_RESIDUAL, x_next, s, Lw.mlp_proj_w3, Lw.mlp_proj_h2, bf16))) return rc;
+    } else if ((rc = conv1d(Wp, f, x_mid, M, EPI_RESIDUAL, x_next, s, fwd))) return rc;
     return R4D_OK;
 }
 
@@ -612,6 +588,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         const r4d_gpt2_layer_grads& Lg = frozen ? kNone : gr->layers[l];
         R4D_REQUIRE(frozen || Lg.ln_1_w && Lg.ln_1_b && Lg.c_attn_w && Lg.c_attn_b && Lg.attn_proj_w && Lg.attn_proj_b && Lg.ln_2_w &&
                     Lg.ln_2_b && Lg.c_fc_w && Lg.c_fc_b && Lg.mlp_proj_w && Lg.mlp_proj_b, "gpt2 train backward: null gradient in layer %d", l);
+        const Conv1DW Wqkv = conv1d_w(Lw, C_ATTN, d), Wo = conv1d_w(Lw, ATTN_PROJ, d), Wfc = conv1d_w(Lw, C_FC, d), Wp = conv1d_w(Lw, MLP_PROJ, d);
         float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
         float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
         // activations recompute: this layer's ln1 .. f (and P) into the shared set again, by the forward's launches on x_in[l].
@@ -628,17 +605,16 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dy, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
             dbr = dy;
         }
-        if (!frozen && (rc = bwd_weight(f, dbr, M, 4 * d, d, Lg.mlp_proj_w, Lg.mlp_proj_b, xT, red, s, md.bf16))) return rc;
-        if (train_fuse_gelu() && (data_grad_bf16(md.bf16, Lw.mlp_proj_w3t, 1, M, 4 * d, d) ||
-                                  (Lw.mlp_proj_w3t && g_gemm_split3 && gemm_s3_supported(M, d, 4 * d)))) {
+        if (!frozen && (rc = weight_grad(f, dbr, Lg.mlp_proj_w, Lg.mlp_proj_b, 4 * d, d, M, 4 * d, d, xT, red, s, md.bf16))) return rc;
+        if (train_fuse_gelu() && dgrad_route(Wp, M, md.bf16) != ROUTE_DGRAD_F32) {
             // d(pre) = (d(branch) . Wp^T) * gelu_new'(pre): the derivative is applied in the GEMM's epilogue
-            if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, pre, md.bf16))) return rc;
+            if ((rc = data_grad(Wp, dbr, M, dbig, nullptr, pre, s, md.bf16))) return rc;
         } else {
-            if ((rc = bwd_data(dbr, Lw.mlp_proj_w, M, 4 * d, d, dbig, s, Lw.mlp_proj_w3t, nullptr, md.bf16))) return rc;                    // d(f)
+            if ((rc = data_grad(Wp, dbr, M, dbig, nullptr, nullptr, s, md.bf16))) return rc;                  // d(f)
             if ((rc = launch_gelu_bwd(pre, dbig, (long long)M * 4 * d, dbig, s))) return rc;              // d(pre), in place
         }
-        if (!frozen && (rc = bwd_weight(ln2, dbig, M, d, 4 * d, Lg.c_fc_w, Lg.c_fc_b, xT, red, s, md.bf16))) return rc;
-        if ((rc = bwd_data(dbig, Lw.c_fc_w, M, d, 4 * d, dy, s, Lw.c_fc_w3t, nullptr, md.bf16))) return rc;                              // d(ln_2 out)
+        if (!frozen && (rc = weight_grad(ln2, dbig, Lg.c_fc_w, Lg.c_fc_b, d, 4 * d, M, d, 4 * d, xT, red, s, md.bf16))) return rc;
+        if ((rc = data_grad(Wfc, dbig, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                      // d(ln_2 out)
         if ((rc = launch_ln_bwd(x_mid, Lw.ln_2_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_2_w, Lg.ln_2_b, red, 0, s))) return rc;   // dx = d(x_mid)
         // ---- attention: x_mid = x_in + attn(ln_1(x_in)) Wo + bo
         dbr = dx;
@@ -646,14 +622,14 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dbig, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
             dbr = dbig;
         }
-        if (!frozen && (rc = bwd_weight(att, dbr, M, d, d, Lg.attn_proj_w, Lg.attn_proj_b, xT, red, s, md.bf16))) return rc;
-        if ((rc = bwd_data(dbr, Lw.attn_proj_w, M, d, d, dy, s, Lw.attn_proj_w3t, nullptr, md.bf16))) return rc;                              // d(att), merged heads
+        if (!frozen && (rc = weight_grad(att, dbr, Lg.attn_proj_w, Lg.attn_proj_b, d, d, M, d, d, xT, red, s, md.bf16))) return rc;
+        if ((rc = data_grad(Wo, dbr, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                        // d(att), merged heads
         for (const TrainGroup& G : gs)                               // stored mode: the kept P, and no block A (pA does not exist)
             if ((rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
                                dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, s,
                                dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
-        if (!frozen && (rc = bwd_weight(ln1, dqkv, M, d, 3 * d, Lg.c_attn_w, Lg.c_attn_b, xT, red, s, md.bf16))) return rc;
-        if ((rc = bwd_data(dqkv, Lw.c_attn_w, M, d, 3 * d, dy, s, Lw.c_attn_w3t, nullptr, md.bf16))) return rc;                            // d(ln_1 out)
+        if (!frozen && (rc = weight_grad(ln1, dqkv, Lg.c_attn_w, Lg.c_attn_b, d, 3 * d, M, d, 3 * d, xT, red, s, md.bf16))) return rc;
+        if ((rc = data_grad(Wqkv, dqkv, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                     // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)
     }
     // embeddings: x_in[0] = drop(wte[ids] + wpe[0..T-1])

@@ -204,7 +204,7 @@ class GeneratorTrainer:
         if self.freeze or not backward:
             g = None                                                     # frozen transformer / forward only
         head = self.head.struct()
-        self.enc.set_attention_mode()                                    # before the size query: the step call below reads the same mode
+        self.enc.select_modes()                                    # before the size query: the step call below reads the same mode
         nbytes = lib.r4d_rag_train_workspace_bytes(ctypes.byref(c), B, Ta, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("rag train step: bad batch shape")

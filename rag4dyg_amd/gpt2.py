@@ -251,74 +251,52 @@ class GPT2Model(_PreTrained):
     def __getstate__(self):
         return {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
 
-    def _wt(self, w):
-        """Contiguous transposed copy [out,in] of a static Conv1D weight, cached until the weight changes
-        (keyed by storage pointer and in-place version counter)."""
-        cache = self.__dict__.setdefault("_wt_cache", {})
-        key = id(w)
-        ent = cache.get(key)
-        stamp = (w.data_ptr(), w._version, _RAW_WRITE_GENERATION[0])
+    def _derived(self, kind, w, make, extra_stamp=()):
+        """``make()`` of the static weight ``w``, cached in ``_<kind>_cache`` until ``w`` (or what ``extra_stamp`` names) changes:
+        keyed by the parameter, stamped with its storage pointer, its in-place version counter and the raw-write generation."""
+        cache = self.__dict__.setdefault(f"_{kind}_cache", {})
+        stamp = (w.data_ptr(), w._version, *extra_stamp, _RAW_WRITE_GENERATION[0])
+        ent = cache.get(id(w))
         if ent is None or ent[0] != stamp:
-            ent = (stamp, w.detach().t().contiguous())
-            cache[key] = ent
-        return ent[1].data_ptr()
+            ent = (stamp, make())
+            cache[id(w)] = ent
+        return ent[1]
+
+    def _wt_copy(self, w):
+        return self._derived("wt", w, lambda: w.detach().t().contiguous())
+
+    def _wt(self, w):
+        """Contiguous transposed copy [out,in] of a static Conv1D weight."""
+        return self._wt_copy(w).data_ptr()
 
     def _w3(self, w):
-        """bf16x3 planes [3,out,in] of a static Conv1D weight (``ops.split3_planes``), cached like ``_wt``; None when the
-        split GEMM is switched off (``ops.set_gemm_split3(False)`` / ``R4D_GEMM_SPLIT3=0``) or the shape has no kernel."""
+        """bf16x3 planes [3,out,in] of a static Conv1D weight (``ops.split3_planes``); None when the split GEMM is switched off
+        (``ops.set_gemm_split3(False)`` / ``R4D_GEMM_SPLIT3=0``) or the shape has no kernel."""
         if not ops.gemm_split3_enabled() or w.shape[0] % 32 != 0:
             return None
-        cache = self.__dict__.setdefault("_w3_cache", {})
-        key = id(w)
-        ent = cache.get(key)
-        stamp = (w.data_ptr(), w._version, _RAW_WRITE_GENERATION[0])
-        if ent is None or ent[0] != stamp:
-            ent = (stamp, ops.split3_planes(w.detach()))
-            cache[key] = ent
-        return ent[1].data_ptr()
+        return self._derived("w3", w, lambda: ops.split3_planes(w.detach())).data_ptr()
 
     def _b1(self, w):
-        """The ONE bf16 plane [out,in] of a static Conv1D weight (``ops.bf16_plane``) for ``ops.encode_precision() == "bf16"``, cached
-        like ``_wt``; None when the shape has no kernel."""
+        """The ONE bf16 plane [out,in] of a static Conv1D weight (``ops.bf16_plane``) for ``ops.encode_precision() == "bf16"``;
+        None when the shape has no kernel."""
         if w.shape[0] % 32 != 0:
             return None
-        cache = self.__dict__.setdefault("_b1_cache", {})
-        key = id(w)
-        ent = cache.get(key)
-        stamp = (w.data_ptr(), w._version, _RAW_WRITE_GENERATION[0])
-        if ent is None or ent[0] != stamp:
-            ent = (stamp, ops.bf16_plane(w.detach()))
-            cache[key] = ent
-        return ent[1].data_ptr()
+        return self._derived("b1", w, lambda: ops.bf16_plane(w.detach())).data_ptr()
 
     def _h2(self, w):
-        """f16x2 lines [out, in/32, 2, 32] of a static Conv1D weight (``ops.split2_planes``), cached like ``_wt``; None unless
+        """f16x2 lines [out, in/32, 2, 32] of a static Conv1D weight (``ops.split2_planes``); None unless
         ``ops.gemm_mode() == "f16x2"``, and for a weight outside the fp16 range or a shape without a kernel."""
         if ops.gemm_mode() != "f16x2" or w.shape[0] % 32 != 0:
             return None
-        cache = self.__dict__.setdefault("_h2_cache", {})
-        key = id(w)
-        ent = cache.get(key)
-        stamp = (w.data_ptr(), w._version, _RAW_WRITE_GENERATION[0])
-        if ent is None or ent[0] != stamp:
-            ent = (stamp, ops.split2_planes(w.detach()))
-            cache[key] = ent
-        return ent[1].data_ptr() if ent[1] is not None else None
+        planes = self._derived("h2", w, lambda: ops.split2_planes(w.detach()))
+        return planes.data_ptr() if planes is not None else None
 
     def _fold(self, w, ln):
         """Decode-only (pointer to gain-folded [out,in] copy, pointer to its [2,out] column constants) of a Conv1D weight that
         reads LayerNorm ``ln`` (``ops.fold_layernorm``), cached until the weight or the LayerNorm changes."""
-        cache = self.__dict__.setdefault("_fold_cache", {})
-        key = id(w)
-        stamp = (w.data_ptr(), w._version, ln.weight.data_ptr(), ln.weight._version, ln.bias.data_ptr(), ln.bias._version,
-                 _RAW_WRITE_GENERATION[0])
-        ent = cache.get(key)
-        if ent is None or ent[0] != stamp:
-            self._wt(w)
-            wT = self._wt_cache[id(w)][1]
-            ent = (stamp, ops.fold_layernorm(wT, ln.weight.detach(), ln.bias.detach()))
-            cache[key] = ent
-        return ent[1][0].data_ptr(), ent[1][1].data_ptr()
+        wTg, lnc = self._derived("fold", w, lambda: ops.fold_layernorm(self._wt_copy(w), ln.weight.detach(), ln.bias.detach()),
+                                 (ln.weight.data_ptr(), ln.weight._version, ln.bias.data_ptr(), ln.bias._version))
+        return wTg.data_ptr(), lnc.data_ptr()
 
     def _c_structs(self, decode=False):
         cfg = self.config

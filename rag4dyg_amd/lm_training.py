@@ -10,15 +10,12 @@ generator (``EncoderTrainer``), not torch's RNG stream; in ``model.eval()`` term
 """
 import argparse
 import ctypes
-import glob
 import os
-import re
-import shutil
 
 import torch
 
 from . import _lib, gpt2, ops
-from .training import AdamW, EncoderTrainer, distributed_setup
+from .training import AdamW, EncoderTrainer, distributed_setup, write_checkpoint_dir
 
 
 def padded_vocab(V):
@@ -141,7 +138,7 @@ class LMTrainer:
         lib = _lib.load()
         c, w, g, keep = self.enc._structs()
         head = self.head.struct()
-        self.enc.set_attention_mode()                              # before the size query: the step call below reads the same mode
+        self.enc.select_modes()                              # before the size query: the step call below reads the same mode
         nbytes = lib.r4d_gpt2_lm_train_workspace_bytes(ctypes.byref(c), B, T, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("lm train step: bad batch shape")
@@ -231,21 +228,7 @@ def optimizer_state_dict(optimizer, model, lr):
 def save_checkpoint(model, optimizer, scheduler, tokenizer, args, global_step):
     """``utils/model.py:56-69``: ``<output_dir>/checkpoint-<n>/{config.json, pytorch_model.bin, tokenizer files, training_args.bin,
     optimizer.pt, scheduler.pt}``, with ``--save_total_limit`` rotation (:41-53) before the optimizer state is written."""
-    out = os.path.join(args.output_dir, f"checkpoint-{global_step}")
-    os.makedirs(out, exist_ok=True)
-    model.save_pretrained(out)
-    tokenizer.save_pretrained(out)
-    keep = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, list, tuple, type(None)))}
-    torch.save(argparse.Namespace(**keep), os.path.join(out, "training_args.bin"))     # a Namespace, as upstream (device dropped)
-    limit = getattr(args, "save_total_limit", None)
-    if limit and limit > 0:
-        found = []
-        for path in glob.glob(os.path.join(args.output_dir, "checkpoint-*")):
-            m_ = re.match(r".*checkpoint-([0-9]+)", path)
-            if m_:
-                found.append((int(m_.group(1)), path))
-        for _n, path in sorted(found)[:max(0, len(found) - limit)]:
-            shutil.rmtree(path)
+    out = write_checkpoint_dir(model, tokenizer, args, global_step, pack_args=argparse.Namespace)    # a Namespace, as upstream (device dropped)
     os.makedirs(out, exist_ok=True)
     torch.save(optimizer_state_dict(optimizer, model, scheduler.lr), os.path.join(out, "optimizer.pt"))
     torch.save(scheduler.state_dict(), os.path.join(out, "scheduler.pt"))

@@ -11,15 +11,21 @@ torch ops (and torch autograd) on the [5, B, d] embeddings only.  In ``model.eva
 parameter gradient equal the reference's (tests/golden/g8); in training mode dropout draws its masks from the library's
 counter-based generator (the reference's torch RNG stream cannot be reproduced), checked against the oracle given the same masks.
 """
+import ctypes
+import glob
 import math
 import os
 import random
+import re
+import shutil
 import warnings
 
 import numpy as np
 import torch
 
+from . import _lib, ops
 from .dataloader import read_nonblank_lines
+from .gpt2 import GPT2Model, note_raw_parameter_write
 
 
 class PairSequenceDataset(torch.utils.data.Dataset):
@@ -115,32 +121,34 @@ def training_step_forward(args, model, batch, all_query_time):
 
 
 # ------------------------------------------------------------------------------------------------ backward + optimizer
-import ctypes                                                                   # noqa: E402
-
-from . import _lib, ops                                                         # noqa: E402
-from .gpt2 import note_raw_parameter_write                                     # noqa: E402
-
 _LAYER_PARAMS = (("ln_1_w", "ln_1.weight"), ("ln_1_b", "ln_1.bias"), ("c_attn_w", "attn.c_attn.weight"),
                  ("c_attn_b", "attn.c_attn.bias"), ("attn_proj_w", "attn.c_proj.weight"), ("attn_proj_b", "attn.c_proj.bias"),
                  ("ln_2_w", "ln_2.weight"), ("ln_2_b", "ln_2.bias"), ("c_fc_w", "mlp.c_fc.weight"), ("c_fc_b", "mlp.c_fc.bias"),
                  ("mlp_proj_w", "mlp.c_proj.weight"), ("mlp_proj_b", "mlp.c_proj.bias"))
+# the four Conv1D weights of a block: (struct field, parameter name)
+_CONV1D = tuple((f, name) for f, name in _LAYER_PARAMS if f.endswith("_w") and not f.startswith("ln_"))
 
 
 TRAIN_ATTENTION_MODES = {"stored": 0, "recompute": 1}
+TRAIN_ACTIVATION_MODES = {"stored": 0, "recompute": 1}
+TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}
+
+
+def _resolve(what, value, env, table, default):
+    """``value``, or -- when it is None -- the environment variable ``env``, or ``default`` when that is unset or empty; anything
+    outside ``table`` raises."""
+    if value is None:
+        value = os.environ.get(env) or default
+    if value not in table:
+        raise ValueError(f"{what} {value!r}: expected one of {sorted(table)}")
+    return value
 
 
 def resolve_train_attention(attention=None):
     """``"stored"`` (the forward keeps the attention probabilities of every layer) or ``"recompute"`` (the backward forms them
     again: same bits, a smaller workspace; ``r4d_set_train_attention``).  None -> the environment variable
     ``R4D_TRAIN_ATTENTION``, ``stored`` when it is unset or empty.  Anything else raises."""
-    if attention is None:
-        attention = os.environ.get("R4D_TRAIN_ATTENTION") or "stored"
-    if attention not in TRAIN_ATTENTION_MODES:
-        raise ValueError(f"train attention mode {attention!r}: expected one of {sorted(TRAIN_ATTENTION_MODES)}")
-    return attention
-
-
-TRAIN_ACTIVATION_MODES = {"stored": 0, "recompute": 1}
+    return _resolve("train attention mode", attention, "R4D_TRAIN_ATTENTION", TRAIN_ATTENTION_MODES, "stored")
 
 
 def resolve_train_activations(activations=None):
@@ -148,14 +156,7 @@ def resolve_train_activations(activations=None):
     forms one layer's activations at a time again: same bits, a workspace that no longer grows with 16 * rows * d per layer;
     ``r4d_set_train_activations``).  None -> the environment variable ``R4D_TRAIN_ACTIVATIONS``, ``stored`` when it is unset or
     empty.  Anything else raises."""
-    if activations is None:
-        activations = os.environ.get("R4D_TRAIN_ACTIVATIONS") or "stored"
-    if activations not in TRAIN_ACTIVATION_MODES:
-        raise ValueError(f"train activations mode {activations!r}: expected one of {sorted(TRAIN_ACTIVATION_MODES)}")
-    return activations
-
-
-TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}
+    return _resolve("train activations mode", activations, "R4D_TRAIN_ACTIVATIONS", TRAIN_ACTIVATION_MODES, "stored")
 
 
 def resolve_train_precision(precision=None):
@@ -163,11 +164,7 @@ def resolve_train_precision(precision=None):
     block on bf16 operands with fp32 accumulation -- NOT fp32-accurate; master weights, gradients, AdamW, LayerNorm, softmax,
     GELU and the losses stay fp32; ``r4d_set_train_bf16``).  None -> the environment variable ``R4D_TRAIN_PRECISION``, ``fp32``
     when it is unset or empty.  Anything else raises."""
-    if precision is None:
-        precision = os.environ.get("R4D_TRAIN_PRECISION") or "fp32"
-    if precision not in TRAIN_PRECISIONS:
-        raise ValueError(f"train precision {precision!r}: expected one of {sorted(TRAIN_PRECISIONS)}")
-    return precision
+    return _resolve("train precision", precision, "R4D_TRAIN_PRECISION", TRAIN_PRECISIONS, "fp32")
 
 
 class EncoderTrainer:
@@ -218,10 +215,8 @@ class EncoderTrainer:
         self.use_wt = os.environ.get("R4D_TRAIN_WT", "1") != "0"
         self._wt = {}
         if self.use_wt:
-            for i in range(len(tr.h)):
-                for f in ("c_attn_w", "attn_proj_w", "c_fc_w", "mlp_proj_w"):
-                    w = self.params[f"transformer.h.{i}.{dict(_LAYER_PARAMS)[f]}"]
-                    self._wt[(i, f)] = torch.empty(w.shape[1], w.shape[0], dtype=torch.float32, device=dev)
+            for i, f, w in self._conv1d_weights():
+                self._wt[(i, f)] = torch.empty(w.shape[1], w.shape[0], dtype=torch.float32, device=dev)
         # bf16x3 planes of the same weights: [3,out,in] for the forward GEMMs, [3,in,out] for the data gradients dx = dy . W^T
         # (ops.split3_planes; the bf16 matrix cores at fp32 accuracy); refreshed with the copies above
         self.use_s3 = ops.gemm_split3_enabled() and os.environ.get("R4D_TRAIN_SPLIT3", "1") != "0"
@@ -236,30 +231,36 @@ class EncoderTrainer:
         if self.use_wt or self.use_planes:
             self.refresh_transposed()
 
+    def _conv1d_weights(self):
+        """(layer, struct field, parameter) of every Conv1D weight, block by block"""
+        for i in range(len(self.model.transformer.h)):
+            for f, name in _CONV1D:
+                yield i, f, self.params[f"transformer.h.{i}.{name}"]
+
     @torch.no_grad()
     def refresh_transposed(self):
         """Bring the [out,in] weight copies and the bf16x3 planes up to date (call after every optimizer step / load_state_dict)."""
-        for (i, f), wt in self._wt.items():
-            wt.copy_(self.params[f"transformer.h.{i}.{dict(_LAYER_PARAMS)[f]}"].t())
-        if self.use_planes:
-            lib = _lib.load()
-            stream = torch.cuda.current_stream().cuda_stream
-            for i in range(len(self.model.transformer.h)):
-                for f in ("c_attn_w", "attn_proj_w", "c_fc_w", "mlp_proj_w"):
-                    w = self.params[f"transformer.h.{i}.{dict(_LAYER_PARAMS)[f]}"]
-                    K, N = w.shape
-                    if K % 32 or N % 32:
-                        continue
-                    if (i, f) not in self._w3:
-                        self._w3[(i, f)] = torch.empty(3, N, K, dtype=torch.int16, device=w.device)
-                        self._w3t[(i, f)] = torch.empty(3, K, N, dtype=torch.int16, device=w.device)
-                    _lib.check(lib.r4d_split3_planes_bf16(w.data_ptr(), K, N, 0, self._w3[(i, f)].data_ptr(), stream), "split3_planes")
-                    # the data-gradient operand: W itself read as an [N' = K rows, K' = N contiguous] matrix
-                    _lib.check(lib.r4d_split3_planes_bf16(w.data_ptr(), N, K, 1, self._w3t[(i, f)].data_ptr(), stream), "split3_planes")
-                    if self.use_h2:
-                        if (i, f) not in self._h2:
-                            self._h2[(i, f)] = torch.empty(N, K // 32, 2, 32, dtype=torch.int16, device=w.device)
-                        _lib.check(lib.r4d_split2_planes_f16(w.data_ptr(), K, N, 0, self._h2[(i, f)].data_ptr(), stream), "split2_planes")
+        for i, f, w in self._conv1d_weights():
+            if self.use_wt:
+                self._wt[(i, f)].copy_(w.t())
+        if not self.use_planes:
+            return
+        lib = _lib.load()
+        stream = torch.cuda.current_stream().cuda_stream
+        for i, f, w in self._conv1d_weights():
+            K, N = w.shape
+            if K % 32 or N % 32:
+                continue
+            if (i, f) not in self._w3:
+                self._w3[(i, f)] = torch.empty(3, N, K, dtype=torch.int16, device=w.device)
+                self._w3t[(i, f)] = torch.empty(3, K, N, dtype=torch.int16, device=w.device)
+            _lib.check(lib.r4d_split3_planes_bf16(w.data_ptr(), K, N, 0, self._w3[(i, f)].data_ptr(), stream), "split3_planes")
+            # the data-gradient operand: W itself read as an [N' = K rows, K' = N contiguous] matrix
+            _lib.check(lib.r4d_split3_planes_bf16(w.data_ptr(), N, K, 1, self._w3t[(i, f)].data_ptr(), stream), "split3_planes")
+            if self.use_h2:
+                if (i, f) not in self._h2:
+                    self._h2[(i, f)] = torch.empty(N, K // 32, 2, 32, dtype=torch.int16, device=w.device)
+                _lib.check(lib.r4d_split2_planes_f16(w.data_ptr(), K, N, 0, self._h2[(i, f)].data_ptr(), stream), "split2_planes")
 
     def _structs(self):
         tr = self.model.transformer
@@ -270,15 +271,12 @@ class EncoderTrainer:
         glayers = (_lib.GPT2LayerGradsC * cfg.n_layer)()
         for i in range(cfg.n_layer):
             vals = [self.params[f"transformer.h.{i}.{name}"].data_ptr() for _f, name in _LAYER_PARAMS]
-            wts = [self._wt[(i, f)].data_ptr() if self.use_wt else None for f in ("c_attn_w", "attn_proj_w", "c_fc_w", "mlp_proj_w")]
-            fs = ("c_attn_w", "attn_proj_w", "c_fc_w", "mlp_proj_w")
-            w3 = [self._w3[(i, f)].data_ptr() if (i, f) in self._w3 else None for f in fs]
-            w3t = [self._w3t[(i, f)].data_ptr() if (i, f) in self._w3t else None for f in fs]
+            wts, w3, w3t = ([t[(i, f)].data_ptr() if (i, f) in t else None for f, _name in _CONV1D] for t in (self._wt, self._w3, self._w3t))
             layers[i] = _lib.GPT2LayerC(*vals, *wts, *w3, *w3t)                               # copies / planes kept current by refresh_transposed
             if self.use_h2 and ops.gemm_mode() == "f16x2":
-                for f, name in zip(fs, ("c_attn", "attn_proj", "c_fc", "mlp_proj")):
+                for f, _name in _CONV1D:
                     if (i, f) in self._h2:
-                        setattr(layers[i], name + "_h2", self._h2[(i, f)].data_ptr())
+                        setattr(layers[i], f[:-2] + "_h2", self._h2[(i, f)].data_ptr())
             if self.grads is not None:
                 glayers[i] = _lib.GPT2LayerGradsC(*[self.grads[f"transformer.h.{i}.{name}"].data_ptr() for _f, name in _LAYER_PARAMS])
         w = _lib.GPT2WeightsC(tr.wte.weight.data_ptr(), tr.wpe.weight.data_ptr(), tr.ln_f.weight.data_ptr(),
@@ -288,12 +286,14 @@ class EncoderTrainer:
                             self.grads["transformer.ln_f.weight"].data_ptr(), self.grads["transformer.ln_f.bias"].data_ptr(), glayers)
         return c, w, g, (layers, glayers)
 
-    def set_attention_mode(self):
+    def select_modes(self):
         """Select this trainer's attention and activations modes and its precision in the library (process-wide switches: before
         every size query and step call)."""
         _lib.check(_lib.load().r4d_set_train_attention(TRAIN_ATTENTION_MODES[self.attention]), "set_train_attention")
         _lib.check(_lib.load().r4d_set_train_activations(TRAIN_ACTIVATION_MODES[self.activations]), "set_train_activations")
         _lib.load().r4d_set_train_bf16(TRAIN_PRECISIONS[self.precision])                # (returns the previous setting)
+
+    set_attention_mode = select_modes        # the earlier name, kept for scripts written against it (INTEGRATION.md)
 
     def _dropout_struct(self):
         if self.dropout is not None:
@@ -317,7 +317,7 @@ class EncoderTrainer:
         Bs = (ctypes.c_int32 * n)(*[int(t.shape[0]) for t in ids])
         Ts = (ctypes.c_int32 * n)(*[int(t.shape[1]) for t in ids])
         ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ids])
-        self.set_attention_mode()
+        self.select_modes()
         nbytes = lib.r4d_gpt2_train_workspace_bytes(ctypes.byref(c), n, Bs, Ts)
         if nbytes == 0:
             raise _lib.R4DError("gpt2 train: bad batch shapes")
@@ -342,7 +342,7 @@ class EncoderTrainer:
         lib = _lib.load()
         c, w, g, keep = self._structs()
         de = d_embeddings.to(torch.float32).contiguous()
-        self.set_attention_mode()
+        self.select_modes()
         _lib.check(lib.r4d_gpt2_train_backward_f32(ctypes.byref(c), ctypes.byref(w), ctypes.byref(g), n, ptrs, Bs, Ts, de.data_ptr(),
                                                    ctypes.byref(self._drop_struct) if self._drop_struct is not None else None,
                                                    self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream),
@@ -465,8 +465,9 @@ def training_step(args, model, trainer, optimizer, batch, all_query_time, micro_
         trainer.all_reduce_mean()
         optimizer.step(getattr(args, "max_grad_norm", 0.0))
         trainer.refresh_transposed()
-        for c in ("_wt_cache", "_w3_cache", "_h2_cache", "_fold_cache"):       # the inference path's derived weights are stale now (also
-            model.transformer.__dict__.pop(c, None)               # guarded by gpt2.note_raw_parameter_write in AdamW.step)
+        for c in GPT2Model._TRANSIENT:                            # the inference path's derived weights are stale now (also
+            if c.endswith("_cache"):                              # guarded by gpt2.note_raw_parameter_write in AdamW.step)
+                model.transformer.__dict__.pop(c, None)
     if not sync:
         return dict(loss=loss, cl_loss=cl, aug_loss=au, stepped=stepped)
     return dict(loss=float(loss.item()), cl_loss=float(cl.item()), aug_loss=float(au.item()), stepped=stepped)
@@ -485,21 +486,17 @@ def adjust_learning_rate(args, optimizer, epoch, base_lr, i, iteration_per_epoch
     optimizer.lr = lr
 
 
-def save_checkpoint(model, optimizer, tokenizer, args, global_step):
-    """``utils/model.py:56-69`` layout: ``<output_dir>/checkpoint-<n>/{config.json, pytorch_model.bin, tokenizer files,
-    training_args.bin}`` (+ rotation by ``--save_total_limit``, :41-53).  The optimizer / schedule state goes to
-    ``r4d_optimizer.pt`` / ``r4d_scheduler.pt`` in this build's own layout -- NOT under the reference's ``optimizer.pt`` /
-    ``scheduler.pt`` names, which ``get_optimizer_scheduler`` (utils/model.py:96-102) would try to ``load_state_dict`` as a
-    ``transformers.AdamW`` / ``LambdaLR`` state when pointed at this directory (INTEGRATION.md)."""
-    import glob
-    import re
-    import shutil
+def write_checkpoint_dir(model, tokenizer, args, global_step, pack_args=dict):
+    """The part of a checkpoint every trainer writes (``utils/model.py:41-69``): ``<output_dir>/checkpoint-<n>/{config.json,
+    pytorch_model.bin, tokenizer files, training_args.bin}``, then the rotation by ``--save_total_limit`` (oldest step numbers
+    first).  ``pack_args``: what ``training_args.bin`` holds of the plain-valued arguments (a dict, or ``argparse.Namespace`` as
+    upstream).  Returns the directory; the caller adds its optimizer / schedule files."""
     out = os.path.join(args.output_dir, f"checkpoint-{global_step}")
     os.makedirs(out, exist_ok=True)
     model.save_pretrained(out)
     tokenizer.save_pretrained(out)
     keep = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, list, tuple, type(None)))}
-    torch.save(keep, os.path.join(out, "training_args.bin"))
+    torch.save(pack_args(**keep), os.path.join(out, "training_args.bin"))
     limit = getattr(args, "save_total_limit", None)
     if limit and limit > 0:
         found = []
@@ -509,6 +506,16 @@ def save_checkpoint(model, optimizer, tokenizer, args, global_step):
                 found.append((int(m_.group(1)), path))
         for _n, path in sorted(found)[:max(0, len(found) - limit)]:
             shutil.rmtree(path)
+    return out
+
+
+def save_checkpoint(model, optimizer, tokenizer, args, global_step):
+    """``utils/model.py:56-69`` layout: ``<output_dir>/checkpoint-<n>/{config.json, pytorch_model.bin, tokenizer files,
+    training_args.bin}`` (+ rotation by ``--save_total_limit``, :41-53).  The optimizer / schedule state goes to
+    ``r4d_optimizer.pt`` / ``r4d_scheduler.pt`` in this build's own layout -- NOT under the reference's ``optimizer.pt`` /
+    ``scheduler.pt`` names, which ``get_optimizer_scheduler`` (utils/model.py:96-102) would try to ``load_state_dict`` as a
+    ``transformers.AdamW`` / ``LambdaLR`` state when pointed at this directory (INTEGRATION.md)."""
+    out = write_checkpoint_dir(model, tokenizer, args, global_step)
     torch.save({"format": "rag4dyg_amd.AdamW", "t": optimizer.t, "lr": optimizer.lr,
                 "m": {k: v.cpu() for k, v in optimizer.m.items()}, "v": {k: v.cpu() for k, v in optimizer.v.items()}},
                os.path.join(out, "r4d_optimizer.pt"))

@@ -131,7 +131,7 @@ def _lm_forward_only(dev, tr, ids):
     B, T = ids.shape
     Bs, Ts = (ctypes.c_int32 * 1)(B), (ctypes.c_int32 * 1)(T)
     ptrs = (ctypes.c_void_p * 1)(ids.data_ptr())
-    tr.enc.set_attention_mode()
+    tr.enc.select_modes()
     ws = torch.empty(int(lib.r4d_gpt2_train_workspace_bytes(ctypes.byref(c), 1, Bs, Ts)), dtype=torch.uint8, device=dev)
     h = torch.empty(B, T, tr.d, device=dev)
     _lib.check(lib.r4d_gpt2_train_forward_hidden_f32(ctypes.byref(c), ctypes.byref(w), 1, ptrs, Bs, Ts, h.data_ptr(), None, ws.data_ptr(),
