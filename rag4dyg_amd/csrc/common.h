@@ -181,10 +181,25 @@ int launch_split2_lines(const float* x, long long rows, int K, unsigned short* l
 int launch_gemm_b1(const S3Args& a, hipStream_t stream);
 // gemm_b1tn.hip: out[I,J] (one slice) or partials [S][I][J] <- RN_bf16(X[M,I])^T . RN_bf16(dY[M,J]) over S slices of the M rows,
 // db_out (nullable) [J] or [S][J] <- column sums of the unrounded dY; gemm_s3tn's shape contract
-int gemm_b1tn_slices(int I, int J, int M, int max_slices);
 int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out, int I, int J, int M, int lda, int ldb, int S,
                      hipStream_t stream);
-// slices that hold rows when M token rows are cut into S slices of whole 32-row steps (gemm_s3tn / gemm_b1tn)
+// gemm_s3tn.hip: partials [slices][I][J] <- X[M,I]^T . dY[M,J] on the bf16 matrix cores at fp32 accuracy, db_partials (nullable)
+// [slices][J] <- column sums of dY; one slice is a partial too
+int launch_gemm_s3tn(const float* X, const float* dY, float* out, float* db_partials, int I, int J, int M, int lda, int ldb, int S,
+                     hipStream_t stream);
+// Slices both kernels WANT over the M token rows: enough 128 x 256 workgroups for two rounds of the 256 CUs (gemm_s3tn at one
+// workgroup per CU; gemm_b1tn at two per CU: one round -- the same 512), at least 8 k-tiles of 32 rows each, never more than
+// `max_slices`: the room of the caller's scratch.  One rule because both walk the same tiles over the same rows; every caller's
+// `max_slices` is at most 64 (tn_splits, or the b1tn callers' own cap).
+static inline int gemm_tn_slices(int I, int J, int M, int max_slices) {
+    const int tiles = (I / 128) * (J / 256);
+    int S = cdiv(512, tiles);
+    const int smax = cdiv(M, 256);
+    if (S > smax) S = smax;
+    if (S > max_slices) S = max_slices;
+    return S < 1 ? 1 : S;
+}
+// slices that HOLD rows when M token rows are cut into S slices of whole 32-row steps
 static inline int tn_row_slices(int M, int S) { return cdiv(M, cdiv(cdiv(M, S), 32) * 32); }
 // gemm_f32.hip: C[4 n4] = part[0] + part[1] + ... + part[S-1] (slices of 4 n4 floats), added in that order
 int launch_splitk_reduce(const float* part, long long n4, int S, float* C, hipStream_t stream);
@@ -197,10 +212,6 @@ struct Conv1DOpts {
     int bf16 = BF16_OFF;               // Bf16Use: who asks for plain bf16
 };
 int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts = {});
-// gemm_s3tn.hip: C[I,J] = X[M,I]^T . dY[M,J] on the bf16 matrix cores at fp32 accuracy, split over the token rows
-int gemm_s3tn_slices(int I, int J, int M, int max_slices);
-int launch_gemm_s3tn(const float* X, const float* dY, float* out, int I, int J, int M, int lda, int ldb, int S, int* slices_out,
-                     hipStream_t stream, float* db_partials = nullptr);
 int launch_split3_planes(const float* w, int N, int K, long long ld_k, long long ld_n, unsigned short* planes, hipStream_t s);
 
 // ------------------------------------------------------------------ train_ops.hip

@@ -15,21 +15,13 @@
 // workgroups, no atomics.
 #include <stdlib.h>
 #include <string.h>
-#include "gemm_common.h"
+#include "bf16x3.h"               // cvt_pk_bf16: the rounding
 
 #ifndef B1_LOAD_EARLY
 #define B1_LOAD_EARLY 0   // tuning aid: 1 requests k-tile kt+3 during k-step 0 (behind the LDS stores) instead of k-step 1
 #endif
 
 namespace r4d {
-
-typedef __bf16 bf16x2b __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8b __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned cvt_pk_bf16_b1(float a, float b) {   // v_cvt_pk_bf16_f32: low half = bf16(a), RNE
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2b));
-}
 
 struct B1Shape { int M, N, K, lda, ldc, ldr; };
 
@@ -94,8 +86,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
             /* (cast the WHOLE vector: __builtin_bit_cast on an ext-vector element reads element 0) */ \
             const f32x4 lo_ = __builtin_bit_cast(f32x4, ra[i][0]), hi_ = __builtin_bit_cast(f32x4, ra[i][1]); \
             u32x4 h_;                                                                             \
-            h_[0] = cvt_pk_bf16_b1(lo_[0], lo_[1]); h_[1] = cvt_pk_bf16_b1(lo_[2], lo_[3]);        \
-            h_[2] = cvt_pk_bf16_b1(hi_[0], hi_[1]); h_[3] = cvt_pk_bf16_b1(hi_[2], hi_[3]);        \
+            h_[0] = cvt_pk_bf16(lo_[0], lo_[1]); h_[1] = cvt_pk_bf16(lo_[2], lo_[3]);              \
+            h_[2] = cvt_pk_bf16(hi_[0], hi_[1]); h_[3] = cvt_pk_bf16(hi_[2], hi_[3]);              \
             st_[a_dst[i]] = h_;                                                                    \
         }                                                                                          \
         _Pragma("unroll") for (int i = 0; i < NIB; ++i) st_[b_dst[i]] = rb[i];                     \
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
     }
 #define B1_MFMAS(SET)                                                                              \
     _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j)  \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8b, fa[SET][i]), __builtin_bit_cast(bf16x8b, fb[SET][j]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[SET][i]), __builtin_bit_cast(bf16x8, fb[SET][j]), acc[i][j], 0, 0, 0);
 
     // prologue: k-tiles 0 .. D-1 into their stages, k-tile D into the staging registers (loads beyond the last k-tile repeat it)
 #pragma unroll

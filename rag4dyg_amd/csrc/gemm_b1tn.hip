@@ -2,7 +2,7 @@
 // with ONE v_mfma_f32_32x32x16_bf16 per k-step and fp32 accumulation -- gemm_s3tn.hip without the split arithmetic, the way
 // gemm_b1.hip is gemm_s3.hip without it.  NOT fp32-accurate: both operands carry 8 significant bits.
 //   * both tiles (32 tokens x 128 features of X, 32 tokens x 256 features of dY) are rounded to bf16 (round to nearest even,
-//     v_cvt_pk_bf16_f32) while they are staged: one conversion per pair instead of split3_pair_t's three and two subtractions;
+//     v_cvt_pk_bf16_f32) while they are staged: one conversion per pair instead of split3_pair's three and two subtractions;
 //   * the LDS images stay token-major and the k-contiguous MFMA fragments come out of `ds_read_b64_tr_b16` with gemm_s3tn's
 //     XOR swizzle (chunk index ^ (token & 3) << 2), one image per operand instead of three;
 //   * the contraction is split over the workgroups: slice z writes its own fp32 partial, summed in slice order by the caller's
@@ -14,30 +14,15 @@
 // kinds of wait, where a third stage fills only the first.  The cap of 128 VGPRs that goes with it leaves room for ONE fragment
 // set (the reads of k-step 1 are issued behind the MFMAs of k-step 0, not under them; a second set spilled).  I % 128 == 0, J % 256 == 0, M >= 32; rows past M read as zero
 // through the buffer range check.
+// Shared with gemm_s3tn.hip (gemm_tn_common.h, gemm_tn_tail.h): the shape, the A item's staging coordinates, the column sums, the
+// transposed fragment read, the pipeline (TN_PIPELINE) and the tail.  This file's own: one image, BT_ROUND8, one fragment set, the second B item's addresses by
+// uniform terms, the k-tile offset in the vector offset, the 128-VGPR cap.
 #include <string.h>
-#include "common.h"
+#include "gemm_tn_common.h"
 
 namespace r4d {
 
-typedef float f32x16n __attribute__((ext_vector_type(16)));
-typedef float f32x2n __attribute__((ext_vector_type(2)));
-typedef float f32x4n __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4n __attribute__((ext_vector_type(4)));
-typedef short s16x4n __attribute__((ext_vector_type(4)));
-typedef short s16x8n __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2n __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8n __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned cvt_pk_bf16_n(float a, float b) {    // v_cvt_pk_bf16_f32: low half = bf16(a), RNE
-    const f32x2n v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2n));
-}
-
-struct B1TnShape {
-    int M;                 // token rows in all
-    int I, J, lda, ldb;    // features of X / dY and their row strides (floats)
-    int kper;              // token rows per slice (multiple of 32)
-};
+struct B1TnShape : TnShape {};                                         // (its own name: the kernel's symbol carries it)
 
 // `dbp` (nullable): partial column sums of dY per slice, [slices][J], by the workgroups of the first I tile (gemm_s3tn.hip)
 __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restrict__ Xg, const float* __restrict__ Yg,
@@ -55,11 +40,9 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wi = wid >> 2, wj = wid & 3;
 
-    // staging: a thread owns 8 consecutive features of one token: A item (token = tid >> 4, chunk = tid & 15), B items
-    // (token = idx >> 5, chunk = idx & 31) for idx = tid, tid + 512.  Rows past M: the buffer range check returns zeros.
-    const int a_tok = tid >> 4, a_ch = tid & 15;
-    const int a_voff = (a_tok * g.lda + i0 + a_ch * 8) * 4;
-    const int a_dst = a_tok * A_ROW + ((a_ch ^ ((a_tok & 3) << 2)) << 4);
+    // staging: a thread owns 8 consecutive features of one token: the A item (TN_A_ITEM), B items (token = idx >> 5,
+    // chunk = idx & 31) for idx = tid, tid + 512.  Rows past M: the buffer range check returns zeros.
+    TN_A_ITEM
     // (the second B item is 16 tokens further down: the same swizzle class, so both of its addresses are the first one's plus a
     //  uniform term -- kept as such, every VGPR counts under the 128 cap)
     const int b_tok = tid >> 5, b_ch = tid & 31;
@@ -69,19 +52,11 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
     // behind its last feature, inside the caller's wider buffer.
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xg), 0, (int)(((long long)(g.M - 1) * g.lda + g.I) * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Yg), 0, (int)(((long long)(g.M - 1) * g.ldb + g.J) * 4), 0x00020000);
-    u32x4n ra[2], rb[2][2];
+    u32x4 ra[2], rb[2][2];
     const bool do_cs = dbp != nullptr && ti == 0;                     // workgroup-uniform
-    float cs[8];
+    float cs[8];                                                      // TN_COLSUM
 #pragma unroll
     for (int e = 0; e < 8; ++e) cs[e] = 0.f;
-    // column sums over the staged dY items of a k-tile that belongs to this slice (the registers hold k-tile KT)
-#define BT_COLSUM(KT)                                                                              \
-    if (do_cs && (KT) < nkt) {                                                                     \
-        _Pragma("unroll") for (int r = 0; r < 2; ++r) {                                            \
-            const f32x4n c0_ = __builtin_bit_cast(f32x4n, rb[r][0]), c1_ = __builtin_bit_cast(f32x4n, rb[r][1]); \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e) { cs[e] += c0_[e]; cs[4 + e] += c1_[e]; } \
-        }                                                                                          \
-    }
 #define BT_LOAD(KT)                                                                                \
     {   /* the k-tile's row offset travels in the VECTOR offset: the range check then covers it whatever it does with a scalar one */ \
         const int so_a_ = (m_lo + (KT) * BK) * g.lda * 4, so_b_ = (m_lo + (KT) * BK) * g.ldb * 4; \
@@ -95,45 +70,34 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
     // (cast the WHOLE vector: __builtin_bit_cast on an ext-vector element reads element 0)
 #define BT_ROUND8(R0, R1, H)                                                                       \
     {                                                                                              \
-        const f32x4n s0_ = __builtin_bit_cast(f32x4n, R0), s1_ = __builtin_bit_cast(f32x4n, R1);  \
-        H = u32x4n{cvt_pk_bf16_n(s0_[0], s0_[1]), cvt_pk_bf16_n(s0_[2], s0_[3]), cvt_pk_bf16_n(s1_[0], s1_[1]), cvt_pk_bf16_n(s1_[2], s1_[3])}; \
+        const f32x4 s0_ = __builtin_bit_cast(f32x4, R0), s1_ = __builtin_bit_cast(f32x4, R1);    \
+        H = u32x4{cvt_pk_bf16(s0_[0], s0_[1]), cvt_pk_bf16(s0_[2], s0_[3]), cvt_pk_bf16(s1_[0], s1_[1]), cvt_pk_bf16(s1_[2], s1_[3])}; \
     }
 #define BT_STORE(STG)                                                                              \
     {                                                                                              \
         unsigned char* st_ = lds + (STG) * STAGE;                                                  \
-        u32x4n h_;                                                                                 \
+        u32x4 h_;                                                                                  \
         BT_ROUND8(ra[0], ra[1], h_)                                                                \
-        *reinterpret_cast<u32x4n*>(st_ + a_dst) = h_;                                              \
+        *reinterpret_cast<u32x4*>(st_ + a_dst) = h_;                                               \
         _Pragma("unroll") for (int r = 0; r < 2; ++r) {                                            \
             BT_ROUND8(rb[r][0], rb[r][1], h_)                                                      \
-            *reinterpret_cast<u32x4n*>(st_ + b_dst0 + r * 16 * B_ROW) = h_;                        \
+            *reinterpret_cast<u32x4*>(st_ + b_dst0 + r * 16 * B_ROW) = h_;                         \
         }                                                                                          \
     }
-    // transposed fragment reads, gemm_s3tn's addressing.  Lane l: h = l >> 5 (tokens 8h .. 8h+7 of the k-step), 16-lane group
-    // g16 = (l >> 4) & 1 (features 16 g16 .. +15 of the 32-wide tile), q = (l & 15) >> 2 (token row of the 4 x 16 block),
-    // p = l & 3 (features 4p .. 4p+3 of the group): row (16 s + 8 h + 4 u + q), chunk ((F / 8) + 2 g16 + (p >> 1)) ^ (q << 2),
-    // byte 8 (p & 1).
+    // transposed fragment reads (TN_FRAG has the lane decomposition).  32-feature tile index ft inside the image: a wave's first
+    // tile is even, its second the next one -- (ft ^ q) << 6 differs in bit 6
     const int fh = lane >> 5, fg = (lane >> 4) & 1, fq = (lane & 15) >> 2, fp = lane & 3;
-    // 32-feature tile index ft inside the image: a wave's first tile is even, its second the next one -- (ft ^ q) << 6 differs in bit 6
     const int a_foff0 = (8 * fh + fq) * A_ROW + (((((wi * WI) >> 5) ^ fq) << 2 | (2 * fg + (fp >> 1))) << 4) + 8 * (fp & 1);
     const int b_foff0 = A_IMG + (8 * fh + fq) * B_ROW + (((((wj * WJ) >> 5) ^ fq) << 2 | (2 * fg + (fp >> 1))) << 4) + 8 * (fp & 1);
     static_assert(TI == 2 && TJ == 2 && WI == 64 && WJ == 64, "the second tile's offset is the first one's with bit 6 flipped");
-    typedef __attribute__((address_space(3))) s16x4n* lds_tr_t;
-    u32x4n fa[1][TI], fb[1][TJ];                                      // ONE fragment set: a second one spills under the 128-VGPR cap
-#define BT_TR(PTR) __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(PTR))
-#define BT_FRAG(DST, BASE, ROWB, S)                                                                \
-    {                                                                                              \
-        const s16x4n lo_ = BT_TR((BASE) + (16 * (S)) * (ROWB)), hi_ = BT_TR((BASE) + (16 * (S) + 4) * (ROWB)); \
-        const s16x8n v_ = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);               \
-        DST = __builtin_bit_cast(u32x4n, v_);                                                      \
-    }
+    u32x4 fa[1][TI], fb[1][TJ];                                       // ONE fragment set: a second one spills under the 128-VGPR cap
 #define BT_FRAGS(SET, STG, S)                                                                      \
     {                                                                                              \
         const unsigned char* st_ = lds + (STG) * STAGE;                                            \
-        _Pragma("unroll") for (int t = 0; t < TI; ++t) BT_FRAG(fa[SET][t], st_ + (a_foff0 ^ (t << 6)), A_ROW, S) \
-        _Pragma("unroll") for (int t = 0; t < TJ; ++t) BT_FRAG(fb[SET][t], st_ + (b_foff0 ^ (t << 6)), B_ROW, S) \
+        _Pragma("unroll") for (int t = 0; t < TI; ++t) TN_FRAG(fa[SET][t], st_ + (a_foff0 ^ (t << 6)), A_ROW, S) \
+        _Pragma("unroll") for (int t = 0; t < TJ; ++t) TN_FRAG(fb[SET][t], st_ + (b_foff0 ^ (t << 6)), B_ROW, S) \
     }
-    f32x16n acc[TI][TJ];
+    f32x16 acc[TI][TJ];
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -142,14 +106,14 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 #define BT_MFMAS(SET)                                                                              \
     _Pragma("unroll") for (int i = 0; i < TI; ++i) _Pragma("unroll") for (int j = 0; j < TJ; ++j)  \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8n, fa[SET][i]), __builtin_bit_cast(bf16x8n, fb[SET][j]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[SET][i]), __builtin_bit_cast(bf16x8, fb[SET][j]), acc[i][j], 0, 0, 0);
     // iteration kt: registers (k-tile kt+1) -> the other stage, loads of k-tile kt+2 (rows past m_hi of THIS slice are real rows
     // of the next slice -- they must not be added here: the loop bound keeps kt + 1 < nkt for every store that is used, and the
     // slice length is a multiple of BK, so only the global tail relies on the zero fill)
 #define BT_ITER(CUR)                                                                               \
     {                                                                                              \
         BT_FRAGS(0, CUR, 0)                                                                        \
-        BT_COLSUM(kt + 1)                                                                          \
+        TN_COLSUM(kt + 1)                                                                          \
         BT_STORE((CUR) ^ 1)                                                                        \
         BT_LOAD(kt + 2)                                                                            \
         BT_MFMAS(0)                                                                                \
@@ -157,62 +121,14 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
         BT_MFMAS(0)                                                                                \
         __syncthreads();                                                                           \
     }
-    BT_LOAD(0)
-    BT_COLSUM(0)
-    BT_STORE(0)
-    BT_LOAD(1)
-    __syncthreads();
-    int kt = 0;
-    for (; kt + 1 < nkt; kt += 2) {
-        BT_ITER(0)
-        { ++kt; BT_ITER(1) }
-        --kt;
-    }
-    if (kt < nkt) BT_ITER(0)
+    TN_PIPELINE(BT_LOAD, BT_STORE, BT_ITER)
 #undef BT_ITER
-#undef BT_COLSUM
 #undef BT_MFMAS
 #undef BT_FRAGS
-#undef BT_FRAG
-#undef BT_TR
 #undef BT_STORE
 #undef BT_ROUND8
 #undef BT_LOAD
-    if (do_cs) {                                                      // thread (token row t16 = tid >> 5, chunk tid & 31): 16 rows per chunk
-        float* red = reinterpret_cast<float*>(lds);                  // the last iteration's barrier has passed: the stages are free
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[(tid >> 5) * 256 + (tid & 31) * 8 + e] = cs[e];
-        __syncthreads();
-        if (tid < 256) {
-            float sum = 0.f;
-#pragma unroll
-            for (int t16 = 0; t16 < 16; ++t16) sum += red[t16 * 256 + tid];
-            dbp[(size_t)blockIdx.z * g.J + j0 + tid] = sum;
-        }
-    }
-    // partial tile of slice z (whole tiles only: I % 128 == 0, J % 256 == 0)
-    float* C = Cg + (size_t)blockIdx.z * g.I * g.J;
-    const int li = lane & 31, lh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = i0 + wi * WI + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh, col = j0 + wj * WJ + j * 32 + li;
-                C[(size_t)row * g.J + col] = acc[i][j][r];
-            }
-}
-
-// slices: enough workgroups for one round of the chip at two per CU, at least 8 k-tiles each, never more than `max_slices`
-int gemm_b1tn_slices(int I, int J, int M, int max_slices) {
-    const int tiles = (I / 128) * (J / 256);
-    int S = cdiv(512, tiles);
-    const int smax = cdiv(M, 256);
-    if (S > smax) S = smax;
-    if (S > 64) S = 64;
-    if (S > max_slices) S = max_slices;
-    return S < 1 ? 1 : S;
+#include "gemm_tn_tail.h"
 }
 
 // out (S slices with rows: [S][I][J], else [I][J]) <- RN(X)^T . RN(dY) per slice, db_out (nullable; [S][J] / [J]) <- the slices' column
@@ -223,11 +139,9 @@ int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out,
     R4D_REQUIRE(gemm_b1tn_supported(I, J, M, lda, ldb), "gemm_b1tn: unsupported shape I=%d J=%d M=%d lda=%d ldb=%d (I %% 128 == 0, J %% 256 == 0, M >= 32 wanted)", I, J, M, lda, ldb);
     R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)db_out % 16) == 0,
                 "gemm_b1tn: 16-byte alignment");
-    B1TnShape sh;
-    sh.M = M; sh.I = I; sh.J = J; sh.lda = lda; sh.ldb = ldb;
-    sh.kper = cdiv(cdiv(M, S), 32) * 32;
+    const B1TnShape sh{tn_shape(I, J, M, lda, ldb, S)};
     ProfScope prof(PK_GEMM_B1TN, 2.0 * (double)I * J * M, stream);
-    hipLaunchKernelGGL(gemm_b1tn_kernel, dim3((I / 128) * (J / 256), 1, cdiv(M, sh.kper)), dim3(512), 0, stream, X, dY, out, sh, db_out);
+    hipLaunchKernelGGL(gemm_b1tn_kernel, tn_grid(sh), dim3(512), 0, stream, X, dY, out, sh, db_out);
     R4D_CHECK_LAUNCH("gemm_b1tn");
     return R4D_OK;
 }

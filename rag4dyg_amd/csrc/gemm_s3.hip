@@ -23,7 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
-#include "gemm_common.h"
+#include "bf16x3.h"               // split3_pair: the split itself
 
 #ifndef S3_NRS
 #define S3_NRS 1   // register stages of the 128 x 256 tile; 2 measured no faster (K = 512: 157-166 vs 163-168 TFLOP/s, 240 vs 206 VGPRs): the k-tile loads are not latency-bound
@@ -33,23 +33,6 @@
 #endif
 
 namespace r4d {
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32: low half = bf16(a), RNE
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-// two fp32 -> packed (hi, hi), (mid, mid), (lo, lo)
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - __builtin_bit_cast(float, m << 16), s1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = cvt_pk_bf16(s0, s1);
-}
-
 
 struct S3Shape {
     int M, N, K, lda, ldc, ldr;
@@ -96,7 +79,7 @@ __global__ __launch_bounds__(256) void split3_planes_kernel(const float* __restr
 //     one (`fin`) and cleared after every NG k-tiles;
 //   * within a line, MFMA step s of lane half h holds k = 16 s + 4 h + {0..3} and 16 s + 8 + 4 h + {0..3} (the scan's two
 //     16-byte loads per step): the staging loads fetch those two pieces, 32 bytes apart, instead of 8 consecutive k;
-//   * same split (split3_pair == scan_split_pair), same six products in the same order, queries as the MFMA's first operand.
+//   * same split (both call split3_pair of bf16x3.h), same six products in the same order, queries as the MFMA's first operand.
 template <int BM, int BN, int WGM, int WGN, int NBUF, int NRS, int EPI, bool BF32 = false, int SCAN = 0>
 __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void gemm_s3_kernel(
     const float* __restrict__ Ag, const unsigned short* __restrict__ Bp, float* __restrict__ Cg,

@@ -6,7 +6,7 @@
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
-#include "common.h"
+#include "bf16x3.h"               // split3_pair: the split of the bf16x3 GEMMs, here per lane
 
 #ifndef SCAN_RING_P
 #define SCAN_RING_P 3   // ring slots per wavefront of the long-shard form (tuning aid: 4 = deeper ring, single-buffered partial tiles)
@@ -70,35 +70,18 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
 // v_mfma_f32_32x32x2_f32: 2.67x fewer matrix-pipe cycles per pool byte, which takes the scan OFF the fp32 ridge (the timeline
 // of tools/scan_timeline.py at a 12.5k-row shard: 4 of 11 us were exact-f32 MFMA on two tiles per CU).  The arithmetic of a
 // score does not depend on the tile, the workgroup or the shard the row falls in (shard merge == single GPU bit for bit).
-typedef float f32x16s __attribute__((ext_vector_type(16)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned scan_cvt_pk(float a, float b) {   // v_cvt_pk_bf16_f32: low half = bf16(a), RNE
-    const f32x2v v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-}
-// two fp32 -> packed (hi, hi), (mid, mid), (lo, lo): x == hi + mid + lo exactly (gemm_s3.hip)
-__device__ __forceinline__ void scan_split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-    h = scan_cvt_pk(x0, x1);
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = scan_cvt_pk(r0, r1);
-    const float s0 = r0 - __builtin_bit_cast(float, m << 16), s1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = scan_cvt_pk(s0, s1);
-}
+// The split is split3_pair of bf16x3.h, the one the GEMMs call.
 // a lane's 8 k of one bf16 MFMA step (two 16-byte pieces) -> three bf16x8 operands
-__device__ __forceinline__ void scan_split8(const float4& a, const float4& b, u32x4v& h, u32x4v& m, u32x4v& l) {
+__device__ __forceinline__ void scan_split8(const float4& a, const float4& b, u32x4& h, u32x4& m, u32x4& l) {
     unsigned hh[4], mm[4], ll[4];
-    scan_split_pair(a.x, a.y, hh[0], mm[0], ll[0]); scan_split_pair(a.z, a.w, hh[1], mm[1], ll[1]);
-    scan_split_pair(b.x, b.y, hh[2], mm[2], ll[2]); scan_split_pair(b.z, b.w, hh[3], mm[3], ll[3]);
-    h = u32x4v{hh[0], hh[1], hh[2], hh[3]}; m = u32x4v{mm[0], mm[1], mm[2], mm[3]}; l = u32x4v{ll[0], ll[1], ll[2], ll[3]};
+    split3_pair(a.x, a.y, hh[0], mm[0], ll[0]); split3_pair(a.z, a.w, hh[1], mm[1], ll[1]);
+    split3_pair(b.x, b.y, hh[2], mm[2], ll[2]); split3_pair(b.z, b.w, hh[3], mm[3], ll[3]);
+    h = u32x4{hh[0], hh[1], hh[2], hh[3]}; m = u32x4{mm[0], mm[1], mm[2], mm[3]}; l = u32x4{ll[0], ll[1], ll[2], ll[3]};
 }
 // the six products of one 16-k step, smallest terms first: lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (gemm_s3.hip)
 #define SCAN_STEP6(ACC_, Q_, BH_, BM_, BL_) do { SCAN_MFMA16(Q_[2], BH_, ACC_); SCAN_MFMA16(Q_[0], BL_, ACC_); SCAN_MFMA16(Q_[1], BM_, ACC_); \
     SCAN_MFMA16(Q_[1], BH_, ACC_); SCAN_MFMA16(Q_[0], BM_, ACC_); SCAN_MFMA16(Q_[0], BH_, ACC_); } while (0)
-#define SCAN_MFMA16(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8v, A_), __builtin_bit_cast(bf16x8v, B_), ACC_, 0, 0, 0)
+#define SCAN_MFMA16(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, B_), ACC_, 0, 0, 0)
 
 template <int KW, int NG, bool TWO, bool S3>            // d == 32 * KW * NG; TWO: two tiles of a workgroup in flight; S3: bf16x3
 __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_scan_ks_kernel(const float* __restrict__ qhat, const float* __restrict__ pool,
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
     // S3: MFMA step s of line g takes loads 2s and 2s + 1 of the lane as its 8 consecutive "k" (the same bijection on both
     // operands), q3[g][s][plane] holding the query side split once
     float4 qf[NG][4];
-    u32x4v q3[S3 ? NG : 1][2][3];
+    u32x4 q3[S3 ? NG : 1][2][3];
     float4 b1[TWO ? NG : 1][4];
     {
         const bool ok = q0 + li < Q;
@@ -193,16 +176,16 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
     if constexpr (S3) { asm volatile("" :: "v"(q3[NG - 1][1][2])); if (lane == 0) wst[3] = __builtin_amdgcn_s_memrealtime(); }
 #endif
     // the MFMAs of one 128-byte line group of the staged rows
-    auto mfma_group = [&](f32x16s& acc, int g, const float4 (&b)[4]) {
+    auto mfma_group = [&](f32x16& acc, int g, const float4 (&b)[4]) {
         if constexpr ((SCAN_DBG & 1) != 0) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[u] += b[u].x + b[u].y + b[u].z + b[u].w;
         } else if constexpr (S3) {
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                u32x4v bh, bm, bl;
+                u32x4 bh, bm, bl;
                 if constexpr ((SCAN_DBG & 16) != 0) {
-                    bh = __builtin_bit_cast(u32x4v, b[2 * st]); bm = __builtin_bit_cast(u32x4v, b[2 * st + 1]); bl = bh ^ bm;
+                    bh = __builtin_bit_cast(u32x4, b[2 * st]); bm = __builtin_bit_cast(u32x4, b[2 * st + 1]); bl = bh ^ bm;
                 } else {
                     scan_split8(b[2 * st], b[2 * st + 1], bh, bm, bl);
                 }
@@ -228,7 +211,7 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
     // its MFMAs (program order, no copies), cross-wave reduction, (x+1)/2, store
     auto do_tile = [&](float4 (&bb)[NG][4], int tcur, int trefill) {
         const float4* __restrict__ pn = tile_ptr(trefill >= 0 ? trefill : tcur);
-        f32x16s acc;
+        f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -290,7 +273,7 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
         // tile's reduction waits 1.8 us for the wave whose loads landed last, while the matrix pipe idles)
         for (int t = 0; t < ntiles; t += 2) {
             const bool has2 = t + 1 < ntiles;                             // workgroup-uniform
-            f32x16s acc2[2];
+            f32x16 acc2[2];
             if constexpr (S3 && !(SCAN_DBG & 17)) {
                 // The split of a step's pool operand (36 VALU instructions) is issued INSIDE the six MFMAs of the step before
                 // it, six per MFMA gap (sched_group_barrier): left to the compiler the stream is split, split, ..., MFMA x 6,
@@ -298,12 +281,12 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
                 // vector ALU and the matrix pipe take turns (timeline: 4,600 cycles per tile and SIMD = 48 x 32 + 704 x 4.2).
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { acc2[0][r] = 0.f; acc2[1][r] = 0.f; }
-                u32x4v ch, cm, cl;
+                u32x4 ch, cm, cl;
                 scan_split8(b0[0][0], b0[0][1], ch, cm, cl);
 #pragma unroll
                 for (int i = 0; i < 2 * NG; ++i) {
                     const int g = i >> 1, st = i & 1, gn = (i + 1) >> 1, un = 2 * ((i + 1) & 1);
-                    u32x4v nh, nm, nl;
+                    u32x4 nh, nm, nl;
                     if (i + 1 < 2 * NG) scan_split8(b0[gn][un], b0[gn][un + 1], nh, nm, nl);
                     else scan_split8(b1[0][0], b1[0][1], nh, nm, nl);
                     SCAN_STEP6(acc2[0], q3[g][st], ch, cm, cl);
@@ -319,7 +302,7 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
 #pragma unroll
                     for (int i = 0; i < 2 * NG; ++i) {
                         const int g = i >> 1, st = i & 1, gn = (i + 1) >> 1, un = 2 * ((i + 1) & 1);
-                        u32x4v nh, nm, nl;
+                        u32x4 nh, nm, nl;
                         if (i + 1 < 2 * NG) scan_split8(b1[gn][un], b1[gn][un + 1], nh, nm, nl);
                         SCAN_STEP6(acc2[1], q3[g][st], ch, cm, cl);
                         if (i + 1 < 2 * NG) {
@@ -498,7 +481,7 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
 #pragma unroll
         for (int u = 0; u < 4; ++u) f[u] = base[(2 * u + lh) ^ fsw];
     };
-    f32x16s acc2[2];
+    f32x16 acc2[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc2[0][r] = 0.f; acc2[1][r] = 0.f; }
     const bool has2 = r1 - r0 > 32;                       // workgroup-uniform
@@ -510,7 +493,7 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
 #pragma unroll
         for (int p = 0; p < P && p < NP; ++p) issue(p);
         SCAN_WSTAMP(1);
-        u32x4v q3[NG][2][3];
+        u32x4 q3[NG][2][3];
         const bool ok = q0 + li < Q;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
@@ -537,12 +520,12 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
         read_piece(NG, cur);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (NG + P < NP) issue(NG + P);
-        u32x4v ch, cm, cl;
+        u32x4 ch, cm, cl;
         scan_split8(cur[0], cur[1], ch, cm, cl);
 #pragma unroll
         for (int tp = 0; tp < NTP; ++tp) {
             const int p = NG + tp, g = tp % NG, h = tp / NG;
-            u32x4v nh, nm, nl;
+            u32x4 nh, nm, nl;
             scan_split8(cur[2], cur[3], nh, nm, nl);                         // ... inside the six MFMAs of the step before it
             SCAN_STEP6(acc2[h], q3[g][0], ch, cm, cl);
 #pragma unroll
@@ -683,7 +666,7 @@ __global__ __launch_bounds__(64 * KW, KW == 8 ? 1 : 2) void pool_scan_ring_kerne
     };
 #pragma unroll
     for (int p = 0; p < P; ++p) issue_next();
-    u32x4v q3[NG][2][3];
+    u32x4 q3[NG][2][3];
     {
         const bool ok = q0 + li < Q;
 #pragma unroll
@@ -706,16 +689,16 @@ __global__ __launch_bounds__(64 * KW, KW == 8 ? 1 : 2) void pool_scan_ring_kerne
     read_piece(cur);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     issue_next();
-    u32x4v ch, cm, cl;
+    u32x4 ch, cm, cl;
     scan_split8(cur[0], cur[1], ch, cm, cl);
     int buf = 0;
     for (int j = 0; j < ntl; ++j) {
-        f32x16s acc;
+        f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            u32x4v nh, nm, nl;
+            u32x4 nh, nm, nl;
 #if SCAN_DBG & 1
             acc[0] += cur[0].x + cur[1].y + cur[2].z + cur[3].w; nh = ch; nm = cm; nl = cl;
 #else

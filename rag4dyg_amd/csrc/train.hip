@@ -174,8 +174,15 @@ int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* 
     return launch_gemm_f32(gemm_args(dy, W.w ? W.w : W.wT, W.w != nullptr, nullptr, resid, M, W.out, W.in, epi, dx), s);
 }
 
+// the matrix-core weight gradients' slices, added in slice order: dW <- part [Sx][I][J], db <- db_part [Sx][J] (null: no db)
+static int reduce_slices(const float* part, const float* db_part, int Sx, float* dW, float* db, int I, int J, hipStream_t s) {
+    const int rc = launch_splitk_reduce(part, (long long)I * J / 4, Sx, dW, s);
+    return (rc || !db_part) ? rc : launch_splitk_reduce(db_part, (long long)(J / 4), Sx, db, s);
+}
+
 // gemm_b1tn and its reduces: dW <- RN(X)^T . RN(dY), db (nullable) <- column sums of dY.  `part` / `db_part`: room for the slices'
-// partials (the slice count follows the smaller room, one slice needs none).  *db_done: whether db was written.
+// partials (the slice count follows the room of `part`, at most 64; ONE slice writes dW / db itself and needs none).  *db_done:
+// whether db was written.
 static int wgrad_b1tn(const float* X, const float* dY, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part,
                       size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t s) {
     R4D_REQUIRE(X && dY && dW, "gemm_b1tn: null pointer");
@@ -183,23 +190,20 @@ static int wgrad_b1tn(const float* X, const float* dY, float* dW, float* db, int
     R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)dW % 16) == 0 && ((uintptr_t)part % 16) == 0,
                 "gemm_b1tn: 16-byte alignment");
     const int max_s = part ? (int)(part_floats / ((size_t)I * J) > 64 ? 64 : part_floats / ((size_t)I * J)) : 1;
-    const int S = gemm_b1tn_slices(I, J, M, max_s), Sx = tn_row_slices(M, S);
+    const int S = gemm_tn_slices(I, J, M, max_s), Sx = tn_row_slices(M, S);
     const bool want_db = db && ((uintptr_t)db % 16) == 0 &&
                          (Sx == 1 || (db_part && ((uintptr_t)db_part % 16) == 0 && (size_t)Sx * J <= db_part_floats));
     int rc = launch_gemm_b1tn(X, dY, Sx > 1 ? part : dW, want_db ? (Sx > 1 ? db_part : db) : nullptr, I, J, M, lda, ldb, S, s);
-    if (rc) return rc;
-    if (Sx > 1) {
-        if ((rc = launch_splitk_reduce(part, (long long)I * J / 4, Sx, dW, s))) return rc;
-        if (want_db && (rc = launch_splitk_reduce(db_part, (long long)(J / 4), Sx, db, s))) return rc;
-    }
-    *db_done = want_db;
-    return R4D_OK;
+    if (!rc && Sx > 1) rc = reduce_slices(part, want_db ? db_part : nullptr, Sx, dW, db, I, J, s);
+    if (!rc) *db_done = want_db;
+    return rc;
 }
 
 // dW[I,J] = x[M,I]^T . dy[M,J]: both operands read row by row over the contracted token index, split over it into slices whose
 // partials (in `part`) are summed in slice order; db[J] = column sums of dy -- by the matrix-core kernels while they stage dy where
-// `red` has the room for their slices' sums, else by the column-sum kernel.  wgrad_route names the kernel; the slice rules are
-// each kernel's own (the bits of dW depend on them): gemm_b1tn_slices within the room of `part`, gemm_s3tn_slices within tn_splits
+// `red` has the room for their slices' sums, else by the column-sum kernel.  wgrad_route names the kernel; the matrix-core
+// kernels share one slice rule (the bits of dW depend on it): gemm_tn_slices, for gemm_b1tn within the room of `part` and 64, for
+// gemm_s3tn within tn_splits
 int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part, float* red,
                 hipStream_t s, int bf16) {
     const GemmRoute route = wgrad_route(I, J, M, lda, ldb, bf16);
@@ -211,12 +215,11 @@ int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, in
         rc = wgrad_b1tn(x, dy, dW, db, I, J, M, lda, ldb, part, gemm_tn_scratch_floats(I, J, M), red, red_floats, &db_done, s);
     } else if (route == ROUTE_WGRAD_S3TN) {
         R4D_REQUIRE(I > 0 && J > 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dW % 16) == 0, "gemm_tn: 16-byte alignment");
-        const int S = gemm_s3tn_slices(I, J, M, tn_splits(I, J, M));
-        int Sx = 1;
+        const int S = gemm_tn_slices(I, J, M, tn_splits(I, J, M));
         const bool cs = db && red && (size_t)S * J <= red_floats && ((uintptr_t)red % 16) == 0 && ((uintptr_t)db % 16) == 0;
-        if ((rc = launch_gemm_s3tn(x, dy, part, I, J, M, lda, ldb, S, &Sx, s, cs ? red : nullptr))) return rc;
-        rc = launch_splitk_reduce(part, (long long)I * J / 4, Sx, dW, s);
-        if (!rc && cs) rc = launch_splitk_reduce(red, (long long)(J / 4), Sx, db, s);     // the slices' column sums, added in slice order
+        // (always partials and a reduce, also when only one slice holds rows)
+        if ((rc = launch_gemm_s3tn(x, dy, part, cs ? red : nullptr, I, J, M, lda, ldb, S, s))) return rc;
+        rc = reduce_slices(part, cs ? red : nullptr, tn_row_slices(M, S), dW, db, I, J, s);
         db_done = cs;
     } else {
         rc = launch_gemm_f32_tn(x, dy, dW, I, J, M, lda, ldb, part, s);
@@ -395,7 +398,7 @@ int r4d_conv1d_bf16_dgrad_f32(const float* dy_d, const uint16_t* wt_bf16_d, int3
 
 // workspace of the single op: the slices' dW partials (64-float aligned), behind them their db partials
 static size_t wgrad_bf16_part_floats(int rows, int I, int J, int* S) {
-    *S = gemm_b1tn_slices(I, J, rows, 64);
+    *S = gemm_tn_slices(I, J, rows, 64);
     return *S > 1 ? ((size_t)*S * I * J + 63) / 64 * 64 : 0;
 }
 size_t r4d_weight_grad_bf16_workspace_bytes(int32_t rows, int32_t in_features, int32_t out_features) {

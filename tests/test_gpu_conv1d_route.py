@@ -195,6 +195,50 @@ def test_weight_gradient_reaches_s3tn_beyond_one_slice(dev):
             assert torch.allclose(db.double(), dy.double().sum(0), rtol=1e-5, atol=1e-4)
 
 
+def _tn_slices(rows, I, J):
+    """(wanted slices, k-tiles of each slice that holds rows) of gemm_s3tn under weight_grad: csrc/common.h gemm_tn_slices within
+    csrc/conv1d_route.h tn_splits, cut into whole 32-row steps (tn_row_slices)."""
+    cdiv = lambda a, b: -(-a // b)
+    splits = max(1, min(cdiv(1024, cdiv(I, 128) * cdiv(J, 128)), cdiv(rows, 256), 64))
+    S = max(1, min(cdiv(512, (I // 128) * (J // 256)), cdiv(rows, 256), splits))
+    kper = cdiv(cdiv(rows, S), 32) * 32
+    return S, [cdiv(min(rows, lo + kper) - lo, 32) for lo in range(0, rows, kper)]
+
+
+@pytest.mark.parametrize("rows", (257, 545))
+def test_weight_gradient_on_s3tn_at_uneven_slices(dev, rows):
+    """gemm_s3tn as a single op in bf16x3 mode, in 128, out 512, at the row counts where its two-stage loop and its tail differ:
+    257 rows = two slices of 5 and 4 k-tiles (both parities of the loop, a last k-tile of ONE row), 545 rows = three slices of 6
+    k-tiles, the last one again ending on one row.  The route, the launch counters, dW and db against float64 at the bounds of
+    the 390-row test above, and the same bits from a second run."""
+    from rag4dyg_amd import _lib, ops
+    lib = _lib.load()
+    I, J = 128, 512
+    assert _tn_slices(rows, I, J) == {257: (2, [5, 4]), 545: (3, [6, 6, 6])}[rows]
+    assert rows % 32 == 1
+    ops.set_gemm_mode("bf16x3")
+    g = torch.Generator().manual_seed(rows)
+    x, dy = torch.randn(rows, I, generator=g).to(dev), torch.randn(rows, J, generator=g).to(dev)
+    r = route(5, rows, I, J, NONE, 0, 0)
+    assert r == "wgrad_s3tn"
+    ws = torch.empty(max(int(lib.r4d_weight_grad_workspace_bytes(rows, I, J)), 256), dtype=torch.uint8, device=dev)
+    runs = []
+    for _ in range(2):
+        dw, db = torch.empty(I, J, device=dev), torch.empty(J, device=dev)
+        lib.r4d_dispatch_reset()
+        _lib.check(lib.r4d_weight_grad_f32(x.data_ptr(), dy.data_ptr(), rows, I, J, dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), torch.cuda.current_stream().cuda_stream), "weight_grad")
+        torch.cuda.synchronize()
+        got = launches()
+        assert got == predicted([r]), (rows, got)
+        runs.append((dw, db))
+    dw, db = runs[0]
+    ref = x.double().t() @ dy.double()
+    assert float((dw.double() - ref).abs().max() / ref.abs().max()) < 1e-5
+    assert torch.allclose(db.double(), dy.double().sum(0), rtol=1e-5, atol=1e-4)
+    assert torch.equal(runs[1][0], dw) and torch.equal(runs[1][1], db)
+
+
 def test_decode_step_takes_the_skinny_route(dev):
     from rag4dyg_amd import _lib, ops
     lib = _lib.load()
