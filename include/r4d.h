@@ -272,6 +272,19 @@ int r4d_set_attention_h2(int32_t on);
  * r4d_pack_kblk_words builds it from row-major qkv words (tests, external producers); r4d_attention_h2_kblk_f32 is
  * r4d_attention_h2_f32 reading K from it (the K columns of qkv_words_d are not read) -- bit-identical results. */
 int r4d_set_attention_kblk(int32_t on);
+/* LAYER 0's REPEATED PAD ROWS.  In layer 0 the c_attn row of a position depends on (token, position) only, and the reference's
+ * batching makes most rows of a call [PAD] rows (70 % in the bench step).  On the path above (f16x2 lines, h2 words, the
+ * key-blocked image, ids given, qkv not handed out) the layer-0 c_attn GEMM therefore skips every 32-row block (by global row
+ * index) whose rows all carry one candidate token -- the most frequent last-position token of the call, found on the device --
+ * and a copy kernel fills those rows from round_up(Tmax, 32) table rows (token, p) that the same launch computes: the bits of
+ * every row are those of the full GEMM.  r4d_set_layer0_pad_rows(0) keeps the full GEMM (returns the previous setting; env
+ * R4D_LAYER0_PAD_ROWS=0 does the same; process-wide).  Either way the encoder workspaces hold the table rows and the plan:
+ * with Mp = round_up(rows, 32), Tcap = round_up(Tmax, 32), x, the LayerNorm rows, qkv and the key-blocked image have Mp + Tcap
+ * rows, and 8 + 2 Tcap + 2 Mp + round_up(Mp / 32 + Tcap / 32, 4) + Mp / 32 + vocab 32-bit words follow the key-blocked image.
+ * r4d_gpt2_layer0_pad_rows_offset (tests): the byte offset of those words in a workspace of r4d_gpt2_groups_workspace_bytes;
+ * word 0 = listed blocks, 1 = dropped blocks, 2 = the token, 3 / 4 = the word offsets of the two block lists. */
+int r4d_set_layer0_pad_rows(int32_t on);
+size_t r4d_gpt2_layer0_pad_rows_offset(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts);
 int r4d_pack_kblk_words(const uint32_t* qkv_words_d, int64_t rows, int32_t n_head, int32_t d, uint32_t* kblk_d, void* stream);
 int r4d_attention_h2_kblk_f32(const uint32_t* qkv_words_d, const uint32_t* kblk_d, int32_t B, int32_t T, int32_t n_head, int32_t d,
                               float* a_d, void* stream);

@@ -77,6 +77,8 @@ PROTOTYPES = {
     "r4d_set_attention_fused": (c_int32, [c_int32]),
     "r4d_set_attention_h2": (c_int32, [c_int32]),
     "r4d_set_attention_kblk": (c_int32, [c_int32]),
+    "r4d_set_layer0_pad_rows": (c_int32, [c_int32]),
+    "r4d_gpt2_layer0_pad_rows_offset": (c_size_t, [POINTER(GPT2ConfigC), c_int32, POINTER(c_int32), POINTER(c_int32)]),
     "r4d_pack_kblk_words": (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P]),
     "r4d_attention_h2_kblk_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "r4d_set_range_flag": (c_int32, [_P]),

@@ -45,7 +45,7 @@ enum ProfClass {
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
-    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_COUNT
+    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -65,7 +65,7 @@ struct ProfScope {
     X(KC_128x128x16, "gemm_kc:128x128x16") X(KC_128x64x16, "gemm_kc:128x64x16") X(KC_64x64x32, "gemm_kc:64x64x32")       \
     X(KC_128x128x32, "tuning:gemm_kc:128x128x32") X(KC_ROWSPLIT, "gemm_kc:row-split (two launches)")                      \
     X(S3_128x256, "gemm_s3:128x256x32") X(S3_PERSISTENT, "gemm_s3:128x256x32 persistent (pipeline across tiles)") X(S3_128x128, "gemm_s3:128x128x32") X(S3_F32B, "gemm_s3:both operands split on the fly (scoring GEMM)") X(S3_TN, "gemm_s3tn:128x256x32 (weight gradients, transposing LDS reads)")      \
-    X(H2_128x256, "gemm_h2:128x256x32 (f16x2)") X(H2_128x128, "gemm_h2:128x128x32 (f16x2)") X(H2P_128x256, "gemm_h2p:128x256x32 (f16x2, A as lines, LDS-DMA)") X(H2P_128x128, "gemm_h2p:128x128x32 (f16x2, A as lines, LDS-DMA)") \
+    X(H2_128x256, "gemm_h2:128x256x32 (f16x2)") X(H2_128x128, "gemm_h2:128x128x32 (f16x2)") X(H2P_128x256, "gemm_h2p:128x256x32 (f16x2, A as lines, LDS-DMA)") X(H2P_128x128, "gemm_h2p:128x128x32 (f16x2, A as lines, LDS-DMA)") X(H2P_ROWMAP, "gemm_h2p:row-block map (layer 0 c_attn without the repeated pad-row blocks)") \
     X(F32_128x128, "gemm_f32:128x128") X(F32_128x64, "gemm_f32:128x64") X(F32_64x64, "gemm_f32:64x64")                   \
     X(F32_NT, "gemm_f32:B as [N,K]") X(F32_NN, "gemm_f32:B as [K,N]") X(TN_SPLITK, "gemm_tn:split-K") X(TN_SINGLE, "gemm_tn:one slice") \
     X(SK16_NG2, "skinny16:ng2") X(SK16_NG3, "skinny16:ng3") X(SK16_NG2_LN, "skinny16:ng2+layernorm") X(SK16_LN_FOLDED, "skinny16:LayerNorm pre-folded into the weight") X(SK16_NG3_LN, "skinny16:ng3+layernorm") \
@@ -337,6 +337,42 @@ int launch_attention_fused_groups(const float* qkv, int n, const int* Bs, const 
                                   int d, float* out, hipStream_t s);
 extern int g_attention_variant;
 extern int g_attention_fused;        // -1 auto (default), 1 fused, 0 three-launch GEMM form (r4d_set_attention_fused)
+// Layer 0's repeated pad rows (encoder.hip: encode_impl).  The layer-0 c_attn row depends on (token, position) only,
+// so 32-row blocks (by GLOBAL row index, as in the key-blocked image) whose rows all carry one candidate token c are dropped from
+// that GEMM and filled afterwards from `Tcap` TABLE rows (c, p), p = 0 .. Tcap - 1, that ride along at row Mp = round_up(M, 32).
+// One region of 32-bit words in the workspace holds the plan of a call, all of it written on the device before it is read:
+//   hdr[0] n_list (kept blocks + table blocks, padded with repeats of the last entry to a multiple of 4), hdr[1] n_drop, hdr[2] c,
+//   hdr[3] / hdr[4] the word offsets of the two lists from hdr;  int64 tab_ids[Tcap];  tok[Mp];  pos[Mp];  list[lmax];  drop[nblk];
+//   hist[vocab] (counts of the sequences' last-position tokens: c = the most frequent, ties to the lowest id)
+constexpr int PAD_ROWS_HDR = 8;
+struct PadRowsPlan {
+    int M, Mp, Tmax, Tcap, nblk, ntab, lmax, vocab;
+    size_t words() const { return (size_t)PAD_ROWS_HDR + 2 * (size_t)Tcap + lmax + nblk + 2 * (size_t)Mp + vocab; }
+    size_t rows() const { return (size_t)Mp + Tcap; }            // rows of x, the LayerNorm lines, qkv and the key-blocked image
+};
+static inline PadRowsPlan pad_rows_plan(size_t M, int Tmax, int vocab) {
+    PadRowsPlan p;
+    p.M = (int)M; p.Mp = (int)((M + 31) / 32 * 32); p.Tmax = Tmax; p.Tcap = (Tmax + 31) / 32 * 32;
+    p.nblk = p.Mp / 32; p.ntab = p.Tcap / 32; p.lmax = (p.nblk + p.ntab + 3) / 4 * 4; p.vocab = vocab;
+    return p;
+}
+struct PadRowsBuf {
+    int* hdr; long long* tab_ids; int *list, *drop, *tok, *pos, *hist;
+};
+static inline PadRowsBuf pad_rows_buf(int* hdr, const PadRowsPlan& p) {
+    PadRowsBuf b;
+    b.hdr = hdr; b.tab_ids = reinterpret_cast<long long*>(hdr + PAD_ROWS_HDR);
+    b.tok = hdr + PAD_ROWS_HDR + 2 * p.Tcap; b.pos = b.tok + p.Mp; b.list = b.pos + p.Mp; b.drop = b.list + p.lmax; b.hist = b.drop + p.nblk;      // (tok: 16-byte aligned)
+    return b;
+}
+// tok / pos of the rows of up to ATT_MAXG batches (first row: row_base) and the last-position counts (hist cleared by the caller)
+int launch_pad_rows_gather(const RowGroups& G, int vocab, long long row_base, const PadRowsBuf& b, hipStream_t s);
+// c, the two block lists, the header and the table's ids; one workgroup, no host synchronisation
+int launch_pad_rows_classify(const PadRowsPlan& p, const PadRowsBuf& b, hipStream_t s);
+// q and v words and the key-blocked K pieces of every dropped block's rows, from the table rows of their positions
+int launch_pad_rows_fill(const PadRowsPlan& p, const PadRowsBuf& b, unsigned* qkv_words, unsigned* kblk, int d, hipStream_t s);
+// gemm_h2p.hip with the row-block map: the h2-word c_attn over the listed blocks only (a.M = the rows that exist: p.rows())
+int launch_gemm_h2p_rowmap(const S3Args& a, const unsigned short* a_lines, const PadRowsPlan& p, const PadRowsBuf& b, hipStream_t stream);
 constexpr int LNF_ROWS_PER_CHUNK = 16;
 size_t lnf_meanpool_scratch_floats(int B, int T, int d);
 // x / hidden_out: first row of the first batch; pool_out: first sequence of the first batch; scratch: the sum over the

@@ -111,22 +111,39 @@ static RowGroups row_groups(const Group* groups, int g0, int n_groups) {
 struct Workspace {
     float *x, *ln, *qkv, *att, *fc, *scores, *pool;
     unsigned* kblk;       // key-blocked K words of the f16x2 attention (attention_h2.hip): ceil32(M) x d
+    int* pad_rows;        // the plan of layer 0's repeated pad rows (common.h: PadRowsPlan); null in the decode workspaces
+    size_t pad_rows_off;
     size_t bytes;
 };
-static Workspace carve(void* base, size_t M, size_t score_floats, size_t pool_floats, int d) {
+// `pr` (the encoder calls): x, the LayerNorm rows, qkv and the key-blocked image get room for the table rows behind
+// round_up(M, 32) -- pr->rows() rows where there were M -- and the plan's words follow the key-blocked image
+static Workspace carve(void* base, size_t M, size_t score_floats, size_t pool_floats, int d, const PadRowsPlan* pr = nullptr) {
     size_t off = 0;
     auto take = [&](size_t nfloat) {
         float* p = base ? (float*)((char*)base + off) : nullptr;
         off += align_up(nfloat * sizeof(float), 256);
         return p;
     };
+    const size_t Mx = pr ? pr->rows() : M;
     Workspace w;
-    w.x = take(M * d); w.ln = take(M * d); w.qkv = take(M * 3 * d); w.att = take(M * d); w.fc = take(M * 4 * d);
+    w.x = take(Mx * d); w.ln = take(Mx * d); w.qkv = take(Mx * 3 * d); w.att = take(M * d); w.fc = take(M * 4 * d);
     w.scores = take(score_floats);
     w.pool = take(pool_floats);
-    w.kblk = reinterpret_cast<unsigned*>(take(kblk_words(M, d)));
+    w.kblk = reinterpret_cast<unsigned*>(take(kblk_words(Mx, d)));
+    w.pad_rows_off = off;
+    w.pad_rows = pr ? reinterpret_cast<int*>(take(pr->words())) : nullptr;
     w.bytes = off;
     return w;
+}
+static int g_layer0_pad_rows = -1;    // r4d_set_layer0_pad_rows; -1: R4D_LAYER0_PAD_ROWS in the environment, read once (default on)
+static int layer0_pad_rows_on() {
+    if (g_layer0_pad_rows < 0) { const char* e = getenv("R4D_LAYER0_PAD_ROWS"); g_layer0_pad_rows = e ? atoi(e) != 0 : 1; }
+    return g_layer0_pad_rows;
+}
+static PadRowsPlan groups_pad_rows_plan(const r4d_gpt2_config* cfg, size_t M, int n_groups, const int32_t* Ts) {
+    int Tmax = 1;
+    for (int g = 0; g < n_groups; ++g) Tmax = Ts[g] > Tmax ? Ts[g] : Tmax;
+    return pad_rows_plan(M, Tmax, cfg->vocab > 0 ? cfg->vocab : 1);
 }
 static size_t score_floats(int B, int H, int T) { return (size_t)B * H * T * tpad(T); }
 
@@ -185,8 +202,9 @@ const char* r4d_last_error(void) { return g_err; }
 
 size_t r4d_gpt2_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t T) {
     if (!cfg || B <= 0 || T <= 0) return 0;
+    const PadRowsPlan pr = groups_pad_rows_plan(cfg, (size_t)B * T, 1, &T);
     return carve(nullptr, (size_t)B * T, score_floats(B, cfg->n_head, T), lnf_meanpool_scratch_floats(B, T, cfg->n_embd),
-                 cfg->n_embd).bytes;
+                 cfg->n_embd, &pr).bytes;
 }
 
 size_t r4d_gpt2_groups_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs,
@@ -200,7 +218,29 @@ size_t r4d_gpt2_groups_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_gro
         if (f > sc) sc = f;
         pl += lnf_meanpool_scratch_floats(Bs[g], Ts[g], cfg->n_embd);      // all batches pooled by one launch
     }
-    return carve(nullptr, M, sc, pl, cfg->n_embd).bytes;
+    const PadRowsPlan pr = groups_pad_rows_plan(cfg, M, n_groups, Ts);
+    return carve(nullptr, M, sc, pl, cfg->n_embd, &pr).bytes;
+}
+
+// tests: the byte offset of the pad-row plan's header in a workspace of r4d_gpt2_groups_workspace_bytes (0: bad arguments)
+size_t r4d_gpt2_layer0_pad_rows_offset(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts) {
+    if (!cfg || n_groups <= 0 || !Bs || !Ts) return 0;
+    size_t M = 0, sc = 0, pl = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (Bs[g] <= 0 || Ts[g] <= 0) return 0;
+        M += (size_t)Bs[g] * Ts[g];
+        const size_t f = score_floats(Bs[g], cfg->n_head, Ts[g]);
+        if (f > sc) sc = f;
+        pl += lnf_meanpool_scratch_floats(Bs[g], Ts[g], cfg->n_embd);
+    }
+    const PadRowsPlan pr = groups_pad_rows_plan(cfg, M, n_groups, Ts);
+    return carve(nullptr, M, sc, pl, cfg->n_embd, &pr).pad_rows_off;
+}
+
+int r4d_set_layer0_pad_rows(int32_t on) {
+    const int prev = layer0_pad_rows_on();
+    g_layer0_pad_rows = on != 0;
+    return prev;
 }
 
 }  // extern "C"
@@ -220,8 +260,12 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
     R4D_REQUIRE(out_hidden_d || out_meanpool_d, "gpt2: no output requested");
     const int d = cfg->n_embd, H = cfg->n_head;
     size_t Mtot = 0, sc = 0, pl = 0;
+    int Tmax = 1;
+    bool all_ids = true;
     for (int g = 0; g < n_groups; ++g) {
         const Group& G = groups[g];
+        Tmax = G.T > Tmax ? G.T : Tmax;
+        all_ids = all_ids && G.ids != nullptr;
         R4D_REQUIRE((G.ids != nullptr) != (G.emb != nullptr),
                     "gpt2: specify exactly one of input_ids and inputs_embeds");     // modeling_gpt2.py:400-401,409
         R4D_REQUIRE(G.B >= 1 && G.T >= 1, "gpt2: empty batch B=%d T=%d", G.B, G.T);
@@ -233,7 +277,8 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
     }
     R4D_REQUIRE(Mtot <= 0x7fffffff / (size_t)(16 * d), "gpt2: %zu rows in one call is too many", Mtot);   // [M,4d] f32 byte offsets fit 31 bits
     const int M = (int)Mtot;
-    Workspace ws = carve(workspace_d, Mtot, sc, pl, d);
+    const PadRowsPlan pr = pad_rows_plan(Mtot, Tmax, cfg->vocab > 0 ? cfg->vocab : 1);
+    Workspace ws = carve(workspace_d, Mtot, sc, pl, d, &pr);
     if (!workspace_d || workspace_bytes < ws.bytes) {
         set_error("gpt2: workspace %zu bytes < required %zu", workspace_bytes, ws.bytes);
         return R4D_ERR_WORKSPACE;
@@ -252,24 +297,6 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
                            gemm_h2p_supported(M, d, 3 * d) && gemm_h2p_supported(M, d, 4 * d) && gemm_h2p_supported(M, 4 * d, d);
         unsigned short* ln_lines = reinterpret_cast<unsigned short*>(ws.ln);
         unsigned short* fc_lines = reinterpret_cast<unsigned short*>(ws.fc);
-        if (l == 0) {
-            for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {          // ATT_MAXG batches per launch
-                const RowGroups R = row_groups(groups, g0, n_groups);
-                const size_t r0 = groups[g0].row0;
-                rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, L.ln_1_w, L.ln_1_b, cfg->ln_eps,
-                                                   ws.x + r0 * d, ws.ln + r0 * d, s, lines);
-                if (rc) return rc;
-            }
-        } else if ((rc = lines ? launch_layernorm_lines(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ln_lines, s)
-                               : launch_layernorm(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ws.ln, s))) {
-            return rc;
-        }
-        if (out_layers_d &&
-            hipMemcpyAsync(out_layers_d + (size_t)l * M * d, ws.x, (size_t)M * d * sizeof(float),
-                           hipMemcpyDeviceToDevice, s) != hipSuccess) {
-            set_error("gpt2: layer copy failed");
-            return R4D_ERR_HIP;
-        }
         float* qkv = out_qkv_d ? out_qkv_d + (size_t)l * M * 3 * d : ws.qkv;
         // f16x2 mode, head_dim 128 / 256, qkv not handed out: c_attn writes h2 words (csrc/h2.h) and the attention runs on
         // the fp16 matrix cores (attention_h2.hip); every other case: fp32 qkv and the exact-f32 kernels below
@@ -283,12 +310,53 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         // ... and its K third as the key-blocked image the head_dim 128 / 256 kernel loads by whole cache lines (attention_h2.hip)
         if (g_attention_kblk < 0) { const char* e = getenv("R4D_ATT_KBLK"); g_attention_kblk = e ? atoi(e) != 0 : 1; }
         const bool kblk = words && lines && g_attention_kblk && (d / H) % 32 == 0;      // every head_dim attention_h2.hip serves
-        if (kblk && (M & 31) &&        // the last block's rows past M are never written: keep them finite (they are masked keys at most)
+        // Layer 0 on that path, every batch given as ids: the c_attn row of a position depends on (token, position) only, so the
+        // 32-row blocks that hold ONE token throughout -- the reference's right padding, 58 % of the bench step's blocks -- leave
+        // the GEMM and are filled from `Tcap` table rows that ride along behind round_up(M, 32) (common.h: PadRowsPlan; bit-identical)
+        const bool pad0 = l == 0 && kblk && all_ids && layer0_pad_rows_on() && (3 * d) % 256 == 0 && gemm_h2p_supported((int)pr.rows(), d, 3 * d) &&
+                          pr.rows() <= 0x7fffffff / (size_t)(16 * d);
+        const PadRowsBuf pb = pad_rows_buf(ws.pad_rows, pr);
+        if (pad0) {
+            if (hipMemsetAsync(pb.hist, 0, (size_t)pr.vocab * sizeof(int), s) != hipSuccess) { set_error("gpt2: memset of the token counts failed"); return R4D_ERR_HIP; }
+            for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG)
+                if ((rc = launch_pad_rows_gather(row_groups(groups, g0, n_groups), cfg->vocab, (long long)groups[g0].row0, pb, s))) return rc;
+            if ((rc = launch_pad_rows_classify(pr, pb, s))) return rc;
+        }
+        if (l == 0) {
+            for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {          // ATT_MAXG batches per launch
+                const RowGroups R = row_groups(groups, g0, n_groups);
+                const size_t r0 = groups[g0].row0;
+                rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, L.ln_1_w, L.ln_1_b, cfg->ln_eps,
+                                                   ws.x + r0 * d, ws.ln + r0 * d, s, lines);
+                if (rc) return rc;
+            }
+            if (pad0) {                                                   // the table: one sequence of Tmax positions, every id = c
+                RowGroups R = {};
+                R.n = 1; R.B[0] = 1; R.T[0] = pr.Tmax; R.ids[0] = reinterpret_cast<const int64_t*>(pb.tab_ids);
+                if ((rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, L.ln_1_w, L.ln_1_b, cfg->ln_eps,
+                                                        ws.x + (size_t)pr.Mp * d, ws.ln + (size_t)pr.Mp * d, s, lines))) return rc;
+            }
+        } else if ((rc = lines ? launch_layernorm_lines(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ln_lines, s)
+                               : launch_layernorm(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ws.ln, s))) {
+            return rc;
+        }
+        if (out_layers_d &&
+            hipMemcpyAsync(out_layers_d + (size_t)l * M * d, ws.x, (size_t)M * d * sizeof(float),
+                           hipMemcpyDeviceToDevice, s) != hipSuccess) {
+            set_error("gpt2: layer copy failed");
+            return R4D_ERR_HIP;
+        }
+        if (kblk && !pad0 && (M & 31) &&        // the last block's rows past M are never written: keep them finite (they are masked keys at most)
             hipMemsetAsync(ws.kblk + (size_t)(M / 32) * 32 * d, 0, (size_t)32 * d * sizeof(unsigned), s) != hipSuccess) {
             set_error("gpt2: memset of the key-block tail failed");
             return R4D_ERR_HIP;
         }
-        if (lines) rc = conv1d_lines(Wqkv, ln_lines, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s, kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
+        if (pad0) {                    // (writes the last block whole: its rows past M as copies of row M - 1)
+            S3Args a = s3_args(nullptr, Wqkv.h2, Wqkv.b, nullptr, (int)pr.rows(), d, 3 * d, EPI_H2WORDS, qkv);
+            a.kblk = ws.kblk; a.kb_hd = d / H;
+            if ((rc = launch_gemm_h2p_rowmap(a, ln_lines, pr, pb, s))) return rc;
+            rc = launch_pad_rows_fill(pr, pb, reinterpret_cast<unsigned*>(qkv), ws.kblk, d, s);
+        } else if (lines) rc = conv1d_lines(Wqkv, ln_lines, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s, kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
         else rc = conv1d(Wqkv, ws.ln, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, s, enc);
         if (rc) return rc;
         // ... and with them the attention output: attn_h2_kernel writes its merged-head rows as lines for attn.c_proj

@@ -708,4 +708,133 @@ int launch_lnf_meanpool_groups(const RowGroups& G, const float* x, const float* 
     return R4D_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- layer 0's repeated pad rows
+// (common.h: PadRowsPlan).  Integer work only: the counts are commutative atomic adds, the lists come from a scan
+// inside ONE workgroup, so a call's plan depends on its ids alone.
+__global__ __launch_bounds__(256) void pad_rows_gather_kernel(const RowTable G, const RowInputs in, int vocab, long long row_base,
+                                                              int* __restrict__ tok, int* __restrict__ pos, int* __restrict__ hist) {
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= G.row_prefix[G.n]) return;
+    int g = 0;
+    while (g + 1 < G.n && row >= G.row_prefix[g + 1]) ++g;
+    const long long local = row - G.row_prefix[g];
+    const long long id = in.ids[g][local];
+    const bool ok = id >= 0 && id < vocab;                   // an out-of-vocabulary row is poisoned by the embedding: never shared
+    const int t = (int)(local % G.T[g]);
+    tok[row_base + row] = ok ? (int)id : -1;
+    pos[row_base + row] = t;
+    if (ok && t == G.T[g] - 1) atomicAdd(&hist[id], 1);
+}
+
+__global__ __launch_bounds__(1024) void pad_rows_classify_kernel(const PadRowsPlan p, const PadRowsBuf b) {
+    __shared__ unsigned long long red[1024];
+    __shared__ int scan[1024];
+    __shared__ int base[2];                                  // kept / dropped blocks listed so far
+    const int tid = threadIdx.x;
+    // c: the largest count, ties to the lowest id -- the largest key (count, ~id)
+    unsigned long long best = 0;
+    for (int v = tid; v < p.vocab; v += 1024) {
+        const unsigned long long key = ((unsigned long long)(unsigned)b.hist[v] << 32) | (0xffffffffu - (unsigned)v);
+        best = key > best ? key : best;
+    }
+    red[tid] = best;
+    if (tid == 0) { base[0] = 0; base[1] = 0; }
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = red[tid + o] > red[tid] ? red[tid + o] : red[tid];
+        __syncthreads();
+    }
+    const int c = (int)(0xffffffffu - (unsigned)(red[0] & 0xffffffffu));
+    for (int t = tid; t < p.Tcap; t += 1024) b.tab_ids[t] = c;
+    for (int b0 = 0; b0 < p.nblk; b0 += 1024) {
+        const int blk = b0 + tid;
+        bool kept = false, in = blk < p.nblk;
+        if (in) {
+            kept = blk * 32 + 32 > p.M;                      // the last block of an M % 32 != 0 call holds rows nobody embeds
+            if (!kept) {
+                const int4* t4 = reinterpret_cast<const int4*>(b.tok + blk * 32);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { const int4 v = t4[i]; kept |= (v.x != c) | (v.y != c) | (v.z != c) | (v.w != c); }
+            }
+        }
+        scan[tid] = kept ? 1 : 0;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {                 // inclusive scan
+            const int add = tid >= o ? scan[tid - o] : 0;
+            __syncthreads();
+            scan[tid] += add;
+            __syncthreads();
+        }
+        const int kept_before = scan[tid] - (kept ? 1 : 0), n_kept = scan[1023];
+        const int k0 = base[0], d0 = base[1];
+        if (in) {
+            if (kept) b.list[k0 + kept_before] = blk;
+            else b.drop[d0 + (tid - kept_before)] = blk;
+        }
+        __syncthreads();
+        if (tid == 0) { base[0] = k0 + n_kept; base[1] = d0 + (min(p.nblk - b0, 1024) - n_kept); }
+        __syncthreads();
+    }
+    const int n_kept = base[0], n_real = n_kept + p.ntab, n_list = (n_real + 3) / 4 * 4;
+    for (int j = tid; j < n_list - n_kept; j += 1024) b.list[n_kept + j] = p.nblk + min(j, p.ntab - 1);
+    if (tid == 0) {
+        b.hdr[0] = n_list; b.hdr[1] = base[1]; b.hdr[2] = c;
+        b.hdr[3] = (int)(b.list - b.hdr); b.hdr[4] = (int)(b.drop - b.hdr);
+        b.hdr[5] = 0; b.hdr[6] = 0; b.hdr[7] = 0;
+    }
+}
+
+// One workgroup per dropped block (the grid is sized for the worst case; the count is on the device).  16-byte pieces, a
+// wavefront's 64 consecutive pieces are whole lines of the destination: per row d / 4 pieces of q, d / 4 of v (row-major words),
+// and per (head, step, half) 32 pieces of K, one per row, 512 consecutive bytes of the key-blocked image.
+__global__ __launch_bounds__(256) void pad_rows_fill_kernel(const PadRowsPlan p, const PadRowsBuf b, uint4* __restrict__ qkv,
+                                                            uint4* __restrict__ kblk, int d) {
+    if ((int)blockIdx.x >= b.hdr[1]) return;
+    const int blk = b.drop[blockIdx.x];
+    __shared__ int prow[32];                                 // the table row of each of the block's rows
+    if (threadIdx.x < 32) prow[threadIdx.x] = p.Mp + min(b.pos[blk * 32 + threadIdx.x], p.Tcap - 1);
+    __syncthreads();
+    const int dq = d / 4;                                    // 16-byte pieces per row and third
+    for (int i = threadIdx.x; i < 32 * dq; i += 256) {
+        const int r = i / dq, j = i - r * dq;
+        const long long dst = (long long)(blk * 32 + r) * (3 * dq) + j, src = (long long)prow[r] * (3 * dq) + j;
+        qkv[dst] = qkv[src];
+        qkv[dst + 2 * dq] = qkv[src + 2 * dq];
+    }
+    for (int i = threadIdx.x; i < 32 * dq; i += 256) {
+        const int ch = i >> 5, r = i & 31, sr = prow[r];
+        kblk[((long long)blk * dq + ch) * 32 + r] = kblk[((long long)(sr >> 5) * dq + ch) * 32 + (sr & 31)];
+    }
+}
+
+int launch_pad_rows_gather(const RowGroups& G, int vocab, long long row_base, const PadRowsBuf& b, hipStream_t s) {
+    R4D_REQUIRE(G.n >= 1 && G.n <= ATT_MAXG, "pad_rows: %d batches per launch (max %d)", G.n, ATT_MAXG);
+    const RowTable t = make_table(G);
+    const long long rows = t.row_prefix[G.n];
+    if (rows <= 0) return R4D_OK;
+    RowInputs in;
+    for (int g = 0; g < ATT_MAXG; ++g) { in.ids[g] = g < G.n ? G.ids[g] : nullptr; in.emb[g] = nullptr; }
+    for (int g = 0; g < G.n; ++g) R4D_REQUIRE(in.ids[g], "pad_rows: batches given as embeddings have no tokens to classify");
+    ProfScope prof(PK_PAD_CLASSIFY, 16.0 * rows, s);            // bytes: ids in, tok + pos out
+    hipLaunchKernelGGL(pad_rows_gather_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, s, t, in, vocab, row_base, b.tok, b.pos, b.hist);
+    R4D_CHECK_LAUNCH("pad_rows_gather");
+    return R4D_OK;
+}
+
+int launch_pad_rows_classify(const PadRowsPlan& p, const PadRowsBuf& b, hipStream_t s) {
+    ProfScope prof(PK_PAD_CLASSIFY, 4.0 * p.Mp + 4.0 * p.vocab + 8.0 * p.nblk, s);
+    hipLaunchKernelGGL(pad_rows_classify_kernel, dim3(1), dim3(1024), 0, s, p, b);
+    R4D_CHECK_LAUNCH("pad_rows_classify");
+    return R4D_OK;
+}
+
+int launch_pad_rows_fill(const PadRowsPlan& p, const PadRowsBuf& b, unsigned* qkv_words, unsigned* kblk, int d, hipStream_t s) {
+    R4D_REQUIRE(qkv_words && kblk && d % 32 == 0 && ((((uintptr_t)qkv_words | (uintptr_t)kblk)) & 15) == 0, "pad_rows_fill: bad arguments");
+    ProfScope prof(PK_PAD_FILL, 24.0 * p.Mp * d, s);             // bytes if EVERY block were dropped (the count is on the device): 3 d words read and written per row
+    hipLaunchKernelGGL(pad_rows_fill_kernel, dim3(p.nblk), dim3(256), 0, s, p, b, reinterpret_cast<uint4*>(qkv_words),
+                       reinterpret_cast<uint4*>(kblk), d);
+    R4D_CHECK_LAUNCH("pad_rows_fill");
+    return R4D_OK;
+}
+
 }  // namespace r4d

@@ -358,6 +358,13 @@ def set_attention_kblk(on):
     return bool(_lib.load().r4d_set_attention_kblk(int(bool(on))))
 
 
+def set_layer0_pad_rows(on):
+    """f16x2 encoder: the layer-0 c_attn GEMM skips the 32-row blocks that hold one repeated token (the right padding) and a
+    copy fills them from a per-call table of (token, position) rows (default on; ``R4D_LAYER0_PAD_ROWS=0`` in the environment
+    switches it off).  Same bits either way.  Returns the previous setting.  Process-wide."""
+    return bool(_lib.load().r4d_set_layer0_pad_rows(int(bool(on))))
+
+
 def pack_kblk_words(qkv_words, n_head):
     """Row-major qkv words [B, T, 3d] -> the key-blocked K image (``include/r4d.h``) as a flat int32 tensor."""
     B, T, d3 = qkv_words.shape
