@@ -611,6 +611,55 @@ def g8_training_step():
     _save("g8_training_step", **out)
 
 
+def g14_loss_head_edges():
+    """The reference's own ``CLtime_loss`` / ``info_nce`` (with the passed and with the rebuilt mask) / ``mask_correlated_samples``
+    (train/train_retriever.py:40-98) in float32 on the edge inputs of ``tests/_loss_head_ref.py``: every regime at B in {2, 3, 17}
+    (d <= 65), ``unit`` at B = 65, d = 80; and the record that ``CLtime_loss`` raises at B = 1."""
+    print("G14 loss head edges")
+    _import_utils_model()
+    import train.train_retriever as tr
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import _loss_head_ref as lh
+    out, tags = {}, []
+    for tag, regime, B, d, tau, lam in lh.g14_entries():
+        emb, ta, tp, tn = lh.make_inputs(regime, B, d)
+        args = types.SimpleNamespace(temperature=tau, lambda_decay=lam, per_gpu_train_batch_size=B)
+        mask = tr.mask_correlated_samples(B)
+        cl = tr.CLtime_loss(args, emb[0], emb[1], emb[2], ta, tp, tn).item()
+        nce = tr.info_nce(args, emb[3], emb[4], tau, B, mask).item()
+        args.per_gpu_train_batch_size = B + 1                      # last partial batch: the mask is rebuilt (:92-93)
+        rebuilt = tr.info_nce(args, emb[3], emb[4], tau, B, None).item()
+        assert np.array_equal(mask.numpy(), lh_mask(B))
+        c64, n64 = (x.item() for x in lh.loss_head(tau, lam, 1.0, emb.double(), ta, tp, tn))
+        own = lh.loss_err([cl, nce], [c64, n64])                   # a pin at 1e-5 must itself resolve the value
+        assert own < 1e-5 / G14_SPARE, f"{tag}: the reference's float32 value is {own:.2e} from float64"
+        tags.append(tag)
+        out[tag + ":emb"] = emb.numpy(); out[tag + ":time"] = torch.stack([ta, tp, tn]).numpy()
+        out[tag + ":hyper"] = np.array([tau, lam], np.float64)
+        out[tag + ":losses"] = np.array([cl, nce, rebuilt], np.float64)
+        print(f"  {tag}: tau {tau} lam {lam}: CLtime {cl:.6f} info_nce {nce:.6f} (rebuilt mask {rebuilt:.6f})")
+    emb, ta, tp, tn = lh.make_inputs("unit", 1, 7)
+    try:
+        tr.CLtime_loss(types.SimpleNamespace(temperature=0.07, lambda_decay=0.05, per_gpu_train_batch_size=1), emb[0], emb[1], emb[2], ta, tp, tn)
+        raised = ""
+    except Exception as e:                                         # the 0-d decay "matrix" after .squeeze()
+        raised = f"{type(e).__name__}: {e}"
+    print(f"  B = 1: CLtime_loss raises {raised!r}")
+    _save("g14_loss_head_edges", tags=np.array(tags), b1_raises=np.array(bool(raised)), b1_message=np.array(raised), **out)
+
+
+G14_SPARE = 4.0                     # the pin's own distance from float64: twice it (as much again on the other side) in half of 1e-5
+
+
+def lh_mask(B):
+    """``mask_correlated_samples`` as a plain statement: every pair but the diagonal and the two partner diagonals."""
+    m = ~np.eye(2 * B, dtype=bool)
+    i = np.arange(B)
+    m[i, B + i] = False
+    m[B + i, i] = False
+    return m
+
+
 def g8b_lr_schedule():
     """``adjust_learning_rate`` (train/train_retriever.py:120-130) sampled over warm-up and cosine epochs."""
     _import_utils_model()
@@ -985,7 +1034,7 @@ def main():
         return
     groups = {"g1": g1_tiny_forward, "g2": g2_ops, "g3": g3_config_shapes, "g4": g4_g6_uci_retrieval, "g5": g5_jaccard,
               "g6b": g6_more_tokenizers, "g7": g7_generator, "g8": g8_training_step, "g8b": g8b_lr_schedule, "g9": g9_query_times,
-              "g10": g10_trained, "g12": g12_real_wikiv2_reddit, "g13": g13_h2_attention_stress}
+              "g10": g10_trained, "g12": g12_real_wikiv2_reddit, "g13": g13_h2_attention_stress, "g14": g14_loss_head_edges}
     want = [a for a in sys.argv[1:] if a in groups] or list(groups)
     torch.set_num_threads(os.cpu_count() or 1)
     _install_stubs()

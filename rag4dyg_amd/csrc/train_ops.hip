@@ -534,7 +534,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float coef = 1.f;
-    if (sumsq && max_norm > 0.f) coef = fminf(1.f, max_norm / (sqrtf(sumsq[0]) + 1e-6f));
+    if (sumsq && max_norm > 0.f) {                             // a NaN norm gives a NaN coefficient (clip_grad_norm_'s clamp(max=1)
+        const float c = max_norm / (sqrtf(sumsq[0]) + 1e-6f);  // keeps it): fminf would return the 1 and apply the step unclipped
+        coef = c >= 1.f ? 1.f : c;
+    }
     const float gi = g[i] * coef;
     const float mi = b1 * m[i] + omb1 * gi;                    // scalars rounded to f32 like torch's mul_ / add_(alpha=)
     const float vi = b2 * v[i] + omb2 * gi * gi;
