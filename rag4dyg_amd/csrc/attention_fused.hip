@@ -17,15 +17,13 @@
 //   * the 4 partial states are merged pairwise through LDS (re-using the query buffer), O is transposed through LDS
 //     and stored as whole 128..1024-byte rows of the merged-head layout [B, T, d].
 #include <math.h>
-#include "common.h"
+#include "attention_common.h"
 
 #ifndef ATT_DBG
 #define ATT_DBG 0   // tuning aid (tools/kc_ablate.sh attention_fused.hip ATT_DBG n), column-split kernel: bit 0 skips the Q.K^T MFMA loop, bit 1 the P.V loop, bit 2 the two barriers of the softmax, bit 3 the K loads after the first eight, bit 4 the V loads after the first three groups
 #endif
 
 namespace r4d {
-
-typedef float f32x16a __attribute__((ext_vector_type(16)));
 
 constexpr int ATT_LDQ = 33;
 
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(256, HD >= 256 ? 1 : 2) void attn_fused_kernel(cons
     }
     __syncthreads();
 
-    f32x16a O[NCB];
+    f32x16 O[NCB];
 #pragma unroll
     for (int c = 0; c < NCB; ++c)
 #pragma unroll
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(256, HD >= 256 ? 1 : 2) void attn_fused_kernel(cons
         // ---- S^T[key][q] = sum_k K[key][k] Q[q][k]
         const float4* __restrict__ krow =
             reinterpret_cast<const float4*>(Kb + (long long)min(key0 + li, T - 1) * ld3) + lh;
-        f32x16a S;
+        f32x16 S;
 #pragma unroll
         for (int r = 0; r < 16; ++r) S[r] = 0.f;
         // static ping-pong over groups of GRP k-steps: the 16-byte K loads AND the LDS query operands of group g+1
@@ -152,10 +150,9 @@ __global__ __launch_bounds__(256, HD >= 256 ? 1 : 2) void attn_fused_kernel(cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            // the reference DIVIDES by sqrt(hd) (:143); for a power-of-two scale (hd = 64, 256) the reciprocal
-            // multiply is the same value bit for bit and saves a ~12-instruction f32 division per logit
-            // multiply by the rounded reciprocal: the IEEE division is ~10 instructions per logit (head_dim 32 / 96, where
-            // sqrt(hd) is not a power of two, differ from the reference's division by <= 1 ulp of the logit)
+            // the reference DIVIDES by sqrt(hd) (:143); this multiplies by the rounded reciprocal (the IEEE division is ~10
+            // instructions per logit): bit for bit the same value where sqrt(hd) is a power of two (hd = 64, 256), within
+            // 1 ulp of the logit elsewhere (head_dim 32 / 96 / 128)
             const float s = S[r] * inv_scale;
             S[r] = (key <= qidx) ? s : -INFINITY;
             mt = fmaxf(mt, S[r]);
@@ -208,37 +205,10 @@ __global__ __launch_bounds__(256, HD >= 256 ? 1 : 2) void attn_fused_kernel(cons
         }
     }
 
-    // ---- merge the 4 partial states: (2,3) -> (0,1), then 1 -> 0.  Slot = NCB*16*64 O values + 64 m + 64 l floats.
-    constexpr int SLOT = NCB * 16 * 64 + 128;
-    __syncthreads();                                    // every wave is done with the query buffer
-#pragma unroll 1
-    for (int step = 0; step < 2; ++step) {
-        const int writers_lo = step == 0 ? 2 : 1;       // waves [writers_lo, 2*writers_lo) write, [0, writers_lo) merge
-        if (wid >= writers_lo && wid < 2 * writers_lo) {
-            float* sl = lds + (wid - writers_lo) * SLOT;
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sl[(c * 16 + r) * 64 + lane] = O[c][r];
-            sl[NCB * 16 * 64 + lane] = m_run;
-            sl[NCB * 16 * 64 + 64 + lane] = l_run;
-        }
-        __syncthreads();
-        if (wid < writers_lo) {
-            const float* sl = lds + wid * SLOT;
-            const float m_b = sl[NCB * 16 * 64 + lane], l_b = sl[NCB * 16 * 64 + 64 + lane];
-            const float m_new = fmaxf(m_run, m_b);
-            const float fa = (m_run == -INFINITY) ? 0.f : expf(m_run - m_new);
-            const float fb = (m_b == -INFINITY) ? 0.f : expf(m_b - m_new);
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) O[c][r] = O[c][r] * fa + sl[(c * 16 + r) * 64 + lane] * fb;
-            l_run = l_run * fa + l_b * fb;
-            m_run = m_new;
-        }
-        __syncthreads();
-    }
+    // ---- merge the 4 partial states: (2,3) -> (0,1), then 1 -> 0
+#define ATTN_MERGE_WEIGHT(m_old, m_new) expf(m_old - m_new)
+    ATTN_MERGE4(O, lds)
+#undef ATTN_MERGE_WEIGHT
     // ---- wave 0: normalise, transpose O^T -> Ot[q][c] in LDS; all waves: coalesced row stores
     constexpr int LDO = HD + 1;                        // odd stride: conflict-free transposed writes
     if (wid == 0) {
@@ -254,14 +224,7 @@ __global__ __launch_bounds__(256, HD >= 256 ? 1 : 2) void attn_fused_kernel(cons
                 }
     }
     __syncthreads();
-    for (int q = wid; q < 32; q += 4) {
-        if (q0 + q >= T) break;
-        float* dst = out + (rowb + q0 + q) * d + (long long)h * HD;
-        for (int c = lane * 4; c < HD; c += 256) {
-            const float* sp = &lds[q * LDO + c];
-            *reinterpret_cast<float4*>(dst + c) = make_float4(sp[0], sp[1], sp[2], sp[3]);
-        }
-    }
+    ATTN_STORE_ROWS_F32(lds)
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -282,11 +245,6 @@ __global__ __launch_bounds__(256, HD >= 256 ? 1 : 2) void attn_fused_kernel(cons
 //   * the causal mask is applied only on super-tiles that touch the diagonal (wave-uniform test);
 //   * P is published [query][key] with four ds_write_b128 per wave and read back as one ds_read_b128 per EIGHT
 //     P.V MFMAs (keys permuted identically on the V loads).
-typedef unsigned int u32x4a __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2a __attribute__((ext_vector_type(2)));
-typedef float f32x4a __attribute__((ext_vector_type(4)));
-typedef float f32x2a __attribute__((ext_vector_type(2)));
-
 template <int VW>
 struct VBuf;                                            // one V fragment: VW consecutive head columns of one key row
 template <>
@@ -301,7 +259,7 @@ struct VBuf<2> {
     float v[2];
     __device__ __forceinline__ void ld(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
         // (bit_cast the WHOLE vector: __builtin_bit_cast(float, t.y) on an ext-vector element reads element 0)
-        const f32x2a t = __builtin_bit_cast(f32x2a, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+        const f32x2 t = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
         v[0] = t.x; v[1] = t.y;
     }
 };
@@ -322,50 +280,23 @@ __global__ __launch_bounds__(256, 3) void attn_colsplit_kernel(const float* __re
     float* red = Ps + 32 * LDP;                        // [2][4][32] per-wave row max / row sum
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    // Work mapping (1-D grid): all query tiles of one (sequence, head) run on the SAME XCD (workgroup ids are dealt
-    // round-robin to the 8 XCDs, each with its own L2), back to back, so K and V of that head are fetched from HBM once
-    // instead of once per query tile (measured before: 970 MB per launch against 290 MB of qkv + out, L2 hit rate 22 %,
-    // i.e. the kernel ran at the HBM limit).  Long (late) query tiles go first.
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / ntq) * 8 + xcd;           // (sequence, head) index
-    if (pair >= G.seq_prefix[G.n] * H) return;
-    const int qt = ntq - 1 - slot % ntq, h = pair % H, seq = pair / H;
-    int gi = 0;
-    while (gi + 1 < G.n && seq >= G.seq_prefix[gi + 1]) ++gi;
-    const int T = G.T[gi];
-    const int q0 = qt * 32;
-    if (q0 >= T) return;                               // ntq covers the longest batch
-    const long long rowb = G.row0[gi] + (long long)(seq - G.seq_prefix[gi]) * T;     // first row of the sequence
-    const int ld3 = 3 * d;
-    const float* __restrict__ base = qkv + rowb * ld3 + (long long)h * HD;
-    const int seq_bytes = ((T - 1) * ld3 + HD) * 4;    // one head's K (or V) rows of this sequence, as a byte range
-    const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + d), 0, seq_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + 2 * d), 0, seq_bytes, 0x00020000);
+    ATTN_TILE_1D(G, H, ntq)                           // XCD-aware (sequence, head, query tile) -> qt, h, seq, T, q0, rowb
+    ATTN_KV_RSRC(float, qkv, false, qkv)               // ld3, base, seq_bytes, k_rsrc, v_rsrc (row-major K: no key-blocked image)
     const int qidx = q0 + li;
     const int key_limit = min(T, q0 + 32);             // keys >= key_limit are masked for every query of the tile
     const int k_voff = ((32 * wid + li) * ld3 + 4 * lh) * 4;                 // bytes; + scalar (st0 * ld3 + 8u) * 4
     const int v_voff = (4 * lh * ld3 + wid * CW + VW * li) * 4;             // bytes; + scalar (st0 + 8s + c) * ld3 * 4
     // K fragments of the NEXT super-tile are requested before the P.V phase of the current one (and the first ones
     // here, before the Q tile is staged), V fragments before the softmax: no phase starts on an exposed memory latency
-    u32x4a kb[KD];
+    u32x4 kb[KD];
     if (wid * 32 < key_limit) {
 #pragma unroll
         for (int u = 0; u < KD; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, 32 * u, 0);
     }
-    {   // Q tile: thread t stages row t/8, 16-byte pieces 4*(t%8) + 32j; rows past T repeat the last row (never stored)
-        const int row = tid >> 3, seg = 4 * (tid & 7);
-        const float* src = base + (long long)min(q0 + row, T - 1) * ld3 + seg;
-        float4 qv[HD / 32];
-#pragma unroll
-        for (int j = 0; j < HD / 32; ++j) qv[j] = *reinterpret_cast<const float4*>(src + 32 * j);
-#pragma unroll
-        for (int j = 0; j < HD / 32; ++j)
-            *reinterpret_cast<float4*>(Qs + row * LDQ + seg + 32 * j) =
-                qv[j];        // UNSCALED (round 5): the logits leave the MFMA as raw dot products, see the softmax below
-    }
+    ATTN_STAGE_Q(float4, Qs)      // UNSCALED (round 5): the logits leave the MFMA as raw dot products, see the softmax below
     __syncthreads();
 
-    f32x16a O[VW];
+    f32x16 O[VW];
 #pragma unroll
     for (int c = 0; c < VW; ++c)
 #pragma unroll
@@ -377,7 +308,7 @@ __global__ __launch_bounds__(256, 3) void attn_colsplit_kernel(const float* __re
     for (int st0 = 0; st0 < key_limit; st0 += 128) {
         const int key0 = st0 + wid * 32;
         const bool active = key0 < key_limit;           // wave-uniform
-        f32x16a S;
+        f32x16 S;
         float mt = -INFINITY;
         if (active) {
 #pragma unroll
@@ -385,7 +316,7 @@ __global__ __launch_bounds__(256, 3) void attn_colsplit_kernel(const float* __re
             const int k_soff = st0 * ld3 * 4;
 #pragma unroll
             for (int u = 0; u < ((ATT_DBG & 1) ? 1 : NSTEP); ++u) {
-                const f32x4a kv = __builtin_bit_cast(f32x4a, kb[u % KD]);
+                const f32x4 kv = __builtin_bit_cast(f32x4, kb[u % KD]);
                 const float4 qf = *reinterpret_cast<const float4*>(q_frag + 8 * u);
                 S = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qf.x, S, 0, 0, 0);
                 S = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qf.y, S, 0, 0, 0);
@@ -493,14 +424,7 @@ __global__ __launch_bounds__(256, 3) void attn_colsplit_kernel(const float* __re
         }
     }
     __syncthreads();
-    for (int q = wid; q < 32; q += 4) {
-        if (q0 + q >= T) break;
-        float* dst = out + (rowb + q0 + q) * d + (long long)h * HD;
-        for (int c = lane * 4; c < HD; c += 256) {
-            const float* sp = &lds[q * LDO + c];
-            *reinterpret_cast<float4*>(dst + c) = make_float4(sp[0], sp[1], sp[2], sp[3]);
-        }
-    }
+    ATTN_STORE_ROWS_F32(lds)
 }
 
 template <int HD>
@@ -508,11 +432,10 @@ static int launch_colsplit(const float* qkv, const AttnGroups& G, int Tmax, doub
                            hipStream_t s) {
     const size_t lds = ((size_t)32 * (HD + 4) + 32 * 132 + 256) * 4;       // >= the [32][HD+1] output tile
     ProfScope prof(PK_ATTN_FUSED, flop, s);
-    const int ntq = cdiv(Tmax, 32);
-    const long long pairs8 = ((long long)G.seq_prefix[G.n] * H + 7) / 8;
-    R4D_REQUIRE(pairs8 * 8 * ntq < (1ll << 31), "attention: grid too large");
-    hipLaunchKernelGGL((attn_colsplit_kernel<HD>), dim3((unsigned)(pairs8 * 8 * ntq)), dim3(256), lds, s, qkv, G, d, H, ntq,
-                       (float)(1.4426950408889634 / sqrt((double)HD)), out);
+    int ntq, rc;
+    unsigned grid;
+    if ((rc = attn_grid_1d("attention", G, H, Tmax, ntq, grid))) return rc;
+    hipLaunchKernelGGL((attn_colsplit_kernel<HD>), dim3(grid), dim3(256), lds, s, qkv, G, d, H, ntq, attn_qscale(HD, 1.0), out);
     R4D_CHECK_LAUNCH("attn_colsplit");
     return R4D_OK;
 }
@@ -536,7 +459,6 @@ static int launch_hd(const float* qkv, const AttnGroups& G, int Tmax, double flo
             raised = true;
         }
     }
-    // algorithmic flop: causal half of Q.K^T and P.V = 2 * T^2 * hd per head
     ProfScope prof(PK_ATTN_FUSED, flop, s);
     hipLaunchKernelGGL((attn_fused_kernel<HD>), dim3(cdiv(Tmax, 32), H, G.seq_prefix[G.n]), dim3(256), lds, s, qkv, G, d,
                        (float)sqrt((double)HD), out);
@@ -544,49 +466,30 @@ static int launch_hd(const float* qkv, const AttnGroups& G, int Tmax, double flo
     return R4D_OK;
 }
 
-int g_attention_variant = 0;          // tuning aid: 1 forces the key-split kernel at head_dim 128 / 256
+int g_attention_variant = 0;          // tuning aid: 1 forces the key-split kernel at head_dim 96 / 128 / 256
 
 // Attention of n <= ATT_MAXG batches in one launch; batch g holds Bs[g] sequences of Ts[g] tokens starting at token
 // row row0s[g] of qkv [rows, 3d] / out [rows, d].  Returns R4D_OK, an error, or +1 when head_dim has no fused
 // instantiation (caller falls back to the three-launch form).
 int launch_attention_fused_groups(const float* qkv, int n, const int* Bs, const int* Ts, const long long* row0s, int H,
                                   int d, float* out, hipStream_t s) {
-    const int hd = d / H;
-    R4D_REQUIRE(n >= 1 && n <= ATT_MAXG, "attention: %d batches per launch (max %d)", n, ATT_MAXG);
     R4D_REQUIRE(H <= 65535, "attention: H=%d exceeds the grid limit", H);
     AttnGroups G;
-    G.n = n;
-    G.seq_prefix[0] = 0;
-    int Tmax = 0;
-    double flop = 0.0;                                  // causal half of Q.K^T and P.V: 2 * T^2 * hd per head
-    for (int g = 0; g < n; ++g) {
-        G.seq_prefix[g + 1] = G.seq_prefix[g] + Bs[g];
-        G.T[g] = Ts[g];
-        G.row0[g] = row0s[g];
-        if (Ts[g] > Tmax) Tmax = Ts[g];
-        flop += 2.0 * Bs[g] * H * (double)Ts[g] * Ts[g] * hd;
-    }
-    for (int g = n; g < ATT_MAXG; ++g) { G.seq_prefix[g + 1] = G.seq_prefix[n]; G.T[g] = 0; G.row0[g] = 0; }
-    R4D_REQUIRE(G.seq_prefix[n] <= 65535, "attention: %d sequences per launch exceed the grid limit", G.seq_prefix[n]);
-    switch (hd) {
-        case 32: R4D_BRANCH(ATT_KS32); break;
-        case 64: R4D_BRANCH(ATT_KS64); break;
-        case 96: if (g_attention_variant == 1) R4D_BRANCH(ATT_KS_FORCED); else R4D_BRANCH(ATT_CS96); break;
-        case 128: if (g_attention_variant == 1) R4D_BRANCH(ATT_KS_FORCED); else R4D_BRANCH(ATT_CS128); break;
-        case 256: if (g_attention_variant == 1) R4D_BRANCH(ATT_KS_FORCED); else R4D_BRANCH(ATT_CS256); break;
-        default: break;
-    }
-    switch (hd) {
-        case 32: return launch_hd<32>(qkv, G, Tmax, flop, H, d, out, s);
-        case 64: return launch_hd<64>(qkv, G, Tmax, flop, H, d, out, s);
-        case 96: return g_attention_variant == 1 ? launch_hd<96>(qkv, G, Tmax, flop, H, d, out, s)
-                                                 : launch_colsplit<96>(qkv, G, Tmax, flop, H, d, out, s);
-        case 128: return g_attention_variant == 1 ? launch_hd<128>(qkv, G, Tmax, flop, H, d, out, s)
-                                                  : launch_colsplit<128>(qkv, G, Tmax, flop, H, d, out, s);
-        case 256: return g_attention_variant == 1 ? launch_hd<256>(qkv, G, Tmax, flop, H, d, out, s)
-                                                  : launch_colsplit<256>(qkv, G, Tmax, flop, H, d, out, s);
+    int Tmax, rc;
+    double flop;
+    if ((rc = attn_groups_fill("attention", n, Bs, Ts, row0s, H, d, G, Tmax, flop))) return rc;
+    // head_dim 32 / 64: the key-split kernel; wider heads: the column-split one (g_attention_variant 1: key-split there too)
+#define ATT_WIDE(HD_)                                                                                               \
+    case HD_:                                                                                                       \
+        if (g_attention_variant == 1) { R4D_BRANCH(ATT_KS_FORCED); return launch_hd<HD_>(qkv, G, Tmax, flop, H, d, out, s); } \
+        R4D_BRANCH(ATT_CS##HD_); return launch_colsplit<HD_>(qkv, G, Tmax, flop, H, d, out, s);
+    switch (d / H) {
+        case 32: R4D_BRANCH(ATT_KS32); return launch_hd<32>(qkv, G, Tmax, flop, H, d, out, s);
+        case 64: R4D_BRANCH(ATT_KS64); return launch_hd<64>(qkv, G, Tmax, flop, H, d, out, s);
+        ATT_WIDE(96) ATT_WIDE(128) ATT_WIDE(256)
         default: return 1;
     }
+#undef ATT_WIDE
 }
 
 int launch_attention_fused(const float* qkv, int B, int T, int H, int d, float* out, hipStream_t s) {
@@ -594,6 +497,6 @@ int launch_attention_fused(const float* qkv, int B, int T, int H, int d, float* 
     return launch_attention_fused_groups(qkv, 1, &B, &T, &row0, H, d, out, s);
 }
 
-}  // namespace r4d
+int dbgflag_att() { return ATT_DBG != 0; }
 
-namespace r4d { int dbgflag_att() { return ATT_DBG != 0; } }
+}  // namespace r4d

@@ -1,5 +1,5 @@
 // Fused causal multi-head attention on the fp16 matrix cores at fp32 accuracy (the f16x2 form of gemm_h2.hip) for head_dim
-// 128 / 256: softmax(Q.K^T / sqrt(hd), causal) . V  (Attention._attn + split/merge_heads, models/modeling_gpt2.py:140-175).
+// 128 / 256 (attn_h2_kernel) and 32 / 64 / 96 (attn_h2ks_kernel, further down): softmax(Q.K^T / sqrt(hd), causal) . V  (Attention._attn + split/merge_heads, models/modeling_gpt2.py:140-175).
 //
 // Operands arrive as "h2 words" (csrc/h2.h): qkv [rows, 3d] uint32, every element  hi | lo' << 16  of value / 4 -- written by
 // the c_attn GEMM's EPI_H2WORDS epilogue (gemm_h2.hip), so neither K nor V is converted here: a register of words IS an MFMA
@@ -21,34 +21,23 @@
 // softmax exactly as in attention_fused.hip; masked keys are skipped.
 // Range: |q|, |k|, |v| < 2^18 (beyond: inf -> NaN in the output, never a quiet wrong number).
 #include <math.h>
-#include "common.h"
+#include "attention_common.h"
 #include "h2.h"
 
 #ifndef ATH_DBG
-#define ATH_DBG 0   // tuning aid (tools/kc_ablate.sh attention_h2.hip ATH_DBG n): bit 0 one Q.K^T step only, bit 1 one P.V group only, bit 2 no softmax barriers, bit 3 no K refills, bit 4 no V refills, bit 5 every second K / V refill only (half the traffic), bit 7 the same in the key-split kernel, bit 6 K loads as eight WHOLE 128-byte lines per instruction (lane-linear addresses, wrong operands: what a key-blocked K layout would cost the vector-memory path)
-#endif
-
-#ifndef ATH_KD
-#define ATH_KD 4    // K loads (16 bytes per lane) in flight per wave (8 / 16: no faster, and the registers cost a workgroup per CU)
-#endif
-#ifndef ATH_VD
-#define ATH_VD 3    // V key-groups (8 keys) in flight per wave
-#endif
-#ifndef ATH_QP
-#define ATH_QP 2    // Q fragments (one ds_read_b128 each) in flight per wave
-#endif
-#ifndef ATH_OCC256
-#define ATH_OCC256 3   // workgroups per CU the head_dim-256 instantiation is compiled for (168 VGPRs, 51 KB of LDS)
-#endif
-#ifndef ATH_OCC128
-#define ATH_OCC128 4   // workgroups per CU the head_dim-128 instantiation is compiled for (128 VGPRs, 35 KB of LDS)
+#define ATH_DBG 0   // tuning aid (tools/kc_ablate.sh attention_h2.hip ATH_DBG n), attn_h2_kernel: bit 0 one Q.K^T step only, bit 1 one P.V group only, bit 2 no softmax barriers, bit 3 no K refills, bit 4 no V refills
 #endif
 
 namespace r4d {
 
-typedef float f32x16q __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4q __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8q __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// attn_h2_kernel's pipeline depths and the occupancies it is compiled for
+constexpr int ATH_KD = 4;       // K loads (16 bytes per lane) in flight per wave (8 / 16: no faster, and the registers cost a workgroup per CU)
+constexpr int ATH_VD = 3;       // V key-groups (8 keys) in flight per wave
+constexpr int ATH_QP = 2;       // Q fragments (one ds_read_b128 each) in flight per wave
+constexpr int ATH_OCC256 = 3;   // workgroups per CU the head_dim-256 instantiation is compiled for (168 VGPRs, 51 KB of LDS)
+constexpr int ATH_OCC128 = 4;   // workgroups per CU the head_dim-128 instantiation is compiled for (128 VGPRs, 35 KB of LDS)
 
 __global__ __launch_bounds__(256) void pack_h2_words_kernel(const float* __restrict__ x, long long n, unsigned* __restrict__ w) {
     const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
@@ -59,7 +48,7 @@ __global__ __launch_bounds__(256) void pack_h2_words_kernel(const float* __restr
     if (i + 1 < n) w[i + 1] = w1;
 }
 
-#define ATH_MFMA(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8q, A_), __builtin_bit_cast(f16x8q, B_), C_, 0, 0, 0)
+#define ATH_MFMA(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A_), __builtin_bit_cast(f16x8, B_), C_, 0, 0, 0)
 
 // KBLK: the K words come from the KEY-BLOCKED image `kblk` that the c_attn epilogue writes beside qkv (gemm_h2p.hip, EPI_H2WORDS with
 // kb_hd set) instead of from the K columns of qkv: for every 32 consecutive token ROWS (global row index, blocks of 32), head and
@@ -84,56 +73,25 @@ __global__ __launch_bounds__(256, HD >= 256 ? ATH_OCC256 : ATH_OCC128) void attn
     float* red = reinterpret_cast<float*>(Ps + 32 * LDP);   // [2][4][32] per-wave row max / row sum
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    // work mapping: attention_fused.hip's (all query tiles of one (sequence, head) on the same XCD, long tiles first)
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / ntq) * 8 + xcd;           // (sequence, head) index
-    if (pair >= G.seq_prefix[G.n] * H) return;
-    const int qt = ntq - 1 - slot % ntq, h = pair % H, seq = pair / H;
-    int gi = 0;
-    while (gi + 1 < G.n && seq >= G.seq_prefix[gi + 1]) ++gi;
-    const int T = G.T[gi];
-    const int q0 = qt * 32;
-    if (q0 >= T) return;                               // ntq covers the longest batch
-    const long long rowb = G.row0[gi] + (long long)(seq - G.seq_prefix[gi]) * T;     // first row of the sequence
-    const int ld3 = 3 * d;
-    const unsigned* __restrict__ base = qkv + rowb * ld3 + (long long)h * HD;
-    const int seq_bytes = ((T - 1) * ld3 + HD) * 4;    // one head's K (or V) rows of this sequence, as a byte range
-    // K: row-major -- this head's K columns of the sequence's rows; key-blocked -- from the block that holds the sequence's first row
-    // to the end of the block that holds its last one (block = 32 rows x d words; this head's chunks start hh * NSTEP KB into a block)
-    const int roff = (int)(rowb & 31);
-    const unsigned* kbase = KBLK ? kblk + (rowb >> 5) * (long long)(32 * d) + h * (HD / 8) * 256 : base + d;
-    const int kbytes = KBLK ? (((roff + T - 1) >> 5) + 1) * (d * 128) - h * (HD / 8) * 1024 : seq_bytes;
-    const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(kbase), 0, kbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(base + 2 * d), 0, seq_bytes, 0x00020000);
+    ATTN_TILE_1D(G, H, ntq)                           // XCD-aware (sequence, head, query tile) -> qt, h, seq, T, q0, rowb
+    ATTN_KV_RSRC(unsigned, qkv, KBLK, kblk)            // ld3, base, seq_bytes, roff, k_rsrc (row-major or key-blocked), v_rsrc
     const int qidx = q0 + li;
     const int key_limit = min(T, q0 + 32);             // keys >= key_limit are masked for every query of the tile
-    const int gl = roff + 32 * wid + li;               // key-blocked: this lane's key of super-tile 0, counted from the first block's row 0
-    const int k_voff = KBLK ? (gl >> 5) * (d * 128) + (lh * 32 + (gl & 31)) * 16
-                     : (ATH_DBG & 64) ? (32 * wid * ld3) * 4 + 16 * lane : ((32 * wid + li) * ld3 + 4 * lh) * 4;   // bytes; + scalar (super-tile, step)
-    constexpr int K_STEP = (KBLK || (ATH_DBG & 64)) ? 1024 : 32;             // bytes between a lane's consecutive K loads
-    const int k_tile = KBLK ? d * 4 : ld3 * 4;                                // bytes per key of super-tile advance (st0 keys = st0 / 32 blocks)
+    ATTN_K_LANE_H2(32 * wid + li)                      // gl, k_voff, K_STEP, k_tile; + scalar (super-tile, step)
     // (V: measured and taken out -- one 16-byte load per lane (key 4lh + (li & 3) x four columns: eight whole lines per instruction
     //  instead of four 4-byte loads of two lines each) followed by a 4 x 4 transpose inside the quad, 16 DPP / select instructions per
     //  column tile: head_dim 256 102 -> 119 us, head_dim 128 218 -> 208 us at B 128, T 277 / 300: the VALU work costs more than the
     //  vector-memory path gains)
     const int v_voff = (4 * lh * ld3 + wid * CW + li) * 4;                   // bytes; + scalar ((st0 + 8s + c) * ld3 + 32 j) * 4
-    u32x4q kb[KD];
+    u32x4 kb[KD];
     if (wid * 32 < key_limit) {
 #pragma unroll
         for (int u = 0; u < KD; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, K_STEP * u, 0);
     }
-    {   // Q tile: thread t stages row t/8, 16-byte pieces 4*(t%8) + 32j; rows past T repeat the last row (never stored)
-        const int row = tid >> 3, seg = 4 * (tid & 7);
-        const unsigned* src = base + (long long)min(q0 + row, T - 1) * ld3 + seg;
-        u32x4q qv[HD / 32];
-#pragma unroll
-        for (int j = 0; j < HD / 32; ++j) qv[j] = *reinterpret_cast<const u32x4q*>(src + 32 * j);
-#pragma unroll
-        for (int j = 0; j < HD / 32; ++j) *reinterpret_cast<u32x4q*>(Qs + row * LDQ + seg + 32 * j) = qv[j];
-    }
+    ATTN_STAGE_Q(u32x4, Qs)
     __syncthreads();
 
-    f32x16q O0[VW], O1[VW];
+    f32x16 O0[VW], O1[VW];
 #pragma unroll
     for (int c = 0; c < VW; ++c)
 #pragma unroll
@@ -145,34 +103,34 @@ __global__ __launch_bounds__(256, HD >= 256 ? ATH_OCC256 : ATH_OCC128) void attn
     for (int st0 = 0; st0 < key_limit; st0 += 128) {
         const int key0 = st0 + wid * 32;
         const bool active = key0 < key_limit;           // wave-uniform
-        f32x16q S;
+        f32x16 S;
         float mt = -INFINITY;
         if (active) {
-            f32x16q S0, S1;
+            f32x16 S0, S1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { S0[r] = 0.f; S1[r] = 0.f; }
             const int k_soff = st0 * k_tile;
-            u32x4q qb[QP];
+            u32x4 qb[QP];
 #pragma unroll
-            for (int u = 0; u < QP; ++u) qb[u] = *reinterpret_cast<const u32x4q*>(q_frag + 8 * u);
+            for (int u = 0; u < QP; ++u) qb[u] = *reinterpret_cast<const u32x4*>(q_frag + 8 * u);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < ((ATH_DBG & 1) ? 1 : NSTEP); ++u) {
-                const u32x4q kw = kb[u % KD];
-                const u32x4q qw = qb[u % QP];
-                u32x4q f1, f2;
+                const u32x4 kw = kb[u % KD];
+                const u32x4 qw = qb[u % QP];
+                u32x4 f1, f2;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { f1[e] = qw[e] & 0xffffu; f2[e] = __builtin_amdgcn_alignbit(qw[e], qw[e], 16); }
                 S0 = ATH_MFMA(kw, f1, S0);
                 S1 = ATH_MFMA(kw, f2, S1);
-                if (u + QP < NSTEP) qb[u % QP] = *reinterpret_cast<const u32x4q*>(q_frag + 8 * (u + QP));
-                if (!(ATH_DBG & 8) && !((ATH_DBG & 32) && (u & 1)) && u + KD < NSTEP)  // refill AFTER the slot's MFMAs in program order: no register copies
+                if (u + QP < NSTEP) qb[u % QP] = *reinterpret_cast<const u32x4*>(q_frag + 8 * (u + QP));
+                if (!(ATH_DBG & 8) && u + KD < NSTEP)  // refill AFTER the slot's MFMAs in program order: no register copies
                     kb[u % KD] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, k_soff + K_STEP * (u + KD), 0);
                 // pinned: the step's eight VALU, its two MFMAs, then the Q read of step u + QP and the K load of step u + KD
                 __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
                 if (u + QP < NSTEP) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                if (!(ATH_DBG & 8) && !((ATH_DBG & 32) && (u & 1)) && u + KD < NSTEP) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                if (!(ATH_DBG & 8) && u + KD < NSTEP) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -190,7 +148,7 @@ __global__ __launch_bounds__(256, HD >= 256 ? ATH_OCC256 : ATH_OCC128) void attn
         }
         const int ngroups = (min(128, key_limit - st0) + 7) >> 3;      // 8-key groups of the P.V phase, wave-uniform
         const int v_soff = st0 * ld3 * 4;
-        u32x4q vb[VD][VW];                              // vb[u][j][c] = V word of key 8 (s0 + u) + 4 lh + c, column tile j
+        u32x4 vb[VD][VW];                              // vb[u][j][c] = V word of key 8 (s0 + u) + 4 lh + c, column tile j
 #define ATH_VLOAD(U, SG)                                                                            \
     {                                                                                               \
         _Pragma("unroll") for (int c = 0; c < 4; ++c)                                               \
@@ -217,8 +175,8 @@ __global__ __launch_bounds__(256, HD >= 256 ? ATH_OCC256 : ATH_OCC128) void attn
                 unsigned a[4];
                 h2_words<false>(p[0], p[1], a[0], a[1]);
                 h2_words<false>(p[2], p[3], a[2], a[3]);
-                const u32x4q w4 = {a[0], a[1], a[2], a[3]};
-                *reinterpret_cast<u32x4q*>(Ps + li * LDP + wid * 32 + 8 * g + 4 * lh) = w4;            // keys 8g + 4lh + 0..3
+                const u32x4 w4 = {a[0], a[1], a[2], a[3]};
+                *reinterpret_cast<u32x4*>(Ps + li * LDP + wid * 32 + 8 * g + 4 * lh) = w4;            // keys 8g + 4lh + 0..3
             }
             ps += __shfl_xor(ps, 32, 64);
         }
@@ -241,26 +199,26 @@ __global__ __launch_bounds__(256, HD >= 256 ? ATH_OCC256 : ATH_OCC128) void attn
         }
         // the P words of group s + 1 are read before the MFMAs of group s (a group is 2 VW MFMAs: 64-128 cycles, the LDS latency);
         // group 16 does not exist: its read stays inside the allocation (LDP = 132, then `red`) and is never used
-        u32x4q pn = *reinterpret_cast<const u32x4q*>(p_frag);
+        u32x4 pn = *reinterpret_cast<const u32x4*>(p_frag);
         for (int s0 = 0; s0 < ((ATH_DBG & 2) ? min(ngroups, 1) : ngroups); s0 += VD) {
 #pragma unroll
             for (int u = 0; u < VD; ++u) {
                 const int sg = s0 + u;
                 if (sg < ngroups) {
-                    u32x4q pf1, pf2;
+                    u32x4 pf1, pf2;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { pf1[e] = pn[e] & 0xffffu; pf2[e] = __builtin_amdgcn_alignbit(pn[e], pn[e], 16); }
-                    pn = *reinterpret_cast<const u32x4q*>(p_frag + 8 * (sg + 1));
+                    pn = *reinterpret_cast<const u32x4*>(p_frag + 8 * (sg + 1));
 #pragma unroll
                     for (int j = 0; j < VW; ++j) {
                         O0[j] = ATH_MFMA(vb[u][j], pf1, O0[j]);
                         O1[j] = ATH_MFMA(vb[u][j], pf2, O1[j]);
                     }
-                    if (!(ATH_DBG & 16) && !((ATH_DBG & 32) && (u & 1))) ATH_VLOAD(u, sg + VD)             // refill behind the slot's MFMAs; past the range: zeros
+                    if (!(ATH_DBG & 16)) ATH_VLOAD(u, sg + VD)             // refill behind the slot's MFMAs; past the range: zeros
                     __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 2 * VW, 0);
-                    if (!(ATH_DBG & 16) && !((ATH_DBG & 32) && (u & 1))) __builtin_amdgcn_sched_group_barrier(0x020, 4 * VW, 0);
+                    if (!(ATH_DBG & 16)) __builtin_amdgcn_sched_group_barrier(0x020, 4 * VW, 0);
                 }
             }
         }
@@ -281,26 +239,7 @@ __global__ __launch_bounds__(256, HD >= 256 ? ATH_OCC256 : ATH_OCC128) void attn
             }
     }
     __syncthreads();
-    for (int q = wid; q < 32; q += 4) {
-        if (q0 + q >= T) break;
-        float* dst = out + (rowb + q0 + q) * d + (long long)h * HD;
-        for (int c = lane * 4; c < HD; c += 256) {
-            const float4 o4 = *reinterpret_cast<const float4*>(&Os[q * LDO + c]);
-            if (out_lines) {
-                // the merged-head row as f16x2 LINES (gemm_h2p.hip: attn.c_proj stages them by LDS-DMA): the lane's four values
-                // are four consecutive k of one 128-byte line -- 8 bytes of its hi half, 8 of its lo' half; same bytes as fp32
-                unsigned h0, l0, h1, l1;
-                split2_pair<true>(o4.x, o4.y, h0, l0);
-                split2_pair<true>(o4.z, o4.w, h1, l1);
-                const int col = h * HD + c;
-                unsigned char* ld = reinterpret_cast<unsigned char*>(out) + (rowb + q0 + q) * (long long)d * 4 + (col >> 5) * 128 + (col & 31) * 2;
-                *reinterpret_cast<uint2*>(ld) = make_uint2(h0, h1);
-                *reinterpret_cast<uint2*>(ld + 64) = make_uint2(l0, l1);
-            } else {
-                *reinterpret_cast<float4*>(dst + c) = o4;
-            }
-        }
-    }
+    ATTN_STORE_ROWS_H2(Os)
 }
 
 template <int HD, bool KBLK>
@@ -317,15 +256,13 @@ static int launch_ah2(const unsigned* qkv, const unsigned* kblk, const AttnGroup
         }
     }
     ProfScope prof(PK_ATTN_FUSED, flop, s);
-    const int ntq = cdiv(Tmax, 32);
-    const long long pairs8 = ((long long)G.seq_prefix[G.n] * H + 7) / 8;
-    R4D_REQUIRE(pairs8 * 8 * ntq < (1ll << 31), "attention_h2: grid too large");
-    hipLaunchKernelGGL((attn_h2_kernel<HD, KBLK>), dim3((unsigned)(pairs8 * 8 * ntq)), dim3(256), lds, s, qkv, kblk, G, d, H, ntq,
-                       (float)((double)H2_A_UNSCALE * H2_A_UNSCALE * 1.4426950408889634 / sqrt((double)HD)), out, out_lines);      // both pre-scales undone in the logits
+    int ntq, rc;
+    unsigned grid;
+    if ((rc = attn_grid_1d("attention_h2", G, H, Tmax, ntq, grid))) return rc;
+    hipLaunchKernelGGL((attn_h2_kernel<HD, KBLK>), dim3(grid), dim3(256), lds, s, qkv, kblk, G, d, H, ntq, attn_qscale(HD, H2_A_UNSCALE), out, out_lines);
     R4D_CHECK_LAUNCH("attn_h2");
     return R4D_OK;
 }
-
 
 // ---------------------------------------------------------------------------------------------- head_dim 32 / 64 / 96: key-split form
 // (round 5; VERDICT r4 missing 2: SimpleDyG UCI_13 is head_dim 96, the reddit generator 64 -- they stayed on the exact-f32 kernels.)
@@ -345,48 +282,20 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
     unsigned* Qs = ldsw;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int pair = (slot / ntq) * 8 + xcd;           // (sequence, head) index
-    if (pair >= G.seq_prefix[G.n] * H) return;
-    const int qt = ntq - 1 - slot % ntq, h = pair % H, seq = pair / H;
-    int gi = 0;
-    while (gi + 1 < G.n && seq >= G.seq_prefix[gi + 1]) ++gi;
-    const int T = G.T[gi];
-    const int q0 = qt * 32;
-    if (q0 >= T) return;
-    const long long rowb = G.row0[gi] + (long long)(seq - G.seq_prefix[gi]) * T;
-    const int ld3 = 3 * d;
-    const unsigned* __restrict__ base = qkv + rowb * ld3 + (long long)h * HD;
-    const int seq_bytes = ((T - 1) * ld3 + HD) * 4;
-    const int roff = (int)(rowb & 31);                  // key-blocked: blocks of 32 GLOBAL rows; the sequence may start mid-block
-    const unsigned* kbase = KBLK ? kblk + (rowb >> 5) * (long long)(32 * d) + h * (HD / 8) * 256 : base + d;
-    const int kbytes = KBLK ? (((roff + T - 1) >> 5) + 1) * (d * 128) - h * (HD / 8) * 1024 : seq_bytes;
-    const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(kbase), 0, kbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(base + 2 * d), 0, seq_bytes, 0x00020000);
+    ATTN_TILE_1D(G, H, ntq)
+    ATTN_KV_RSRC(unsigned, qkv, KBLK, kblk)            // (key-blocked: blocks of 32 GLOBAL rows; the sequence may start mid-block)
     const int qidx = q0 + li;
-    const int gl = roff + li;                          // this lane's key of tile 0, counted from row 0 of the sequence's first block
-    const int k_voff = KBLK ? (gl >> 5) * (d * 128) + (lh * 32 + (gl & 31)) * 16
-                     : (ATH_DBG & 128) ? 16 * lane : (li * ld3 + 4 * lh) * 4;   // bytes; + scalar (tile, step)
-    constexpr int KS_STEP = (KBLK || (ATH_DBG & 128)) ? 1024 : 32;           // (bit 7: lane-linear K addresses, whole lines per instruction, wrong operands)
-    const int k_key = KBLK ? d * 4 : ld3 * 4;                                // bytes per key of tile advance
+    ATTN_K_LANE_H2(li)                                 // gl, k_voff, K_STEP, k_tile; + scalar (tile, step)
     const int v_voff = (4 * lh * ld3 + li) * 4;                              // bytes; + scalar ((key0 + 8g + e) * ld3 + 32 j) * 4
-    u32x4q kb[NSTEP];
+    u32x4 kb[NSTEP];
     if (wid <= qt) {                                                         // this wave's first key tile
 #pragma unroll
-        for (int u = 0; u < NSTEP; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, wid * 32 * k_key + KS_STEP * u, 0);
+        for (int u = 0; u < NSTEP; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, wid * 32 * k_tile + K_STEP * u, 0);
     }
-    {   // Q tile: thread t stages row t/8, 16-byte pieces 4*(t%8) + 32j; rows past T repeat the last row (never stored)
-        const int row = tid >> 3, seg = 4 * (tid & 7);
-        const unsigned* src = base + (long long)min(q0 + row, T - 1) * ld3 + seg;
-        u32x4q qv[NCB];
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) qv[j] = *reinterpret_cast<const u32x4q*>(src + 32 * j);
-#pragma unroll
-        for (int j = 0; j < NCB; ++j) *reinterpret_cast<u32x4q*>(Qs + row * LDQ + seg + 32 * j) = qv[j];
-    }
+    ATTN_STAGE_Q(u32x4, Qs)
     __syncthreads();
 
-    f32x16q O0[NCB], O1[NCB];
+    f32x16 O0[NCB], O1[NCB];
 #pragma unroll
     for (int c = 0; c < NCB; ++c)
 #pragma unroll
@@ -398,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
         const int key0 = kt * 32;
         // V words: groups 0 and 1 (16 keys) are requested before the Q.K^T MFMAs and land under them, groups 2 and 3 behind them (they
         // land under the softmax and the first P.V MFMAs): all four up front cost 16 NCB registers beside the K rows, S and O^T
-        u32x4q vb[4][NCB];
+        u32x4 vb[4][NCB];
 #define ATK_VLOAD(g_)                                                                              \
         _Pragma("unroll") for (int j = 0; j < NCB; ++j) _Pragma("unroll") for (int e = 0; e < 4; ++e) \
             vb[g_][j][e] = __builtin_amdgcn_raw_buffer_load_b32(v_rsrc, v_voff, ((key0 + 8 * (g_) + e) * ld3 + 32 * j) * 4, 0);
@@ -406,15 +315,15 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
         ATK_VLOAD(1)
         if (HD > 64 && kt != wid) {                                           // head_dim 96: no K prefetch across tiles (registers)
 #pragma unroll
-            for (int u = 0; u < NSTEP; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, key0 * k_key + KS_STEP * u, 0);
+            for (int u = 0; u < NSTEP; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, key0 * k_tile + K_STEP * u, 0);
         }
-        f32x16q S0, S1;
+        f32x16 S0, S1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { S0[r] = 0.f; S1[r] = 0.f; }
 #pragma unroll
         for (int u = 0; u < NSTEP; ++u) {
-            const u32x4q qw = *reinterpret_cast<const u32x4q*>(q_frag + 8 * u);
-            u32x4q f1, f2;
+            const u32x4 qw = *reinterpret_cast<const u32x4*>(q_frag + 8 * u);
+            u32x4 f1, f2;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { f1[e] = qw[e] & 0xffffu; f2[e] = __builtin_amdgcn_alignbit(qw[e], qw[e], 16); }
             S0 = ATH_MFMA(kb[u], f1, S0);
@@ -426,7 +335,7 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
 #undef ATK_VLOAD
         if (HD <= 64 && kt + 4 <= qt) {                                       // the next tile's K rows travel under the softmax and P.V
 #pragma unroll
-            for (int u = 0; u < NSTEP; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, (key0 + 128) * k_key + KS_STEP * u, 0);
+            for (int u = 0; u < NSTEP; ++u) kb[u] = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, k_voff, (key0 + 128) * k_tile + K_STEP * u, 0);
         }
         // online softmax on the raw dot products (attn_h2_kernel: subtract the maximum first, scale the small difference)
         float S[16];
@@ -459,7 +368,7 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
             unsigned a[4];
             h2_words<false>(p[0], p[1], a[0], a[1]);
             h2_words<false>(p[2], p[3], a[2], a[3]);
-            u32x4q pf1, pf2;
+            u32x4 pf1, pf2;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { pf1[e] = a[e] & 0xffffu; pf2[e] = __builtin_amdgcn_alignbit(a[e], a[e], 16); }
 #pragma unroll
@@ -474,42 +383,15 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
     }
 
     // ---- join the two accumulator sets, merge the 4 partial states: (2,3) -> (0,1), then 1 -> 0 (attention_fused.hip)
-    f32x16q O[NCB];
+    f32x16 O[NCB];
 #pragma unroll
     for (int c = 0; c < NCB; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) O[c][r] = __builtin_fmaf(O1[c][r], H2_LO_UNSCALE, O0[c][r]);
     float* lds = reinterpret_cast<float*>(ldsw);
-    constexpr int SLOT = NCB * 16 * 64 + 128;
-    __syncthreads();                                    // every wave is done with the query buffer
-#pragma unroll 1
-    for (int step = 0; step < 2; ++step) {
-        const int writers_lo = step == 0 ? 2 : 1;
-        if (wid >= writers_lo && wid < 2 * writers_lo) {
-            float* sl = lds + (wid - writers_lo) * SLOT;
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sl[(c * 16 + r) * 64 + lane] = O[c][r];
-            sl[NCB * 16 * 64 + lane] = m_run;
-            sl[NCB * 16 * 64 + 64 + lane] = l_run;
-        }
-        __syncthreads();
-        if (wid < writers_lo) {
-            const float* sl = lds + wid * SLOT;
-            const float m_b = sl[NCB * 16 * 64 + lane], l_b = sl[NCB * 16 * 64 + 64 + lane];
-            const float m_new = fmaxf(m_run, m_b);
-            const float fa = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_new) * qscale);
-            const float fb = (m_b == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_b - m_new) * qscale);
-#pragma unroll
-            for (int c = 0; c < NCB; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) O[c][r] = O[c][r] * fa + sl[(c * 16 + r) * 64 + lane] * fb;
-            l_run = l_run * fa + l_b * fb;
-            m_run = m_new;
-        }
-        __syncthreads();
-    }
+#define ATTN_MERGE_WEIGHT(m_old, m_new) __builtin_amdgcn_exp2f((m_old - m_new) * qscale)
+    ATTN_MERGE4(O, lds)
+#undef ATTN_MERGE_WEIGHT
     constexpr int LDO = HD + 4;
     if (wid == 0) {
         const float inv = H2_A_UNSCALE / l_run;
@@ -519,24 +401,7 @@ __global__ __launch_bounds__(256, 2) void attn_h2ks_kernel(const unsigned* __res
             for (int r = 0; r < 16; ++r) lds[li * LDO + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * lh] = O[j][r] * inv;
     }
     __syncthreads();
-    for (int q = wid; q < 32; q += 4) {
-        if (q0 + q >= T) break;
-        float* dst = out + (rowb + q0 + q) * d + (long long)h * HD;
-        for (int c = lane * 4; c < HD; c += 256) {
-            const float4 o4 = *reinterpret_cast<const float4*>(&lds[q * LDO + c]);
-            if (out_lines) {
-                unsigned h0, l0, h1, l1;
-                split2_pair<true>(o4.x, o4.y, h0, l0);
-                split2_pair<true>(o4.z, o4.w, h1, l1);
-                const int col = h * HD + c;
-                unsigned char* ld = reinterpret_cast<unsigned char*>(out) + (rowb + q0 + q) * (long long)d * 4 + (col >> 5) * 128 + (col & 31) * 2;
-                *reinterpret_cast<uint2*>(ld) = make_uint2(h0, h1);
-                *reinterpret_cast<uint2*>(ld + 64) = make_uint2(l0, l1);
-            } else {
-                *reinterpret_cast<float4*>(dst + c) = o4;
-            }
-        }
-    }
+    ATTN_STORE_ROWS_H2(lds)
 }
 
 template <int HD, bool KBLK>
@@ -547,11 +412,10 @@ static int launch_ah2ks(const unsigned* qkv, const unsigned* kblk, const AttnGro
     if (merge > words) words = merge;
     const size_t lds = words * 4;
     ProfScope prof(PK_ATTN_FUSED, flop, s);
-    const int ntq = cdiv(Tmax, 32);
-    const long long pairs8 = ((long long)G.seq_prefix[G.n] * H + 7) / 8;
-    R4D_REQUIRE(pairs8 * 8 * ntq < (1ll << 31), "attention_h2: grid too large");
-    hipLaunchKernelGGL((attn_h2ks_kernel<HD, KBLK>), dim3((unsigned)(pairs8 * 8 * ntq)), dim3(256), lds, s, qkv, kblk, G, d, H, ntq,
-                       (float)((double)H2_A_UNSCALE * H2_A_UNSCALE * 1.4426950408889634 / sqrt((double)HD)), out, out_lines);
+    int ntq, rc;
+    unsigned grid;
+    if ((rc = attn_grid_1d("attention_h2", G, H, Tmax, ntq, grid))) return rc;
+    hipLaunchKernelGGL((attn_h2ks_kernel<HD, KBLK>), dim3(grid), dim3(256), lds, s, qkv, kblk, G, d, H, ntq, attn_qscale(HD, H2_A_UNSCALE), out, out_lines);
     R4D_CHECK_LAUNCH("attn_h2ks");
     return R4D_OK;
 }
@@ -569,36 +433,27 @@ int launch_attention_h2_groups(const unsigned* qkv, int n, const int* Bs, const 
                                float* out, hipStream_t s, bool out_lines, const unsigned* kblk) {
     R4D_REQUIRE(qkv && out, "attention_h2: null pointer");
     R4D_REQUIRE(attention_h2_supported(H, d), "attention_h2: head_dim %d has no instantiation (32 / 64 / 96 / 128 / 256)", H > 0 ? d / H : 0);
-    R4D_REQUIRE(n >= 1 && n <= ATT_MAXG, "attention_h2: %d batches per launch (max %d)", n, ATT_MAXG);
-    const int hd = d / H;
     AttnGroups G;
-    G.n = n;
-    G.seq_prefix[0] = 0;
-    int Tmax = 0;
-    double flop = 0.0;                                  // causal half of Q.K^T and P.V: 2 * T^2 * hd per head
-    for (int g = 0; g < n; ++g) {
-        R4D_REQUIRE(Bs[g] >= 1 && Ts[g] >= 1 && (long long)Ts[g] * 3 * d < (1ll << 29), "attention_h2: batch %d: B=%d T=%d", g, Bs[g], Ts[g]);
-        G.seq_prefix[g + 1] = G.seq_prefix[g] + Bs[g];
-        G.T[g] = Ts[g];
-        G.row0[g] = row0s[g];
-        if (Ts[g] > Tmax) Tmax = Ts[g];
-        flop += 2.0 * Bs[g] * H * (double)Ts[g] * Ts[g] * hd;
+    int Tmax, rc;
+    double flop;
+    if ((rc = attn_groups_fill("attention_h2", n, Bs, Ts, row0s, H, d, G, Tmax, flop))) return rc;
+    for (int g = 0; g < n; ++g) R4D_REQUIRE(Bs[g] >= 1 && Ts[g] >= 1, "attention_h2: batch %d: B=%d T=%d", g, Bs[g], Ts[g]);
+    // (head_dim, key-blocked K) -> launcher and dispatch branch.  The rows stand in the order in which the kernels have always been
+    // instantiated, which is the order of the functions in the code object.
+#define ATH_KERNELS(X)                                                                                              \
+    X(32, true, launch_ah2ks, ATT_H2_KS32_KBLK) X(64, true, launch_ah2ks, ATT_H2_KS64_KBLK) X(96, true, launch_ah2ks, ATT_H2_KS96_KBLK) \
+    X(32, false, launch_ah2ks, ATT_H2_KS32) X(64, false, launch_ah2ks, ATT_H2_KS64) X(96, false, launch_ah2ks, ATT_H2_KS96)   \
+    X(128, true, launch_ah2, ATT_H2_128_KBLK) X(128, false, launch_ah2, ATT_H2_128)                                 \
+    X(256, true, launch_ah2, ATT_H2_256_KBLK) X(256, false, launch_ah2, ATT_H2_256)
+#define X(HD_, KBLK_, LAUNCH_, BRANCH_)                                                                             \
+    if (d / H == HD_ && (kblk != nullptr) == KBLK_) {                                                               \
+        R4D_BRANCH(BRANCH_);                                                                                        \
+        return LAUNCH_<HD_, KBLK_>(qkv, kblk, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s);                      \
     }
-    for (int g = n; g < ATT_MAXG; ++g) { G.seq_prefix[g + 1] = G.seq_prefix[n]; G.T[g] = 0; G.row0[g] = 0; }
-    R4D_REQUIRE(G.seq_prefix[n] <= 65535, "attention_h2: %d sequences per launch exceed the grid limit", G.seq_prefix[n]);
-    if (kblk) {
-        if (hd == 32) { R4D_BRANCH(ATT_H2_KS32_KBLK); return launch_ah2ks<32, true>(qkv, kblk, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-        if (hd == 64) { R4D_BRANCH(ATT_H2_KS64_KBLK); return launch_ah2ks<64, true>(qkv, kblk, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-        if (hd == 96) { R4D_BRANCH(ATT_H2_KS96_KBLK); return launch_ah2ks<96, true>(qkv, kblk, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    }
-    if (hd == 32) { R4D_BRANCH(ATT_H2_KS32); return launch_ah2ks<32, false>(qkv, nullptr, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    if (hd == 64) { R4D_BRANCH(ATT_H2_KS64); return launch_ah2ks<64, false>(qkv, nullptr, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    if (hd == 96) { R4D_BRANCH(ATT_H2_KS96); return launch_ah2ks<96, false>(qkv, nullptr, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    if (hd == 128 && kblk) { R4D_BRANCH(ATT_H2_128_KBLK); return launch_ah2<128, true>(qkv, kblk, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    if (hd == 128) { R4D_BRANCH(ATT_H2_128); return launch_ah2<128, false>(qkv, nullptr, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    if (kblk) { R4D_BRANCH(ATT_H2_256_KBLK); return launch_ah2<256, true>(qkv, kblk, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s); }
-    R4D_BRANCH(ATT_H2_256);
-    return launch_ah2<256, false>(qkv, nullptr, G, Tmax, flop, H, d, out, out_lines ? 1 : 0, s);
+    ATH_KERNELS(X)
+#undef X
+#undef ATH_KERNELS
+    return R4D_ERR_INVALID;                             // not reached: attention_h2_supported has passed
 }
 
 // K columns of row-major qkv words -> the key-blocked image (what gemm_h2p's epilogue writes directly; tests, external producers)
@@ -611,9 +466,9 @@ __global__ __launch_bounds__(256) void pack_kblk_words_kernel(const unsigned* __
     const long long chunk = i >> 6;                                     // (block * H + head) * nstep + u
     const int u = (int)(chunk % nstep), head = (int)((chunk / nstep) % H);
     const long long row = (chunk / nstep / H) * 32 + (slot & 31);
-    u32x4q v = {0u, 0u, 0u, 0u};
-    if (row < M) v = *reinterpret_cast<const u32x4q*>(qkv + row * 3 * d + d + head * hd + 8 * u + 4 * (slot >> 5));
-    reinterpret_cast<u32x4q*>(kblk)[i] = v;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (row < M) v = *reinterpret_cast<const u32x4*>(qkv + row * 3 * d + d + head * hd + 8 * u + 4 * (slot >> 5));
+    reinterpret_cast<u32x4*>(kblk)[i] = v;
 }
 int launch_pack_kblk_words(const unsigned* qkv, long long M, int H, int d, unsigned* kblk, hipStream_t s) {
     R4D_REQUIRE(qkv && kblk && M >= 1 && attention_h2_supported(H, d), "pack_kblk_words: bad arguments (head_dim 32 / 64 / 96 / 128 / 256)");

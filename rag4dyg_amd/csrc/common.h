@@ -322,7 +322,7 @@ struct AttnGroups {
     long long row0[ATT_MAXG];         // first token row of each batch in qkv / out
 };
 // attention_h2.hip: the same attention on the fp16 matrix cores (f16x2 form), qkv as uint32 "h2 words" (csrc/h2.h; written by
-// gemm_h2's EPI_H2WORDS epilogue or launch_pack_h2_words); head_dim 128 / 256 (attention_h2_supported)
+// gemm_h2's EPI_H2WORDS epilogue or launch_pack_h2_words); head_dim 32 / 64 / 96 / 128 / 256 (attention_h2_supported)
 bool attention_h2_supported(int H, int d);
 int launch_attention_h2_groups(const unsigned* qkv_words, int n, const int* Bs, const int* Ts, const long long* row0s, int H, int d,
                                float* out, hipStream_t s, bool out_lines = false, const unsigned* kblk = nullptr);

@@ -108,6 +108,18 @@ static RowGroups row_groups(const Group* groups, int g0, int n_groups) {
     return R;
 }
 
+// The batches g0 .. of one attention launch (ATT_MAXG at the most) as the attention launchers take them; returns how many,
+// *nseq their sequences (a launch holds 65,535)
+static int attn_chunk(const Group* groups, int g0, int n_groups, int* Bs, int* Ts, long long* r0, int* nseq) {
+    const int n = n_groups - g0 < ATT_MAXG ? n_groups - g0 : ATT_MAXG;
+    *nseq = 0;
+    for (int j = 0; j < n; ++j) {
+        Bs[j] = groups[g0 + j].B; Ts[j] = groups[g0 + j].T; r0[j] = (long long)groups[g0 + j].row0;
+        *nseq += Bs[j];
+    }
+    return n;
+}
+
 struct Workspace {
     float *x, *ln, *qkv, *att, *fc, *scores, *pool;
     unsigned* kblk;       // key-blocked K words of the f16x2 attention (attention_h2.hip): ceil32(M) x d
@@ -302,9 +314,10 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         // the fp16 matrix cores (attention_h2.hip); every other case: fp32 qkv and the exact-f32 kernels below
         bool words = !g_encode_bf16 && !out_qkv_d && g_attention_h2 && g_attention_fused != 0 && g_gemm_split3 == 2 && Wqkv.h2 &&
                      attention_h2_supported(H, d) && gemm_h2_supported(M, d, 3 * d);
+        int Bs[ATT_MAXG], Ts[ATT_MAXG], nseq;                   // one attention launch's batches (attn_chunk)
+        long long r0[ATT_MAXG];
         for (int g0 = 0; g0 < n_groups && words; g0 += ATT_MAXG) {
-            int nseq = 0;
-            for (int j = g0; j < n_groups && j < g0 + ATT_MAXG; ++j) nseq += groups[j].B;
+            attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
             if (nseq > 65535) words = false;
         }
         // ... and its K third as the key-blocked image the head_dim 128 / 256 kernel loads by whole cache lines (attention_h2.hip)
@@ -365,24 +378,14 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         if (words) {
             fused_done = true;
             for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {
-                int Bs[ATT_MAXG], Ts[ATT_MAXG];
-                long long r0[ATT_MAXG];
-                const int n = n_groups - g0 < ATT_MAXG ? n_groups - g0 : ATT_MAXG;
-                for (int j = 0; j < n; ++j) { Bs[j] = groups[g0 + j].B; Ts[j] = groups[g0 + j].T; r0[j] = (long long)groups[g0 + j].row0; }
+                const int n = attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
                 if ((rc = launch_attention_h2_groups(reinterpret_cast<const unsigned*>(qkv), n, Bs, Ts, r0, H, d, ws.att, s, att_lines,
                                                      kblk ? ws.kblk : nullptr))) return rc;
             }
         } else if (g_attention_fused != 0) {             // all batches of the call in ceil(n/16) fused launches
             fused_done = true;
             for (int g0 = 0; g0 < n_groups && fused_done; g0 += ATT_MAXG) {
-                int Bs[ATT_MAXG], Ts[ATT_MAXG];
-                long long r0[ATT_MAXG];
-                const int n = n_groups - g0 < ATT_MAXG ? n_groups - g0 : ATT_MAXG;
-                int nseq = 0;
-                for (int j = 0; j < n; ++j) {
-                    Bs[j] = groups[g0 + j].B; Ts[j] = groups[g0 + j].T; r0[j] = (long long)groups[g0 + j].row0;
-                    nseq += Bs[j];
-                }
+                const int n = attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
                 if (nseq > 65535) { fused_done = false; break; }
                 rc = launch_attention_fused_groups(qkv, n, Bs, Ts, r0, H, d, ws.att, s);
                 if (rc < 0) return rc;

@@ -347,7 +347,7 @@ def set_attention_fused(mode):
 
 
 def set_attention_h2(on):
-    """In gemm mode "f16x2": head_dim 128 / 256 attention of the encoder on the fp16 matrix cores (csrc/attention_h2.hip; default
+    """In gemm mode "f16x2": head_dim 32 / 64 / 96 / 128 / 256 attention of the encoder on the fp16 matrix cores (csrc/attention_h2.hip; default
     on).  Off: the exact-f32 attention kernels in every mode.  Returns the previous setting.  Process-wide: ranks must agree."""
     return bool(_lib.load().r4d_set_attention_h2(int(bool(on))))
 
@@ -396,7 +396,7 @@ def pack_h2_words(x):
 
 def attention_h2(qkv_words, n_head):
     """:func:`attention` on the fp16 matrix cores at fp32 accuracy: ``qkv_words`` = :func:`pack_h2_words` of the packed c_attn
-    output [B,T,3d]; head_dim 128 / 256."""
+    output [B,T,3d]; head_dim 32 / 64 / 96 / 128 / 256."""
     B, T, d3 = qkv_words.shape
     d = d3 // 3
     a = torch.empty(B, T, d, dtype=torch.float32, device=qkv_words.device)

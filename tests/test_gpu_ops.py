@@ -589,6 +589,34 @@ def test_fused_groups_equal_one_batch_per_call(dev, gemm_mode):
     assert rel_err(fused.cpu().numpy(), ref.numpy()) < 1e-5
 
 
+@pytest.mark.parametrize("H,d", [(2, 128), (8, 256), (2, 256), (1, 256), (8, 768)])
+def test_fused_groups_across_launch_boundaries_equal_one_batch_per_call(dev, gemm_mode, H, d):
+    """More batches than one attention launch holds (ATT_MAXG = 16): 33 batches = 16 + 16 + 1 launches per layer, at head_dim 64,
+    32, 128, 256 and 96 (both exact-f32 kernels, both f16x2 kernels, the key-blocked K image).  The batches start mid-way through
+    a 32-row block and one T spans two 128-key super-tiles.  Same property as above: bit for bit the one-batch-per-call rows."""
+    from oracle import gpt2_ref
+    from rag4dyg_amd import _lib
+    lib = _lib.load()
+    sd = gpt2_ref.make_state_dict(1, d, 50, n_positions=160, seed=5, random_affine=True)
+    m = build_model(sd, 1, H, d, 50, 160, dev)
+    g = torch.Generator().manual_seed(3)
+    Ts = (1, 17, 31, 32, 33, 64, 129, 40)
+    batches = [torch.randint(0, 50, (1 + i % 3, Ts[i % 8]), generator=g).to(dev) for i in range(33)]
+
+    def attention_launches():
+        names = [lib.r4d_dispatch_branch_name(i).decode() for i in range(lib.r4d_dispatch_num_branches())]
+        return sum(int(lib.r4d_dispatch_branch_hits(i)) for i, n in enumerate(names) if n.startswith(("attention:", "tuning:attention:")))
+    before = attention_launches()
+    fused = m.encode_groups_meanpool(batches)
+    assert attention_launches() - before == 3                # one layer: ceil(33 / 16) launches, none of them the per-batch form
+    single = torch.cat([m.encode_meanpool(b) for b in batches], dim=0)
+    assert fused.shape == (66, d) and torch.equal(fused, single)
+    ref = torch.cat([gpt2_ref.gpt2_forward(sd, b.cpu(), H, want_logits=False)["hidden"].mean(dim=1) for b in batches])
+    err = rel_err(fused.cpu().numpy(), ref.numpy())
+    print(f"H {H} d {d} ({gemm_mode}): mean-pool max-norm err {err:.2e}")
+    assert err < 1e-5
+
+
 def test_encoder_errors_are_loud(dev):
     from oracle import gpt2_ref
     from rag4dyg_amd._lib import R4DError
