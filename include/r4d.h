@@ -557,7 +557,7 @@ int r4d_get_train_activations(void);
  *   data gradient  dx = RN(dy) . RN(W)^T                     plane 0 of *_w3t (RN(W) as [in][out])
  *   weight grad.   dW = RN(x)^T . RN(dy),  db = column sums of the UNROUNDED dy
  * Master weights, gradients, the optimizer, LayerNorm, softmax, GELU, the losses, the embedding scatter and every accumulator stay
- * fp32; the attention GEMMs stay exact f32; the LM head's three GEMMs, r4d_weight_grad_f32, the GCN projection of the RAG step
+ * fp32; the attention GEMMs stay exact f32 (their own switch: r4d_set_train_attention_bf16 below); the LM head's three GEMMs, r4d_weight_grad_f32, the GCN projection of the RAG step
  * and every encoder / decode entry do not read the switch.  A layer GEMM is switched in EVERY gemm mode (f32 included) whenever
  * the layer carries the plane and the shape is supported (K % 32 == 0; weight gradient: in % 128 == 0, out % 256 == 0, rows >=
  * 32); anything else keeps the gemm mode's kernel.  Only plane 0 of the plane sets is read by the switched GEMMs.
@@ -583,6 +583,36 @@ int r4d_conv1d_bf16_dgrad_f32(const float* dy_d, const uint16_t* wt_bf16_d /* [i
 size_t r4d_weight_grad_bf16_workspace_bytes(int32_t rows, int32_t in_features, int32_t out_features);
 int r4d_weight_grad_bf16_f32(const float* x_d, int32_t ldx, const float* dy_d, int32_t ldy, int32_t rows, int32_t in_features,
                              int32_t out_features, float* dw_d, float* db_d, void* workspace_d, size_t workspace_bytes, void* stream);
+
+/* The attention products of the training steps on plain bf16 operands (process-wide; additive ABI v6 entries; csrc/gemm_b1h.hip).
+ * A second, INDEPENDENT axis beside r4d_set_train_bf16, whose meaning and return values it leaves alone.  NOT fp32-accurate: while
+ * on, both fp32 operands of the six per-head products of every block are rounded to bf16 (round to nearest even) where they are
+ * staged and multiplied ONCE on v_mfma_f32_32x32x16_bf16 with fp32 accumulation in a fixed order:
+ *   0  S  = RN(Q) . RN(K)^T / sqrt(hd)   (tiles above the diagonal skipped)      3  dQ = RN(dS) . RN(K)
+ *   1  O  = RN(P) . RN(V)                (trimmed to the keys a row tile sees)   4  dK = RN(dS^T) . RN(Q)
+ *   2  dP = RN(dO) . RN(V)^T                                                     5  dV = RN(Pd^T) . RN(dO)
+ * in stored and recompute attention alike.  The scale division acts on the fp32 accumulator; softmax, its backward, dropout, the
+ * transposes, P and every other buffer stay fp32, and nothing outside the training steps reads the switch.
+ * r4d_set_train_attention_bf16(on != 0) returns the previous setting; default 0.  Read like r4d_set_train_bf16: set it BEFORE the
+ * size query (the sizes do not depend on it) and keep it until the step's backward has been issued; a backward on the workspace of
+ * the most recent training forward under the other setting is refused (R4D_ERR_INVALID). */
+int r4d_set_train_attention_bf16(int32_t on);
+int r4d_get_train_attention_bf16(void);
+/* ONE of the six products above (which = 0 .. 5) over a [B, T] batch with H heads of d / H columns, for per-product tests and tools:
+ * the launch the step issues, whatever the switch says.  a_d / b_d / c_d point at the first element of the (sequence 0, head 0)
+ * block in the step's layouts: a Q / K / V slice of [B, T, 3d] (row stride 3d), merged heads [B, T, d], or a P-shaped block
+ * [B*H, T, ld] with ld = r4d_train_attn_probs_ld(T) floats (T rounded up to 128):
+ *   which   a_d            b_d          c_d              which   a_d             b_d           c_d
+ *   0       Q slice        K slice      P-shaped         3       P-shaped dS     K slice       Q slice of dqkv
+ *   1       P-shaped       V slice      merged           4       P-shaped dS^T   Q slice       K slice of dqkv
+ *   2       merged dO      V slice      P-shaped         5       P-shaped Pd^T   merged dO     V slice of dqkv
+ * Of a P-shaped OPERAND only columns [0, T) of its T rows are used, of every other operand only its T rows and its head's d / H
+ * columns; whatever else that memory holds (NaN included) reaches no product.  Only C's [T, N] block per (sequence, head) is
+ * written (product 0: the tiles that touch the lower triangle; the rest is the softmax's to fill).  head_dim % 16 == 0, T <= 1024,
+ * B * H <= 65535; operands 16-byte aligned. */
+size_t r4d_train_attn_probs_ld(int32_t T);
+int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float* b_d, float* c_d, int32_t B, int32_t T, int32_t H,
+                                    int32_t d, void* stream);
 
 /* Scratch of one step: the activations the backward pass needs (16 * rows * d floats per layer + the attention
  * probabilities in stored mode) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */

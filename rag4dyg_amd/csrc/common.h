@@ -45,7 +45,7 @@ enum ProfClass {
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
-    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_COUNT
+    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_GEMM_B1H_NT, PK_GEMM_B1H_NN, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -86,7 +86,8 @@ struct ProfScope {
     X(JAC_PREP_DENSE_LDS, "jaccard_prep:dense tokens, LDS histogram") X(JAC_PREP_DENSE_GLOBAL, "jaccard_prep:dense tokens, global histogram") X(JAC_PREP_ORDER, "jaccard_prep:rows longest first") \
     X(ARGSORT_ONE, "argsort:one chunk") X(ARGSORT_MULTI, "argsort:chunk sort + rank scatter")                              \
     X(B1_128x256, "tuning:encode_bf16:128x256x32") X(B1_128x128, "tuning:encode_bf16:128x128x32")                           \
-    X(TB_FWD, "tuning:train_bf16:fwd") X(TB_DGRAD, "tuning:train_bf16:dgrad") X(TB_WGRAD, "tuning:train_bf16:wgrad") X(TB_WGRAD_FALLBACK, "tuning:train_bf16:wgrad_fallback")
+    X(TB_FWD, "tuning:train_bf16:fwd") X(TB_DGRAD, "tuning:train_bf16:dgrad") X(TB_WGRAD, "tuning:train_bf16:wgrad") X(TB_WGRAD_FALLBACK, "tuning:train_bf16:wgrad_fallback") \
+    X(TBA_NT, "tuning:train_bf16_attn:nt") X(TBA_NN, "tuning:train_bf16_attn:nn")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -183,6 +184,10 @@ int launch_gemm_b1(const S3Args& a, hipStream_t stream);
 // db_out (nullable) [J] or [S][J] <- column sums of the unrounded dY; gemm_s3tn's shape contract
 int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out, int I, int J, int M, int lda, int ldb, int S,
                      hipStream_t stream);
+// gemm_b1h.hip: the per-head attention products of the training steps on plain bf16 operands (r4d_set_train_attention_bf16; NOT
+// fp32-accurate): the GemmArgs of launch_gemm_f32's batched form -- both operand forms, epilogues none / scale-div, the three causal
+// flags, no bias, no residual
+int launch_gemm_b1h(const GemmArgs& g, hipStream_t stream);
 // gemm_s3tn.hip: partials [slices][I][J] <- X[M,I]^T . dY[M,J] on the bf16 matrix cores at fp32 accuracy, db_partials (nullable)
 // [slices][J] <- column sums of dY; one slice is a partial too
 int launch_gemm_s3tn(const float* X, const float* dY, float* out, float* db_partials, int I, int J, int M, int lda, int ldb, int S,

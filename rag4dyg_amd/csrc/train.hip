@@ -53,10 +53,13 @@ static int g_train_activations = 0;
 // r4d_set_train_bf16: 0 the gemm mode's arithmetic (default), 1 the twelve Conv1D GEMMs of a block on plain bf16 operands
 // (gemm_b1.hip, gemm_b1tn.hip) wherever the layer carries the plane and the shape is supported.  NOT fp32-accurate.
 static int g_train_bf16 = 0;
-// The three modes as a value: every entry point (size queries, forward, backward) reads the globals ONCE, here, and hands the
+// r4d_set_train_attention_bf16: 0 the six per-head attention products of a block on the exact-f32 kernel (default), 1 on plain bf16
+// operands (gemm_b1h.hip).  Independent of g_train_bf16.  NOT fp32-accurate.
+static int g_train_attn_bf16 = 0;
+// The modes as a value: every entry point (size queries, forward, backward) reads the globals ONCE, here, and hands the
 // value down; nothing below an entry point looks at a global.
-struct TrainModes { int attention, activations, bf16; };
-static TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations, g_train_bf16}; }
+struct TrainModes { int attention, activations, bf16, attn_bf16; };
+static TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16}; }
 // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
 static bool train_fuse_gelu() {
     static const int v = [] { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); return e ? atoi(e) : 1; }();
@@ -65,7 +68,7 @@ static bool train_fuse_gelu() {
 // The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
 // activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
 // would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
-static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0}, -1};
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -266,27 +269,51 @@ static GemmArgs head_gemm(const HeadDims& D, const float* A, HeadLd a, const flo
     return g;
 }
 
+// The six per-head products of a block's attention, forward and backward.  Operands are pointers to the first element of the
+// (sequence 0, head 0) block: Q / K / V slices of [B, T, 3d], merged-heads [B, T, d] or P-shaped [B*H, T, ld] as listed.
+enum HeadProduct {
+    HP_S = 0,       // S  [probs]  = Q [qkv] . K [qkv]^T / sqrt(hd)    NT, K = hd, tiles above the diagonal skipped
+    HP_PV,          // O  [merged] = P [probs] . V [qkv]               NN, K = T, trimmed to the keys a row tile sees
+    HP_DP,          // dP [probs]  = dO [merged] . V [qkv]^T           NT, K = hd
+    HP_DQ,          // dQ [qkv]    = dS [probs] . K [qkv]              NN, K = up4(T)
+    HP_DK,          // dK [qkv]    = dS^T [probs] . Q [qkv]            NN, K = up4(T)
+    HP_DV,          // dV [qkv]    = Pd^T [probs] . dO [merged]        NN, K = up4(T)
+    HP_COUNT
+};
+static GemmArgs head_product_args(const HeadDims& D, int which, const float* A, const float* Bm, float* C) {
+    switch (which) {
+        case HP_S: return head_gemm(D, A, D.qkv, Bm, D.qkv, C, D.probs, D.T, D.hd, 1, 0, EPI_SCALE_DIV, (float)sqrt((double)D.hd), CAUSAL_QK);
+        case HP_PV: return head_gemm(D, A, D.probs, Bm, D.qkv, C, D.merged, D.hd, D.T, 0, D.ld, EPI_NONE, 1.f, CAUSAL_PV);
+        case HP_DP: return head_gemm(D, A, D.merged, Bm, D.qkv, C, D.probs, D.T, D.hd, 1, 0);
+        case HP_DV: return head_gemm(D, A, D.probs, Bm, D.merged, C, D.qkv, D.hd, D.Tp, 0, D.Tp);
+        default: return head_gemm(D, A, D.probs, Bm, D.qkv, C, D.qkv, D.hd, D.Tp, 0, D.Tp);          // HP_DQ, HP_DK
+    }
+}
+// one of the six on the kernel the mode names: `abf` (TrainModes::attn_bf16) -> gemm_b1h, else the exact-f32 kernel
+static int head_product(const HeadDims& D, int which, const float* A, const float* Bm, float* C, int abf, hipStream_t s) {
+    const GemmArgs g = head_product_args(D, which, A, Bm, C);
+    return abf ? launch_gemm_b1h(g, s) : launch_gemm_f32(g, s);
+}
+
 // P [B*H, T, ld] = causal softmax(Q . K^T / sqrt(hd)): the forward's two launches (recompute mode runs them again in the backward)
-static int attn_probs(const HeadDims& D, const float* qkv, float* P, hipStream_t s) {
-    const int rc = launch_gemm_f32(head_gemm(D, qkv, D.qkv, qkv + D.d, D.qkv, P, D.probs, D.T, D.hd, 1, 0, EPI_SCALE_DIV,
-                                             (float)sqrt((double)D.hd), CAUSAL_QK), s);
+static int attn_probs(const HeadDims& D, const float* qkv, float* P, int abf, hipStream_t s) {
+    const int rc = head_product(D, HP_S, qkv, qkv + D.d, P, abf, s);
     if (rc) return rc;
     return launch_causal_softmax(P, D.B * D.H, D.T, D.ld, D.ld, s);                // row_tile = ld: zero-fill the whole row
 }
 
 // Attention._attn forward over one batch, probabilities kept in P [B*H, T, ld] with EVERY column right of the diagonal zero
 // `Pdrop` (with attn_p > 0): scratch for the dropped-out probabilities the P.V product reads; P keeps the softmax output
-static int attn_fwd(const HeadDims& D, const float* qkv, float* P, float* out, hipStream_t s, float attn_p, DropKey key,
+static int attn_fwd(const HeadDims& D, const float* qkv, float* P, float* out, int abf, hipStream_t s, float attn_p, DropKey key,
                     unsigned site, unsigned long long pbase, float* Pdrop) {
-    int rc = attn_probs(D, qkv, P, s);
+    int rc = attn_probs(D, qkv, P, abf, s);
     if (rc) return rc;
     const float* Pv = P;
     if (attn_p > 0.f) {                                                            // attn_dropout(w), modeling_gpt2.py:153
         if ((rc = launch_dropout(P, nullptr, (long long)D.B * D.H * D.T * D.ld, Pdrop, attn_p, key, site, pbase, s))) return rc;
         Pv = Pdrop;
     }
-    return launch_gemm_f32(head_gemm(D, Pv, D.probs, qkv + 2 * D.d, D.qkv, out, D.merged, D.hd, D.T, 0, D.ld, EPI_NONE, 1.f,
-                                     CAUSAL_PV), s);
+    return head_product(D, HP_PV, Pv, qkv + 2 * D.d, out, abf, s);
 }
 
 // Attention backward over one batch: dao [B,T,d] (merged heads) -> dqkv [B,T,3d].  `P`: the probabilities the forward kept, or
@@ -295,18 +322,18 @@ static int attn_fwd(const HeadDims& D, const float* qkv, float* P, float* out, h
 // element-wise steps between them are separate launches in stored mode and the two fused row kernels, written to leave those
 // launches' bits, in recompute mode (stored mode can take the fused kernels over once they have been timed against it).
 static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const float* dao, float* dqkv, float* A, float* Bs, float* C,
-                    hipStream_t s, float attn_p, DropKey key, unsigned site, unsigned long long pbase) {
+                    int abf, hipStream_t s, float attn_p, DropKey key, unsigned site, unsigned long long pbase) {
     const int d = D.d, BH = D.B * D.H;
     const long long n = (long long)BH * D.T * D.ld;
     const float sd = (float)sqrt((double)D.hd);                  // the logits were divided by sqrt(hd) before the softmax
     const bool fused = P == nullptr;
     int rc;
     if (!P) {
-        if ((rc = attn_probs(D, qkv, A, s))) return rc;
+        if ((rc = attn_probs(D, qkv, A, abf, s))) return rc;
         P = A;
     }
     // dP = dO . V^T
-    if ((rc = launch_gemm_f32(head_gemm(D, dao, D.merged, qkv + 2 * d, D.qkv, Bs, D.probs, D.T, D.hd, 1, 0), s))) return rc;
+    if ((rc = head_product(D, HP_DP, dao, qkv + 2 * d, Bs, abf, s))) return rc;
     // dS in place on Bs (through the dropout mask: d(softmax out) = mask * dP / (1 - p)), dS^T into C
     if (fused) {
         if ((rc = launch_softmax_bwd_t(P, Bs, C, BH, D.T, D.ld, sd, attn_p, key, site, pbase, s))) return rc;
@@ -315,9 +342,9 @@ static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const f
         if ((rc = launch_softmax_bwd(P, Bs, BH, D.T, D.ld, sd, s))) return rc;
     }
     // dQ = dS . K,  dK = dS^T . Q
-    if ((rc = launch_gemm_f32(head_gemm(D, Bs, D.probs, qkv + d, D.qkv, dqkv, D.qkv, D.hd, D.Tp, 0, D.Tp), s))) return rc;
+    if ((rc = head_product(D, HP_DQ, Bs, qkv + d, dqkv, abf, s))) return rc;
     if (!fused && (rc = launch_transpose(Bs, D.T, D.T, D.ld, D.probs.s1, C, D.ld, D.probs.s1, BH, s))) return rc;
-    if ((rc = launch_gemm_f32(head_gemm(D, C, D.probs, qkv, D.qkv, dqkv + d, D.qkv, D.hd, D.Tp, 0, D.Tp), s))) return rc;
+    if ((rc = head_product(D, HP_DK, C, qkv, dqkv + d, abf, s))) return rc;
     // dV = Pd^T . dO: the probabilities the forward multiplied V with, after dropout, transposed into C (free once the dK GEMM
     // ahead in the stream has read it; Bs is free by now)
     if (fused) {
@@ -326,7 +353,7 @@ static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const f
         if (attn_p > 0.f && (rc = launch_dropout(P, nullptr, n, Bs, attn_p, key, site, pbase, s))) return rc;
         if ((rc = launch_transpose(attn_p > 0.f ? Bs : P, D.T, D.T, D.ld, D.probs.s1, C, D.ld, D.probs.s1, BH, s))) return rc;
     }
-    return launch_gemm_f32(head_gemm(D, C, D.probs, dao, D.merged, dqkv + 2 * d, D.qkv, D.hd, D.Tp, 0, D.Tp), s);
+    return head_product(D, HP_DV, C, dao, dqkv + 2 * d, abf, s);
 }
 
 static RowGroups row_groups_of(const std::vector<TrainGroup>& gs) {
@@ -381,6 +408,24 @@ int r4d_set_train_bf16(int32_t on) {
     return prev;
 }
 int r4d_get_train_bf16(void) { return g_train_bf16; }
+
+int r4d_set_train_attention_bf16(int32_t on) {
+    const int prev = g_train_attn_bf16;
+    g_train_attn_bf16 = on != 0;
+    return prev;
+}
+int r4d_get_train_attention_bf16(void) { return g_train_attn_bf16; }
+
+size_t r4d_train_attn_probs_ld(int32_t T) { return T > 0 ? (size_t)tpad128(T) : 0; }
+
+int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float* b_d, float* c_d, int32_t B, int32_t T, int32_t H,
+                                    int32_t d, void* stream) {
+    R4D_REQUIRE(which >= 0 && which < HP_COUNT, "train_attn_product_bf16: product %d not in 0 .. %d", (int)which, HP_COUNT - 1);
+    R4D_REQUIRE(a_d && b_d && c_d, "train_attn_product_bf16: null pointer");
+    R4D_REQUIRE(B >= 1 && T >= 1 && T <= 1024 && H >= 1 && d >= 1 && d % H == 0 && (d / H) % 16 == 0 && (long long)B * H <= 65535,
+                "train_attn_product_bf16: bad shape B=%d T=%d H=%d d=%d (head_dim %% 16 == 0, T <= 1024, B * H <= 65535 wanted)", B, T, H, d);
+    return launch_gemm_b1h(head_product_args(HeadDims(B, T, H, d), which, a_d, b_d, c_d), (hipStream_t)stream);
+}
 
 int r4d_conv1d_bf16_keep_f32(const float* x_d, const uint16_t* w_bf16_d, const float* bias_d, int32_t M, int32_t K, int32_t N,
                              float* pre_d, float* y_d, void* stream) {
@@ -467,7 +512,8 @@ size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, con
 static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int l, const TrainLayout& t,
                          const std::vector<TrainGroup>& gs, const RowGroups& R, const DropCtx& dc, float* ws,
                          const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const SpliceIn* sp, bool again,
-                         int bf16, hipStream_t s) {
+                         TrainModes md, hipStream_t s) {
+    const int bf16 = md.bf16;
     const int d = cfg->n_embd, H = cfg->n_head, M = (int)t.M;
     const r4d_gpt2_layer& Lw = w->layers[l];
     R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
@@ -493,7 +539,7 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
     if ((rc = conv1d(Wqkv, ln1, nullptr, M, EPI_NONE, qkv, s, fwd))) return rc;
     for (const TrainGroup& G : gs)
         if ((rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
-                           att + G.row0 * d, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
+                           att + G.row0 * d, md.attn_bf16, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
     float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
     if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
         if ((rc = conv1d(Wo, att, nullptr, M, EPI_NONE, branch, s, fwd))) return rc;
@@ -538,7 +584,7 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
     const int d = cfg->n_embd;
     const RowGroups R = row_groups_of(gs);
     for (int l = 0; l < cfg->n_layer; ++l)
-        if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, false, md.bf16, s))) return rc;
+        if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, false, md, s))) return rc;
     return launch_lnf_meanpool_groups(R, ws + t.x_out, w->ln_f_w, w->ln_f_b, d, cfg->ln_eps, out_hidden_d, out_meanpool_d,
                                       ws + t.pool_scratch, s);
 }
@@ -567,6 +613,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(!after_fwd || md.bf16 == g_last_fwd.modes.bf16,
                 "gpt2 train backward: this workspace was filled by a forward with train-bf16 %d, the current setting is %d",
                 g_last_fwd.modes.bf16, md.bf16);
+    R4D_REQUIRE(!after_fwd || md.attn_bf16 == g_last_fwd.modes.attn_bf16,
+                "gpt2 train backward: this workspace was filled by a forward with train-attention-bf16 %d, the current setting is %d",
+                g_last_fwd.modes.attn_bf16, md.attn_bf16);
     const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -599,7 +648,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         // holds the last layer's activations when this backward follows its forward directly: nothing to run again then.
         if (t.act_recompute && !(after_fwd && g_last_fwd.shared_layer == l)) {
             if (after_fwd) g_last_fwd.shared_layer = -1;
-            if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, true, md.bf16, s))) return rc;
+            if ((rc = layer_forward(cfg, w, l, t, gs, R, dc, ws, ids_d, Bs, Ts, sp, true, md, s))) return rc;
             if (after_fwd) g_last_fwd.shared_layer = l;
         }
         // ---- MLP: x_out = x_mid + gelu(ln_2(x_mid) Wfc + bfc) Wp + bp ;  dx holds d(x_out)
@@ -629,7 +678,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         if ((rc = data_grad(Wo, dbr, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                        // d(att), merged heads
         for (const TrainGroup& G : gs)                               // stored mode: the kept P, and no block A (pA does not exist)
             if ((rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
-                               dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, s,
+                               dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, md.attn_bf16, s,
                                dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
         if (!frozen && (rc = weight_grad(ln1, dqkv, Lg.c_attn_w, Lg.c_attn_b, d, 3 * d, M, d, 3 * d, xT, red, s, md.bf16))) return rc;
         if ((rc = data_grad(Wqkv, dqkv, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                     // d(ln_1 out)

@@ -364,7 +364,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Total optimization steps = {}".format(t_total))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION)".format(trainer.enc.precision))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too)".format(trainer.enc.precision))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

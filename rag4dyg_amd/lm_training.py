@@ -290,7 +290,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Gradient Accumulation steps = {}".format(gas))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION)".format(trainer.enc.precision))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too)".format(trainer.enc.precision))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

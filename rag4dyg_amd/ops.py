@@ -341,6 +341,29 @@ def weight_grad_bf16(x, dy, want_db=True, workspace=None):
     return dw, db
 
 
+TRAIN_ATTN_PRODUCTS = ("s", "pv", "dp", "dq", "dk", "dv")
+
+
+def train_attn_probs_ld(T):
+    """Row stride (floats) of a P-shaped block [B*H, T, ld] of the training steps: T rounded up to 128."""
+    return int(_lib.load().r4d_train_attn_probs_ld(int(T)))
+
+
+def train_attn_product_bf16(which, a, b, c, B, T, H, d):
+    """ONE of the six per-head attention products of the ``+attn`` training precisions (``r4d_train_attn_product_bf16_f32``;
+    ``which``: a name of ``TRAIN_ATTN_PRODUCTS`` or its index) over a [B, T] batch with H heads of d / H columns.  ``a`` / ``b`` /
+    ``c``: fp32 device tensors whose FIRST element is the (sequence 0, head 0) element of the operand in the step's layout (a Q / K / V
+    slice view of [B, T, 3d], merged heads [B, T, d], or a P-shaped block [B*H, T, ``train_attn_probs_ld(T)``]); ``c`` is written in
+    place (its [T, N] block per (sequence, head) only) and returned."""
+    idx = TRAIN_ATTN_PRODUCTS.index(which) if isinstance(which, str) else int(which)
+    for t, n in ((a, "a"), (b, "b"), (c, "c")):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise R4DError(f"train_attn_product_bf16: {n} must be an fp32 device tensor")
+    check(_lib.load().r4d_train_attn_product_bf16_f32(idx, a.data_ptr(), b.data_ptr(), c.data_ptr(), int(B), int(T), int(H), int(d),
+                                                      _stream()), "train_attn_product_bf16")
+    return c
+
+
 def set_attention_fused(mode):
     """-1 / None: auto by head_dim (default); True: fused flash-style kernel; False: three-launch GEMM form."""
     _lib.load().r4d_set_attention_fused(-1 if mode is None or mode == -1 else (2 if mode == 2 else int(bool(mode))))

@@ -131,7 +131,10 @@ _CONV1D = tuple((f, name) for f, name in _LAYER_PARAMS if f.endswith("_w") and n
 
 TRAIN_ATTENTION_MODES = {"stored": 0, "recompute": 1}
 TRAIN_ACTIVATION_MODES = {"stored": 0, "recompute": 1}
-TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1}
+# precision name -> the layer axis (r4d_set_train_bf16: the twelve Conv1D GEMMs of a block) ...
+TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1, "fp32+attn": 0, "bf16+attn": 1}
+# ... and the attention axis (r4d_set_train_attention_bf16: the six per-head products of a block); the two are independent
+TRAIN_ATTENTION_BF16 = {"fp32": 0, "bf16": 0, "fp32+attn": 1, "bf16+attn": 1}
 
 
 def _resolve(what, value, env, table, default):
@@ -162,7 +165,9 @@ def resolve_train_activations(activations=None):
 def resolve_train_precision(precision=None):
     """``"fp32"`` (the gemm mode's fp32-accurate arithmetic) or ``"bf16"`` (mixed precision: the twelve Conv1D GEMMs of every
     block on bf16 operands with fp32 accumulation -- NOT fp32-accurate; master weights, gradients, AdamW, LayerNorm, softmax,
-    GELU and the losses stay fp32; ``r4d_set_train_bf16``).  None -> the environment variable ``R4D_TRAIN_PRECISION``, ``fp32``
+    GELU and the losses stay fp32; ``r4d_set_train_bf16``); or either of them with ``+attn`` (``"fp32+attn"``, ``"bf16+attn"``):
+    the six per-head attention products of every block on bf16 operands as well (``r4d_set_train_attention_bf16``; an independent
+    axis, ``"bf16"`` alone keeps attention in exact f32).  None -> the environment variable ``R4D_TRAIN_PRECISION``, ``fp32``
     when it is unset or empty.  Anything else raises."""
     return _resolve("train precision", precision, "R4D_TRAIN_PRECISION", TRAIN_PRECISIONS, "fp32")
 
@@ -176,8 +181,8 @@ class EncoderTrainer:
     def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None):
         """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``);
         ``activations``: the same two words for the per-layer activations (:func:`resolve_train_activations`; None ->
-        ``R4D_TRAIN_ACTIVATIONS``); ``precision``: ``"fp32"`` / ``"bf16"`` (:func:`resolve_train_precision`; None ->
-        ``R4D_TRAIN_PRECISION``).  The trainer sets the three library switches before every size query and step call of its own, so
+        ``R4D_TRAIN_ACTIVATIONS``); ``precision``: ``"fp32"`` / ``"bf16"`` / ``"fp32+attn"`` / ``"bf16+attn"`` (:func:`resolve_train_precision`;
+        None -> ``R4D_TRAIN_PRECISION``).  The trainer sets the four library switches before every size query and step call of its own, so
         trainers of different modes can share a process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
@@ -220,8 +225,9 @@ class EncoderTrainer:
         # bf16x3 planes of the same weights: [3,out,in] for the forward GEMMs, [3,in,out] for the data gradients dx = dy . W^T
         # (ops.split3_planes; the bf16 matrix cores at fp32 accuracy); refreshed with the copies above
         self.use_s3 = ops.gemm_split3_enabled() and os.environ.get("R4D_TRAIN_SPLIT3", "1") != "0"
-        # precision "bf16" reads plane 0 of both sets in EVERY gemm mode: the planes are kept then even where use_s3 is false
-        self.use_planes = self.use_s3 or self.precision == "bf16"
+        # the bf16 LAYER axis reads plane 0 of both sets in EVERY gemm mode: the planes are kept then even where use_s3 is false
+        # (the attention axis rounds its operands on the fly and needs none)
+        self.use_planes = self.use_s3 or TRAIN_PRECISIONS[self.precision] == 1
         self._w3, self._w3t = {}, {}
         # f16x2 mode (round 5): f16x2 lines [out, in/32, 2, 32] of the same weights for the FORWARD GEMMs -- the fp16 matrix cores with
         # three products per fp32 product (csrc/gemm_h2.hip).  Every gradient GEMM keeps bf16x3: a gradient operand (1e-5 .. 1e-8) needs
@@ -292,6 +298,7 @@ class EncoderTrainer:
         _lib.check(_lib.load().r4d_set_train_attention(TRAIN_ATTENTION_MODES[self.attention]), "set_train_attention")
         _lib.check(_lib.load().r4d_set_train_activations(TRAIN_ACTIVATION_MODES[self.activations]), "set_train_activations")
         _lib.load().r4d_set_train_bf16(TRAIN_PRECISIONS[self.precision])                # (returns the previous setting)
+        _lib.load().r4d_set_train_attention_bf16(TRAIN_ATTENTION_BF16[self.precision])
 
     set_attention_mode = select_modes        # the earlier name, kept for scripts written against it
 
@@ -619,7 +626,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION)".format(trainer.precision))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too)".format(trainer.precision))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

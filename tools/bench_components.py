@@ -410,7 +410,7 @@ print(json.dumps({"rows": rows, "cols": len(lists), "seconds": el}))
 
 def training(attention=None, activations=None, precision=None):
     """(``--attention stored|recompute``: how the step keeps the attention probabilities, ``EncoderTrainer(attention=)``;
-    ``--activations stored|recompute``: the same for the per-layer activations; ``--precision fp32|bf16``: the arithmetic of the
+    ``--activations stored|recompute``: the same for the per-layer activations; ``--precision fp32|bf16|fp32+attn|bf16+attn``: the arithmetic of the
     blocks' Conv1D GEMMs, ``EncoderTrainer(precision=)``; the line reports the three modes, the trainer's
     workspace bytes and torch's peak allocated bytes.)  SURVEY 8f-4: one retriever training iteration (five forwards with saved activations, losses, encoder backward, clip,
     AdamW) at the UCI_13 script's shape (L4 H2 d512, batch 64: scripts/train_retriever/train_retriever_UCI_13.sh:8-12) on
@@ -525,7 +525,7 @@ def jaccard_cpu_all_cores():
 
 if __name__ == "__main__":
     for flag, words in (("--attention", ("stored", "recompute")), ("--activations", ("stored", "recompute")),
-                        ("--precision", ("fp32", "bf16"))):      # training entry only
+                        ("--precision", ("fp32", "bf16", "fp32+attn", "bf16+attn"))):      # training entry only
         if flag in sys.argv:
             i = sys.argv.index(flag)
             if sys.argv[i + 1] not in words:

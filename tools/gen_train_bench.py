@@ -5,7 +5,7 @@ configuration) and unfrozen (tied); the per-class breakdown of ``r4d_profile_*``
 frozen step in torch autograd, fp32 on the GPU (a plain-torch GPT-2 with fused causal attention, ``oracle.generator_ref``'s GCN).  Eval mode: no
 dropout launches in either.
 
-    python tools/gen_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,reddit] [--one-step uci13] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16]
+    python tools/gen_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,reddit] [--one-step uci13] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn]
 """
 import argparse
 import ctypes
@@ -123,7 +123,7 @@ def main():
                     help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
     ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
                     help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
-    ap.add_argument("--precision", default=None, choices=("fp32", "bf16"),
+    ap.add_argument("--precision", default=None, choices=("fp32", "bf16", "fp32+attn", "bf16+attn"),
                     help="arithmetic of the blocks' Conv1D GEMMs (default: R4D_TRAIN_PRECISION, else fp32)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")

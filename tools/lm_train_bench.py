@@ -6,7 +6,7 @@ spec, the head's share of the step (step minus forward_hidden + backward_hidden 
 adds the chunk rows, the bytes the materialised logits alone would take next to the step's workspace, and the time of ONE sweep of
 logits GEMMs over the chunks (the GEMM the chunked head runs twice) with its share of the step.
 
-    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16]
+    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn]
 """
 import argparse
 import ctypes
@@ -80,7 +80,7 @@ def main():
                     help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
     ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
                     help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
-    ap.add_argument("--precision", default=None, choices=("fp32", "bf16"),
+    ap.add_argument("--precision", default=None, choices=("fp32", "bf16", "fp32+attn", "bf16+attn"),
                     help="arithmetic of the blocks' Conv1D GEMMs (default: R4D_TRAIN_PRECISION, else fp32)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -158,7 +158,7 @@ def main():
                        ce_hbm_fraction=(ce_bytes / (ce["ms"] / 1e3) / HBM_BPS) if ce else None,
                        head_flop=head_flop, body_ms=body_ms, head_ms=ms - body_ms, head_share=(ms - body_ms) / ms,
                        head_tflops=head_flop / ((ms - body_ms) / 1e3) / 1e12, torch_head_ms=torch_ms, profiled_ms=total_prof,
-                       classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"]) for k, v in sorted(head_like.items(), key=lambda kv: -kv[1]["ms"])})
+                       classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"], work=v["work"]) for k, v in sorted(head_like.items(), key=lambda kv: -kv[1]["ms"])})
             if chunked:
                 sweep_ms = _time(_logits_sweep(tr, h), a.steps, a.warmup)
                 rec.update(chunk_rows=int(lib.r4d_lm_head_chunk_rows(ldV)), materialised_logits_bytes=N * ldV * 4,

@@ -79,6 +79,9 @@ def bench_class(k):
     m = re.match(r"gemm_h2p?_kernel<(\d+), (\d+), ", k)          # gemm_h2p_kernel (A as f16x2 lines, LDS-DMA): the same tile, the same bench.py class
     if m:
         return f"gemm_h2_{m.group(1)}x{m.group(2)}x32"
+    m = re.match(r"gemm_b1h_kernel<(false|true), ", k)         # the "+attn" training precisions' per-head products (B as [N,K]: true)
+    if m:
+        return "gemm_bf16h_nt" if m.group(1) == "true" else "gemm_bf16h_nn"
     if k.startswith("gemm_b1tn_kernel"):                     # the bf16 training precision's weight gradients
         return "gemm_bf16tn_32"
     if k.startswith("gemm_b1_kernel"):                       # plain bf16 (ops.set_encode_precision("bf16")): one class for both tiles

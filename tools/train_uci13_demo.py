@@ -57,8 +57,8 @@ def build_workdir(root):
 def main():
     if "--precision" in sys.argv:                               # fp32 | bf16: the trainer reads R4D_TRAIN_PRECISION
         i = sys.argv.index("--precision")
-        if sys.argv[i + 1] not in ("fp32", "bf16"):
-            sys.exit("--precision: fp32 or bf16")
+        if sys.argv[i + 1] not in ("fp32", "bf16", "fp32+attn", "bf16+attn"):
+            sys.exit("--precision: fp32, bf16, fp32+attn or bf16+attn")
         os.environ["R4D_TRAIN_PRECISION"] = sys.argv[i + 1]
         del sys.argv[i:i + 2]
     epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 8
