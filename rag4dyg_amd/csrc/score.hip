@@ -6,14 +6,10 @@
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
-#include "bf16x3.h"               // split3_pair: the split of the bf16x3 GEMMs, here per lane
-
 #ifndef SCAN_RING_P
 #define SCAN_RING_P 3   // ring slots per wavefront of the long-shard form (tuning aid: 4 = deeper ring, single-buffered partial tiles)
 #endif
-#ifndef SCAN_DBG
-#define SCAN_DBG 0   // tuning aid (tools/kc_ablate.sh score.hip SCAN_DBG n): bit 0 skips the MFMAs (and the split), bit 1 the score stores, bit 2 the cross-wave reduction (one-tile form), bit 3 writes s_memrealtime stamps (100 MHz) of workgroup phases over the score rows of queries >= 16 (tools/scan_timeline.py), bit 4 skips the bf16x3 split arithmetic only, bit 5 makes every query load read ONE line, bit 6 makes every pool load read 8 whole lines (timing of other access patterns)
-#endif
+#include "scan_common.h"          // SCAN_DBG and its hooks; the split, MFMA step, reduction, store and DMA staging the three forms share
 
 namespace r4d {
 
@@ -70,31 +66,16 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
 // v_mfma_f32_32x32x2_f32: 2.67x fewer matrix-pipe cycles per pool byte, which takes the scan OFF the fp32 ridge (the timeline
 // of tools/scan_timeline.py at a 12.5k-row shard: 4 of 11 us were exact-f32 MFMA on two tiles per CU).  The arithmetic of a
 // score does not depend on the tile, the workgroup or the shard the row falls in (shard merge == single GPU bit for bit).
-// The split is split3_pair of bf16x3.h, the one the GEMMs call.
-// a lane's 8 k of one bf16 MFMA step (two 16-byte pieces) -> three bf16x8 operands
-__device__ __forceinline__ void scan_split8(const float4& a, const float4& b, u32x4& h, u32x4& m, u32x4& l) {
-    unsigned hh[4], mm[4], ll[4];
-    split3_pair(a.x, a.y, hh[0], mm[0], ll[0]); split3_pair(a.z, a.w, hh[1], mm[1], ll[1]);
-    split3_pair(b.x, b.y, hh[2], mm[2], ll[2]); split3_pair(b.z, b.w, hh[3], mm[3], ll[3]);
-    h = u32x4{hh[0], hh[1], hh[2], hh[3]}; m = u32x4{mm[0], mm[1], mm[2], mm[3]}; l = u32x4{ll[0], ll[1], ll[2], ll[3]};
-}
-// the six products of one 16-k step, smallest terms first: lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (gemm_s3.hip)
-#define SCAN_STEP6(ACC_, Q_, BH_, BM_, BL_) do { SCAN_MFMA16(Q_[2], BH_, ACC_); SCAN_MFMA16(Q_[0], BL_, ACC_); SCAN_MFMA16(Q_[1], BM_, ACC_); \
-    SCAN_MFMA16(Q_[1], BH_, ACC_); SCAN_MFMA16(Q_[0], BM_, ACC_); SCAN_MFMA16(Q_[0], BH_, ACC_); } while (0)
-#define SCAN_MFMA16(A_, B_, ACC_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A_), __builtin_bit_cast(bf16x8, B_), ACC_, 0, 0, 0)
-
-template <int KW, int NG, bool TWO, bool S3>            // d == 32 * KW * NG; TWO: two tiles of a workgroup in flight; S3: bf16x3
+// The split is split3_pair of bf16x3.h, the one the GEMMs call; split, MFMA step, pinning, cross-wave reduction and score store
+// are the pieces of scan_common.h, one copy for the three forms.  (SCAN_DBG, the ablation and timeline builds: hooks of that header.)
+template <int KW, int NG, bool TWO, bool S3>          // d == 32 * KW * NG; TWO: two tiles of a workgroup in flight; S3: bf16x3
 __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_scan_ks_kernel(const float* __restrict__ qhat, const float* __restrict__ pool,
                                                               int Q, int N, int rpw, float* __restrict__ scores,
                                                               unsigned* __restrict__ zero_d, int nzero) {
     constexpr int D = 32 * KW * NG;
     constexpr int R = 16 / KW;                          // accumulator registers a wave finishes
-    __shared__ float red[KW > 1 ? 2 * KW * KW * 64 * R : 1];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int q0 = blockIdx.y * 32;
-    if (blockIdx.x == 0 && blockIdx.y == 0)             // ticket counters of the top-k launch that follows on this stream
-        for (int i = tid; i < nzero; i += 64 * KW) zero_d[i] = 0u;
+    __shared__ float red[KW > 1 ? 2 * SCAN_RED_TILE : 1];
+    SCAN_PROLOGUE();
     // rpw > 0: workgroup b owns the CONTIGUOUS rows [b rpw, (b+1) rpw) of the shard, walked in 32-row tiles (the last one
     // partial): rows, i.e. bytes, are dealt evenly -- a 12,500-row shard is 49 rows (100 KB) per CU instead of 391 whole
     // tiles over 256 CUs (two tiles on half of them, one on the rest).  rpw == 0 (long shards): the 32-row tiles are dealt
@@ -105,27 +86,15 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
     const int r1 = rpw > 0 ? min(N, r0 + rpw) : N;
     const int tstep = rpw > 0 ? 32 : 32 * G;                 // rows between consecutive tiles of this workgroup
     if (r0 >= N) return;
-#if SCAN_DBG & 8
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(scores + (long long)16 * N) + blockIdx.x * 16;
-    if (tid == 0) { stamps[0] = __builtin_amdgcn_s_memrealtime(); stamps[5] = __builtin_amdgcn_s_memtime(); stamps[10] = gridDim.x; }
-    unsigned long long* wst = reinterpret_cast<unsigned long long*>(scores + (long long)16 * N) + gridDim.x * 16 + (blockIdx.x * KW + w) * 8;   // per wavefront
-    if (lane == 0) wst[0] = __builtin_amdgcn_s_memrealtime();
-#endif
+    SCAN_STAMP_DECL();
     const int ntiles = rpw > 0 ? (r1 - r0 + 31) / 32 : ((N + 31) / 32 - (int)blockIdx.x + G - 1) / G;
     // k order: load u of lane half h of row j is the 16-byte piece 2u + h of the wave's 128-byte line g, so ONE load
     // instruction touches a whole 32-byte sector of each of its 32 rows; component c of that load is
     // k = 32 (g KW + w) + 8 u + 4 h + c on BOTH operands.
-#if SCAN_DBG & 64                                       // WRONG results: every load instruction reads 8 whole 128-byte lines (timing of the coalesced pattern)
-#define SCAN_TIDX(g, u) (8 * KW * (g) + (u) * 8 * (D / 4))
-    auto tile_ptr = [&](int tt) {
-        return reinterpret_cast<const float4*>(pool + (long long)min(r0 + tt * tstep + (lane >> 3), N - 25) * D) + (lane & 7) + 8 * w;
-    };
-#else
 #define SCAN_TIDX(g, u) (8 * KW * (g) + 2 * (u))
     auto tile_ptr = [&](int tt) {                       // rows past the shard are clamped (always valid); rows past r1 belong to the
         return reinterpret_cast<const float4*>(pool + (long long)min(r0 + tt * tstep + li, N - 1) * D) + lh + 8 * w;   // next workgroup: computed, not stored
     };
-#endif
     auto load_tile = [&](float4 (&bb)[NG][4], int tt) {
         const float4* __restrict__ p = tile_ptr(tt);
 #pragma unroll
@@ -142,7 +111,7 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
     float4 b1[TWO ? NG : 1][4];
     {
         const bool ok = q0 + li < Q;
-        const float4* src = reinterpret_cast<const float4*>(qhat + (long long)((SCAN_DBG & 32) ? 0 : min(q0 + li, Q - 1)) * D) + ((SCAN_DBG & 32) ? 0 : lh);   // bit 5: one line per query load (WRONG results)
+        const float4* src = reinterpret_cast<const float4*>(qhat + (long long)min(q0 + li, Q - 1) * D) + lh;
 #pragma unroll
         for (int g = 0; g < NG; ++g)
 #pragma unroll
@@ -155,46 +124,28 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
                 for (int u = 0; u < 4; ++u) b1[g][u] = p1[SCAN_TIDX(g, u)];
         }
         __builtin_amdgcn_sched_barrier(0);              // ... and the compiler does not sink them below the query split
-#if SCAN_DBG & 8
-        if (lane == 0) wst[1] = __builtin_amdgcn_s_memrealtime();
-        asm volatile("" :: "v"(qf[NG - 1][3].w));
-        if (lane == 0) wst[2] = __builtin_amdgcn_s_memrealtime();
-#endif
+        SCAN_WSTAMP(1);
+        SCAN_KEEP(qf[NG - 1][3].w);
+        SCAN_WSTAMP(2);
 #pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            if (!ok) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { qf[g][u].x = 0.f; qf[g][u].y = 0.f; qf[g][u].z = 0.f; qf[g][u].w = 0.f; }
-            }
-            if constexpr (S3) {
-                scan_split8(qf[g][0], qf[g][1], q3[g][0][0], q3[g][0][1], q3[g][0][2]);
-                scan_split8(qf[g][2], qf[g][3], q3[g][1][0], q3[g][1][1], q3[g][1][2]);
-            }
-        }
+        for (int g = 0; g < NG; ++g) SCAN_SPLIT_QUERIES(q3[g], qf[g], ok, S3);
     }
-#if SCAN_DBG & 8
-    if constexpr (S3) { asm volatile("" :: "v"(q3[NG - 1][1][2])); if (lane == 0) wst[3] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+    if constexpr (S3) { SCAN_KEEP(q3[NG - 1][1][2]); SCAN_WSTAMP(3); }
     // the MFMAs of one 128-byte line group of the staged rows
     auto mfma_group = [&](f32x16& acc, int g, const float4 (&b)[4]) {
-        if constexpr ((SCAN_DBG & 1) != 0) {
+        if constexpr (SCAN_NO_MFMA) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[u] += b[u].x + b[u].y + b[u].z + b[u].w;
         } else if constexpr (S3) {
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
                 u32x4 bh, bm, bl;
-                if constexpr ((SCAN_DBG & 16) != 0) {
+                if constexpr (SCAN_NO_SPLIT) {
                     bh = __builtin_bit_cast(u32x4, b[2 * st]); bm = __builtin_bit_cast(u32x4, b[2 * st + 1]); bl = bh ^ bm;
                 } else {
                     scan_split8(b[2 * st], b[2 * st + 1], bh, bm, bl);
                 }
-                SCAN_MFMA16(q3[g][st][2], bh, acc);                      // smallest terms first: lo.hi, hi.lo, mid.mid,
-                SCAN_MFMA16(q3[g][st][0], bl, acc);                      // mid.hi, hi.mid, hi.hi (gemm_s3.hip)
-                SCAN_MFMA16(q3[g][st][1], bm, acc);
-                SCAN_MFMA16(q3[g][st][1], bh, acc);
-                SCAN_MFMA16(q3[g][st][0], bm, acc);
-                SCAN_MFMA16(q3[g][st][0], bh, acc);
+                SCAN_STEP6(acc, q3[g][st], bh, bm, bl);
             }
         } else {
 #pragma unroll
@@ -222,50 +173,25 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
                 for (int u = 0; u < 4; ++u) bb[g][u] = pn[SCAN_TIDX(g, u)];
             }
         }
-#if SCAN_DBG & 8
-        if (tcur < 2) { asm volatile("" :: "v"(acc[0]), "v"(acc[15])); if (tid == 0) stamps[8 + 4 * tcur] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+        if (tcur < 2) { SCAN_KEEP(acc[0]); SCAN_KEEP(acc[15]); SCAN_STAMP(8 + 4 * tcur); }
         float fin[R];
-        if (KW > 1 && !(SCAN_DBG & 4)) {
-            // red[buf][src wave][dst wave][lane][R]: lane-contiguous vectors, conflict-free on both sides
-            float* base = red + buf * (KW * KW * 64 * R);
-#pragma unroll
-            for (int wd = 0; wd < KW; ++wd)
-#pragma unroll
-                for (int i = 0; i < R; ++i) base[((w * KW + wd) * 64 + lane) * R + i] = acc[wd * R + i];
+        if (KW > 1) {
+            float* base = red + buf * SCAN_RED_TILE;                     // double-buffered: ONE barrier per tile
+            SCAN_RED_WRITE(base, acc);
             __syncthreads();
-#pragma unroll
-            for (int i = 0; i < R; ++i) fin[i] = 0.f;
-#pragma unroll
-            for (int p = 0; p < KW; ++p)                                 // fixed order: deterministic sums
-#pragma unroll
-                for (int i = 0; i < R; ++i) fin[i] += base[((p * KW + w) * 64 + lane) * R + i];
+            SCAN_RED_SUM(fin, base);
             buf ^= 1;
         } else {
 #pragma unroll
             for (int i = 0; i < R; ++i) fin[i] = acc[w * R + i];
         }
-#if SCAN_DBG & 8
-        if (tcur < 2) { asm volatile("" :: "v"(fin[0])); if (tid == 0) stamps[9 + 4 * tcur] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+        if (tcur < 2) { SCAN_KEEP(fin[0]); SCAN_STAMP(9 + 4 * tcur); }
         const int row = r0 + tcur * tstep + li;
-        if (row < r1 && !(SCAN_DBG & 2)) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const int r = w * R + i;
-                const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (q < Q && (!(SCAN_DBG & 8) || q < 16)) scores[(long long)q * N + row] = (fin[i] + 1.0f) / 2.0f;
-            }
-        }
+        SCAN_STORE_ROW(fin, row, row < r1);
     };
-#if SCAN_DBG & 8
-    if (tid == 0) stamps[1] = __builtin_amdgcn_s_memrealtime();              // all loads issued
-    {   // wait for the first tile and the queries
-        float sink = qf[0][0].x + b0[NG - 1][3].w;
-        asm volatile("" :: "v"(sink));
-        if (tid == 0) stamps[2] = __builtin_amdgcn_s_memrealtime();          // first tile landed
-    }
-#endif
+    SCAN_STAMP(1);                                                           // all loads issued
+    SCAN_KEEP(qf[0][0].x + b0[NG - 1][3].w);                                 // wait for the first tile and the queries
+    SCAN_STAMP(2);                                                           // first tile landed
     if constexpr (TWO) {
         // short ranges (a shard of a few ten thousand rows: 2-3 tiles per workgroup): the second tile's loads go out together
         // with the first's -- ONE memory latency in front of the MFMAs instead of one per tile -- and the two tiles share ONE
@@ -274,11 +200,8 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
         for (int t = 0; t < ntiles; t += 2) {
             const bool has2 = t + 1 < ntiles;                             // workgroup-uniform
             f32x16 acc2[2];
-            if constexpr (S3 && !(SCAN_DBG & 17)) {
-                // The split of a step's pool operand (36 VALU instructions) is issued INSIDE the six MFMAs of the step before
-                // it, six per MFMA gap (sched_group_barrier): left to the compiler the stream is split, split, ..., MFMA x 6,
-                // and two wavefronts of a SIMD fall into lock step -- both splitting, then both multiplying -- so that the
-                // vector ALU and the matrix pipe take turns (timeline: 4,600 cycles per tile and SIMD = 48 x 32 + 704 x 4.2).
+            if constexpr (S3 && !SCAN_NO_MFMA && !SCAN_NO_SPLIT) {
+                // the split of a step's pool operand goes INSIDE the six MFMAs of the step before it (SCAN_PIN_SPLIT_IN_STEP)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { acc2[0][r] = 0.f; acc2[1][r] = 0.f; }
                 u32x4 ch, cm, cl;
@@ -290,14 +213,11 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
                     if (i + 1 < 2 * NG) scan_split8(b0[gn][un], b0[gn][un + 1], nh, nm, nl);
                     else scan_split8(b1[0][0], b1[0][1], nh, nm, nl);
                     SCAN_STEP6(acc2[0], q3[g][st], ch, cm, cl);
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 6, 0); }
+                    SCAN_PIN_SPLIT_IN_STEP();
                     ch = nh; cm = nm; cl = nl;
                 }
                 if (t + 2 < ntiles) load_tile(b0, t + 2);
-#if SCAN_DBG & 8
-                if (t == 0) { asm volatile("" :: "v"(acc2[0][0])); if (lane == 0) wst[4] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+                if (t == 0) { SCAN_KEEP(acc2[0][0]); SCAN_WSTAMP(4); }
                 if (has2) {
 #pragma unroll
                     for (int i = 0; i < 2 * NG; ++i) {
@@ -306,17 +226,13 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
                         if (i + 1 < 2 * NG) scan_split8(b1[gn][un], b1[gn][un + 1], nh, nm, nl);
                         SCAN_STEP6(acc2[1], q3[g][st], ch, cm, cl);
                         if (i + 1 < 2 * NG) {
-#pragma unroll
-                            for (int j = 0; j < 6; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 6, 0); }
+                            SCAN_PIN_SPLIT_IN_STEP();
                             ch = nh; cm = nm; cl = nl;
                         }
                     }
                     if (t + 3 < ntiles) load_tile(b1, t + 3);
                 }
-#if SCAN_DBG & 8
-                if (t == 0) { asm volatile("" :: "v"(acc2[0][0]), "v"(acc2[1][15])); if (tid == 0) { stamps[8] = __builtin_amdgcn_s_memrealtime(); stamps[12] = stamps[8]; }
-                              if (lane == 0) wst[5] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+                if (t == 0) { SCAN_KEEP(acc2[0][0]); SCAN_KEEP(acc2[1][15]); SCAN_STAMP(8); SCAN_STAMP_COPY(12, 8); SCAN_WSTAMP(5); }
             } else
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -335,55 +251,27 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
                         }
                     }
                 }
-#if SCAN_DBG & 8
-                if (t == 0) { asm volatile("" :: "v"(acc2[h][0]), "v"(acc2[h][15])); if (tid == 0) stamps[8 + 4 * h] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+                if (t == 0) { SCAN_KEEP(acc2[h][0]); SCAN_KEEP(acc2[h][15]); SCAN_STAMP(8 + 4 * h); }
             }
-            // red[tile h][src wave][dst wave][lane][R]; same fixed summation order as the one-tile form: identical bits
+            // red[tile h]: the two tiles share ONE barrier; same fixed summation order as the one-tile form: identical bits
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float* base = red + h * (KW * KW * 64 * R);
-#pragma unroll
-                for (int wd = 0; wd < KW; ++wd)
-#pragma unroll
-                    for (int i = 0; i < R; ++i) base[((w * KW + wd) * 64 + lane) * R + i] = acc2[h][wd * R + i];
-            }
+            for (int h = 0; h < 2; ++h) SCAN_RED_WRITE(red + h * SCAN_RED_TILE, acc2[h]);
             __syncthreads();
-#if SCAN_DBG & 8
-            if (t == 0 && tid == 0) { stamps[9] = __builtin_amdgcn_s_memrealtime(); stamps[13] = stamps[9]; }
-            if (t == 0 && lane == 0) wst[6] = __builtin_amdgcn_s_memrealtime();
-#endif
+            if (t == 0) { SCAN_STAMP(9); SCAN_STAMP_COPY(13, 9); SCAN_WSTAMP(6); }
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const float* base = red + h * (KW * KW * 64 * R);
                 float fin[R];
-#pragma unroll
-                for (int i = 0; i < R; ++i) fin[i] = 0.f;
-#pragma unroll
-                for (int p = 0; p < KW; ++p)
-#pragma unroll
-                    for (int i = 0; i < R; ++i) fin[i] += base[((p * KW + w) * 64 + lane) * R + i];
+                SCAN_RED_SUM(fin, red + h * SCAN_RED_TILE);
                 const int row = r0 + (t + h) * tstep + li;
-                if (row < r1 && (h == 0 || has2)) {
-#pragma unroll
-                    for (int i = 0; i < R; ++i) {
-                        const int r = w * R + i;
-                        const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                        if (q < Q && (!(SCAN_DBG & 8) || q < 16) && !(SCAN_DBG & 2)) scores[(long long)q * N + row] = (fin[i] + 1.0f) / 2.0f;
-                    }
-                }
+                SCAN_STORE_ROW(fin, row, row < r1 && (h == 0 || has2));
             }
             if (t + 2 < ntiles) __syncthreads();                          // the LDS buffers are reused by the next pair
         }
     } else {
         for (int t = 0; t < ntiles; ++t) do_tile(b0, t, t + 1 < ntiles ? t + 1 : -1);
     }
-#if SCAN_DBG & 8
-    if (tid == 0) stamps[7] = __builtin_amdgcn_s_memrealtime();              // all stores issued
-    if (lane == 0) wst[7] = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) { stamps[3] = __builtin_amdgcn_s_memrealtime(); stamps[6] = __builtin_amdgcn_s_memtime(); stamps[4] = (unsigned long long)__builtin_amdgcn_s_getreg(6164); }   // end; XCC id
-#endif
+    SCAN_STAMP_END();                                                        // all stores issued; end; XCC id
+#undef SCAN_TIDX
 }
 
 
@@ -407,24 +295,8 @@ __global__ __launch_bounds__(64 * KW, (KW == 4 && NG == 4) ? 3 : 1) void pool_sc
 //     not two whole tiles (the form above reads 64);
 //   * arithmetic: the same chunk -> MFMA-slot bijection, the same six products in the same order and the same reduction
 //     order as pool_scan_ks_kernel<.., S3 = true>: scores are bit-identical to the long-shard form (shard merge == one GPU).
-// one piece = four DMA instructions of 1 KB: global address = base + 32-bit lane offset + i KB, LDS address = M0 + i KB + 16 lane
-// (the instruction offset moves BOTH sides, so the lane offsets of instruction i are built i KB short); M0 is written in the
-// statement that uses it and restored (the compiler owns it)
-__device__ __forceinline__ void scan_glds_piece(const void* base, unsigned v0, unsigned v1, unsigned v2, unsigned v3, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %5\n\t"
-                 "global_load_lds_dwordx4 %2, %5 offset:1024\n\t"
-                 "global_load_lds_dwordx4 %3, %5 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %4, %5 offset:3072\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(base), "s"(lds_dst) : "memory");
-}
-template <int N_> __device__ __forceinline__ void scan_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N_) : "memory"); }
-__device__ __forceinline__ void scan_wait_vmcnt(int n) {                                   // n is a constant after unrolling
-    switch (n) { case 0: scan_wait_vm<0>(); break; case 4: scan_wait_vm<4>(); break; case 8: scan_wait_vm<8>(); break;
-                 default: scan_wait_vm<12>(); break; }
-}
+// The staging itself (lane offsets, piece issue, fragment read, counted wait) is the SCAN_DMA_* part of scan_common.h, shared
+// with pool_scan_ring_kernel.
 template <int N_> struct ScanInt { static constexpr int value = N_; };
 
 template <int KW, int NG>
@@ -435,52 +307,25 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
     constexpr int R = 16 / KW;
     constexpr int P = 4;                                  // ring slots of 4 KB per wavefront
     extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int q0 = blockIdx.y * 32;
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int i = tid; i < nzero; i += 64 * KW) zero_d[i] = 0u;
+    SCAN_PROLOGUE();
     const int r0 = blockIdx.x * rpw, r1 = min(N, r0 + rpw);              // rpw <= 64: one or two tiles
     if (r0 >= N) return;
-#if SCAN_DBG & 8
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(scores + (long long)16 * N) + blockIdx.x * 16;
-    unsigned long long* wst = reinterpret_cast<unsigned long long*>(scores + (long long)16 * N) + gridDim.x * 16 + (blockIdx.x * KW + w) * 8;
-    if (tid == 0) { stamps[0] = __builtin_amdgcn_s_memrealtime(); stamps[5] = __builtin_amdgcn_s_memtime(); stamps[10] = gridDim.x; }
-    if (lane == 0) wst[0] = __builtin_amdgcn_s_memrealtime();
-#define SCAN_WSTAMP(i) do { if (lane == 0) wst[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SCAN_WSTAMP(i) do { } while (0)
-#endif
-    unsigned char* ring = scan_lds + w * (P * 4096);
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ring);
-    // DMA sources: instruction i of a piece copies rows 8 i + lane / 8 of the piece, lane % 8 picking the (permuted) chunk:
-    // byte offsets from (pointer - 3 KB), instruction i's built i KB short (scan_glds_piece); rows past the share / the
-    // query block are clamped to its last row
-    unsigned voff[3][4];                                  // queries, tile 0, tile 1
-    {
-        const int c0 = (lane & 7) ^ (lane >> 4);          // chunk of instruction i: c0 ^ 4 (i & 1)   [= (lane & 7) ^ ((row >> 1) & 7)]
-        const int lrow = lane >> 3;
+    SCAN_STAMP_DECL();
+    SCAN_DMA_RING();
+    unsigned voff[3][4];                                  // queries, tile 0, tile 1; rows past the share are clamped to its last row
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned in_row = 128u * w + 16u * (c0 ^ (4 * (i & 1))) + 3072u - 1024u * i;
-            voff[0][i] = (unsigned)min(q0 + 8 * i + lrow, Q - 1) * (unsigned)(D * 4) + in_row;
-            voff[1][i] = (unsigned)min(r0 + 8 * i + lrow, r1 - 1) * (unsigned)(D * 4) + in_row;
-            voff[2][i] = (unsigned)min(r0 + 32 + 8 * i + lrow, r1 - 1) * (unsigned)(D * 4) + in_row;
-        }
+    for (int i = 0; i < 4; ++i) {
+        const unsigned in_row = SCAN_DMA_IN_ROW(i);
+        voff[0][i] = SCAN_DMA_OFFSET(in_row, i, q0, Q - 1);
+        voff[1][i] = SCAN_DMA_OFFSET(in_row, i, r0, r1 - 1);
+        voff[2][i] = SCAN_DMA_OFFSET(in_row, i, r0 + 32, r1 - 1);
     }
-    const char* qbase = reinterpret_cast<const char*>(qhat) - 3072;
-    const char* pbase = reinterpret_cast<const char*>(pool) - 3072;
+    SCAN_DMA_BASES();
     auto issue = [&](int p) {                             // piece p: kind p / NG, line group p % NG -> ring slot p % P
         const int kind = p / NG;
-        scan_glds_piece((kind == 0 ? qbase : pbase) + 128 * KW * (p % NG), voff[kind][0], voff[kind][1], voff[kind][2], voff[kind][3],
-                        ring_lds + (p % P) * 4096);
+        SCAN_DMA_ISSUE(kind == 0 ? qbase : pbase, p % NG, voff[kind], p % P);
     };
-    const int fsw = (li >> 1) & 7;
-    auto read_piece = [&](int p, float4 (&f)[4]) {        // lane (row li, half lh): chunks lh, 2 + lh, 4 + lh, 6 + lh of its row
-        const float4* base = reinterpret_cast<const float4*>(ring + (p % P) * 4096 + li * 128);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f[u] = base[(2 * u + lh) ^ fsw];
-    };
+    auto read_piece = [&](int p, float4 (&f)[4]) { SCAN_DMA_READ(f, p % P); };
     f32x16 acc2[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc2[0][r] = 0.f; acc2[1][r] = 0.f; }
@@ -503,17 +348,10 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
             read_piece(g, f);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (g + P < NP) issue(g + P);
-            if (!ok) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { f[u].x = 0.f; f[u].y = 0.f; f[u].z = 0.f; f[u].w = 0.f; }
-            }
-            scan_split8(f[0], f[1], q3[g][0][0], q3[g][0][1], q3[g][0][2]);
-            scan_split8(f[2], f[3], q3[g][1][0], q3[g][1][1], q3[g][1][2]);
+            SCAN_SPLIT_QUERIES(q3[g], f, ok, true);
         }
-#if SCAN_DBG & 8
-        asm volatile("" :: "v"(q3[NG - 1][1][2]));
+        SCAN_KEEP(q3[NG - 1][1][2]);
         SCAN_WSTAMP(3);
-#endif
         constexpr int NTP = NG * NT;                      // tile pieces; piece NG + tp = (tile tp / NG, line group tp % NG)
         float4 cur[4], nxt[4];
         scan_wait_vmcnt(SCAN_BEHIND(NG));
@@ -528,8 +366,7 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
             u32x4 nh, nm, nl;
             scan_split8(cur[2], cur[3], nh, nm, nl);                         // ... inside the six MFMAs of the step before it
             SCAN_STEP6(acc2[h], q3[g][0], ch, cm, cl);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 6, 0); }
+            SCAN_PIN_SPLIT_IN_STEP();
             if (tp + 1 < NTP) {
                 scan_wait_vmcnt(SCAN_BEHIND(p + 1));
                 read_piece(p + 1, nxt);
@@ -537,28 +374,22 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
             }
             SCAN_STEP6(acc2[h], q3[g][1], nh, nm, nl);
             if (tp + 1 < NTP) {
-                // the next piece's fragments are still on their way from LDS: two MFMAs first, then the split in the gaps
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { __builtin_amdgcn_sched_group_barrier(0x002, 9, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
+                SCAN_PIN_SPLIT_BEHIND_LDS_READ();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (p + 1 + P < NP) issue(p + 1 + P);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
             }
-#if SCAN_DBG & 8
-            if (tp == NG - 1) { asm volatile("" :: "v"(acc2[0][0])); SCAN_WSTAMP(4); }
-#endif
+            if (tp == NG - 1) { SCAN_KEEP(acc2[0][0]); SCAN_WSTAMP(4); }
         }
-#if SCAN_DBG & 8
-        asm volatile("" :: "v"(acc2[0][0]), "v"(acc2[1][0]));
+        SCAN_KEEP(acc2[0][0]); SCAN_KEEP(acc2[1][0]);
         SCAN_WSTAMP(5);
-#endif
 #undef SCAN_BEHIND
     };
     if (has2) body(ScanInt<2>{}); else body(ScanInt<1>{});
-    // cross-wave reduction: wavefront w's partial tiles go into ITS OWN ring (all of its pieces are consumed), 4 KB per tile,
-    // [dst wave][lane][R]; same fixed summation order as pool_scan_ks_kernel
+    // cross-wave reduction, NOT the [src][dst][lane][R] layout of SCAN_RED_WRITE / SCAN_RED_SUM: wavefront w's partial tiles go
+    // into ITS OWN ring (all of its pieces are consumed: no LDS beyond the ring), 4 KB per tile, [dst wave][lane][R]; same
+    // fixed summation order as the other forms
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         float* base = reinterpret_cast<float*>(ring + h * 4096);
@@ -581,23 +412,11 @@ __global__ __launch_bounds__(64 * KW, 1) void pool_scan_dma_kernel(const float* 
             for (int i = 0; i < R; ++i) fin[i] += base[(w * 64 + lane) * R + i];
         }
         const int row = r0 + 32 * h + li;
-        if (row < r1) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const int r = w * R + i;
-                const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (q < Q && (!(SCAN_DBG & 8) || q < 16) && !(SCAN_DBG & 2)) scores[(long long)q * N + row] = (fin[i] + 1.0f) / 2.0f;
-            }
-        }
+        SCAN_STORE_ROW(fin, row, row < r1);
     }
-#if SCAN_DBG & 8
-    SCAN_WSTAMP(7);
-    if (tid == 0) stamps[7] = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) { stamps[3] = __builtin_amdgcn_s_memrealtime(); stamps[6] = __builtin_amdgcn_s_memtime(); stamps[4] = (unsigned long long)__builtin_amdgcn_s_getreg(6164);
-                    stamps[1] = stamps[0]; stamps[2] = stamps[0]; stamps[8] = stamps[9] = stamps[12] = stamps[13] = stamps[3]; }
-#endif
-#undef SCAN_WSTAMP
+    SCAN_STAMP_END();
+    SCAN_STAMP_COPY(1, 0); SCAN_STAMP_COPY(2, 0);                             // no workgroup-level phases in this form
+    SCAN_STAMP_COPY(8, 3); SCAN_STAMP_COPY(9, 3); SCAN_STAMP_COPY(12, 3); SCAN_STAMP_COPY(13, 3);
 }
 
 
@@ -617,50 +436,37 @@ __global__ __launch_bounds__(64 * KW, KW == 8 ? 1 : 2) void pool_scan_ring_kerne
     constexpr int R = 16 / KW;
     constexpr int P = SCAN_RING_P;                        // 3: partial tiles double-buffered, one barrier per tile; 4: one buffer, two barriers
     extern __shared__ __attribute__((aligned(16))) unsigned char scan_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int q0 = blockIdx.y * 32;
-    if (blockIdx.x == 0 && blockIdx.y == 0)
-        for (int i = tid; i < nzero; i += 64 * KW) zero_d[i] = 0u;
+    SCAN_PROLOGUE();
     const int G = (int)gridDim.x;
     const int ntl = ((N + 31) / 32 - (int)blockIdx.x + G - 1) / G;       // tiles of this workgroup (>= 1: G <= tiles)
     const int NPt = NG * (1 + ntl);                                       // pieces: the queries', then NG per tile
-    unsigned char* ring = scan_lds + w * (P * 4096);
-    float* red = reinterpret_cast<float*>(scan_lds + KW * (P * 4096));
-    const unsigned ring_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ring);
-    const int c0 = (lane & 7) ^ (lane >> 4), lrow = lane >> 3;
+    SCAN_DMA_RING();
+    float* red = reinterpret_cast<float*>(scan_lds + KW * (P * 4096));   // behind the KW rings
     unsigned in_row[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) in_row[i] = 128u * w + 16u * (c0 ^ (4 * (i & 1))) + 3072u - 1024u * i;
-    const char* qbase = reinterpret_cast<const char*>(qhat) - 3072;
-    const char* pbase = reinterpret_cast<const char*>(pool) - 3072;
+    for (int i = 0; i < 4; ++i) in_row[i] = SCAN_DMA_IN_ROW(i);
+    SCAN_DMA_BASES();
     // issue side: piece `ik` goes to slot `islot`; its lane offsets are the queries' or those of tile (ik - NG) / NG
     int ik = 0, islot = 0, ig = 0, itile = (int)blockIdx.x;
     unsigned ivoff[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) ivoff[i] = (unsigned)min(q0 + 8 * i + lrow, Q - 1) * (unsigned)(D * 4) + in_row[i];
+    for (int i = 0; i < 4; ++i) ivoff[i] = SCAN_DMA_OFFSET(in_row[i], i, q0, Q - 1);
     auto issue_next = [&]() {                             // workgroup-uniform control flow
         if (ik >= NPt) return;
-        scan_glds_piece((ik < NG ? qbase : pbase) + 128 * KW * ig, ivoff[0], ivoff[1], ivoff[2], ivoff[3], ring_lds + islot * 4096);
+        SCAN_DMA_ISSUE(ik < NG ? qbase : pbase, ig, ivoff, islot);
         ++ik;
         islot = islot + 1 == P ? 0 : islot + 1;
         if (++ig == NG) {
             ig = 0;
             if (ik > NG) itile += G;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) ivoff[i] = (unsigned)min(itile * 32 + 8 * i + lrow, N - 1) * (unsigned)(D * 4) + in_row[i];
+            for (int i = 0; i < 4; ++i) ivoff[i] = SCAN_DMA_OFFSET(in_row[i], i, itile * 32, N - 1);
         }
     };
-    const int fsw = (li >> 1) & 7;
     int ck = 0, cslot = 0;                                // consume side
-    auto wait_piece = [&]() {                             // pieces issued behind piece ck: min(NPt, ck + P) - ck - 1
-        const int behind = min(NPt, ck + P) - ck - 1;
-        if (behind >= 3) scan_wait_vm<12>(); else if (behind == 2) scan_wait_vm<8>(); else if (behind == 1) scan_wait_vm<4>(); else scan_wait_vm<0>();
-    };
+    auto wait_piece = [&]() { scan_wait_vmcnt(4 * (min(NPt, ck + P) - ck - 1)); };      // pieces issued behind piece ck: min(NPt, ck + P) - ck - 1
     auto read_piece = [&](float4 (&f)[4]) {
-        const float4* base = reinterpret_cast<const float4*>(ring + cslot * 4096 + li * 128);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f[u] = base[(2 * u + lh) ^ fsw];
+        SCAN_DMA_READ(f, cslot);
         ++ck;
         cslot = cslot + 1 == P ? 0 : cslot + 1;
     };
@@ -676,12 +482,7 @@ __global__ __launch_bounds__(64 * KW, KW == 8 ? 1 : 2) void pool_scan_ring_kerne
             read_piece(f);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             issue_next();
-            if (!ok) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { f[u].x = 0.f; f[u].y = 0.f; f[u].z = 0.f; f[u].w = 0.f; }
-            }
-            scan_split8(f[0], f[1], q3[g][0][0], q3[g][0][1], q3[g][0][2]);
-            scan_split8(f[2], f[3], q3[g][1][0], q3[g][1][1], q3[g][1][2]);
+            SCAN_SPLIT_QUERIES(q3[g], f, ok, true);
         }
     }
     float4 cur[4], nxt[4];
@@ -699,59 +500,39 @@ __global__ __launch_bounds__(64 * KW, KW == 8 ? 1 : 2) void pool_scan_ring_kerne
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             u32x4 nh, nm, nl;
-#if SCAN_DBG & 1
-            acc[0] += cur[0].x + cur[1].y + cur[2].z + cur[3].w; nh = ch; nm = cm; nl = cl;
-#else
-            scan_split8(cur[2], cur[3], nh, nm, nl);
-            SCAN_STEP6(acc, q3[g][0], ch, cm, cl);
-#endif
-#pragma unroll
-            for (int jj = 0; jj < 6; ++jj) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 6, 0); }
+            if constexpr (SCAN_NO_MFMA) {
+                acc[0] += cur[0].x + cur[1].y + cur[2].z + cur[3].w; nh = ch; nm = cm; nl = cl;
+            } else {
+                scan_split8(cur[2], cur[3], nh, nm, nl);
+                SCAN_STEP6(acc, q3[g][0], ch, cm, cl);
+            }
+            SCAN_PIN_SPLIT_IN_STEP();
             if (ck < NPt) {                               // workgroup-uniform: false only at the very last piece
                 wait_piece();
                 read_piece(nxt);
-#if !(SCAN_DBG & 1)
-                scan_split8(nxt[0], nxt[1], ch, cm, cl);
-                SCAN_STEP6(acc, q3[g][1], nh, nm, nl);
-#endif
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) { __builtin_amdgcn_sched_group_barrier(0x002, 9, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
+                if constexpr (!SCAN_NO_MFMA) {
+                    scan_split8(nxt[0], nxt[1], ch, cm, cl);
+                    SCAN_STEP6(acc, q3[g][1], nh, nm, nl);
+                }
+                SCAN_PIN_SPLIT_BEHIND_LDS_READ();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 issue_next();
 #pragma unroll
                 for (int u = 0; u < 4; ++u) cur[u] = nxt[u];
             } else {
-#if !(SCAN_DBG & 1)
-                SCAN_STEP6(acc, q3[g][1], nh, nm, nl);
-#endif
+                if constexpr (!SCAN_NO_MFMA) SCAN_STEP6(acc, q3[g][1], nh, nm, nl);
             }
         }
-        // cross-wave reduction of the tile: red[buf][src wave][dst wave][lane][R], fixed summation order
-        float* base = red + (P == 3 ? buf : 0) * (KW * KW * 64 * R);
-#pragma unroll
-        for (int wd = 0; wd < KW; ++wd)
-#pragma unroll
-            for (int i = 0; i < R; ++i) base[((w * KW + wd) * 64 + lane) * R + i] = acc[wd * R + i];
+        // cross-wave reduction of the tile behind a raw barrier (see above)
+        float* base = red + (P == 3 ? buf : 0) * SCAN_RED_TILE;
+        SCAN_RED_WRITE(base, acc);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         float fin[R];
-#pragma unroll
-        for (int i = 0; i < R; ++i) fin[i] = 0.f;
-#pragma unroll
-        for (int p = 0; p < KW; ++p)
-#pragma unroll
-            for (int i = 0; i < R; ++i) fin[i] += base[((p * KW + w) * 64 + lane) * R + i];
+        SCAN_RED_SUM(fin, base);
         buf ^= 1;
         if (P != 3) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the one buffer is rewritten by the next tile
         const int row = ((int)blockIdx.x + j * G) * 32 + li;
-        if (row < N) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const int r = w * R + i;
-                const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (q < Q && !(SCAN_DBG & 2)) scores[(long long)q * N + row] = (fin[i] + 1.0f) / 2.0f;
-            }
-        }
+        SCAN_STORE_ROW(fin, row, row < N);
     }
 }
 
@@ -778,37 +559,45 @@ static int launch_scan_variant_p(const float* qhat, const float* pool, int Q, in
     // the register-staged forms (any dword-aligned pointer, 64-bit addressing) take the call
     const bool dma_ok = ((reinterpret_cast<uintptr_t>(qhat) | reinterpret_cast<uintptr_t>(pool)) & 15u) == 0 &&
                         (unsigned long long)N * (32ull * KW * NG) * 4ull < (1ull << 32) && (unsigned long long)Q * (32ull * KW * NG) * 4ull < (1ull << 32);
-    if (S3 && (dma & 1) && dma_ok && KW * NG >= 8 && ntiles <= 2 * 256) { // <= 64 rows per CU: the LDS-DMA staged form
-        R4D_BRANCH(SCAN_DMA);
-        constexpr int lds_bytes = KW * 4 * 4096;
-        static bool attr = false;
-        if (!attr) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pool_scan_dma_kernel<KW, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
-                set_error("pool_scan: cannot reserve %d bytes of LDS", lds_bytes);
-                return R4D_ERR_HIP;
+    if constexpr (KW * NG >= 8) {                         // the LDS-DMA forms exist for d >= 256 only (no instantiation below)
+        if (S3 && (dma & 1) && dma_ok && ntiles <= 2 * 256) { // <= 64 rows per CU: the LDS-DMA staged form
+            R4D_BRANCH(SCAN_DMA);
+            constexpr int lds_bytes = KW * 4 * 4096;
+            static bool attr = false;
+            if (!attr) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pool_scan_dma_kernel<KW, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
+                    set_error("pool_scan: cannot reserve %d bytes of LDS", lds_bytes);
+                    return R4D_ERR_HIP;
+                }
+                attr = true;
             }
-            attr = true;
+            const int rpw = max(8, cdiv(N, 256));            // rows dealt evenly over the CUs (a share below 32 rows leaves MFMA columns idle, not CUs)
+            hipLaunchKernelGGL((pool_scan_dma_kernel<KW, NG>), dim3(cdiv(N, rpw), cdiv(Q, 32)), dim3(64 * KW), lds_bytes, s, qhat, pool, Q, N,
+                               rpw, scores, zero_d, nzero);
+            R4D_CHECK_LAUNCH("pool_scan");
+            return R4D_OK;
         }
-        const int rpw = max(8, cdiv(N, 256));            // rows dealt evenly over the CUs (a share below 32 rows leaves MFMA columns idle, not CUs)
-        hipLaunchKernelGGL((pool_scan_dma_kernel<KW, NG>), dim3(cdiv(N, rpw), cdiv(Q, 32)), dim3(64 * KW), lds_bytes, s, qhat, pool, Q, N,
-                           rpw, scores, zero_d, nzero);
-    } else if (S3 && (dma & 2) && dma_ok && KW * NG >= 8) {   // long shards: the ring form
-        R4D_BRANCH(SCAN_RING);
-        constexpr int lds_bytes = KW * SCAN_RING_P * 4096 + (SCAN_RING_P == 3 ? 2 : 1) * KW * KW * 64 * (16 / KW) * 4;
-        static int ring_per_cu = 0;
-        if (ring_per_cu == 0) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pool_scan_ring_kernel<KW, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
-                set_error("pool_scan: cannot reserve %d bytes of LDS", lds_bytes);
-                return R4D_ERR_HIP;
+        if (S3 && (dma & 2) && dma_ok) {                      // long shards: the ring form
+            R4D_BRANCH(SCAN_RING);
+            constexpr int lds_bytes = KW * SCAN_RING_P * 4096 + (SCAN_RING_P == 3 ? 2 : 1) * KW * KW * 64 * (16 / KW) * 4;
+            static int ring_per_cu = 0;
+            if (ring_per_cu == 0) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pool_scan_ring_kernel<KW, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
+                    set_error("pool_scan: cannot reserve %d bytes of LDS", lds_bytes);
+                    return R4D_ERR_HIP;
+                }
+                int nb = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pool_scan_ring_kernel<KW, NG>, 64 * KW, lds_bytes) != hipSuccess || nb < 1) nb = 1;
+                ring_per_cu = nb;
             }
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pool_scan_ring_kernel<KW, NG>, 64 * KW, lds_bytes) != hipSuccess || nb < 1) nb = 1;
-            ring_per_cu = nb;
+            const int gx = max(1, min(ntiles, 256 * (force > 0 ? force : ring_per_cu)));
+            hipLaunchKernelGGL((pool_scan_ring_kernel<KW, NG>), dim3(gx, cdiv(Q, 32)), dim3(64 * KW), lds_bytes, s, qhat, pool, Q, N, scores,
+                               zero_d, nzero);
+            R4D_CHECK_LAUNCH("pool_scan");
+            return R4D_OK;
         }
-        const int gx = max(1, min(ntiles, 256 * (force > 0 ? force : ring_per_cu)));
-        hipLaunchKernelGGL((pool_scan_ring_kernel<KW, NG>), dim3(gx, cdiv(Q, 32)), dim3(64 * KW), lds_bytes, s, qhat, pool, Q, N, scores,
-                           zero_d, nzero);
-    } else if (shortr) {
+    }
+    if (shortr) {
         R4D_BRANCH(SCAN_SHORT);
         const int rpw = cdiv(N, 256);
         hipLaunchKernelGGL((pool_scan_ks_kernel<KW, NG, (KW * NG >= 8), S3>), dim3(cdiv(N, rpw), cdiv(Q, 32)), dim3(64 * KW), 0, s, qhat,

@@ -738,6 +738,39 @@ def test_short_shard_scan_forms_agree_bit_for_bit(dev, d):
             assert rel_err(S, ref) < 1e-5 and elementwise_err(S, ref) < 1, (d, Q)
 
 
+@pytest.mark.parametrize("d", [256, 512, 768])
+def test_small_share_scan_forms_agree_bit_for_bit(dev, d):
+    """The scan forms at their small-share paths, bit for bit (no tolerance): 16-byte-aligned operands take the LDS-DMA forms,
+    operands that are only dword-aligned the register-staged ones, and both must equal the first N columns of one long call.
+    N = 8: the minimum row share; 31, 32, 33: one tile in 8-row shares, the last share whole, partial or a single row; 300: 8-row
+    shares, the last one 4 rows; 8192: 32-row shares, one tile each; 8193: 33-row shares, a second tile of one row (and a last
+    workgroup with one tile only); 16385: ring form against the two-tile register form, last tile one row; 24608: ring form
+    against the round-robin register form.  (Top-10, or top-N at N = 8.)"""
+    from rag4dyg_amd import ops
+    g = torch.Generator().manual_seed(2000 + d)
+    n_long = 24608
+    ph = ops.normalize_rows((torch.randn(n_long, d, generator=g) + 0.1).to(dev))
+    for Q in (1, 33):
+        qh = ops.normalize_rows(torch.randn(Q, d, generator=g).to(dev))
+        bq = torch.empty(Q * d + 3, device=dev)
+        qu = bq[3:].view(Q, d)
+        qu.copy_(qh)
+        S_long = ops.score_topk(qh, ph, 10, want_scores=True)[2]
+        for n in (8, 31, 32, 33, 300, 8192, 8193, 16385, n_long):
+            k = min(10, n)
+            pa = ph[:n].contiguous()
+            buf = torch.empty(n * d + 1, device=dev)
+            pu = buf[1:].view(n, d)
+            pu.copy_(pa)
+            assert pa.data_ptr() % 16 == 0 and qh.data_ptr() % 16 == 0
+            assert pu.data_ptr() % 16 == 4 and qu.data_ptr() % 16 == 12
+            va, ia, Sa = ops.score_topk(qh, pa, k, index_offset=3, want_scores=True)
+            vu, iu, Su = ops.score_topk(qu, pu, k, index_offset=3, want_scores=True)
+            assert torch.equal(Sa, Su), (d, Q, n)
+            assert torch.equal(va, vu) and torch.equal(ia, iu), (d, Q, n)
+            assert torch.equal(Sa, S_long[:, :n]), (d, Q, n)
+
+
 def _rank_inputs(rows, n, seed, dtype):
     """Score rows full of ties and special values: quantised normals, duplicated columns, +-inf, -0.0, NaN."""
     rng = np.random.default_rng(seed)

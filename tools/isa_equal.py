@@ -8,6 +8,8 @@ differs) with build.py's FLAGS plus `--offload-device-only -S`, once from a chec
 tree, and compares the two assembly files kernel by kernel after
   - dropping lines that are only comments (and trailing comments),
   - dropping lines that name a __hip_cuid_ symbol (a hash of the source text),
+  - dropping the function number from local labels (.LBB12_3 -> .LBB_3, .Lfunc_end12 -> .Lfunc_end: it counts the functions in
+    front of this one, so it shifts in every kernel behind one that was added or removed),
   - treating the two source operands of the scalar bitwise operations in COMMUTATIVE as unordered.
 Everything else -- instructions, register / spill counts, LDS size, kernel descriptors, metadata -- must be equal.  Prints the
 first differing lines per kernel; exit status 1 if anything differs.  `--work DIR` keeps the assembly there and reuses the
@@ -26,6 +28,8 @@ from rag4dyg_amd.build import FLAGS, HIPCC  # noqa: E402
 
 CSRC = "rag4dyg_amd/csrc"
 COMMUTATIVE = ("s_and_b64", "s_or_b64", "s_and_b32", "s_or_b32")
+_LABEL = re.compile(r"\.LBB\d+_(\d+)")       # .LBB<function number>_<block>: the number shifts when a kernel in front is added or removed
+_FUNC_END = re.compile(r"\.Lfunc_end\d+")
 _COMM = re.compile(r"^(\s*(?:%s)\s+)([^,]+),\s*([^,]+),\s*([^,]+)$" % "|".join(COMMUTATIVE))
 
 
@@ -35,6 +39,7 @@ def normalise(text):
         ln = ln.split(";", 1)[0].rstrip()
         if not ln.strip() or "__hip_cuid_" in ln:
             continue
+        ln = _FUNC_END.sub(".Lfunc_end", _LABEL.sub(r".LBB_\1", ln))
         m = _COMM.match(ln)
         if m:
             a, b = sorted((m.group(3).strip(), m.group(4).strip()))
@@ -49,7 +54,11 @@ def sections(lines):
     for ln in lines:
         m = re.match(r"\s*\.globl\s+(\S+)", ln)
         if m:
-            name = m.group(1)
+            prev, name = secs[name], m.group(1)
+            lead = []                             # the .section / .protected lines in front of a .globl belong to its kernel
+            while prev and prev[-1].split()[0] in (".section", ".protected", ".weak", ".text"):
+                lead.insert(0, prev.pop())
+            secs.setdefault(name, []).extend(lead)
         elif ln.strip().startswith(".amdgpu_metadata"):
             name = "<metadata>"
         secs.setdefault(name, []).append(ln)
