@@ -557,8 +557,9 @@ int r4d_get_train_activations(void);
  *   data gradient  dx = RN(dy) . RN(W)^T                     plane 0 of *_w3t (RN(W) as [in][out])
  *   weight grad.   dW = RN(x)^T . RN(dy),  db = column sums of the UNROUNDED dy
  * Master weights, gradients, the optimizer, LayerNorm, softmax, GELU, the losses, the embedding scatter and every accumulator stay
- * fp32; the attention GEMMs stay exact f32 (their own switch: r4d_set_train_attention_bf16 below); the LM head's three GEMMs, r4d_weight_grad_f32, the GCN projection of the RAG step
- * and every encoder / decode entry do not read the switch.  A layer GEMM is switched in EVERY gemm mode (f32 included) whenever
+ * fp32; the attention GEMMs stay exact f32 (their own switch: r4d_set_train_attention_bf16 below); the LM head's three GEMMs
+ * read a switch of their own (r4d_set_train_head_bf16 below) and not this one; r4d_weight_grad_f32, the GCN projection of the RAG step
+ * and every encoder / decode entry read none of the three.  A layer GEMM is switched in EVERY gemm mode (f32 included) whenever
  * the layer carries the plane and the shape is supported (K % 32 == 0; weight gradient: in % 128 == 0, out % 256 == 0, rows >=
  * 32); anything else keeps the gemm mode's kernel.  Only plane 0 of the plane sets is read by the switched GEMMs.
  * r4d_set_train_bf16(on != 0) returns the previous setting; default 0.  Read once by the three workspace queries and by every
@@ -613,6 +614,29 @@ int r4d_get_train_attention_bf16(void);
 size_t r4d_train_attn_probs_ld(int32_t T);
 int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float* b_d, float* c_d, int32_t B, int32_t T, int32_t H,
                                     int32_t d, void* stream);
+
+/* The LM head of the training steps on plain bf16 operands (process-wide; additive ABI v6 entries; csrc/lm_head.hip on
+ * csrc/gemm_b1.hip and csrc/gemm_b1tn.hip).  A third, INDEPENDENT axis beside r4d_set_train_bf16 and r4d_set_train_attention_bf16: it
+ * neither reads nor sets them, and they do not read it.  NOT fp32-accurate: while on, both fp32 operands of the head's three GEMMs
+ * are rounded to bf16 (round to nearest even) where they are staged and multiplied ONCE on v_mfma_f32_32x32x16_bf16 with fp32
+ * accumulation in a fixed order, per vocabulary chunk k of the r4d_lm_head operand -- rows [c0, c0 + Ck) of wte_pad; one chunk when ldV <= 15872:
+ *   logits_k             = RN(h) . RN(wte_k)^T           plane 0 of the chunk's w3  (RN(wte_k) as [Ck][d])
+ *   dh (+)=                RN(dlogits_k) . RN(wte_k)     plane 0 of the chunk's w3t (RN(wte_k) as [d][Ck]); chunks added in ascending order
+ *   dwte[c0 : c0 + Ck]   = RN(dlogits_k)^T . RN(h)       no plane: both operands are rounded on the fly
+ * The logits and their gradient in memory, the cross entropy, dh, dwte, the tied add into grads->wte and the master weights stay
+ * fp32.  Only plane 0 of w3 / w3t is read, in the chunk layout r4d_lm_head describes; the planes are used in EVERY gemm mode (exact
+ * f32 included) while the switch is on, and change no route while it is off.  Each product falls back on its own to the gemm mode's
+ * kernel ("anything else keeps the gemm mode's kernel"): logits without w3 or with d % 32 != 0; dh without w3t or with B*T * Ck >= 2^29;
+ * dwte with d % 256 != 0, fewer than 32 rows, or (B*T + 64) * Ck >= 2^29.  Both sweeps of the chunked head form a chunk's logits by the
+ * same launch, so the gradient comes from the logits the statistics came from; no float atomics: the same bits on every launch.
+ * A loss-only step call (grads == NULL && d_fused_d == NULL, the evaluation loss) reads the switch like any other: its loss equals
+ * the training call's on the same inputs bit for bit, and differs from the loss with the switch off.
+ * r4d_set_train_head_bf16(on != 0) returns the previous setting; default 0.  Read once at the top of r4d_gpt2_lm_train_step_f32,
+ * r4d_rag_train_step_f32 and r4d_lm_head_train_f32; the workspace sizes do NOT depend on it (gemm_b1tn cuts its slices to the room
+ * the gemm mode's weight gradient is given), so the size queries do not read it.  The retriever step has no LM head and does not read
+ * it; nothing outside the training steps reads it (r4d_lm_logits_f32, the encoder and the decode step included). */
+int r4d_set_train_head_bf16(int32_t on);
+int r4d_get_train_head_bf16(void);
 
 /* Scratch of one step: the activations the backward pass needs (16 * rows * d floats per layer + the attention
  * probabilities in stored mode) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */
@@ -683,7 +707,8 @@ typedef struct {
 } r4d_lm_head;
 /* One SimpleDyG training step on one right-padded id batch ids_d int64 [B, T] (labels == inputs): forward_hidden -> logits (the
  * forward GEMM family of the current r4d_set_gemm_split3 mode) -> r4d_lm_ce_f32 -> dh = dlogits . wte (bf16x3 like every data
- * gradient) and dwte_head = dlogits^T . h (the weight-gradient GEMM) -> backward_hidden.  grads->wte = embedding scatter +
+ * gradient) and dwte_head = dlogits^T . h (the weight-gradient GEMM) -> backward_hidden (the three head GEMMs on plain bf16 under
+ * r4d_set_train_head_bf16).  grads->wte = embedding scatter +
  * dwte_head, added in that fixed order.  loss_d f32[1] stays on the device.  grad_scale scales every gradient (1 / accumulation
  * steps), not the loss.
  * ldV > 15872: the logits exist one vocabulary chunk [B*T, C] at a time (r4d_lm_head above): a first sweep over the chunks forms
@@ -693,6 +718,19 @@ size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, 
 int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                                const r4d_lm_head* head, const int64_t* ids_d, int32_t B, int32_t T, float grad_scale, float* loss_d,
                                const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream);
+/* The head of the two steps alone, for per-op tests and tools: exactly the call they make, in the current r4d_set_gemm_split3 mode and
+ * r4d_set_train_head_bf16 setting.  h_d f32 [N, d] (N = B * T rows: the ln_f output); labels_src_d int64 [N]: the label of row r is
+ * labels_src_d[r + 1] within a sequence of T rows (the last row of a sequence has none; -100 is not counted), as in r4d_lm_ce_f32.
+ * loss_d f32[1] <- the mean over the counted rows; dh_d (nullable) f32 [N, d] <- grad_scale * dLoss/dh; dwte_d (nullable) f32
+ * [ldV, d] <- grad_scale * dlogits^T . h (rows [V, ldV) exact zeros).  dh_d == dwte_d == NULL: loss only, the same loss bits.
+ * ldV % 128 == 0, ldV >= V, d % 4 == 0, N % T == 0; N * r4d_lm_head_chunk_rows(ldV), ldV * d and N * d below 2^31; every pointer
+ * 16-byte aligned.  The workspace size depends on neither switch.  On return the workspace BEGINS with the last chunk's dlogits f32
+ * [N, Ck] (the whole [N, ldV] gradient of the logits when ldV <= 15872; after a loss-only call of the chunked head: that chunk's
+ * logits), for tests that want the device's own operand of dh and dwte. */
+size_t r4d_lm_head_train_workspace_bytes(int32_t N, int32_t d, int32_t ldV);
+int r4d_lm_head_train_f32(const float* h_d /* [N,d] */, int32_t N, int32_t V, int32_t d, const r4d_lm_head* head,
+                          const int64_t* labels_src_d, int32_t T, float grad_scale, float* loss_d, float* dh_d /* nullable */,
+                          float* dwte_d /* nullable, [ldV,d] */, void* workspace_d, size_t workspace_bytes, void* stream);
 /* ------------------------------------------------------------------------------------------------
  * RAG generator training (train/train_generator.py, utils/model.py:105-224; csrc/rag_train.hip).  One step on a SPLICED batch:
  * aug_ids_d int64 [B, Ta] holds the token ids with -100 at the r fused positions 2 .. 2 + r - 1 of every sequence (Ta = T + r);
@@ -790,7 +828,9 @@ int r4d_dispatch_reset(void);
  *          5 weight gradient dW[K, N] = x[M, K]^T . dy[M, N] (dense rows)
  *   have   what the caller carries of the weight: bit 0 the [N, K] copy wT, 1 the planes w3, 2 the planes w3t, 3 the planes h2,
  *          4 (kind 1) the decode step's split-K scratch, i.e. batch <= 32
- *   bf16   the kind's precision switch: r4d_set_encode_bf16 (kind 0), r4d_set_train_bf16 (kinds 2, 3, 5); ignored otherwise
+ *   bf16   the kind's precision switch: r4d_set_encode_bf16 (kind 0), r4d_set_train_bf16 (kinds 2, 3, 5); ignored otherwise.
+ *          2 (kinds 2, 4, 5): the LM head under r4d_set_train_head_bf16 -- its logits (N = a vocabulary chunk), its dh (kind 4 then
+ *          takes plane 0 of w3t), its dwte (K = the chunk, N = d)
  * Returns a route id, or -1 for an unknown kind or M, K or N <= 0; r4d_conv1d_route_name gives its name ("unknown" outside the table). */
 int32_t r4d_conv1d_route(int32_t kind, int32_t M, int32_t K, int32_t N, int32_t epilogue, uint32_t have, int32_t bf16);
 const char* r4d_conv1d_route_name(int32_t route);

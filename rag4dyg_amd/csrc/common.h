@@ -87,7 +87,8 @@ struct ProfScope {
     X(ARGSORT_ONE, "argsort:one chunk") X(ARGSORT_MULTI, "argsort:chunk sort + rank scatter")                              \
     X(B1_128x256, "tuning:encode_bf16:128x256x32") X(B1_128x128, "tuning:encode_bf16:128x128x32")                           \
     X(TB_FWD, "tuning:train_bf16:fwd") X(TB_DGRAD, "tuning:train_bf16:dgrad") X(TB_WGRAD, "tuning:train_bf16:wgrad") X(TB_WGRAD_FALLBACK, "tuning:train_bf16:wgrad_fallback") \
-    X(TBA_NT, "tuning:train_bf16_attn:nt") X(TBA_NN, "tuning:train_bf16_attn:nn")
+    X(TBA_NT, "tuning:train_bf16_attn:nt") X(TBA_NN, "tuning:train_bf16_attn:nn") \
+    X(TBH_LOGITS, "tuning:train_head_bf16:logits") X(TBH_DGRAD, "tuning:train_head_bf16:dgrad") X(TBH_WGRAD, "tuning:train_head_bf16:wgrad") X(TBH_WGRAD_FALLBACK, "tuning:train_head_bf16:wgrad_fallback")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -239,6 +240,11 @@ static inline int emb_lg_rows(long long table_rows) {
 int launch_embedding_fix_to_f32(const unsigned long long* acc, long long n, long long table_rows, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------ train.hip (the training forward / backward, shared with lm_head.hip)
+// The process-wide training switches as a value (r4d_set_train_attention, _activations, _bf16, _attention_bf16, _head_bf16): every
+// entry point reads them ONCE, through train_modes(), and hands the value down; nothing below an entry point looks at a global.
+// head_bf16 is the LM head's alone (lm_head.hip): the transformer's forward and backward do not look at it.
+struct TrainModes { int attention, activations, bf16, attn_bf16, head_bf16; };
+TrainModes train_modes();
 size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts);
 // output: EITHER out_meanpool_d [sum B, d] OR out_hidden_d [rows, d] (the ln_f output); the backward takes the matching gradient
 // `sp` (nullable, one batch only): a SPLICED input (RAG generator): ids_d[0] holds -100 at the positions 2 .. 2 + r - 1, whose
@@ -256,10 +262,11 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
                         hipStream_t s, const SpliceIn* sp = nullptr, float* d_fused = nullptr);
 // dx[M, W.in] = epilogue(dy[M, W.out] . W^T) on the kernel dgrad_route names (train.hip): optional residual (dx = resid + ...),
-// optional fused gelu_new' (dx = (...) * gelu_new'(gelu_pre); the planes routes only)
+// optional fused gelu_new' (dx = (...) * gelu_new'(gelu_pre); the planes routes only).  `bf16`: TrainBf16
 int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* resid, const float* gelu_pre, hipStream_t s, int bf16 = 0);
 // dW[I,J] = x[M,I]^T . dy[M,J] on the kernel wgrad_route names, db (nullable) [J] = column sums of dy (train.hip).  `part`: room for
-// the slices' partials (gemm_tn_scratch_floats(I, J, M) floats); `red`: colsum_scratch_floats(M, J) floats (with db only)
+// the slices' partials (gemm_tn_scratch_floats(I, J, M) floats); `red`: colsum_scratch_floats(M, J) floats (with db only).
+// `bf16`: TrainBf16
 int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part, float* red,
                 hipStream_t s, int bf16 = 0);
 int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, const float* wte, const float* wpe, int vocab, int B,
@@ -273,7 +280,7 @@ LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV);
 int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                     const r4d_lm_head* head, int head_mode, float* head_grad, const int64_t* ids_d, const SpliceIn* sp, int B, int T,
                     float gscale, float* loss, float* d_fused, float* hidden_out, const r4d_train_dropout* dropout, void* workspace_d,
-                    size_t workspace_bytes, hipStream_t s);
+                    size_t workspace_bytes, int head_bf16, hipStream_t s);
 
 // ------------------------------------------------------------------ topk.hip
 // rows x n values -> rows x k best (value, global index), canonical order; `counters_zeroed`: the caller already cleared

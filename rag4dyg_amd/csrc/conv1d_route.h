@@ -83,13 +83,16 @@ static inline const char* gemm_route_name(int route) {
                                                    "wgrad_b1tn", "wgrad_s3tn", "wgrad_f32tn"};
     return route >= 0 && route < ROUTE_COUNT ? names[route] : "unknown";
 }
-// Who asks for plain bf16: the encoder calls (r4d_set_encode_bf16) allow it up to EPI_RESIDUAL only, the training forward any epilogue
-enum Bf16Use { BF16_OFF = 0, BF16_ENCODE = 1, BF16_TRAIN = 2 };
+// Who asks for plain bf16: the encoder calls (r4d_set_encode_bf16) allow it up to EPI_RESIDUAL only, the training forward any
+// epilogue; the LM head's logits (r4d_set_train_head_bf16) take the training forward's route and count under their own branch
+enum Bf16Use { BF16_OFF = 0, BF16_ENCODE = 1, BF16_TRAIN = 2, BF16_TRAIN_HEAD = 3 };
+// The `bf16` argument of the two gradient routes: the layers' switch (r4d_set_train_bf16) or the LM head's (r4d_set_train_head_bf16)
+enum TrainBf16 { TRAIN_BF16_OFF = 0, TRAIN_BF16_LAYERS = 1, TRAIN_BF16_HEAD = 2 };
 
 // y = epilogue(x[M, in] . W + b).  `skinny`: the caller has the decode step's split-K scratch.  In order:
 static inline GemmRoute conv1d_route(const Conv1DW& W, int M, int epilogue, bool skinny, int bf16) {
     const int K = W.in, N = W.out;
-    if (bf16 && (bf16 == BF16_TRAIN || epilogue <= EPI_RESIDUAL) && W.w3 && gemm_b1_supported(M, K, N)) return ROUTE_B1;   // plane 0 of w3, one bf16 MFMA per k-step
+    if (bf16 && (bf16 >= BF16_TRAIN || epilogue <= EPI_RESIDUAL) && W.w3 && gemm_b1_supported(M, K, N)) return ROUTE_B1;   // plane 0 of w3, one bf16 MFMA per k-step
     if (skinny && W.wT && gemm_skinny_supported(M, K, N)) return ROUTE_SKINNY;          // decode step: a weight stream, not a tiled GEMM
     // f16x2 planes present and selected: fp16 matrix cores, three products per fp32 product (gemm_h2.hip), for the epilogues it has.
     // NOT gated on M, like the bf16x3 route: a row's result must not depend on how many other rows share the call
@@ -105,10 +108,11 @@ static inline bool conv1d_fuses_gelu_keep(const Conv1DW& W, int M, int bf16) {
     return r == ROUTE_B1 || r == ROUTE_S3 || (r == ROUTE_H2 && W.w3 && gemm_s3_supported(M, W.in, W.out));
 }
 // dx[M, in] = dy[M, out] . W^T.  A Conv1D reads w [in, out] as the k-contiguous operand (b_trans = 1); the LM head (no `w`) reads
-// its table [out, in] as a row-major one (b_trans = 0) and never takes plain bf16.  The data gradients stay on bf16x3 in EVERY
+// its table [out, in] as a row-major one (b_trans = 0) and never takes the LAYERS' plain bf16: only its own switch
+// (bf16 == TRAIN_BF16_HEAD) sends it to plane 0 of its w3t.  The data gradients stay on bf16x3 in EVERY
 // split mode: their A operand is a gradient, which needs fp32's exponent range
 static inline GemmRoute dgrad_route(const Conv1DW& W, int M, int bf16) {
-    if (bf16 && W.w && W.w3t && gemm_b1_supported(M, W.out, W.in)) return ROUTE_DGRAD_B1;
+    if (bf16 && (W.w || bf16 == TRAIN_BF16_HEAD) && W.w3t && gemm_b1_supported(M, W.out, W.in)) return ROUTE_DGRAD_B1;
     if (W.w3t && g_gemm_split3 && gemm_s3_supported(M, W.out, W.in)) return ROUTE_DGRAD_S3;
     return ROUTE_DGRAD_F32;
 }
@@ -120,7 +124,9 @@ static inline GemmRoute wgrad_route(int I, int J, int M, int lda, int ldb, int b
 }
 
 // The query behind r4d_conv1d_route (include/r4d.h): kind 0 encode, 1 decode, 2 train forward, 3 dgrad Conv1D, 4 dgrad head,
-// 5 wgrad (M token rows, dW [K, N]); `have` bits: wT, w3, w3t, h2, skinny scratch.  -1 for an unknown kind or an empty shape
+// 5 wgrad (M token rows, dW [K, N]); `have` bits: wT, w3, w3t, h2, skinny scratch.  -1 for an unknown kind or an empty shape.
+// bf16 == 2 (TRAIN_BF16_HEAD) asks as the LM head under r4d_set_train_head_bf16: kind 2 its logits (N = a vocabulary chunk), kind 4
+// its dh (N = the chunk), kind 5 its dwte (K = the chunk, N = d)
 static inline int conv1d_route_query(int kind, int M, int K, int N, int epilogue, unsigned have, int bf16) {
     if (M <= 0 || K <= 0 || N <= 0) return -1;
     static const float f = 0.f;
@@ -130,7 +136,7 @@ static inline int conv1d_route_query(int kind, int M, int K, int N, int epilogue
     switch (kind) {
         case 0: return conv1d_route(W, M, epilogue, false, bf16 ? BF16_ENCODE : BF16_OFF);
         case 1: return conv1d_route(conv1d_w_decode(W), M, epilogue, (have & 16u) != 0, BF16_OFF);
-        case 2: return conv1d_route(W, M, epilogue, false, bf16 ? BF16_TRAIN : BF16_OFF);
+        case 2: return conv1d_route(W, M, epilogue, false, bf16 == TRAIN_BF16_HEAD ? BF16_TRAIN_HEAD : bf16 ? BF16_TRAIN : BF16_OFF);
         case 3: case 4: return dgrad_route(W, M, bf16);
         case 5: return wgrad_route(K, N, M, K, N, bf16);
         default: return -1;

@@ -25,6 +25,7 @@ int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epil
     switch (route) {
         case ROUTE_B1:
             if (opts.bf16 == BF16_TRAIN) R4D_BRANCH(TB_FWD);
+            else if (opts.bf16 == BF16_TRAIN_HEAD) R4D_BRANCH(TBH_LOGITS);
             return launch_gemm_b1(s3_args(x, W.w3, W.b, resid, M, K, N, epilogue, y), s);
         case ROUTE_SKINNY:
             return launch_gemm_skinny(x, W.wT, W.b, resid, M, K, N, epilogue, y, opts.skinny_scratch, s, nullptr, nullptr, 0.f,

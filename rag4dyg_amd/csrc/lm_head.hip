@@ -18,6 +18,16 @@
 // row's running (max, sum of exponentials, label logit) -- an online softmax -- and a second sweep forms each chunk's logits again
 // (the same launch on the same bits), turns them into their gradient and feeds the two gradient GEMMs.  Scratch does not grow
 // with V; one extra logits GEMM is the price.
+//
+// r4d_set_train_head_bf16 (`hb` below, read by the step entries and handed down; NOT fp32-accurate): per chunk
+//   logits_k = RN(h) . RN(wte_k)^T        gemm_b1 on plane 0 of the chunk's w3 (conv1d, BF16_TRAIN_HEAD)
+//   dh (+)= RN(dlogits_k) . RN(wte_k)     gemm_b1 on plane 0 of the chunk's w3t, K = Ck, the residual epilogue onto dh itself for k > 0
+//   dwte[c0 : c0 + Ck] = RN(dlogits_k)^T . RN(h)    gemm_b1tn (I = Ck, J = d, lda = Ck), slices within the room of `tn`
+// each product on its own: one whose plane is missing or whose shape the bf16 kernel refuses keeps the route above.  The logits and
+// their gradient in memory, the cross entropy, dh, dwte and the tied add stay fp32.  dh in place: the residual epilogue
+// (gemm_epilogue_rowmajor.h) loads an accumulator tile's 16 second-buffer values in the thread that then stores those 16 elements
+// of C, loads first (interior tiles: the res[] loop ahead of the stores; edge tiles: res[r] ahead of the guarded store; a clamped
+// row or column reads an element some other thread writes, and throws it away) -- the bf16x3 route relies on the same text.
 #include <math.h>
 #include <string.h>
 #include "common.h"
@@ -331,6 +341,14 @@ static int check_ce(int N, int V, int ldV, int T) {
     return R4D_OK;
 }
 
+// the weight gradient's slices: room for ONE chunk, the full one or the shorter last one
+static size_t head_tn_floats(int N, int d, int ldV) {
+    const int C = ce_chunk_rows(ldV), tail = ldV % C;
+    size_t tn = gemm_tn_scratch_floats(C, d, N);
+    if (tail) { const size_t tn2 = gemm_tn_scratch_floats(tail, d, N); tn = tn2 > tn ? tn2 : tn; }
+    return tn;
+}
+
 LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
     LMLayout t;
     const size_t N = (size_t)B * T, d = cfg->n_embd;
@@ -338,9 +356,9 @@ LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
     auto take = [&](size_t n) { const size_t o = off; off += up64(n); return o; };
     t.train = take(gpt2_train_workspace_floats(cfg, 1, &B, &T));
     // ldV > CE_MAX_LDV: the logits slot and the weight-gradient scratch hold ONE chunk (the full one or the shorter last one)
-    const int C = ce_chunk_rows(ldV), tail = ldV % C;
-    size_t tn = gemm_tn_scratch_floats(C, (int)d, (int)N);
-    if (tail) { const size_t tn2 = gemm_tn_scratch_floats(tail, (int)d, (int)N); tn = tn2 > tn ? tn2 : tn; }
+    // (the sizes do not depend on r4d_set_train_head_bf16: gemm_b1tn cuts its slices to the room of `tn`)
+    const int C = ce_chunk_rows(ldV);
+    const size_t tn = head_tn_floats((int)N, (int)d, ldV);
     t.h = take(N * d); t.logits = take(N * C); t.dh = take(N * d); t.dwte = take((size_t)ldV * d);
     t.tn = take(tn); t.ce = take(ce_ws_floats((int)N, ldV > CE_MAX_LDV));
     t.total = off;
@@ -364,13 +382,16 @@ static int launch_add_inplace(float* y, const float* x, long long n, hipStream_t
 // The planes are laid chunk by chunk (include/r4d.h: r4d_lm_head), so every GEMM is an ordinary aligned one on a contiguous
 // operand; the chunk order is fixed, so dh carries the same bits on every launch.
 static int lm_head_train_chunked(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale,
-                                 float* loss, float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws_, hipStream_t s) {
+                                 float* loss, float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws_, int hb,
+                                 hipStream_t s) {
     const int ldV = head->ldV, C = CE_CHUNK;
     R4D_REQUIRE((long long)N * C < (1ll << 31) && (long long)ldV * d < (1ll << 31),
                 "lm head: N=%d rows x %d chunk columns or ldV=%d x d=%d reaches 2^31 elements (32-bit index arithmetic)", N, C, ldV, d);
     const CeWs w = ce_ws(ce_ws_, N);
     int rc;
-    auto chunk_logits = [&](int c0, int cn) { return conv1d(conv1d_w(*head, d, c0, cn), h, nullptr, N, EPI_NONE, logits, s); };
+    const Conv1DOpts fwd{nullptr, false, hb ? BF16_TRAIN_HEAD : BF16_OFF};
+    const int gb = hb ? TRAIN_BF16_HEAD : TRAIN_BF16_OFF;
+    auto chunk_logits = [&](int c0, int cn) { return conv1d(conv1d_w(*head, d, c0, cn), h, nullptr, N, EPI_NONE, logits, s, fwd); };
     if ((rc = launch_ce_count(src, N, T, V, w, s))) return rc;
     for (int c0 = 0; c0 < ldV; c0 += C) {
         const int cn = ldV - c0 < C ? ldV - c0 : C;
@@ -383,28 +404,43 @@ static int lm_head_train_chunked(const float* h, int N, int V, int d, const r4d_
         const int cn = ldV - c0 < C ? ldV - c0 : C;
         if ((rc = chunk_logits(c0, cn))) return rc;
         if ((rc = launch_ce_grad(logits, (size_t)cn, c0, cn, N, V, src, T, gscale, w, s))) return rc;
-        if (dh && (rc = data_grad(conv1d_w(*head, d, c0, cn), logits, N, dh, c0 ? dh : nullptr, nullptr, s))) return rc;
-        if (dwte && (rc = weight_grad(logits, h, dwte + (size_t)c0 * d, nullptr, cn, d, N, cn, d, tn_scratch, nullptr, s))) return rc;
+        if (dh && (rc = data_grad(conv1d_w(*head, d, c0, cn), logits, N, dh, c0 ? dh : nullptr, nullptr, s, gb))) return rc;
+        if (dwte && (rc = weight_grad(logits, h, dwte + (size_t)c0 * d, nullptr, cn, d, N, cn, d, tn_scratch, nullptr, s, gb))) return rc;
     }
     return R4D_OK;
 }
 
 // The head of the training step: logits = h . wte_pad^T on the mode's forward GEMM family, loss and dlogits (in place; label of
 // row r: src[r + 1] within a sequence of T rows), then -- when `dh` is given -- dh = dlogits . wte_pad (bf16x3 like every data
-// gradient) and -- when `dwte` is given -- dwte [ldV, d] = dlogits^T . h
+// gradient) and -- when `dwte` is given -- dwte [ldV, d] = dlogits^T . h.  `hb` (TrainModes::head_bf16): each of the three on plain
+// bf16 operands where its plane and shape allow (the head of this file).  A loss-only call (dh == dwte == NULL) forms its logits by
+// the launch the training call uses, so its loss carries the training call's bits.
 static int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head* head, const int64_t* src, int T, float gscale,
-                         float* loss, float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, hipStream_t s) {
+                         float* loss, float* logits, float* dh, float* dwte, float* tn_scratch, float* ce_ws, int hb, hipStream_t s) {
     const int ldV = head->ldV;
-    if (ldV > CE_MAX_LDV) return lm_head_train_chunked(h, N, V, d, head, src, T, gscale, loss, logits, dh, dwte, tn_scratch, ce_ws, s);
+    if (ldV > CE_MAX_LDV) return lm_head_train_chunked(h, N, V, d, head, src, T, gscale, loss, logits, dh, dwte, tn_scratch, ce_ws, hb, s);
     int rc;
+    const int gb = hb ? TRAIN_BF16_HEAD : TRAIN_BF16_OFF;
     // logits = h . wte_pad^T: wte_pad [ldV, d] IS the k-contiguous [N, K] operand (planes when the mode has them)
     const Conv1DW W = conv1d_w(*head, d, 0, ldV);
-    if ((rc = conv1d(W, h, nullptr, N, EPI_NONE, logits, s))) return rc;
+    if ((rc = conv1d(W, h, nullptr, N, EPI_NONE, logits, s, Conv1DOpts{nullptr, false, hb ? BF16_TRAIN_HEAD : BF16_OFF}))) return rc;
     if ((rc = lm_ce(logits, N, V, ldV, src, T, gscale, loss, ce_ws, s))) return rc;
     // dh = dlogits . wte_pad  (K = ldV: the pad columns of dlogits are zero)
-    if (dh && (rc = data_grad(W, logits, N, dh, nullptr, nullptr, s))) return rc;
+    if (dh && (rc = data_grad(W, logits, N, dh, nullptr, nullptr, s, gb))) return rc;
     // dwte [ldV, d] = dlogits^T . h
-    return dwte ? weight_grad(logits, h, dwte, nullptr, ldV, d, N, ldV, d, tn_scratch, nullptr, s) : R4D_OK;
+    return dwte ? weight_grad(logits, h, dwte, nullptr, ldV, d, N, ldV, d, tn_scratch, nullptr, s, gb) : R4D_OK;
+}
+
+// The head alone (r4d_lm_head_train_f32): one chunk of logits, the weight gradient's slices, the cross entropy's words
+struct HeadLayout { size_t logits, tn, ce, total; };
+static HeadLayout head_layout(int N, int d, int ldV) {
+    HeadLayout t;
+    size_t off = 0;
+    auto take = [&](size_t n) { const size_t o = off; off += up64(n); return o; };
+    t.logits = take((size_t)N * ce_chunk_rows(ldV)); t.tn = take(head_tn_floats(N, d, ldV));
+    t.ce = take(ce_ws_floats(N, ldV > CE_MAX_LDV));
+    t.total = off;
+    return t;
 }
 
 // One training step through the head, behind the argument checks of its two exports (`who`: the export's name in a message):
@@ -414,7 +450,7 @@ static int lm_head_train(const float* h, int N, int V, int d, const r4d_lm_head*
 int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                     const r4d_lm_head* head, int head_mode, float* head_grad, const int64_t* ids_d, const SpliceIn* sp, int B, int T,
                     float gscale, float* loss, float* d_fused, float* hidden_out, const r4d_train_dropout* dropout, void* workspace_d,
-                    size_t workspace_bytes, hipStream_t s) {
+                    size_t workspace_bytes, int head_bf16, hipStream_t s) {
     const int V = cfg->vocab, ldV = head->ldV, d = cfg->n_embd, N = B * T;
     int rc = check_ce(N, V, ldV, T);
     if (rc) return rc;
@@ -432,7 +468,7 @@ int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_
     if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &T, nullptr, h, dropout, ws + t.train, train_bytes, s, sp))) return rc;
     if (hidden_out) R4D_HIP(hipMemcpyAsync(hidden_out, h, (size_t)N * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     if ((rc = lm_head_train(h, N, V, d, head, ids_d, T, gscale, loss, logits, backward ? dh : nullptr, head_w ? dwte : nullptr,
-                            ws + t.tn, ws + t.ce, s))) return rc;
+                            ws + t.tn, ws + t.ce, head_bf16, s))) return rc;
     if (!backward) return R4D_OK;
     if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &T, nullptr, dh, dropout, ws + t.train, train_bytes, s, sp, d_fused)))
         return rc;
@@ -495,8 +531,39 @@ int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weight
     R4D_REQUIRE(cfg && w && grads && grads->wte && head && head->wte_pad && ids_d && loss_d, "lm train step: null pointer");
     R4D_REQUIRE(B >= 1 && T >= 1 && head->ldV % 128 == 0 && head->ldV >= cfg->vocab,
                 "lm train step: B=%d T=%d ldV=%d (a multiple of 128 >= V=%d)", B, T, head->ldV, cfg->vocab);
+    const int head_bf16 = train_modes().head_bf16;                  // r4d_set_train_head_bf16, read here and handed down
     return head_train_step("lm train step", cfg, w, grads, head, R4D_HEAD_GRAD_TIED, nullptr, ids_d, nullptr, B, T, grad_scale, loss_d,
-                           nullptr, nullptr, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
+                           nullptr, nullptr, dropout, workspace_d, workspace_bytes, head_bf16, (hipStream_t)stream);
+}
+
+size_t r4d_lm_head_train_workspace_bytes(int32_t N, int32_t d, int32_t ldV) {
+    if (N <= 0 || d <= 0 || ldV <= 0) return 0;
+    return head_layout(N, d, ldV).total * sizeof(float) + 256;
+}
+
+int r4d_lm_head_train_f32(const float* h_d, int32_t N, int32_t V, int32_t d, const r4d_lm_head* head, const int64_t* labels_src_d,
+                          int32_t T, float grad_scale, float* loss_d, float* dh_d, float* dwte_d, void* workspace_d,
+                          size_t workspace_bytes, void* stream) {
+    const int head_bf16 = train_modes().head_bf16;                  // r4d_set_train_head_bf16, read here and handed down
+    R4D_REQUIRE(h_d && head && head->wte_pad && labels_src_d && loss_d, "lm head train: null pointer");
+    R4D_REQUIRE(d >= 4 && d % 4 == 0 && head->ldV % 128 == 0 && head->ldV >= V, "lm head train: d=%d ldV=%d (d %% 4 == 0, ldV a multiple of 128 >= V=%d)",
+                d, head->ldV, V);
+    const int ldV = head->ldV;
+    int rc = check_ce(N, V, ldV, T);
+    if (rc) return rc;
+    R4D_REQUIRE((long long)N * ce_chunk_rows(ldV) < (1ll << 31) && (long long)ldV * d < (1ll << 31) && (long long)N * d < (1ll << 31),
+                "lm head train: N=%d rows x %d chunk columns, ldV=%d x d=%d or N x d reaches 2^31 elements (32-bit index arithmetic)", N,
+                ce_chunk_rows(ldV), ldV, d);
+    R4D_REQUIRE((((uintptr_t)h_d | (uintptr_t)head->wte_pad | (uintptr_t)head->w3 | (uintptr_t)head->w3t | (uintptr_t)head->h2 |
+                  (uintptr_t)dh_d | (uintptr_t)dwte_d | (uintptr_t)workspace_d) & 15) == 0, "lm head train: 16-byte alignment");
+    const HeadLayout t = head_layout(N, d, ldV);
+    if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
+        set_error("lm head train: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
+        return R4D_ERR_WORKSPACE;
+    }
+    float* ws = (float*)workspace_d;
+    return lm_head_train(h_d, N, V, d, head, labels_src_d, T, grad_scale, loss_d, ws + t.logits, dh_d, dwte_d, ws + t.tn, ws + t.ce,
+                         head_bf16, (hipStream_t)stream);
 }
 
 }  // extern "C"

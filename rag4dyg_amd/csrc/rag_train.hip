@@ -195,8 +195,9 @@ int r4d_rag_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w
     R4D_REQUIRE(B >= 1 && r >= 1 && Ta >= r + 3 && head->ldV % 128 == 0 && head->ldV >= cfg->vocab,
                 "rag train step: B=%d Ta=%d r=%d ldV=%d (V=%d)", B, Ta, r, head->ldV, cfg->vocab);
     const SpliceIn sp{fused_d, r};
+    const int head_bf16 = train_modes().head_bf16;                  // r4d_set_train_head_bf16, read here and handed down
     return head_train_step("rag train step", cfg, w, grads, head, head_mode, head_grad_d, aug_ids_d, &sp, B, Ta, grad_scale, loss_d,
-                           d_fused_d, hidden_out_d, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
+                           d_fused_d, hidden_out_d, dropout, workspace_d, workspace_bytes, head_bf16, (hipStream_t)stream);
 }
 
 int r4d_weighted_bag_f32(const float* table_d, int32_t vocab, int32_t d, const int64_t* ids_d, const float* weights_d,

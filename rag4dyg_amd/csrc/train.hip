@@ -56,10 +56,13 @@ static int g_train_bf16 = 0;
 // r4d_set_train_attention_bf16: 0 the six per-head attention products of a block on the exact-f32 kernel (default), 1 on plain bf16
 // operands (gemm_b1h.hip).  Independent of g_train_bf16.  NOT fp32-accurate.
 static int g_train_attn_bf16 = 0;
-// The modes as a value: every entry point (size queries, forward, backward) reads the globals ONCE, here, and hands the
-// value down; nothing below an entry point looks at a global.
-struct TrainModes { int attention, activations, bf16, attn_bf16; };
-static TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16}; }
+// r4d_set_train_head_bf16: 0 the LM head's three GEMMs on the gemm mode's kernels (default), 1 on plain bf16 operands (gemm_b1.hip,
+// gemm_b1tn.hip) wherever the head carries the plane and the shape is supported (lm_head.hip).  Independent of the two above; the
+// retriever step has no head and does not read it.  NOT fp32-accurate.
+static int g_train_head_bf16 = 0;
+// The modes as a value (common.h: TrainModes): every entry point (size queries, forward, backward, the head steps) reads the
+// globals ONCE, here, and hands the value down; nothing below an entry point looks at a global.
+TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16, g_train_head_bf16}; }
 // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
 static bool train_fuse_gelu() {
     static const int v = [] { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); return e ? atoi(e) : 1; }();
@@ -68,7 +71,7 @@ static bool train_fuse_gelu() {
 // The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
 // activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
 // would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
-static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0}, -1};
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0, 0}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -170,7 +173,7 @@ int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* 
     if (route != ROUTE_DGRAD_F32) {
         const S3Args a = s3_args(dy, W.w3t, nullptr, gelu_pre ? gelu_pre : resid, M, W.out, W.in, epi, dx);
         if (route == ROUTE_DGRAD_S3) return launch_gemm_s3(a, s);
-        R4D_BRANCH(TB_DGRAD);
+        if (bf16 == TRAIN_BF16_HEAD) R4D_BRANCH(TBH_DGRAD); else R4D_BRANCH(TB_DGRAD);
         return launch_gemm_b1(a, s);
     }
     R4D_REQUIRE(!gelu_pre, "bwd_data: the fused GELU derivative needs the bf16x3 planes");
@@ -213,7 +216,8 @@ int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, in
     const size_t red_floats = db ? colsum_scratch_floats(M, J) : 0;
     bool db_done = false;
     int rc;
-    if (bf16) { if (route == ROUTE_WGRAD_B1TN) R4D_BRANCH(TB_WGRAD); else R4D_BRANCH(TB_WGRAD_FALLBACK); }
+    if (bf16 == TRAIN_BF16_HEAD) { if (route == ROUTE_WGRAD_B1TN) R4D_BRANCH(TBH_WGRAD); else R4D_BRANCH(TBH_WGRAD_FALLBACK); }
+    else if (bf16) { if (route == ROUTE_WGRAD_B1TN) R4D_BRANCH(TB_WGRAD); else R4D_BRANCH(TB_WGRAD_FALLBACK); }
     if (route == ROUTE_WGRAD_B1TN) {
         rc = wgrad_b1tn(x, dy, dW, db, I, J, M, lda, ldb, part, gemm_tn_scratch_floats(I, J, M), red, red_floats, &db_done, s);
     } else if (route == ROUTE_WGRAD_S3TN) {
@@ -415,6 +419,13 @@ int r4d_set_train_attention_bf16(int32_t on) {
     return prev;
 }
 int r4d_get_train_attention_bf16(void) { return g_train_attn_bf16; }
+
+int r4d_set_train_head_bf16(int32_t on) {
+    const int prev = g_train_head_bf16;
+    g_train_head_bf16 = on != 0;
+    return prev;
+}
+int r4d_get_train_head_bf16(void) { return g_train_head_bf16; }
 
 size_t r4d_train_attn_probs_ld(int32_t T) { return T > 0 ? (size_t)tpad128(T) : 0; }
 

@@ -23,7 +23,8 @@ import torch
 
 from . import _lib, gpt2, ops
 from .lm_training import HeadOperand, LinearWarmupSchedule, save_checkpoint
-from .training import AdamW, EncoderTrainer, adjust_learning_rate, distributed_setup
+from .training import (TRAIN_HEAD_PRECISIONS, AdamW, EncoderTrainer, adjust_learning_rate, distributed_setup,
+                       resolve_train_head_precision)
 
 
 # ------------------------------------------------------------------------------------------------ host preparation
@@ -93,7 +94,9 @@ class GeneratorTrainer:
     """One generator training micro-step on the device for a ``GPT2LMHeadModelRAG`` with ``gnn_fusion`` (one layer).  ``grads``
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
-    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None):
+    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None):
+        """``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
+        ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, beside ``precision``."""
         gnn = getattr(model, "gnn_fusion", None)
         if gnn is None or gnn.n_layers != 1:
             raise _lib.R4DError("GeneratorTrainer: needs a one-layer gnn_fusion (graph pooling)")
@@ -104,6 +107,7 @@ class GeneratorTrainer:
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
         self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations,
                                   precision=precision)
+        self.head_precision = resolve_train_head_precision(head_precision)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
         for n, p in self.params.items():
@@ -117,13 +121,18 @@ class GeneratorTrainer:
         self.flat_accum = None
         wte = model.transformer.wte.weight
         self.V, self.d = int(wte.shape[0]), int(wte.shape[1])
-        self.head = HeadOperand(self.V, self.d, dev, self.enc.use_s3, self.enc.use_h2)
+        self.head = HeadOperand(self.V, self.d, dev, self.enc.use_s3, self.enc.use_h2, TRAIN_HEAD_PRECISIONS[self.head_precision] == 1)
         self.ldV = self.head.ldV
         self._ws = None
         self._scratch = {}
         self._stamp = None
         ops.range_flag(dev)
         self._refresh_head()
+
+    def select_modes(self):
+        """The encoder trainer's switches and this trainer's head precision (process-wide: before every size query and step call)."""
+        self.enc.select_modes()
+        _lib.load().r4d_set_train_head_bf16(TRAIN_HEAD_PRECISIONS[self.head_precision])      # (returns the previous setting)
 
     # ---------------------------------------------------------------- derived operands
     def _current_stamp(self):
@@ -204,7 +213,7 @@ class GeneratorTrainer:
         if self.freeze or not backward:
             g = None                                                     # frozen transformer / forward only
         head = self.head.struct()
-        self.enc.select_modes()                                    # before the size query: the step call below reads the same mode
+        self.select_modes()                                        # before the size query: the step call below reads the same mode
         nbytes = lib.r4d_rag_train_workspace_bytes(ctypes.byref(c), B, Ta, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("rag train step: bad batch shape")
@@ -330,7 +339,7 @@ def evaluate(args, trainer, loader, bags):
     return float(total) / n if n else float("nan")
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None):
     """Drop-in for ``train_generator.train`` (:141-248).  Returns (global_step, tr_loss / global_step)."""
     from .generator import get_eval_metrics_generator, load_and_cache_examples
     check_supported(args)
@@ -347,7 +356,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     else:
         t_total = len(loader) // gas * args.num_train_epochs
     trainer = GeneratorTrainer(model, freeze=bool(getattr(args, "freeze", False)),
-                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision)
+                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
+                               head_precision=head_precision)
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():
@@ -364,7 +374,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Total optimization steps = {}".format(t_total))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too)".format(trainer.enc.precision))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
+          "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

@@ -15,7 +15,8 @@ import os
 import torch
 
 from . import _lib, gpt2, ops
-from .training import AdamW, EncoderTrainer, distributed_setup, write_checkpoint_dir
+from .training import (TRAIN_HEAD_PRECISIONS, AdamW, EncoderTrainer, distributed_setup, resolve_train_head_precision,
+                       write_checkpoint_dir)
 
 
 def padded_vocab(V):
@@ -37,14 +38,16 @@ class HeadOperand:
     """The padded LM-head operand ``pad`` [ldV, d] (the head weight in rows [0, V), zero rows up to ldV) and its GEMM planes, as
     ``r4d_lm_head`` describes them: bf16x3 planes when the split modes are on, f16x2 planes in f16x2 mode.  Beyond 15,872 rows the
     bf16x3 planes are laid chunk by chunk (``head_chunks``: the chunked head of ``csrc/lm_head.hip``); the buffers keep their
-    sizes.  Shared by the SimpleDyG and the RAG-generator training steps; ``refresh(weight)`` after every change of the head
-    weight."""
+    sizes.  ``head_bf16`` (head precision ``bf16``, ``r4d_set_train_head_bf16``): the bf16x3 planes are built in EVERY gemm mode,
+    exact f32 included -- the head's GEMMs read plane 0 of them; with the switch off the library takes no route through them in
+    exact-f32 mode.  Shared by the SimpleDyG and the RAG-generator training steps; ``refresh(weight)`` after every change of the
+    head weight."""
 
-    def __init__(self, V, d, device, use_s3, use_h2):
+    def __init__(self, V, d, device, use_s3, use_h2, head_bf16=False):
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
         self.pad = torch.zeros(self.ldV, self.d, dtype=torch.float32, device=device)
         self._w3 = self._w3t = self._h2 = None
-        if use_s3 and self.d % 32 == 0:
+        if (use_s3 or head_bf16) and self.d % 32 == 0:
             self._w3 = torch.empty(3, self.ldV, self.d, dtype=torch.int16, device=device)       # one chunk: this shape; else per chunk
             self._w3t = torch.empty(3, self.d, self.ldV, dtype=torch.int16, device=device)
             if use_h2:
@@ -70,28 +73,63 @@ class HeadOperand:
                             self._w3t.data_ptr() if self._w3t is not None else None, self._h2.data_ptr() if h2 else None)
 
 
+@torch.no_grad()
+def lm_head_train(head, h, labels_src, T, grad_scale=1.0, dh=None, dwte=None, workspace=None):
+    """The LM head of the two training steps alone (``r4d_lm_head_train_f32``), in the CURRENT gemm mode and head switch
+    (``r4d_set_train_head_bf16``): ``head`` a refreshed :class:`HeadOperand`, ``h`` fp32 [N, d] on the device (N = B T rows),
+    ``labels_src`` int64 [N] (the label of row r is ``labels_src[r + 1]`` inside a sequence of T rows; -100 is not counted).
+    ``dh`` [N, d] / ``dwte`` [ldV, d]: written when given (``grad_scale`` * gradient); both None: the loss alone.  ``workspace``: a
+    uint8 device tensor of at least ``r4d_lm_head_train_workspace_bytes`` (None: a fresh one).  Returns (loss, workspace)."""
+    lib = _lib.load()
+    N, d = int(h.shape[0]), int(h.shape[1])
+    for t, n in ((h, "h"), (dh, "dh"), (dwte, "dwte")):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.R4DError(f"lm_head_train: {n} must be a contiguous fp32 device tensor")
+    if d != head.d or not labels_src.is_cuda or labels_src.dtype != torch.int64 or labels_src.numel() != N:
+        raise _lib.R4DError("lm_head_train: h is [N, head.d], labels_src int64 [N] on the device")
+    nbytes = int(lib.r4d_lm_head_train_workspace_bytes(N, d, head.ldV))
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=h.device)
+    loss = torch.empty((), dtype=torch.float32, device=h.device)
+    st = head.struct()
+    _lib.check(lib.r4d_lm_head_train_f32(h.data_ptr(), N, head.V, d, ctypes.byref(st), labels_src.data_ptr(), int(T), float(grad_scale),
+                                         loss.data_ptr(), dh.data_ptr() if dh is not None else None,
+                                         dwte.data_ptr() if dwte is not None else None, workspace.data_ptr(), workspace.numel(),
+                                         torch.cuda.current_stream().cuda_stream), "lm_head_train")
+    return loss, workspace
+
+
 class LMTrainer:
     """One SimpleDyG training micro-step on the device.  Built on :class:`training.EncoderTrainer` (the flat gradient buffer,
     the per-layer weight copies / planes, the dropout struct, ``accumulate`` / ``take_accumulated`` / ``all_reduce_mean``) plus
     the padded LM-head operand ``wte_pad`` [ldV, d] (zero rows past V) and its planes.  Every derived weight is rebuilt when the
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
-    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None):
+    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None):
+        """``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
+        ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, an axis of its own beside ``precision``.  The
+        trainer sets the head switch with the others before every size query and step call of its own."""
         head = getattr(model, "lm_head", None)
         if head is None or head.weight is not model.transformer.wte.weight:
             raise _lib.R4DError("SimpleDyG training needs lm_head tied to transformer.wte (the reference's model is always tied); "
                                 "this model's lm_head is a separate tensor")
         self.model = model
         self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations, precision=precision)
+        self.head_precision = resolve_train_head_precision(head_precision)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
         dev = wte.device
-        self.head = HeadOperand(V, d, dev, self.enc.use_s3, self.enc.use_h2)
+        self.head = HeadOperand(V, d, dev, self.enc.use_s3, self.enc.use_h2, TRAIN_HEAD_PRECISIONS[self.head_precision] == 1)
         self._ws = None
         self._stamp = None
         ops.range_flag(dev)                                     # registered: the CE kernel reports out-of-range labels there
         self.refresh()
+
+    def select_modes(self):
+        """The encoder trainer's switches and this trainer's head precision (process-wide: before every size query and step call)."""
+        self.enc.select_modes()
+        _lib.load().r4d_set_train_head_bf16(TRAIN_HEAD_PRECISIONS[self.head_precision])      # (returns the previous setting)
 
     # the EncoderTrainer surface the training loop uses
     @property
@@ -138,7 +176,7 @@ class LMTrainer:
         lib = _lib.load()
         c, w, g, keep = self.enc._structs()
         head = self.head.struct()
-        self.enc.select_modes()                              # before the size query: the step call below reads the same mode
+        self.select_modes()                                  # before the size query: the step call below reads the same mode
         nbytes = lib.r4d_gpt2_lm_train_workspace_bytes(ctypes.byref(c), B, T, self.ldV)
         if nbytes == 0:
             raise _lib.R4DError("lm train step: bad batch shape")
@@ -258,7 +296,7 @@ def train_epoch(model, trainer, optimizer, scheduler, train_dataloader, tr_loss,
     return global_step, tr_loss
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None):
     """Drop-in for ``main_SimpleDyG.train`` (:200-343).  Returns (global_step, tr_loss / global_step)."""
     from .evaluation import get_eval_metrics
     if getattr(args, "fp16", False):
@@ -272,7 +310,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
     else:
         t_total = len(train_dataloader) // gas * args.num_train_epochs
-    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision)      # every rank its own dropout masks
+    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
+                        head_precision=head_precision)      # every rank its own dropout masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -290,7 +329,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Gradient Accumulation steps = {}".format(gas))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too)".format(trainer.enc.precision))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
+          "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

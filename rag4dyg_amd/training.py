@@ -135,6 +135,9 @@ TRAIN_ACTIVATION_MODES = {"stored": 0, "recompute": 1}
 TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1, "fp32+attn": 0, "bf16+attn": 1}
 # ... and the attention axis (r4d_set_train_attention_bf16: the six per-head products of a block); the two are independent
 TRAIN_ATTENTION_BF16 = {"fp32": 0, "bf16": 0, "fp32+attn": 1, "bf16+attn": 1}
+# the LM head's axis (r4d_set_train_head_bf16: logits, dh and dwte_head of the LM and RAG-generator steps): a table and an argument
+# of its own, independent of the two above; the retriever step has no head
+TRAIN_HEAD_PRECISIONS = {"fp32": 0, "bf16": 1}
 
 
 def _resolve(what, value, env, table, default):
@@ -170,6 +173,15 @@ def resolve_train_precision(precision=None):
     axis, ``"bf16"`` alone keeps attention in exact f32).  None -> the environment variable ``R4D_TRAIN_PRECISION``, ``fp32``
     when it is unset or empty.  Anything else raises."""
     return _resolve("train precision", precision, "R4D_TRAIN_PRECISION", TRAIN_PRECISIONS, "fp32")
+
+
+def resolve_train_head_precision(head_precision=None):
+    """``"fp32"`` (the LM head's three GEMMs on the gemm mode's fp32-accurate kernels) or ``"bf16"`` (logits = RN(h) . RN(wte)^T,
+    dh = RN(dlogits) . RN(wte), dwte = RN(dlogits)^T . RN(h) on bf16 operands with fp32 accumulation -- NOT fp32-accurate; the
+    logits in memory, the cross entropy and every gradient buffer stay fp32; ``r4d_set_train_head_bf16``).  An axis of its own:
+    it composes with every ``precision``.  None -> the environment variable ``R4D_TRAIN_HEAD_PRECISION``, ``fp32`` when it is
+    unset or empty.  Anything else raises."""
+    return _resolve("train head precision", head_precision, "R4D_TRAIN_HEAD_PRECISION", TRAIN_HEAD_PRECISIONS, "fp32")
 
 
 class EncoderTrainer:
@@ -626,7 +638,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
     print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.attention))
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too)".format(trainer.precision))
+    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too); "
+          "no LM head in this step (R4D_TRAIN_HEAD_PRECISION is not read)".format(trainer.precision))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """SimpleDyG LM-training step (``LMTrainer.step``: forward, LM head, shifted cross entropy, backward) at the reference's script
 shapes: ms per step and tokens/s, the per-class breakdown of ``r4d_profile_*``, the CE kernel's bytes / time against the 8 TB/s HBM
-spec, the head's share of the step (step minus forward_hidden + backward_hidden timed alone; eval mode, no dropout), and as a yardstick the same head (h . wte^T, F.cross_entropy, backward) in torch autograd.
+spec, the head's share of the step (step minus forward_hidden + backward_hidden timed alone; eval mode, no dropout), the head ALONE
+through ``r4d_lm_head_train_f32`` (ms per call and its per-class kernel times), and as a yardstick the same head (h . wte^T, F.cross_entropy, backward) in torch autograd.
 ``wikiv2_v50k`` is the wikiv2 model on a 50,000-token vocabulary: the chunked head (``csrc/lm_head.hip``, ldV > 15,872).  Its record
 adds the chunk rows, the bytes the materialised logits alone would take next to the step's workspace, and the time of ONE sweep of
 logits GEMMs over the chunks (the GEMM the chunked head runs twice) with its share of the step.
 
-    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn]
+    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn] [--head-precision fp32|bf16]
 """
 import argparse
 import ctypes
@@ -82,6 +83,8 @@ def main():
                     help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
     ap.add_argument("--precision", default=None, choices=("fp32", "bf16", "fp32+attn", "bf16+attn"),
                     help="arithmetic of the blocks' Conv1D GEMMs (default: R4D_TRAIN_PRECISION, else fp32)")
+    ap.add_argument("--head-precision", default=None, choices=("fp32", "bf16"),
+                    help="arithmetic of the LM head's three GEMMs (default: R4D_TRAIN_HEAD_PRECISION, else fp32)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -96,7 +99,7 @@ def main():
         # eval mode: no dropout launches, so that the step and its body (timed alone below) differ by the head only
         m = m.to(dev).eval()
         torch.cuda.reset_peak_memory_stats()
-        tr = LMTrainer(m, attention=a.attention, activations=a.activations, precision=a.precision)
+        tr = LMTrainer(m, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision)
         if a.one_step:
             ids = torch.randint(0, s["V"], (s["B"], a.one_step), device=dev)
             tr.step(ids)
@@ -136,6 +139,18 @@ def main():
                                                                   dh.data_ptr(), None, ws.data_ptr(), ws.numel(), stream), "bwd")
             body_ms = _time(body, a.steps, a.warmup)
             del ws
+            # the head alone on the ln_f rows the body left in h: the call the step makes, timed and profiled by itself
+            from rag4dyg_amd.lm_training import lm_head_train
+            tr.select_modes()
+            hd_dh, hd_dw = torch.empty(N, d, device=dev), torch.empty(ldV, d, device=dev)
+            _loss, hd_ws = lm_head_train(tr.head, h, ids.view(-1), T, 1.0, hd_dh, hd_dw)
+            head_alone_ms = _time(lambda: lm_head_train(tr.head, h, ids.view(-1), T, 1.0, hd_dh, hd_dw, hd_ws), a.steps, a.warmup)
+            lib.r4d_profile_enable(1)
+            lm_head_train(tr.head, h, ids.view(-1), T, 1.0, hd_dh, hd_dw, hd_ws)
+            torch.cuda.synchronize()
+            head_prof = _profile(lib)
+            lib.r4d_profile_enable(0)
+            del hd_dh, hd_dw, hd_ws
             hr = h.clone().requires_grad_(True)
             wr = m.transformer.wte.weight.detach().clone().requires_grad_(True)
             lab = ids.view(B, T)[:, 1:].reshape(-1)
@@ -152,6 +167,9 @@ def main():
             total_prof = sum(v["ms"] for v in prof2.values())
             head_like = {k: v for k, v in prof2.items() if v["work"] > 0}
             rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, activations=tr.enc.activations, precision=tr.enc.precision,
+                       head_precision=tr.head_precision, head_alone_ms=head_alone_ms,
+                       head_alone_classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"], work=v["work"]) for k, v in sorted(head_prof.items(), key=lambda kv: -kv[1]["ms"])},
+                       launches={k: v["launches"] for k, v in sorted(prof2.items())},
                        workspace_bytes=ws_bytes, max_memory_allocated=peak, L=s["L"], H=s["H"], d=d, V=V,
                        ldV=ldV, B=B, T=T, ms_per_step=ms,
                        tokens_per_s=N / (ms / 1e3), ce_ms=ce.get("ms"), ce_bytes=ce_bytes,

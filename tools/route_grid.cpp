@@ -1,5 +1,5 @@
 // Host-only walk of the Conv1D routing functions (rag4dyg_amd/csrc/conv1d_route.h) over the grid of
-// tests/test_host_conv1d_route.py, for a sanitizer build on a machine without a GPU:
+// tests/test_host_conv1d_route.py (and the head's precision value 2 of tests/test_host_train_bf16_head.py), for a sanitizer build on a machine without a GPU:
 //     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/route_grid.cpp -o route_grid && ./route_grid
 // Prints the number of points per route; any sanitizer report ends it with a non-zero status.
 #include <initializer_list>
@@ -15,7 +15,7 @@ int main() {
     for (int mode = 0; mode <= 2; ++mode) {
         g_gemm_split3 = mode;
         for (int kind = 0; kind < 6; ++kind)
-            for (int bf16 = 0; bf16 <= 1; ++bf16)
+            for (int bf16 = 0; bf16 <= 2; ++bf16)                     // 2: the LM head under its own switch (kinds 2, 4, 5)
                 for (unsigned have = 0; have < 32; ++have)
                     for (int epi = 0; epi < 8; ++epi)
                         for (int mi = 0; mi < (kind == 5 ? 8 : 4); ++mi)
@@ -29,7 +29,7 @@ int main() {
     for (int mode = 0; mode <= 2; ++mode) {                      // empty and negative shapes: -1, whatever the kind and mode
         g_gemm_split3 = mode;
         for (int kind = 0; kind < 6; ++kind)
-            for (int bf16 = 0; bf16 <= 1; ++bf16)
+            for (int bf16 = 0; bf16 <= 2; ++bf16)                     // 2: the LM head under its own switch (kinds 2, 4, 5)
                 for (int bad : {0, -1, -128, -2147483647 - 1}) {
                     if (conv1d_route_query(kind, bad, 128, 256, 0, 31, bf16) != -1 || conv1d_route_query(kind, 390, bad, 256, 0, 31, bf16) != -1 ||
                         conv1d_route_query(kind, 390, 128, bad, 0, 31, bf16) != -1) { printf("empty shape not refused\n"); return 1; }
