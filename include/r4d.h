@@ -638,6 +638,39 @@ int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float
 int r4d_set_train_head_bf16(int32_t on);
 int r4d_get_train_head_bf16(void);
 
+/* The saved activations of the bf16 training steps kept as bf16 in memory (process-wide; additive ABI v6 entries; csrc/train.hip,
+ * csrc/gemm_b1.hip, csrc/gemm_b1tn.hip, csrc/encoder_ops.hip).  A fifth switch; it acts ONLY while r4d_set_train_bf16 is on, and
+ * with that switch off it changes no byte of the layout and no launch.  While both are on, per transformer block
+ *   ln1 [M, d]  (layers >= 1)   the LayerNorm output that c_attn and its weight gradient read
+ *   ln2 [M, d]                  the LayerNorm output that c_fc and its weight gradient read
+ *   f   [M, 4d]                 gelu_new(pre), which the MLP projection and its weight gradient read
+ * are written by their producers as bf16 [M, width] (round to nearest even, the rounding gemm_b1 / gemm_b1tn apply to the fp32 form
+ * while they stage it) and read by those GEMMs as a bf16 operand: the GEMMs form the operand bits they form with the switch off, so
+ * every loss, output and gradient is BIT-IDENTICAL to the step with the switch off, and the accuracy statement of r4d_set_train_bf16
+ * holds unchanged.  No launch is added or removed.  A block is bf16 where its shape qualifies -- d % 256 == 0, M >= 32 rows in the
+ * step, and both consumers' shape contracts -- and stays fp32 otherwise (at d 64 nothing changes); where it qualifies the layer must
+ * carry the consumer's *_w3 planes (R4D_ERR_INVALID from the forward otherwise).  Layer 0's ln1, att, x_in, x_mid, pre, qkv, P and
+ * every gradient stay fp32.  The workspace of the three size queries shrinks by (12 * n_layer - 2) * M * d bytes in stored
+ * mode, and by 10 * M * d (+ 2 * M * d when n_layer >= 2) bytes under activations recompute.
+ * r4d_set_train_act_bf16(0 | 1) returns the previous setting; default 0; any other value is R4D_ERR_INVALID and changes nothing.
+ * Read like r4d_set_train_bf16: set it BEFORE the size query and keep it until the step's backward has been issued; a backward on the
+ * workspace of the most recent training forward under the other setting is refused (R4D_ERR_INVALID). */
+int r4d_set_train_act_bf16(int32_t on);
+int r4d_get_train_act_bf16(void);
+/* The single ops of that store, for per-op tests and tools (the kernels the step launches; not read by the switch).
+ * r4d_layernorm_bf16_f32: y_bf16_d [rows, d] = RN(LayerNorm(x)) with r4d_layernorm_f32's statistics; d % 256 == 0, 16-byte aligned.
+ * r4d_conv1d_bf16_act_f32: r4d_conv1d_bf16_f32 on x_bf16_d [M, K] bf16 (K % 32 == 0).  kind 0: y_d f32 [M,N]; 1: y_d = second_d + ...;
+ *   2: second_d f32 [M,N] <- the pre-activation, y_d bf16 [M,N] <- RN(gelu_new(pre)) (N even).
+ * r4d_weight_grad_bf16_act_f32: r4d_weight_grad_bf16_f32 on x_bf16_d [rows, in] bf16 with row stride ldx (bf16 elements, a multiple
+ *   of 8); the same workspace (r4d_weight_grad_bf16_workspace_bytes). */
+int r4d_layernorm_bf16_f32(const float* x_d, const float* w_d, const float* b_d, int32_t rows, int32_t d, float eps,
+                           uint16_t* y_bf16_d, void* stream);
+int r4d_conv1d_bf16_act_f32(const uint16_t* x_bf16_d, const uint16_t* w_bf16_d /* [N][K] */, const float* bias_d, int32_t M, int32_t K,
+                            int32_t N, int32_t kind, float* second_d, void* y_d, void* stream);
+int r4d_weight_grad_bf16_act_f32(const uint16_t* x_bf16_d, int32_t ldx, const float* dy_d, int32_t ldy, int32_t rows,
+                                 int32_t in_features, int32_t out_features, float* dw_d, float* db_d, void* workspace_d,
+                                 size_t workspace_bytes, void* stream);
+
 /* Scratch of one step: the activations the backward pass needs (16 * rows * d floats per layer + the attention
  * probabilities in stored mode) and the backward temporaries.  The SAME buffer goes to the forward and to the backward call. */
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts);

@@ -180,6 +180,11 @@ PROTOTYPES = {
     "r4d_get_train_attention_bf16": (c_int32, []),
     "r4d_set_train_head_bf16": (c_int32, [c_int32]),
     "r4d_get_train_head_bf16": (c_int32, []),
+    "r4d_set_train_act_bf16": (c_int32, [c_int32]),
+    "r4d_get_train_act_bf16": (c_int32, []),
+    "r4d_layernorm_bf16_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, c_float, _P, _P]),
+    "r4d_conv1d_bf16_act_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "r4d_weight_grad_bf16_act_f32": (c_int32, [_P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "r4d_lm_head_train_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "r4d_lm_head_train_f32": (c_int32, [_P, c_int32, c_int32, c_int32, POINTER(LMHeadC), _P, c_int32, c_float, _P, _P, _P, _P,
                                         c_size_t, _P]),

@@ -6,15 +6,10 @@
 
 namespace r4d {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));          // (bf16x2 and cvt_pk_bf16: gemm_common.h)
 typedef short s16x4 __attribute__((ext_vector_type(4)));            // what the transposing LDS read returns
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32: low half = bf16(a), RNE
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 // two fp32 -> packed (hi, hi), (mid, mid), (lo, lo)
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
     h = cvt_pk_bf16(x0, x1);

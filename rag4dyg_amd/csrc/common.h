@@ -88,7 +88,8 @@ struct ProfScope {
     X(B1_128x256, "tuning:encode_bf16:128x256x32") X(B1_128x128, "tuning:encode_bf16:128x128x32")                           \
     X(TB_FWD, "tuning:train_bf16:fwd") X(TB_DGRAD, "tuning:train_bf16:dgrad") X(TB_WGRAD, "tuning:train_bf16:wgrad") X(TB_WGRAD_FALLBACK, "tuning:train_bf16:wgrad_fallback") \
     X(TBA_NT, "tuning:train_bf16_attn:nt") X(TBA_NN, "tuning:train_bf16_attn:nn") \
-    X(TBH_LOGITS, "tuning:train_head_bf16:logits") X(TBH_DGRAD, "tuning:train_head_bf16:dgrad") X(TBH_WGRAD, "tuning:train_head_bf16:wgrad") X(TBH_WGRAD_FALLBACK, "tuning:train_head_bf16:wgrad_fallback")
+    X(TBH_LOGITS, "tuning:train_head_bf16:logits") X(TBH_DGRAD, "tuning:train_head_bf16:dgrad") X(TBH_WGRAD, "tuning:train_head_bf16:wgrad") X(TBH_WGRAD_FALLBACK, "tuning:train_head_bf16:wgrad_fallback") \
+    X(TAB_FWD, "tuning:train_act_bf16:fwd") X(TAB_WGRAD, "tuning:train_act_bf16:wgrad") X(TAB_LN, "tuning:train_act_bf16:ln") X(TAB_GELU, "tuning:train_act_bf16:gelu")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -153,6 +154,7 @@ struct S3Args {
     const float* A; const unsigned short* planes; float* C;
     const float* bias; const float* resid;
     int M, N, K, lda, ldc, ldr, epilogue;
+    int a_bf16;                       // gemm_b1 only: A is bf16 [M, K] (lda in bf16 elements) behind the float pointer (r4d_set_train_act_bf16)
     unsigned* kblk; int kb_hd;        // gemm_h2p, EPI_H2WORDS, N = 3 d: columns [d, 2d) go to the key-blocked K image instead (kb_hd = head_dim; 0 = off)
 };
 // y[M,N] = epilogue(x[M,K] . planes + bias) on dense rows (lda = K, ldc = ldr = N): the arguments of every planes kernel
@@ -179,12 +181,14 @@ int launch_gemm_h2p(const S3Args& a, const unsigned short* a_lines, bool out_lin
 int launch_split2_lines(const float* x, long long rows, int K, unsigned short* lines, hipStream_t s);
 // gemm_b1.hip: C = epilogue(RN_bf16(A) . RN_bf16(W)^T + bias), one bf16 MFMA per k-step (NOT fp32-accurate); a.planes = ONE bf16
 // plane [N][K] (plane 0 of the bf16x3 planes); the bf16x3 kernel's shape contract; epilogues none / GELU / residual
-// (training, r4d_set_train_bf16: also GELU_KEEP and GELU_GRAD)
+// (training, r4d_set_train_bf16: also GELU_KEEP and GELU_GRAD).  a.a_bf16 (r4d_set_train_act_bf16): A is already bf16 in memory -- the
+// same operand bits, one 16-byte load per item and no rounding; epilogues none / residual / GELU_KEEP / GELU_KEEP_BF16 (C as bf16)
 int launch_gemm_b1(const S3Args& a, hipStream_t stream);
 // gemm_b1tn.hip: out[I,J] (one slice) or partials [S][I][J] <- RN_bf16(X[M,I])^T . RN_bf16(dY[M,J]) over S slices of the M rows,
 // db_out (nullable) [J] or [S][J] <- column sums of the unrounded dY; gemm_s3tn's shape contract
+// x_bf16: X is bf16 [M, lda] behind the pointer (lda in bf16 elements, a multiple of 8): the same operand bits, no rounding
 int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out, int I, int J, int M, int lda, int ldb, int S,
-                     hipStream_t stream);
+                     hipStream_t stream, bool x_bf16 = false);
 // gemm_b1h.hip: the per-head attention products of the training steps on plain bf16 operands (r4d_set_train_attention_bf16; NOT
 // fp32-accurate): the GemmArgs of launch_gemm_f32's batched form -- both operand forms, epilogues none / scale-div, the three causal
 // flags, no bias, no residual
@@ -216,6 +220,7 @@ struct Conv1DOpts {
     float* skinny_scratch = nullptr;   // decode step: the split-K scratch of the weight-stream kernel (gemm_skinny_scratch_floats)
     bool counters_zeroed = false;      // ... whose ticket counters the caller cleared on this stream
     int bf16 = BF16_OFF;               // Bf16Use: who asks for plain bf16
+    bool x_bf16 = false;               // training, r4d_set_train_act_bf16: x is bf16 [M, W.in] behind the pointer; gemm_b1 only (else refused)
 };
 int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts = {});
 int launch_split3_planes(const float* w, int N, int K, long long ld_k, long long ld_n, unsigned short* planes, hipStream_t s);
@@ -240,10 +245,11 @@ static inline int emb_lg_rows(long long table_rows) {
 int launch_embedding_fix_to_f32(const unsigned long long* acc, long long n, long long table_rows, float* out, hipStream_t s);
 
 // ------------------------------------------------------------------ train.hip (the training forward / backward, shared with lm_head.hip)
-// The process-wide training switches as a value (r4d_set_train_attention, _activations, _bf16, _attention_bf16, _head_bf16): every
+// The process-wide training switches as a value (r4d_set_train_attention, _activations, _bf16, _attention_bf16, _head_bf16, _act_bf16): every
 // entry point reads them ONCE, through train_modes(), and hands the value down; nothing below an entry point looks at a global.
 // head_bf16 is the LM head's alone (lm_head.hip): the transformer's forward and backward do not look at it.
-struct TrainModes { int attention, activations, bf16, attn_bf16, head_bf16; };
+// act_bf16 acts only while bf16 is on: which saved activations are bf16 in memory (conv1d_route.h: train_act_bf16_block).
+struct TrainModes { int attention, activations, bf16, attn_bf16, head_bf16, act_bf16; };
 TrainModes train_modes();
 size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts);
 // output: EITHER out_meanpool_d [sum B, d] OR out_hidden_d [rows, d] (the ln_f output); the backward takes the matching gradient
@@ -266,9 +272,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
 int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* resid, const float* gelu_pre, hipStream_t s, int bf16 = 0);
 // dW[I,J] = x[M,I]^T . dy[M,J] on the kernel wgrad_route names, db (nullable) [J] = column sums of dy (train.hip).  `part`: room for
 // the slices' partials (gemm_tn_scratch_floats(I, J, M) floats); `red`: colsum_scratch_floats(M, J) floats (with db only).
-// `bf16`: TrainBf16
+// `bf16`: TrainBf16.  `x_bf16`: x is bf16 [M, lda] behind the pointer (a block train_act_bf16_block names: gemm_b1tn takes it)
 int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part, float* red,
-                hipStream_t s, int bf16 = 0);
+                hipStream_t s, int bf16 = 0, bool x_bf16 = false);
 int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, const float* wte, const float* wpe, int vocab, int B,
                            int T, int d, const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s);
 
@@ -293,6 +299,8 @@ int topk_rows(const T* vals, const long long* idx_in, int rows, int n, long long
 // ------------------------------------------------------------------ encoder_ops.hip
 int launch_layernorm(const float* x, const float* w, const float* b, int rows, int d, float eps, float* y,
                      hipStream_t s);
+// launch_layernorm's statistics and arithmetic (its 16-byte-lane kernel), y as bf16 [rows, d] (RNE), 16 bytes per store; d % 256 == 0
+int launch_layernorm_bf16(const float* x, const float* w, const float* b, int rows, int d, float eps, unsigned short* y, hipStream_t s);
 bool layernorm_lines_supported(int d);
 int launch_layernorm_lines(const float* x, const float* w, const float* b, int rows, int d, float eps, unsigned short* y_lines, hipStream_t s);
 constexpr int ATT_MAXG = 16;

@@ -13,7 +13,10 @@ enum GemmEpilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_SCALE_DIV 
                     EPI_GELU_KEEP = 5, EPI_GELU_GRAD = 6,
                     // gemm_h2 only: C receives the result as uint32 "h2 words" (fp16 hi | fp16 lo' << 16 of value / 4: csrc/h2.h), the
                     // operand format of attention_h2.hip
-                    EPI_H2WORDS = 7 };
+                    EPI_H2WORDS = 7,
+                    // gemm_b1 only (training, r4d_set_train_act_bf16): GELU_KEEP whose gelu(v) leaves as bf16 [M, N] (RNE; ldc in bf16 elements);
+                    // the pre-activation stays fp32.  Appended: route conditions compare against EPI_RESIDUAL's ordering
+                    EPI_GELU_KEEP_BF16 = 8 };
 
 extern int g_gemm_split3;             // Conv1D arithmetic (r4d_set_gemm_split3): 0 exact-f32 MFMA, 1 bf16x3 planes, 2 f16x2 planes (bf16x3 where a layer carries no f16 planes)
 
@@ -38,6 +41,16 @@ static inline bool gemm_s3tn_supported(int I, int J, int M, int lda, int ldb) {
 static inline bool gemm_b1tn_supported(int I, int J, int M, int lda, int ldb) {
     return I >= 128 && I % 128 == 0 && J >= 256 && J % 256 == 0 && M >= 32 && lda >= I && ldb >= J && lda % 4 == 0 && ldb % 4 == 0 &&
            ((long long)M + 64) * lda < (1ll << 29) && ((long long)M + 64) * ldb < (1ll << 29);
+}
+// The saved activations a bf16 training step may keep as bf16 [M, width] (r4d_set_train_act_bf16): a block's ln1 (layers
+// >= 1: layer 0's leaves the fused embedding kernels), its ln2 and its f.  ONE rule for the layout, the forward and the backward, on
+// shapes alone (the size query has no weights): both switches on (`on`), the producer's 16-byte bf16 stores (d % 256 == 0), and
+// the block's two consumers take it -- gemm_b1 with a bf16 A operand forward, gemm_b1tn with a bf16 X operand for the weight gradient
+enum TrainActBlock { ACT_LN1 = 0, ACT_LN2 = 1, ACT_F = 2 };
+static inline bool train_act_bf16_block(int which, int layer, bool on, long long M, int d) {
+    if (!on || d <= 0 || d % 256 != 0 || M < 32 || M >= (1ll << 29) || (which == ACT_LN1 && layer < 1)) return false;
+    const int m = (int)M, in = which == ACT_F ? 4 * d : d, out = which == ACT_F ? d : which == ACT_LN1 ? 3 * d : 4 * d;
+    return gemm_b1_supported(m, in, out) && gemm_b1tn_supported(in, out, m, in, out);
 }
 // gemm_f32.hip: slices of the exact-f32 weight-gradient GEMM C[M,N] = A[Kt,M]^T . B[Kt,N] over its Kt rows (an empty problem, which the launchers refuse: one)
 static inline int tn_splits(int M, int N, int Kt) {

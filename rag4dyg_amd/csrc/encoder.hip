@@ -22,10 +22,18 @@ int g_encode_bf16 = 0;                // r4d_set_encode_bf16: the encoder calls'
 int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts) {
     const int K = W.in, N = W.out;
     const GemmRoute route = conv1d_route(W, M, epilogue, opts.skinny_scratch != nullptr, opts.bf16);
+    R4D_REQUIRE(!(opts.x_bf16 || epilogue == EPI_GELU_KEEP_BF16) || route == ROUTE_B1,
+                "conv1d: a bf16 activation block (train-act-bf16) needs the plain-bf16 GEMM, but this [%d, %d] weight carries no bf16x3 planes (*_w3)", K, N);
     switch (route) {
         case ROUTE_B1:
             if (opts.bf16 == BF16_TRAIN) R4D_BRANCH(TB_FWD);
             else if (opts.bf16 == BF16_TRAIN_HEAD) R4D_BRANCH(TBH_LOGITS);
+            if (opts.x_bf16) {                                      // a bf16 block of the training step (r4d_set_train_act_bf16)
+                S3Args a = s3_args(x, W.w3, W.b, resid, M, K, N, epilogue, y);
+                a.a_bf16 = 1;
+                R4D_BRANCH(TAB_FWD);
+                return launch_gemm_b1(a, s);
+            }
             return launch_gemm_b1(s3_args(x, W.w3, W.b, resid, M, K, N, epilogue, y), s);
         case ROUTE_SKINNY:
             return launch_gemm_skinny(x, W.wT, W.b, resid, M, K, N, epilogue, y, opts.skinny_scratch, s, nullptr, nullptr, 0.f,
@@ -674,6 +682,12 @@ int r4d_layernorm_lines_f32(const float* x_d, const float* w_d, const float* b_d
                             uint16_t* y_lines_d, void* stream) {
     R4D_REQUIRE(x_d && w_d && b_d && y_lines_d, "layernorm_lines: null pointer");
     return launch_layernorm_lines(x_d, w_d, b_d, rows, d, eps, y_lines_d, (hipStream_t)stream);
+}
+
+int r4d_layernorm_bf16_f32(const float* x_d, const float* w_d, const float* b_d, int32_t rows, int32_t d, float eps,
+                           uint16_t* y_bf16_d, void* stream) {
+    R4D_REQUIRE(x_d && w_d && b_d && y_bf16_d, "layernorm_bf16: null pointer");
+    return launch_layernorm_bf16(x_d, w_d, b_d, rows, d, eps, y_bf16_d, (hipStream_t)stream);
 }
 
 int r4d_conv1d_f32(const float* x_d, const float* w_d, const float* w_t_d, const float* bias_d, const float* residual_d,

@@ -63,7 +63,25 @@ __device__ __forceinline__ void store_lines4(float* y_rows, long long row, int d
     *reinterpret_cast<uint2*>(dst + 64) = make_uint2(l0, l1);
 }
 
-template <int NQ, bool LINES = false>
+// one lane's four outputs of a quad (ONE spelling for the fp32, line and bf16 stores: the same bits in each)
+__device__ __forceinline__ float4 ln4_out(float4 v, float mean, float rstd, float4 ww, float4 bb) {
+    return make_float4((v.x - mean) * rstd * ww.x + bb.x, (v.y - mean) * rstd * ww.y + bb.y,
+                       (v.z - mean) * rstd * ww.z + bb.z, (v.w - mean) * rstd * ww.w + bb.w);
+}
+__device__ __forceinline__ unsigned ln_cvt_pk_bf16(float a, float b) {   // v_cvt_pk_bf16_f32: low half = bf16(a), RNE; a NaN stays a NaN
+    typedef float f2_ __attribute__((ext_vector_type(2)));
+    typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
+    const f2_ v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2_));
+}
+__device__ __forceinline__ unsigned lane_swap1(unsigned x) {            // the value of lane ^ 1 (quad_perm [1,0,3,2])
+    return (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true);
+}
+
+// BF16 (training, r4d_set_train_act_bf16): y as bf16 [rows, d], the RNE rounding of the fp32 form's values.  A lane's four values are
+// 8 bytes; a lane pair swaps halves over two quads (i, i + 1) so that the even lane stores the 16 bytes of quad i and the odd lane
+// those of quad i + 1 (an odd last quad: the even lane alone)
+template <int NQ, bool LINES = false, bool BF16 = false>
 __global__ __launch_bounds__(256) void ln4_kernel(const float* __restrict__ x_in, int rows, int d, const float* __restrict__ w,
                                                   const float* __restrict__ b, float eps, float* __restrict__ y_out) {
     const int lane = threadIdx.x & 63;
@@ -86,13 +104,35 @@ __global__ __launch_bounds__(256) void ln4_kernel(const float* __restrict__ x_in
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
     const float rstd = rsqrtf(wave_sum(q) / (float)d + eps);
+    if constexpr (BF16) {
+        static_assert(NQ % 2 == 0 && !LINES, "quads in pairs");
+        unsigned short* yb = reinterpret_cast<unsigned short*>(y_out) + (long long)row * d;
+        const bool odd = lane & 1;
+#pragma unroll
+        for (int i = 0; i < NQ; i += 2)
+            if (i < nq) {                                              // (wave-uniform)
+                const bool two = i + 1 < nq;
+                const float4* w4 = reinterpret_cast<const float4*>(w);
+                const float4* b4 = reinterpret_cast<const float4*>(b);
+                const float4 ya = ln4_out(v[i], mean, rstd, w4[lane + 64 * i], b4[lane + 64 * i]);
+                const unsigned a0 = ln_cvt_pk_bf16(ya.x, ya.y), a1 = ln_cvt_pk_bf16(ya.z, ya.w);
+                unsigned b0 = 0u, b1 = 0u;
+                if (two) {
+                    const float4 y2 = ln4_out(v[i + 1], mean, rstd, w4[lane + 64 * (i + 1)], b4[lane + 64 * (i + 1)]);
+                    b0 = ln_cvt_pk_bf16(y2.x, y2.y); b1 = ln_cvt_pk_bf16(y2.z, y2.w);
+                }
+                const unsigned r0 = lane_swap1(odd ? a0 : b0), r1 = lane_swap1(odd ? a1 : b1);
+                if (!odd) *reinterpret_cast<uint4*>(yb + 4 * lane + 256 * i) = make_uint4(a0, a1, r0, r1);
+                else if (two) *reinterpret_cast<uint4*>(yb + 4 * (lane - 1) + 256 * (i + 1)) = make_uint4(r0, r1, b0, b1);
+            }
+        return;
+    }
     float4* yr = reinterpret_cast<float4*>(y_out + (long long)row * d) + lane;
 #pragma unroll
     for (int i = 0; i < NQ; ++i)
         if (i < nq) {
             const float4 ww = reinterpret_cast<const float4*>(w)[lane + 64 * i], bb = reinterpret_cast<const float4*>(b)[lane + 64 * i];
-            const float4 y4 = make_float4((v[i].x - mean) * rstd * ww.x + bb.x, (v[i].y - mean) * rstd * ww.y + bb.y,
-                                          (v[i].z - mean) * rstd * ww.z + bb.z, (v[i].w - mean) * rstd * ww.w + bb.w);
+            const float4 y4 = ln4_out(v[i], mean, rstd, ww, bb);
             if constexpr (LINES) store_lines4(y_out, row, d, 4 * lane + 256 * i, y4.x, y4.y, y4.z, y4.w);
             else yr[64 * i] = y4;
         }
@@ -110,6 +150,22 @@ int launch_layernorm_lines(const float* x, const float* w, const float* b, int r
     else if (d <= 1024) { R4D_BRANCH(LN4_4); hipLaunchKernelGGL((ln4_kernel<4, true>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, rows, d, w, b, eps, y); }
     else { R4D_BRANCH(LN4_8); hipLaunchKernelGGL((ln4_kernel<8, true>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, rows, d, w, b, eps, y); }
     R4D_CHECK_LAUNCH("layernorm_lines");
+    return R4D_OK;
+}
+
+// LayerNorm whose output is bf16 [rows, d]: launch_layernorm's 16-byte-lane kernel with the rounding at the store; d % 256 == 0
+int launch_layernorm_bf16(const float* x, const float* w, const float* b, int rows, int d, float eps, unsigned short* y_bf16, hipStream_t s) {
+    R4D_REQUIRE(x && w && b && y_bf16 && d >= 256 && d % 256 == 0 && d <= 64 * MAXV &&
+                (((uintptr_t)x | (uintptr_t)y_bf16 | (uintptr_t)w | (uintptr_t)b) & 15) == 0,
+                "layernorm_bf16: d=%d must be a multiple of 256 (<= %d) and the pointers 16-byte aligned", d, 64 * MAXV);
+    if (rows <= 0) return R4D_OK;
+    ProfScope prof(PK_LAYERNORM, 6.0 * rows * d, s);            // bytes: read x + write y as bf16
+    float* y = reinterpret_cast<float*>(y_bf16);
+    R4D_BRANCH(TAB_LN);
+    if (d <= 512) hipLaunchKernelGGL((ln4_kernel<2, false, true>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, rows, d, w, b, eps, y);
+    else if (d <= 1024) hipLaunchKernelGGL((ln4_kernel<4, false, true>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, rows, d, w, b, eps, y);
+    else hipLaunchKernelGGL((ln4_kernel<8, false, true>), dim3(cdiv(rows, 4)), dim3(256), 0, s, x, rows, d, w, b, eps, y);
+    R4D_CHECK_LAUNCH("layernorm_bf16");
     return R4D_OK;
 }
 

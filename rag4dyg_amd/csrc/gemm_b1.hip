@@ -28,7 +28,11 @@ struct B1Shape { int M, N, K, lda, ldc, ldr; };
 // Registers: two workgroups per CU (<= 128 VGPRs) -- except the 128 x 256 tile with an epilogue that READS the second buffer
 // (residual; training: the GELU derivative), whose 64 accumulators and prefetched second-buffer values do not fit 128 without
 // scratch: those keep the whole file (one workgroup per CU)
-template <int BM, int BN, int WGM, int WGN, int EPI>
+//
+// ABF (training, r4d_set_train_act_bf16): A is bf16 [M, lda] in memory -- the bits its producer rounded once (the same RNE) -- behind
+// the float pointer: an item is ONE 16-byte load of eight bf16 where the fp32 form has two loads of four floats and four
+// conversions; the same LDS image, k order, MFMA sequence and epilogues.  The descriptor's range is the bf16 block's own length.
+template <int BM, int BN, int WGM, int WGN, int EPI, bool ABF = false>
 __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD) && BN == 256) ? 2 : 4) void gemm_b1_kernel(
     const float* __restrict__ Ag, const unsigned short* __restrict__ Bp, float* __restrict__ Cg,
     const float* __restrict__ biasg, const float* __restrict__ residg, const B1Shape g) {
@@ -38,6 +42,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
     constexpr int NIA = BM * 4 / NTHREADS, NIB = BN * 4 / NTHREADS;   // (row, 8-k chunk) items per thread
     constexpr int A_TILE = BM * 4, B_TILE = BN * 4;                   // uint4 units (a row = 4 chunks of 16 bytes)
     constexpr int STAGE = A_TILE + B_TILE;
+    constexpr int ASZ = ABF ? 2 : 4, NLA = ABF ? 1 : 2;                // bytes per A element in memory; 16-byte loads per A item
     static_assert(NIA >= 1 && NIB >= 1 && NIA <= 2 && NIB <= 2 && TM >= 1 && TN >= 1, "tile");
     __shared__ u32x4 lds[NBUF * STAGE];
 
@@ -54,7 +59,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
 #pragma unroll
     for (int i = 0; i < NIA; ++i) {
         const int idx = tid + i * NTHREADS, row = idx >> 2, c = idx & 3;
-        a_off[i] = (min(m0 + row, g.M - 1) * g.lda + c * 8) * 4;
+        a_off[i] = (min(m0 + row, g.M - 1) * g.lda + c * 8) * ASZ;
         a_dst[i] = row * 4 + (c ^ ((row >> 2) & 3));
     }
 #pragma unroll
@@ -64,17 +69,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
         b_dst[i] = A_TILE + row * 4 + (c ^ ((row >> 2) & 3));
     }
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(Ag), 0, (int)(((long long)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
+        const_cast<float*>(Ag), 0, (int)(((long long)(g.M - 1) * g.lda + g.K) * ASZ), 0x00020000);
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned short*>(Bp), 0, (int)((long long)g.N * g.K * 2), 0x00020000);
 
-    u32x4 ra[NIA][2], rb[NIB];                                        // one k-tile in flight: 8 fp32 of A, 8 bf16 of W per item
+    u32x4 ra[NIA][NLA], rb[NIB];                                      // one k-tile in flight: 8 fp32 (ABF: 8 bf16) of A, 8 bf16 of W per item
 #define B1_LOAD(KT)                                                                                \
     {                                                                                              \
         const int kt_ = min((KT), nkt - 1);                                                        \
         _Pragma("unroll") for (int i = 0; i < NIA; ++i) {                                          \
-            ra[i][0] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_off[i], kt_ * (BK * 4), 0); \
-            ra[i][1] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_off[i] + 16, kt_ * (BK * 4), 0); \
+            ra[i][0] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_off[i], kt_ * (BK * ASZ), 0); \
+            if constexpr (!ABF) ra[i][NLA - 1] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_off[i] + 16, kt_ * (BK * ASZ), 0); \
         }                                                                                          \
         _Pragma("unroll") for (int i = 0; i < NIB; ++i)                                            \
             rb[i] = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_off[i], kt_ * (BK * 2), 0);    \
@@ -83,8 +88,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
     {                                                                                              \
         u32x4* st_ = lds + (STG) * STAGE;                                                         \
         _Pragma("unroll") for (int i = 0; i < NIA; ++i) {                                          \
+            if constexpr (ABF) { st_[a_dst[i]] = ra[i][0]; continue; }                             \
             /* (cast the WHOLE vector: __builtin_bit_cast on an ext-vector element reads element 0) */ \
-            const f32x4 lo_ = __builtin_bit_cast(f32x4, ra[i][0]), hi_ = __builtin_bit_cast(f32x4, ra[i][1]); \
+            const f32x4 lo_ = __builtin_bit_cast(f32x4, ra[i][0]), hi_ = __builtin_bit_cast(f32x4, ra[i][NLA - 1]); \
             u32x4 h_;                                                                             \
             h_[0] = cvt_pk_bf16(lo_[0], lo_[1]); h_[1] = cvt_pk_bf16(lo_[2], lo_[3]);              \
             h_[2] = cvt_pk_bf16(hi_[0], hi_[1]); h_[3] = cvt_pk_bf16(hi_[2], hi_[3]);              \
@@ -135,7 +141,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
     //   k-step 1: its MFMAs with the global loads of k-tile kt+D+1 between them;
     //   barrier.
     // sched_group_barrier pins that interleaving, as in gemm_s3_kernel.
-    constexpr int NMF = TM * TN, NFR = TM + TN, NDW = NIA + NIB, NVM = 2 * NIA + NIB;
+    constexpr int NMF = TM * TN, NFR = TM + TN, NDW = NIA + NIB, NVM = NLA * NIA + NIB;
     constexpr int FR_PER = (NFR + NMF - 1) / NMF, DW_PER = (NDW + NMF - 1) / NMF, VM_PER = (NVM + NMF - 1) / NMF;
 #define B1_ITER(CUR, WR)                                                                           \
     {                                                                                              \
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
         _Pragma("unroll") for (int m_ = 0; m_ < NMF; ++m_) {                                       \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                     \
             __builtin_amdgcn_sched_group_barrier(0x100, FR_PER, 0);                                \
-            __builtin_amdgcn_sched_group_barrier(0x002, 2 * NIA, 0);                               \
+            if (!ABF) __builtin_amdgcn_sched_group_barrier(0x002, 2 * NIA, 0);                     \
             __builtin_amdgcn_sched_group_barrier(0x200, DW_PER, 0);                                \
             if (B1_LOAD_EARLY) __builtin_amdgcn_sched_group_barrier(0x020, VM_PER, 0);             \
         }                                                                                          \
@@ -193,6 +199,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
 // what the encoder forward uses, and the two kinds of the training step (c_fc forward with the kept pre-activation; the mlp
 // c_proj data gradient times gelu_new'(pre))
 #define B1_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_GRAD)
+// with a bf16 A operand: the training forward's three consumers of a bf16 block (c_attn, c_fc, mlp c_proj)
+#define B1_KINDS_ABF(X, L) X(L, EPI_NONE) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_KEEP_BF16)
 template <int BM, int BN, int WGM, int WGN>
 static int launch_b1(const S3Args& a, hipStream_t stream) {
     const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
@@ -202,7 +210,15 @@ static int launch_b1(const S3Args& a, hipStream_t stream) {
 #define B1_LAUNCH_(E)                                                                              \
     hipLaunchKernelGGL((gemm_b1_kernel<BM, BN, WGM, WGN, E>), dim3(tiles), dim3(64 * WGM * WGN), 0, stream, a.A, a.planes, a.C, \
                        a.bias, a.resid, sh)
-    R4D_EPI_DISPATCH(a.epilogue, B1_KINDS, B1_LAUNCH_, set_error("gemm_b1: epilogue %d has no instantiation", a.epilogue); return R4D_ERR_INVALID;)
+#define B1_LAUNCH_ABF_(E)                                                                          \
+    hipLaunchKernelGGL((gemm_b1_kernel<BM, BN, WGM, WGN, E, true>), dim3(tiles), dim3(64 * WGM * WGN), 0, stream, a.A, a.planes, a.C, \
+                       a.bias, a.resid, sh)
+    if (a.a_bf16) {
+        R4D_EPI_DISPATCH(a.epilogue, B1_KINDS_ABF, B1_LAUNCH_ABF_, set_error("gemm_b1: epilogue %d has no instantiation with a bf16 A operand", a.epilogue); return R4D_ERR_INVALID;)
+    } else {
+        R4D_EPI_DISPATCH(a.epilogue, B1_KINDS, B1_LAUNCH_, set_error("gemm_b1: epilogue %d has no instantiation", a.epilogue); return R4D_ERR_INVALID;)
+    }
+#undef B1_LAUNCH_ABF_
 #undef B1_LAUNCH_
     R4D_CHECK_LAUNCH("gemm_b1");
     return R4D_OK;
@@ -212,7 +228,9 @@ int launch_gemm_b1(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.A && a.planes && a.C, "gemm_b1: null pointer");
     R4D_REQUIRE(gemm_b1_supported(a.M, a.K, a.N), "gemm_b1: unsupported shape M=%d K=%d N=%d (K %% 32 == 0 wanted)", a.M, a.K, a.N);
     R4D_REQUIRE(a.lda % 4 == 0 && ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.planes % 16) == 0, "gemm_b1: alignment");
-    R4D_REQUIRE((a.epilogue != EPI_RESIDUAL && a.epilogue != EPI_GELU_KEEP && a.epilogue != EPI_GELU_GRAD) || a.resid, "gemm_b1: epilogue %d needs the second buffer", a.epilogue);
+    R4D_REQUIRE((a.epilogue != EPI_RESIDUAL && a.epilogue != EPI_GELU_KEEP && a.epilogue != EPI_GELU_GRAD && a.epilogue != EPI_GELU_KEEP_BF16) || a.resid, "gemm_b1: epilogue %d needs the second buffer", a.epilogue);
+    R4D_REQUIRE(!a.a_bf16 || a.lda % 8 == 0, "gemm_b1: a bf16 A operand wants lda %% 8 == 0 (lda=%d)", a.lda);
+    R4D_REQUIRE(a.epilogue != EPI_GELU_KEEP_BF16 || (a.N % 2 == 0 && a.ldc % 2 == 0 && ((uintptr_t)a.C % 4) == 0), "gemm_b1: the bf16 output wants even N and ldc");
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("R4D_GEMM_B1_TILE"); forced = e ? atoi(e) : -1; }   // tuning aid: 0 / 1 forces a tile
     const int t = (forced == 0 || forced == 1) ? forced : pick_tile_128(a.M, a.N);
@@ -231,6 +249,16 @@ int r4d_conv1d_bf16_f32(const float* x_d, const uint16_t* w_bf16_d, const float*
                         int32_t K, int32_t N, int32_t epilogue, float* y_d, void* stream) {
     R4D_REQUIRE(epilogue >= 0 && epilogue <= 2, "conv1d_bf16: epilogue %d not in {0,1,2}", epilogue);
     return launch_gemm_b1(s3_args(x_d, w_bf16_d, bias_d, residual_d, M, K, N, epilogue, y_d), (hipStream_t)stream);
+}
+
+int r4d_conv1d_bf16_act_f32(const uint16_t* x_bf16_d, const uint16_t* w_bf16_d, const float* bias_d, int32_t M, int32_t K, int32_t N,
+                            int32_t kind, float* second_d, void* y_d, void* stream) {
+    R4D_REQUIRE(kind >= 0 && kind <= 2, "conv1d_bf16_act: kind %d not in {0 none, 1 residual, 2 gelu-keep with a bf16 output}", kind);
+    R4D_REQUIRE(kind == 0 || (second_d && (void*)second_d != y_d), "conv1d_bf16_act: kind %d needs the second buffer", kind);
+    S3Args a = s3_args(reinterpret_cast<const float*>(x_bf16_d), w_bf16_d, bias_d, kind ? second_d : nullptr, M, K, N,
+                       kind == 2 ? EPI_GELU_KEEP_BF16 : kind == 1 ? EPI_RESIDUAL : EPI_NONE, (float*)y_d);
+    a.a_bf16 = 1;
+    return launch_gemm_b1(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

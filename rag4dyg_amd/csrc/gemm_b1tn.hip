@@ -25,6 +25,9 @@ namespace r4d {
 struct B1TnShape : TnShape {};                                         // (its own name: the kernel's symbol carries it)
 
 // `dbp` (nullable): partial column sums of dY per slice, [slices][J], by the workgroups of the first I tile (gemm_s3tn.hip)
+// XBF (training, r4d_set_train_act_bf16): X is bf16 [M, lda] in memory -- the bits its producer rounded once -- behind the float pointer:
+// the A item is ONE 16-byte load of eight bf16 and no rounding; dY stays fp32 (db sums its unrounded values).  Same image, slices, order.
+template <bool XBF>
 __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restrict__ Xg, const float* __restrict__ Yg,
                                                            float* __restrict__ Cg, const B1TnShape g, float* __restrict__ dbp) {
     constexpr int BI = 128, BJ = 256, BK = 32, WI = 64, WJ = 64, TI = 2, TJ = 2;
@@ -43,6 +46,8 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
     // staging: a thread owns 8 consecutive features of one token: the A item (TN_A_ITEM), B items (token = idx >> 5,
     // chunk = idx & 31) for idx = tid, tid + 512.  Rows past M: the buffer range check returns zeros.
     TN_A_ITEM
+    constexpr int XSZ = XBF ? 2 : 4;                                  // bytes per X element in memory
+    const int ax_voff = XBF ? (a_voff >> 1) : a_voff;
     // (the second B item is 16 tokens further down: the same swizzle class, so both of its addresses are the first one's plus a
     //  uniform term -- kept as such, every VGPR counts under the 128 cap)
     const int b_tok = tid >> 5, b_ch = tid & 31;
@@ -50,18 +55,18 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
     const int b_dst0 = A_IMG + b_tok * B_ROW + ((b_ch ^ ((b_tok & 3) << 2)) << 4);
     // descriptors end at row M: whole rows beyond it are out of range (zeros).  With lda > I / ldb > J the last row's range ends
     // behind its last feature, inside the caller's wider buffer.
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xg), 0, (int)(((long long)(g.M - 1) * g.lda + g.I) * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xg), 0, (int)(((long long)(g.M - 1) * g.lda + g.I) * XSZ), 0x00020000);
     const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Yg), 0, (int)(((long long)(g.M - 1) * g.ldb + g.J) * 4), 0x00020000);
-    u32x4 ra[2], rb[2][2];
+    u32x4 ra[XBF ? 1 : 2], rb[2][2];
     const bool do_cs = dbp != nullptr && ti == 0;                     // workgroup-uniform
     float cs[8];                                                      // TN_COLSUM
 #pragma unroll
     for (int e = 0; e < 8; ++e) cs[e] = 0.f;
 #define BT_LOAD(KT)                                                                                \
     {   /* the k-tile's row offset travels in the VECTOR offset: the range check then covers it whatever it does with a scalar one */ \
-        const int so_a_ = (m_lo + (KT) * BK) * g.lda * 4, so_b_ = (m_lo + (KT) * BK) * g.ldb * 4; \
-        ra[0] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_voff + so_a_, 0, 0);               \
-        ra[1] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, a_voff + so_a_ + 16, 0, 0);          \
+        const int so_a_ = (m_lo + (KT) * BK) * g.lda * XSZ, so_b_ = (m_lo + (KT) * BK) * g.ldb * 4; \
+        ra[0] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, ax_voff + so_a_, 0, 0);              \
+        if constexpr (!XBF) ra[XBF ? 0 : 1] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, ax_voff + so_a_ + 16, 0, 0); \
         _Pragma("unroll") for (int r = 0; r < 2; ++r) {                                            \
             rb[r][0] = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_voff0 + r * b_vstep + so_b_, 0, 0); \
             rb[r][1] = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, b_voff0 + r * b_vstep + so_b_ + 16, 0, 0); \
@@ -77,7 +82,7 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
     {                                                                                              \
         unsigned char* st_ = lds + (STG) * STAGE;                                                  \
         u32x4 h_;                                                                                  \
-        BT_ROUND8(ra[0], ra[1], h_)                                                                \
+        if constexpr (XBF) h_ = ra[0]; else BT_ROUND8(ra[0], ra[XBF ? 0 : 1], h_)                  \
         *reinterpret_cast<u32x4*>(st_ + a_dst) = h_;                                               \
         _Pragma("unroll") for (int r = 0; r < 2; ++r) {                                            \
             BT_ROUND8(rb[r][0], rb[r][1], h_)                                                      \
@@ -134,14 +139,16 @@ __global__ __launch_bounds__(512, 4) void gemm_b1tn_kernel(const float* __restri
 // out (S slices with rows: [S][I][J], else [I][J]) <- RN(X)^T . RN(dY) per slice, db_out (nullable; [S][J] / [J]) <- the slices' column
 // sums of dY.  train.hip (wgrad_b1tn) sizes the slices and sums the partials.
 int launch_gemm_b1tn(const float* X, const float* dY, float* out, float* db_out, int I, int J, int M, int lda, int ldb, int S,
-                     hipStream_t stream) {
+                     hipStream_t stream, bool x_bf16) {
     R4D_REQUIRE(X && dY && out && S >= 1, "gemm_b1tn: null pointer");
+    R4D_REQUIRE(!x_bf16 || lda % 8 == 0, "gemm_b1tn: a bf16 X operand wants lda %% 8 == 0 (lda=%d)", lda);
     R4D_REQUIRE(gemm_b1tn_supported(I, J, M, lda, ldb), "gemm_b1tn: unsupported shape I=%d J=%d M=%d lda=%d ldb=%d (I %% 128 == 0, J %% 256 == 0, M >= 32 wanted)", I, J, M, lda, ldb);
     R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)db_out % 16) == 0,
                 "gemm_b1tn: 16-byte alignment");
     const B1TnShape sh{tn_shape(I, J, M, lda, ldb, S)};
     ProfScope prof(PK_GEMM_B1TN, 2.0 * (double)I * J * M, stream);
-    hipLaunchKernelGGL(gemm_b1tn_kernel, tn_grid(sh), dim3(512), 0, stream, X, dY, out, sh, db_out);
+    if (x_bf16) hipLaunchKernelGGL(gemm_b1tn_kernel<true>, tn_grid(sh), dim3(512), 0, stream, X, dY, out, sh, db_out);
+    else hipLaunchKernelGGL(gemm_b1tn_kernel<false>, tn_grid(sh), dim3(512), 0, stream, X, dY, out, sh, db_out);
     R4D_CHECK_LAUNCH("gemm_b1tn");
     return R4D_OK;
 }

@@ -42,16 +42,23 @@
 {
     static_assert(EPI != EPI_H2WORDS || EPILOGUE_PAIR_WORDS, "the h2-word output forms its two words from the pair");
     // the second buffer is read (residual; training backward: the pre-activation) or written (training forward: the pre-activation)
-    constexpr bool USES_R = EPI == EPI_RESIDUAL || EPI == EPI_GELU_KEEP || EPI == EPI_GELU_GRAD;
+    // GELU_KEEP_BF16 (gemm_b1 only): GELU_KEEP whose C is bf16 [M, N] -- ldc counts bf16 elements, N and ldc are even
+    constexpr bool KEEPS = EPI == EPI_GELU_KEEP || EPI == EPI_GELU_KEEP_BF16, C_BF16 = EPI == EPI_GELU_KEEP_BF16;
+    constexpr bool USES_R = EPI == EPI_RESIDUAL || KEEPS || EPI == EPI_GELU_GRAD;
     constexpr bool LOADS_R = EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD;
+    constexpr int C_SZ = C_BF16 ? 2 : 4;
     const bool interior = (m0 + BM <= g.M) & (n0 + BN <= g.N);       // wave-uniform
     if (interior) {
         // buffer stores / loads from the tile's origin: the lane's byte offset is computed once (voffset), the
         // (compile-time row) * ld part lives on the scalar unit (soffset) -- one VALU instruction per element (the bias add)
-        const int lane_c = ((wm * WM + 4 * lh) * g.ldc + wn * WN + li) * 4;
+        // (bf16 C: a lane pair exchanges one value per register pair, so that the even lane stores columns (li, li + 1) of row r2
+        //  and the odd lane the same columns of row r2 + 1 as ONE 32-bit word each: the row of the odd lane is one further down)
+        const int lane_c = C_BF16 ? ((wm * WM + 4 * lh + (li & 1)) * g.ldc + wn * WN + (li & ~1)) * 2
+                                  : ((wm * WM + 4 * lh) * g.ldc + wn * WN + li) * 4;
         const int lane_r = ((wm * WM + 4 * lh) * g.ldr + wn * WN + li) * 4;
         const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            C + (long long)m0 * g.ldc + n0, 0, ((BM - 1) * g.ldc + BN) * 4, 0x00020000);
+            C_BF16 ? (float*)((unsigned short*)C + (long long)m0 * g.ldc + n0) : C + (long long)m0 * g.ldc + n0, 0,
+            ((BM - 1) * g.ldc + BN) * C_SZ, 0x00020000);
         const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(       // (unused kinds: an empty range over C)
             USES_R ? const_cast<float*>(residg) + (long long)m0 * g.ldr + n0 : C, 0,
             USES_R ? ((BM - 1) * g.ldr + BN) * 4 : 0, 0x00020000);
@@ -70,7 +77,7 @@
 #pragma unroll
                 for (int r2 = 0; r2 < 16; r2 += 2) {
                     f32x2 v2 = {EPILOGUE_VALUE(i, j, r2) + bias, EPILOGUE_VALUE(i, j, r2 + 1) + bias};
-                    if (EPI == EPI_GELU_KEEP) {                       // training forward: the pre-activation goes to the second buffer
+                    if (KEEPS) {                                      // training forward: the pre-activation goes to the second buffer
 #pragma unroll
                         for (int h2 = 0; h2 < 2; ++h2) {
                             const int r = r2 + h2;
@@ -78,13 +85,21 @@
                                                                   ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0);
                         }
                     }
-                    if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v2 = gelu_new2(v2);
+                    if (EPI == EPI_GELU || KEEPS) v2 = gelu_new2(v2);
                     else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
                     else if (EPI == EPI_GELU_GRAD) { v2.x *= gelu_new_grad(res[r2]); v2.y *= gelu_new_grad(res[r2 + 1]); }
 #ifdef EPILOGUE_SCALE_DIVISOR
                     else if (EPI == EPI_SCALE_DIV) { v2.x = v2.x / EPILOGUE_SCALE_DIVISOR; v2.y = v2.y / EPILOGUE_SCALE_DIVISOR; }
 #endif
                     else if (EPI == EPI_HALF_PLUS) { v2.x = (v2.x + 1.0f) / 2.0f; v2.y = (v2.y + 1.0f) / 2.0f; }     // train_retriever.py:438
+                    if constexpr (C_BF16) {                           // rows r2 / r2 + 1 of this lane's column -> one word of two columns
+                        const float vx = v2.x, vy = v2.y;
+                        const float send = (li & 1) ? vx : vy;
+                        const float recv = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+                        const unsigned word = (li & 1) ? cvt_pk_bf16(recv, vy) : cvt_pk_bf16(vx, recv);
+                        __builtin_amdgcn_raw_buffer_store_b32(word, c_rsrc, lane_c, ((i * 32 + (r2 & 3) + 8 * (r2 >> 2)) * g.ldc + j * 32) * 2, 0);
+                        continue;
+                    }
                     unsigned o2[2] = {0u, 0u};
                     if (EPILOGUE_PAIR_WORDS) {
                         const float vx = v2.x, vy = v2.y;     // (copies first: __builtin_bit_cast on an ext-vector ELEMENT reads element 0)
@@ -124,8 +139,8 @@
                     const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     float v = EPILOGUE_VALUE(i, j, r) + bias;
                     if (!EPILOGUE_EDGE_PRELOAD && LOADS_R) res[r] = residg[(long long)min(row, g.M - 1) * g.ldr + colc];
-                    if (EPI == EPI_GELU_KEEP && row < g.M && col_ok) const_cast<float*>(residg)[(long long)row * g.ldr + col] = v;
-                    if (EPI == EPI_GELU || EPI == EPI_GELU_KEEP) v = gelu_new1(v);
+                    if (KEEPS && row < g.M && col_ok) const_cast<float*>(residg)[(long long)row * g.ldr + col] = v;
+                    if (EPI == EPI_GELU || KEEPS) v = gelu_new1(v);
                     else if (EPI == EPI_RESIDUAL) v += res[r];
                     else if (EPI == EPI_GELU_GRAD) v *= gelu_new_grad(res[r]);
 #ifdef EPILOGUE_SCALE_DIVISOR
@@ -133,6 +148,10 @@
 #endif
                     else if (EPI == EPI_HALF_PLUS) v = (v + 1.0f) / 2.0f;
                     else if (EPI == EPI_H2WORDS) { unsigned w0, w1; h2_words<true>(v, 0.f, w0, w1); v = __builtin_bit_cast(float, w0); }
+                    if constexpr (C_BF16) {
+                        if (row < g.M && col_ok) reinterpret_cast<unsigned short*>(C)[(long long)row * g.ldc + col] = (unsigned short)cvt_pk_bf16(v, v);
+                        continue;
+                    }
                     if ((!EPILOGUE_DBG_NO_STORES || v == 12345.678f) && row < g.M && col_ok) C[(long long)row * g.ldc + col] = v;
                 }
             }

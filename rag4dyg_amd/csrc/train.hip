@@ -29,6 +29,7 @@ int launch_ln_bwd(const float* x, const float* w, const float* dy, const float* 
 size_t colsum_scratch_floats(long long rows, int n);
 int launch_colsum(const float* x, long long rows, int n, int ld, float* out, float* scratch, int accumulate, hipStream_t s);
 int launch_gelu_fwd(const float* pre, long long n, float* y, hipStream_t s);
+int launch_gelu_fwd_bf16(const float* pre, long long n, unsigned short* y_bf16, hipStream_t s);
 int launch_gelu_bwd(const float* pre, const float* dy, long long n, float* dx, hipStream_t s);
 int launch_softmax_bwd(const float* P, float* dP, int nbh, int T, int ld, float scale_div, hipStream_t s);
 int launch_transpose(const float* in, int rows, int cols, long long ld_in, long long stride_in, float* out, long long ld_out,
@@ -60,9 +61,15 @@ static int g_train_attn_bf16 = 0;
 // gemm_b1tn.hip) wherever the head carries the plane and the shape is supported (lm_head.hip).  Independent of the two above; the
 // retriever step has no head and does not read it.  NOT fp32-accurate.
 static int g_train_head_bf16 = 0;
+// r4d_set_train_act_bf16: 0 every saved activation fp32 (default), 1 -- only while g_train_bf16 is on -- the blocks
+// train_act_bf16_block names (ln1 of layers >= 1, ln2, f) are kept as bf16: their producers round once, with the rounding the
+// GEMMs that read them apply while staging, so every result keeps its bits.
+static int g_train_act_bf16 = 0;
 // The modes as a value (common.h: TrainModes): every entry point (size queries, forward, backward, the head steps) reads the
 // globals ONCE, here, and hands the value down; nothing below an entry point looks at a global.
-TrainModes train_modes() { return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16, g_train_head_bf16}; }
+TrainModes train_modes() {
+    return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16, g_train_head_bf16, g_train_act_bf16};
+}
 // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
 static bool train_fuse_gelu() {
     static const int v = [] { const char* e = getenv("R4D_TRAIN_FUSE_GELU"); return e ? atoi(e) : 1; }();
@@ -71,7 +78,7 @@ static bool train_fuse_gelu() {
 // The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
 // activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
 // would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
-static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0, 0}, -1};
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0, 0, 0}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -87,6 +94,9 @@ struct TrainLayout {
     size_t x_out, pool_scratch;
     bool recompute;                                     // no P blocks; scratch pA holds the P of the batch at hand
     bool act_recompute;                                 // ln1 .. f (and P) of every layer are ONE shared set; x_in stays per layer
+    // r4d_set_train_act_bf16 (train_act_bf16_block): the block is bf16 [M, width] -- half the floats at its offset
+    bool act_on;
+    bool bf(int which, int l) const { return train_act_bf16_block(which, l, act_on, (long long)M, d); }
     // backward temporaries (pA, dP, PT: attn_bwd's scratch blocks A, B, C; pA in recompute mode only)
     size_t dx, dy, dbig, dqkv, xT, pA, dP, PT, red;
     size_t emb_acc;                                     // [vocab, d] 64-bit fixed-point token-gradient table (two floats per entry)
@@ -98,6 +108,7 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
     t.L = cfg->n_layer; t.d = cfg->n_embd;
     t.recompute = md.attention == 1;
     t.act_recompute = md.activations == 1;
+    t.act_on = md.bf16 && md.act_bf16;
     const size_t d = t.d;
     t.M = 0; t.Ptot = 0; t.pmax = 0;
     size_t pool = 0;
@@ -110,18 +121,20 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
     }
     size_t off = 0;
     auto take = [&](size_t nfloat) { const size_t o = off; off += (nfloat + 63) / 64 * 64; return o; };
+    // a block that may be bf16 (two elements per float; M d / 2 is a multiple of 64 wherever a block qualifies)
+    auto take_act = [&](int which, int l, size_t elems) { return take(t.bf(which, l) ? elems / 2 : elems); };
     for (int l = 0; l < t.L; ++l) {
         if (t.act_recompute && l >= 1) {
             // layer 0 owns its ln1 (it left the fused embedding kernel; launch_layernorm is not promised to give its bits);
             // layers 1 .. L-1 share one ln1, and every layer shares the blocks behind it
-            t.x_in.push_back(take(t.M * d)); t.ln1.push_back(l == 1 ? take(t.M * d) : t.ln1[1]); t.qkv.push_back(t.qkv[0]);
+            t.x_in.push_back(take(t.M * d)); t.ln1.push_back(l == 1 ? take_act(ACT_LN1, l, t.M * d) : t.ln1[1]); t.qkv.push_back(t.qkv[0]);
             t.att.push_back(t.att[0]); t.x_mid.push_back(t.x_mid[0]); t.ln2.push_back(t.ln2[0]);
             t.pre.push_back(t.pre[0]); t.f.push_back(t.f[0]); t.P.push_back(t.P[0]);
             continue;
         }
-        t.x_in.push_back(take(t.M * d)); t.ln1.push_back(take(t.M * d)); t.qkv.push_back(take(t.M * 3 * d));
-        t.att.push_back(take(t.M * d)); t.x_mid.push_back(take(t.M * d)); t.ln2.push_back(take(t.M * d));
-        t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take(t.M * 4 * d)); t.P.push_back(t.recompute ? 0 : take(t.Ptot));
+        t.x_in.push_back(take(t.M * d)); t.ln1.push_back(take_act(ACT_LN1, l, t.M * d)); t.qkv.push_back(take(t.M * 3 * d));
+        t.att.push_back(take(t.M * d)); t.x_mid.push_back(take(t.M * d)); t.ln2.push_back(take_act(ACT_LN2, l, t.M * d));
+        t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take_act(ACT_F, l, t.M * 4 * d)); t.P.push_back(t.recompute ? 0 : take(t.Ptot));
     }
     t.x_out = take(t.M * d);
     t.pool_scratch = take(pool);
@@ -190,7 +203,7 @@ static int reduce_slices(const float* part, const float* db_part, int Sx, float*
 // partials (the slice count follows the room of `part`, at most 64; ONE slice writes dW / db itself and needs none).  *db_done:
 // whether db was written.
 static int wgrad_b1tn(const float* X, const float* dY, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part,
-                      size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t s) {
+                      size_t part_floats, float* db_part, size_t db_part_floats, bool* db_done, hipStream_t s, bool x_bf16 = false) {
     R4D_REQUIRE(X && dY && dW, "gemm_b1tn: null pointer");
     R4D_REQUIRE(gemm_b1tn_supported(I, J, M, lda, ldb), "gemm_b1tn: unsupported shape I=%d J=%d M=%d lda=%d ldb=%d (I %% 128 == 0, J %% 256 == 0, M >= 32 wanted)", I, J, M, lda, ldb);
     R4D_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)dW % 16) == 0 && ((uintptr_t)part % 16) == 0,
@@ -199,7 +212,7 @@ static int wgrad_b1tn(const float* X, const float* dY, float* dW, float* db, int
     const int S = gemm_tn_slices(I, J, M, max_s), Sx = tn_row_slices(M, S);
     const bool want_db = db && ((uintptr_t)db % 16) == 0 &&
                          (Sx == 1 || (db_part && ((uintptr_t)db_part % 16) == 0 && (size_t)Sx * J <= db_part_floats));
-    int rc = launch_gemm_b1tn(X, dY, Sx > 1 ? part : dW, want_db ? (Sx > 1 ? db_part : db) : nullptr, I, J, M, lda, ldb, S, s);
+    int rc = launch_gemm_b1tn(X, dY, Sx > 1 ? part : dW, want_db ? (Sx > 1 ? db_part : db) : nullptr, I, J, M, lda, ldb, S, s, x_bf16);
     if (!rc && Sx > 1) rc = reduce_slices(part, want_db ? db_part : nullptr, Sx, dW, db, I, J, s);
     if (!rc) *db_done = want_db;
     return rc;
@@ -211,15 +224,17 @@ static int wgrad_b1tn(const float* X, const float* dY, float* dW, float* db, int
 // kernels share one slice rule (the bits of dW depend on it): gemm_tn_slices, for gemm_b1tn within the room of `part` and 64, for
 // gemm_s3tn within tn_splits
 int weight_grad(const float* x, const float* dy, float* dW, float* db, int I, int J, int M, int lda, int ldb, float* part, float* red,
-                hipStream_t s, int bf16) {
+                hipStream_t s, int bf16, bool x_bf16) {
     const GemmRoute route = wgrad_route(I, J, M, lda, ldb, bf16);
+    R4D_REQUIRE(!x_bf16 || route == ROUTE_WGRAD_B1TN, "weight_grad: a bf16 activation block (train-act-bf16) needs gemm_b1tn (I=%d J=%d M=%d)", I, J, M);
+    if (x_bf16) R4D_BRANCH(TAB_WGRAD);
     const size_t red_floats = db ? colsum_scratch_floats(M, J) : 0;
     bool db_done = false;
     int rc;
     if (bf16 == TRAIN_BF16_HEAD) { if (route == ROUTE_WGRAD_B1TN) R4D_BRANCH(TBH_WGRAD); else R4D_BRANCH(TBH_WGRAD_FALLBACK); }
     else if (bf16) { if (route == ROUTE_WGRAD_B1TN) R4D_BRANCH(TB_WGRAD); else R4D_BRANCH(TB_WGRAD_FALLBACK); }
     if (route == ROUTE_WGRAD_B1TN) {
-        rc = wgrad_b1tn(x, dy, dW, db, I, J, M, lda, ldb, part, gemm_tn_scratch_floats(I, J, M), red, red_floats, &db_done, s);
+        rc = wgrad_b1tn(x, dy, dW, db, I, J, M, lda, ldb, part, gemm_tn_scratch_floats(I, J, M), red, red_floats, &db_done, s, x_bf16);
     } else if (route == ROUTE_WGRAD_S3TN) {
         R4D_REQUIRE(I > 0 && J > 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dW % 16) == 0, "gemm_tn: 16-byte alignment");
         const int S = gemm_tn_slices(I, J, M, tn_splits(I, J, M));
@@ -427,6 +442,14 @@ int r4d_set_train_head_bf16(int32_t on) {
 }
 int r4d_get_train_head_bf16(void) { return g_train_head_bf16; }
 
+int r4d_set_train_act_bf16(int32_t on) {
+    R4D_REQUIRE(on == 0 || on == 1, "set_train_act_bf16: %d is neither 0 (fp32 activations) nor 1 (bf16 store)", (int)on);
+    const int prev = g_train_act_bf16;
+    g_train_act_bf16 = on;
+    return prev;
+}
+int r4d_get_train_act_bf16(void) { return g_train_act_bf16; }
+
 size_t r4d_train_attn_probs_ld(int32_t T) { return T > 0 ? (size_t)tpad128(T) : 0; }
 
 int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float* b_d, float* c_d, int32_t B, int32_t T, int32_t H,
@@ -484,6 +507,26 @@ int r4d_weight_grad_bf16_f32(const float* x_d, int32_t ldx, const float* dy_d, i
     return R4D_OK;
 }
 
+int r4d_weight_grad_bf16_act_f32(const uint16_t* x_bf16_d, int32_t ldx, const float* dy_d, int32_t ldy, int32_t rows, int32_t in_features,
+                                 int32_t out_features, float* dw_d, float* db_d, void* workspace_d, size_t workspace_bytes, void* stream) {
+    R4D_REQUIRE(x_bf16_d && dy_d && dw_d, "weight_grad_bf16_act: null pointer");
+    R4D_REQUIRE(gemm_b1tn_supported(in_features, out_features, rows, ldx, ldy) && ldx % 8 == 0,
+                "weight_grad_bf16_act: unsupported shape rows=%d in=%d out=%d ldx=%d ldy=%d (in %% 128 == 0, out %% 256 == 0, rows >= 32, ldx %% 8 == 0 wanted)",
+                rows, in_features, out_features, ldx, ldy);
+    R4D_REQUIRE(workspace_d && ((uintptr_t)workspace_d % 16) == 0 &&
+                workspace_bytes >= r4d_weight_grad_bf16_workspace_bytes(rows, in_features, out_features), "weight_grad_bf16_act: workspace too small");
+    R4D_REQUIRE(!db_d || ((uintptr_t)db_d % 16) == 0, "weight_grad_bf16_act: db must be 16-byte aligned");
+    int S;
+    const size_t part = wgrad_bf16_part_floats(rows, in_features, out_features, &S);
+    float* ws = (float*)workspace_d;
+    bool db_done = false;
+    const int rc = wgrad_b1tn(reinterpret_cast<const float*>(x_bf16_d), dy_d, dw_d, db_d, in_features, out_features, rows, ldx, ldy, ws, part,
+                              ws + part, S > 1 ? (size_t)S * out_features : 0, &db_done, (hipStream_t)stream, true);
+    if (rc) return rc;
+    R4D_REQUIRE(!db_d || db_done, "weight_grad_bf16_act: the bias gradient was not formed");
+    return R4D_OK;
+}
+
 size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_groups, const int32_t* Bs, const int32_t* Ts) {
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
     for (int g = 0; g < n_groups; ++g)
@@ -530,6 +573,13 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
     R4D_REQUIRE(Lw.ln_1_w && Lw.c_attn_w && Lw.attn_proj_w && Lw.ln_2_w && Lw.c_fc_w && Lw.mlp_proj_w, "gpt2 train: null weight in layer %d", l);
     const Conv1DW Wqkv = conv1d_w(Lw, C_ATTN, d), Wo = conv1d_w(Lw, ATTN_PROJ, d), Wfc = conv1d_w(Lw, C_FC, d), Wp = conv1d_w(Lw, MLP_PROJ, d);
     const Conv1DOpts fwd{nullptr, false, bf16 ? BF16_TRAIN : BF16_OFF};
+    // the blocks kept as bf16 (r4d_set_train_act_bf16; the layout's own rule): their consumers read a bf16 A operand
+    const bool ln1_bf = t.bf(ACT_LN1, l), ln2_bf = t.bf(ACT_LN2, l), f_bf = t.bf(ACT_F, l);
+    Conv1DOpts fwd_ln1 = fwd, fwd_ln2 = fwd, fwd_f = fwd;
+    fwd_ln1.x_bf16 = ln1_bf; fwd_ln2.x_bf16 = ln2_bf; fwd_f.x_bf16 = f_bf;
+    R4D_REQUIRE(!ln1_bf || Lw.c_attn_w3, "gpt2 train: train-act-bf16 keeps layer %d's ln1 as bf16, but the layer carries no c_attn_w3 planes", l);
+    R4D_REQUIRE(!ln2_bf || Lw.c_fc_w3, "gpt2 train: train-act-bf16 keeps layer %d's ln2 as bf16, but the layer carries no c_fc_w3 planes", l);
+    R4D_REQUIRE(!f_bf || Lw.mlp_proj_w3, "gpt2 train: train-act-bf16 keeps layer %d's f as bf16, but the layer carries no mlp_proj_w3 planes", l);
     float *x_in = ws + t.x_in[l], *ln1 = ws + t.ln1[l], *qkv = ws + t.qkv[l], *att = ws + t.att[l];
     float *x_mid = ws + t.x_mid[l], *ln2 = ws + t.ln2[l], *pre = ws + t.pre[l], *f = ws + t.f[l];
     int rc = R4D_OK;
@@ -540,6 +590,8 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
                                     cfg->ln_eps, x_in, ln1, s);
     else if (l == 0)
         rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, Lw.ln_1_w, Lw.ln_1_b, cfg->ln_eps, x_in, ln1, s);
+    else if (ln1_bf)
+        rc = launch_layernorm_bf16(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, (unsigned short*)ln1, s);
     else
         rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s);
     if (rc) return rc;
@@ -547,7 +599,7 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
         if ((rc = launch_dropout(x_in, nullptr, (long long)M * d, x_in, dc.embd_p, dc.key, R4D_DROPOUT_SITE_EMBD, 0, s))) return rc;
         if ((rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s))) return rc;
     }
-    if ((rc = conv1d(Wqkv, ln1, nullptr, M, EPI_NONE, qkv, s, fwd))) return rc;
+    if ((rc = conv1d(Wqkv, ln1, nullptr, M, EPI_NONE, qkv, s, fwd_ln1))) return rc;
     for (const TrainGroup& G : gs)
         if ((rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
                            att + G.row0 * d, md.attn_bf16, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
@@ -556,20 +608,22 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
         if ((rc = conv1d(Wo, att, nullptr, M, EPI_NONE, branch, s, fwd))) return rc;
         if ((rc = launch_dropout(branch, x_in, (long long)M * d, x_mid, dc.resid_p, dc.key, 4u * l + 1u, 0, s))) return rc;
     } else if ((rc = conv1d(Wo, att, x_in, M, EPI_RESIDUAL, x_mid, s, fwd))) return rc;
-    if ((rc = launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
+    if ((rc = ln2_bf ? launch_layernorm_bf16(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, (unsigned short*)ln2, s)
+                     : launch_layernorm(x_mid, Lw.ln_2_w, Lw.ln_2_b, M, d, cfg->ln_eps, ln2, s))) return rc;
     if (train_fuse_gelu() && conv1d_fuses_gelu_keep(Wfc, M, fwd.bf16)) {
         // one launch: f = gelu_new(v) and the pre-activation v (kept for the backward pass) both leave the GEMM's epilogue
-        if ((rc = conv1d(Wfc, ln2, pre, M, EPI_GELU_KEEP, f, s, fwd))) return rc;
+        if ((rc = conv1d(Wfc, ln2, pre, M, f_bf ? EPI_GELU_KEEP_BF16 : EPI_GELU_KEEP, f, s, fwd_ln2))) return rc;
     } else {
-        if ((rc = conv1d(Wfc, ln2, nullptr, M, EPI_NONE, pre, s, fwd))) return rc;
-        if ((rc = launch_gelu_fwd(pre, (long long)M * 4 * d, f, s))) return rc;
+        if ((rc = conv1d(Wfc, ln2, nullptr, M, EPI_NONE, pre, s, fwd_ln2))) return rc;
+        if ((rc = f_bf ? launch_gelu_fwd_bf16(pre, (long long)M * 4 * d, (unsigned short*)f, s)
+                       : launch_gelu_fwd(pre, (long long)M * 4 * d, f, s))) return rc;
     }
     if (again) return R4D_OK;                                    // the MLP projection's output, x_in[l + 1], is there already
     float* x_next = l + 1 < cfg->n_layer ? ws + t.x_in[l + 1] : ws + t.x_out;
     if (dc.resid_p > 0.f) {                                      // x + dropout(c_proj(act(c_fc(x)))), :212,233
-        if ((rc = conv1d(Wp, f, nullptr, M, EPI_NONE, branch, s, fwd))) return rc;
+        if ((rc = conv1d(Wp, f, nullptr, M, EPI_NONE, branch, s, fwd_f))) return rc;
         if ((rc = launch_dropout(branch, x_mid, (long long)M * d, x_next, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
-    } else if ((rc = conv1d(Wp, f, x_mid, M, EPI_RESIDUAL, x_next, s, fwd))) return rc;
+    } else if ((rc = conv1d(Wp, f, x_mid, M, EPI_RESIDUAL, x_next, s, fwd_f))) return rc;
     return R4D_OK;
 }
 
@@ -627,6 +681,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(!after_fwd || md.attn_bf16 == g_last_fwd.modes.attn_bf16,
                 "gpt2 train backward: this workspace was filled by a forward with train-attention-bf16 %d, the current setting is %d",
                 g_last_fwd.modes.attn_bf16, md.attn_bf16);
+    R4D_REQUIRE(!after_fwd || md.act_bf16 == g_last_fwd.modes.act_bf16,
+                "gpt2 train backward: this workspace was filled by a forward with train-act-bf16 %d, the current setting is %d",
+                g_last_fwd.modes.act_bf16, md.act_bf16);
     const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -668,7 +725,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = launch_dropout(dx, nullptr, (long long)M * d, dy, dc.resid_p, dc.key, 4u * l + 2u, 0, s))) return rc;
             dbr = dy;
         }
-        if (!frozen && (rc = weight_grad(f, dbr, Lg.mlp_proj_w, Lg.mlp_proj_b, 4 * d, d, M, 4 * d, d, xT, red, s, md.bf16))) return rc;
+        if (!frozen && (rc = weight_grad(f, dbr, Lg.mlp_proj_w, Lg.mlp_proj_b, 4 * d, d, M, 4 * d, d, xT, red, s, md.bf16, t.bf(ACT_F, l)))) return rc;
         if (train_fuse_gelu() && dgrad_route(Wp, M, md.bf16) != ROUTE_DGRAD_F32) {
             // d(pre) = (d(branch) . Wp^T) * gelu_new'(pre): the derivative is applied in the GEMM's epilogue
             if ((rc = data_grad(Wp, dbr, M, dbig, nullptr, pre, s, md.bf16))) return rc;
@@ -676,7 +733,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = data_grad(Wp, dbr, M, dbig, nullptr, nullptr, s, md.bf16))) return rc;                  // d(f)
             if ((rc = launch_gelu_bwd(pre, dbig, (long long)M * 4 * d, dbig, s))) return rc;              // d(pre), in place
         }
-        if (!frozen && (rc = weight_grad(ln2, dbig, Lg.c_fc_w, Lg.c_fc_b, d, 4 * d, M, d, 4 * d, xT, red, s, md.bf16))) return rc;
+        if (!frozen && (rc = weight_grad(ln2, dbig, Lg.c_fc_w, Lg.c_fc_b, d, 4 * d, M, d, 4 * d, xT, red, s, md.bf16, t.bf(ACT_LN2, l)))) return rc;
         if ((rc = data_grad(Wfc, dbig, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                      // d(ln_2 out)
         if ((rc = launch_ln_bwd(x_mid, Lw.ln_2_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_2_w, Lg.ln_2_b, red, 0, s))) return rc;   // dx = d(x_mid)
         // ---- attention: x_mid = x_in + attn(ln_1(x_in)) Wo + bo
@@ -691,7 +748,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
             if ((rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
                                dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, md.attn_bf16, s,
                                dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
-        if (!frozen && (rc = weight_grad(ln1, dqkv, Lg.c_attn_w, Lg.c_attn_b, d, 3 * d, M, d, 3 * d, xT, red, s, md.bf16))) return rc;
+        if (!frozen && (rc = weight_grad(ln1, dqkv, Lg.c_attn_w, Lg.c_attn_b, d, 3 * d, M, d, 3 * d, xT, red, s, md.bf16, t.bf(ACT_LN1, l)))) return rc;
         if ((rc = data_grad(Wqkv, dqkv, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                     // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)
     }

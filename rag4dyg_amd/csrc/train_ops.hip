@@ -149,6 +149,17 @@ __global__ __launch_bounds__(256) void gelu_fwd_kernel(const float* __restrict__
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) y[i] = gelu_new_t(pre[i]);
 }
+// the same values as bf16 (RNE, v_cvt_pk_bf16_f32), two per thread and one 32-bit store (r4d_set_train_act_bf16, unfused GELU); n even
+__global__ __launch_bounds__(256) void gelu_fwd_bf16_kernel(const float* __restrict__ pre, long long n2, unsigned* __restrict__ y) {
+    typedef float f2_ __attribute__((ext_vector_type(2)));
+    typedef __bf16 b2_ __attribute__((ext_vector_type(2)));
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n2) {
+        const float2 p = reinterpret_cast<const float2*>(pre)[i];
+        const f2_ v = {gelu_new_t(p.x), gelu_new_t(p.y)};
+        y[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, b2_));
+    }
+}
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__ pre, const float* dy, long long n,
                                                        float* dx) {                              // dx may alias dy
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -623,6 +634,14 @@ int launch_gelu_fwd(const float* pre, long long n, float* y, hipStream_t s) {
     if (n <= 0) return R4D_OK;
     hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pre, n, y);
     R4D_CHECK_LAUNCH("gelu_fwd");
+    return R4D_OK;
+}
+int launch_gelu_fwd_bf16(const float* pre, long long n, unsigned short* y_bf16, hipStream_t s) {
+    R4D_REQUIRE(n % 2 == 0 && ((uintptr_t)pre % 8) == 0 && ((uintptr_t)y_bf16 % 4) == 0, "gelu_fwd_bf16: an even count and aligned pointers wanted");
+    if (n <= 0) return R4D_OK;
+    R4D_BRANCH(TAB_GELU);
+    hipLaunchKernelGGL(gelu_fwd_bf16_kernel, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, s, pre, n / 2, reinterpret_cast<unsigned*>(y_bf16));
+    R4D_CHECK_LAUNCH("gelu_fwd_bf16");
     return R4D_OK;
 }
 int launch_gelu_bwd(const float* pre, const float* dy, long long n, float* dx, hipStream_t s) {

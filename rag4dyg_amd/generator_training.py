@@ -94,8 +94,10 @@ class GeneratorTrainer:
     """One generator training micro-step on the device for a ``GPT2LMHeadModelRAG`` with ``gnn_fusion`` (one layer).  ``grads``
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
-    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None):
-        """``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
+    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None,
+                 act_store=None):
+        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``).
+        ``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
         ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, beside ``precision``."""
         gnn = getattr(model, "gnn_fusion", None)
         if gnn is None or gnn.n_layers != 1:
@@ -106,7 +108,7 @@ class GeneratorTrainer:
         self.model, self.freeze, self.tied = model, bool(freeze), tied
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
         self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations,
-                                  precision=precision)
+                                  precision=precision, act_store=act_store)
         self.head_precision = resolve_train_head_precision(head_precision)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
@@ -339,7 +341,7 @@ def evaluate(args, trainer, loader, bags):
     return float(total) / n if n else float("nan")
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None):
     """Drop-in for ``train_generator.train`` (:141-248).  Returns (global_step, tr_loss / global_step)."""
     from .generator import get_eval_metrics_generator, load_and_cache_examples
     check_supported(args)
@@ -357,7 +359,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
         t_total = len(loader) // gas * args.num_train_epochs
     trainer = GeneratorTrainer(model, freeze=bool(getattr(args, "freeze", False)),
                                seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                               head_precision=head_precision)
+                               head_precision=head_precision, act_store=act_store)
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():
@@ -376,6 +378,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
     print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
           "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
+    print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.enc.act_store))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

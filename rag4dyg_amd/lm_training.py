@@ -105,8 +105,10 @@ class LMTrainer:
     the padded LM-head operand ``wte_pad`` [ldV, d] (zero rows past V) and its planes.  Every derived weight is rebuilt when the
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
-    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None):
-        """``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
+    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None,
+                 act_store=None):
+        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``).
+        ``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
         ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, an axis of its own beside ``precision``.  The
         trainer sets the head switch with the others before every size query and step call of its own."""
         head = getattr(model, "lm_head", None)
@@ -114,7 +116,8 @@ class LMTrainer:
             raise _lib.R4DError("SimpleDyG training needs lm_head tied to transformer.wte (the reference's model is always tied); "
                                 "this model's lm_head is a separate tensor")
         self.model = model
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations, precision=precision)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations, precision=precision,
+                                  act_store=act_store)
         self.head_precision = resolve_train_head_precision(head_precision)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
@@ -296,7 +299,7 @@ def train_epoch(model, trainer, optimizer, scheduler, train_dataloader, tr_loss,
     return global_step, tr_loss
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None):
     """Drop-in for ``main_SimpleDyG.train`` (:200-343).  Returns (global_step, tr_loss / global_step)."""
     from .evaluation import get_eval_metrics
     if getattr(args, "fp16", False):
@@ -311,7 +314,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     else:
         t_total = len(train_dataloader) // gas * args.num_train_epochs
     trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                        head_precision=head_precision)      # every rank its own dropout masks
+                        head_precision=head_precision, act_store=act_store)      # every rank its own dropout masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -331,6 +334,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
     print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
           "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
+    print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.enc.act_store))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

@@ -341,7 +341,66 @@ def weight_grad_bf16(x, dy, want_db=True, workspace=None):
     return dw, db
 
 
-TRAIN_ATTN_PRODUCTS = ("s", "pv", "dp", "dq", "dk", "dv")
+# ---- the single ops of the bf16 activation store (``training.resolve_train_act_store``, ``r4d_set_train_act_bf16``): the kernels the
+# step launches where a saved activation is bf16 in memory.  bf16 tensors are torch.bfloat16 [rows, width], contiguous.
+def layernorm_bf16(x, w, b, eps=1e-5):
+    """:func:`layernorm` whose output is torch.bfloat16 [..., d]: the same statistics and arithmetic, rounded to nearest even at
+    the store (d % 256 == 0)."""
+    d = x.shape[-1]
+    rows = x.numel() // d
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    check(_lib.load().r4d_layernorm_bf16_f32(_dev(x, torch.float32, "x"), _dev(w, torch.float32, "w"), _dev(b, torch.float32, "b"),
+                                             rows, d, eps, y.data_ptr(), _stream()), "layernorm_bf16")
+    return y
+
+
+def conv1d_bf16_act(x_bf16, w_bf16, bias, epilogue="none", residual=None):
+    """:func:`conv1d_bf16` / :func:`conv1d_bf16_keep` on an activation that is ALREADY bf16 in memory (``x_bf16`` torch.bfloat16
+    [M, K]): the same operand bits, so the same result bits as on the fp32 activation it was rounded from.  ``epilogue``: "none" ->
+    y fp32; "residual" -> y = residual + ...; "gelu_keep" -> (pre fp32, y torch.bfloat16 = RN(gelu_new(pre)))."""
+    N, K = w_bf16.shape
+    M = x_bf16.numel() // K
+    kind = {"none": 0, "residual": 1, "gelu_keep": 2}[epilogue]
+    dev = x_bf16.device
+    y = torch.empty(x_bf16.shape[:-1] + (N,), dtype=torch.bfloat16 if kind == 2 else torch.float32, device=dev)
+    second = None
+    if kind == 1:
+        second = residual
+        _dev(residual, torch.float32, "residual")
+    elif kind == 2:
+        second = torch.empty(x_bf16.shape[:-1] + (N,), dtype=torch.float32, device=dev)
+    bp = _dev(bias, torch.float32, "bias") if bias is not None else None
+    check(_lib.load().r4d_conv1d_bf16_act_f32(_dev(x_bf16, torch.bfloat16, "x_bf16"), _dev(w_bf16, torch.int16, "w_bf16"), bp, M, K, N, kind,
+                                              second.data_ptr() if second is not None else None, y.data_ptr(), _stream()),
+          "conv1d_bf16_act")
+    return (second, y) if kind == 2 else y
+
+
+def weight_grad_bf16_act(x_bf16, dy, want_db=True, workspace=None):
+    """:func:`weight_grad_bf16` on an ``x_bf16`` that is ALREADY bf16 in memory (torch.bfloat16 [rows, in], or a column block of a
+    wider bf16 buffer with a row stride that is a multiple of 8); ``dy`` stays fp32.  The same bits as on the fp32 x it was
+    rounded from."""
+    lib = _lib.load()
+    if not x_bf16.is_cuda or x_bf16.dtype != torch.bfloat16 or x_bf16.dim() != 2 or x_bf16.stride(1) != 1:
+        raise R4DError("weight_grad_bf16_act: x must be a 2-D bfloat16 device tensor with contiguous rows")
+    if not dy.is_cuda or dy.dtype != torch.float32 or dy.dim() != 2 or dy.stride(1) != 1:
+        raise R4DError("weight_grad_bf16_act: dy must be a 2-D fp32 device tensor with contiguous rows")
+    rows, n_in = x_bf16.shape
+    n_out = dy.shape[1]
+    if dy.shape[0] != rows:
+        raise R4DError("weight_grad_bf16_act: x and dy differ in rows")
+    nbytes = lib.r4d_weight_grad_bf16_workspace_bytes(rows, n_in, n_out)
+    if workspace is None:
+        workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dy.device)
+    dw = torch.empty(n_in, n_out, dtype=torch.float32, device=dy.device)
+    db = torch.empty(n_out, dtype=torch.float32, device=dy.device) if want_db else None
+    check(lib.r4d_weight_grad_bf16_act_f32(x_bf16.data_ptr(), int(x_bf16.stride(0)), dy.data_ptr(), int(dy.stride(0)), rows, n_in, n_out,
+                                           dw.data_ptr(), db.data_ptr() if want_db else None, workspace.data_ptr(), workspace.numel(),
+                                           _stream()), "weight_grad_bf16_act")
+    return dw, db
+
+
+TRAIN_ATTN_PRODUCTS =("s", "pv", "dp", "dq", "dk", "dv")
 
 
 def train_attn_probs_ld(T):

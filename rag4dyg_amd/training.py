@@ -138,6 +138,9 @@ TRAIN_ATTENTION_BF16 = {"fp32": 0, "bf16": 0, "fp32+attn": 1, "bf16+attn": 1}
 # the LM head's axis (r4d_set_train_head_bf16: logits, dh and dwte_head of the LM and RAG-generator steps): a table and an argument
 # of its own, independent of the two above; the retriever step has no head
 TRAIN_HEAD_PRECISIONS = {"fp32": 0, "bf16": 1}
+# how the bf16 LAYER axis keeps its saved activations (r4d_set_train_act_bf16: ln1 of layers >= 1, ln2 and f as bf16 in memory):
+# the same bits, a smaller workspace; meaningful only where TRAIN_PRECISIONS[precision] == 1
+TRAIN_ACT_STORES = {"fp32": 0, "bf16": 1}
 
 
 def _resolve(what, value, env, table, default):
@@ -184,17 +187,35 @@ def resolve_train_head_precision(head_precision=None):
     return _resolve("train head precision", head_precision, "R4D_TRAIN_HEAD_PRECISION", TRAIN_HEAD_PRECISIONS, "fp32")
 
 
+def resolve_train_act_store(act_store=None):
+    """``"fp32"`` (every saved activation fp32) or ``"bf16"`` (under a bf16 layer precision the LayerNorm outputs ln1 -- layers
+    >= 1 -- and ln2 and the GELU output f are written as bf16 by their producers and read as bf16 by the GEMMs that round them
+    anyway: every loss, output and gradient keeps its bits, the workspace shrinks; ``r4d_set_train_act_bf16``).  None -> the
+    environment variable ``R4D_TRAIN_ACT_STORE``, ``fp32`` when it is unset or empty.  Anything else raises.  The pairing with
+    ``precision`` is checked where both are known (:func:`check_act_store`)."""
+    return _resolve("train activation store", act_store, "R4D_TRAIN_ACT_STORE", TRAIN_ACT_STORES, "fp32")
+
+
+def check_act_store(act_store, precision):
+    """``act_store="bf16"`` needs a ``precision`` whose layer axis is bf16: under ``"fp32"`` / ``"fp32+attn"`` the library
+    would ignore it silently -> ValueError."""
+    if TRAIN_ACT_STORES[act_store] == 1 and TRAIN_PRECISIONS[precision] != 1:
+        raise ValueError(f"train activation store 'bf16' needs a bf16 layer precision ('bf16' or 'bf16+attn'), not {precision!r}")
+    return act_store
+
+
 class EncoderTrainer:
     """Forward-with-saved-activations and backward of the SimpleDyG encoder on the HIP kernels
     (``r4d_gpt2_train_forward_f32`` / ``r4d_gpt2_train_backward_f32``), for a ``GPT2LMHeadModelRAG`` whose parameters live
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None):
+    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None, act_store=None):
         """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``);
         ``activations``: the same two words for the per-layer activations (:func:`resolve_train_activations`; None ->
         ``R4D_TRAIN_ACTIVATIONS``); ``precision``: ``"fp32"`` / ``"bf16"`` / ``"fp32+attn"`` / ``"bf16+attn"`` (:func:`resolve_train_precision`;
-        None -> ``R4D_TRAIN_PRECISION``).  The trainer sets the four library switches before every size query and step call of its own, so
+        None -> ``R4D_TRAIN_PRECISION``); ``act_store``: ``"fp32"`` / ``"bf16"`` (:func:`resolve_train_act_store`; None ->
+        ``R4D_TRAIN_ACT_STORE``; ``"bf16"`` needs a bf16 layer precision, ValueError otherwise).  The trainer sets the five library switches before every size query and step call of its own, so
         trainers of different modes can share a process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
@@ -203,6 +224,7 @@ class EncoderTrainer:
         self.attention = resolve_train_attention(attention)
         self.activations = resolve_train_activations(activations)
         self.precision = resolve_train_precision(precision)
+        self.act_store = check_act_store(resolve_train_act_store(act_store), self.precision)
         self.dropout, self.seed, self.step = dropout, int(seed), 0
         self._drop_struct = None
         tr = model.transformer
@@ -311,6 +333,7 @@ class EncoderTrainer:
         _lib.check(_lib.load().r4d_set_train_activations(TRAIN_ACTIVATION_MODES[self.activations]), "set_train_activations")
         _lib.load().r4d_set_train_bf16(TRAIN_PRECISIONS[self.precision])                # (returns the previous setting)
         _lib.load().r4d_set_train_attention_bf16(TRAIN_ATTENTION_BF16[self.precision])
+        _lib.load().r4d_set_train_act_bf16(TRAIN_ACT_STORES[self.act_store])
 
     set_attention_mode = select_modes        # the earlier name, kept for scripts written against it
 
@@ -604,7 +627,7 @@ def distributed_setup(args):
     return dist.get_world_size(), dist.get_rank()
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, act_store=None):
     """Drop-in for ``train/train_retriever.train`` (``:230-354``): AdamW on the time-decayed contrastive + InfoNCE loss, validation
     hit@3 after every epoch, best checkpoint as ``checkpoint-0`` (only once ``epoch > warmup_steps``, as upstream), last as
     ``checkpoint-1``, early stopping after ``--patience`` epochs without improvement, then the test / validation passes on
@@ -625,7 +648,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     gas = max(1, int(getattr(args, "gradient_accumulation_steps", 1)))
     if args.max_steps > 0:
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
-    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision)      # every rank its own masks
+    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
+                             act_store=act_store)      # every rank its own masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -640,6 +664,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.activations))
     print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too); "
           "no LM head in this step (R4D_TRAIN_HEAD_PRECISION is not read)".format(trainer.precision))
+    print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.act_store))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

@@ -4,7 +4,9 @@ stored / recompute), from the library's three size queries alone: no GPU, no all
     python tools/train_workspace_table.py [--json]
 
 Rows are the padded worst case of each script (every sequence at the block size); the retriever step is its five forwards in
-one call.  Vocabularies: rag4dyg_amd/synth.py (retriever flavour with [MASK], SimpleDyG / generator flavour without)."""
+one call.  Each cell is the fp32 store's size; the `bf16 store` column beside it is the same query with the layer precision bf16
+and the activation store bf16 (``r4d_set_train_bf16(1)``, ``r4d_set_train_act_bf16(1)``; DESIGN.md section 7.9: ln1 of layers >= 1,
+ln2 and f as bf16 wherever d % 256 == 0).  Vocabularies: rag4dyg_amd/synth.py (retriever flavour with [MASK], SimpleDyG / generator flavour without)."""
 import ctypes
 import json
 import os
@@ -40,7 +42,7 @@ def workspace_bytes(lib, kind, L, H, d, V, batches):
 
 def table():
     lib = _lib.load()
-    was = lib.r4d_get_train_attention(), lib.r4d_get_train_activations()
+    was = lib.r4d_get_train_attention(), lib.r4d_get_train_activations(), lib.r4d_get_train_bf16(), lib.r4d_get_train_act_bf16()
     out = []
     try:
         for kind, label, L, H, d, V, batches in ROWS:
@@ -48,11 +50,18 @@ def table():
             for att, act in MODES:
                 _lib.check(lib.r4d_set_train_attention(WORD[att]), "set_train_attention")
                 _lib.check(lib.r4d_set_train_activations(WORD[act]), "set_train_activations")
+                lib.r4d_set_train_bf16(0)
+                lib.r4d_set_train_act_bf16(0)
                 rec[f"attention_{att}_activations_{act}"] = workspace_bytes(lib, kind, L, H, d, V, batches)
+                lib.r4d_set_train_bf16(1)                       # (the layer switch alone changes no size)
+                lib.r4d_set_train_act_bf16(1)
+                rec[f"attention_{att}_activations_{act}_act_store_bf16"] = workspace_bytes(lib, kind, L, H, d, V, batches)
             out.append(rec)
     finally:
         lib.r4d_set_train_attention(was[0])
         lib.r4d_set_train_activations(was[1])
+        lib.r4d_set_train_bf16(was[2])
+        lib.r4d_set_train_act_bf16(was[3])
     return out
 
 
@@ -62,11 +71,12 @@ def main():
         for r in rows:
             print(json.dumps(r))
         return
-    print("| step | shape | P stored, activations stored | P recompute, activations stored | P stored, activations recompute | "
-          "P recompute, activations recompute |")
-    print("|---|---|---|---|---|---|")
+    print("| step | shape | P stored, activations stored | bf16 store | P recompute, activations stored | bf16 store | "
+          "P stored, activations recompute | bf16 store | P recompute, activations recompute | bf16 store |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
     for r in rows:
-        cells = [f"{r[f'attention_{att}_activations_{act}'] / 1e9:.2f} GB" for att, act in MODES]
+        cells = [f"{r[k] / 1e9:.2f} GB" for att, act in MODES
+                 for k in (f"attention_{att}_activations_{act}", f"attention_{att}_activations_{act}_act_store_bf16")]
         print(f"| {r['step']} | {r['shape']} | " + " | ".join(cells) + " |")
 
 
