@@ -251,18 +251,20 @@ int r4d_lm_logits_f32(const float* hidden_d, const float* wte_d, int32_t M, int3
 
 /* Attention implementation switch: -1 = auto (default) / 1 = fused flash-style kernels wherever instantiated
  * (head_dim in {32,64}: key-split kernel; {96,128,256}: column-split kernel; scores never leave the CU),
- * 0 = three launches (batched Q.K^T GEMM, causal softmax, P.V GEMM; also the fallback for other head dims),
+ * 0 = three launches (batched Q.K^T GEMM, causal softmax weights, P.V GEMM; also the fallback for other head dims) and a small
+ * fourth that divides the output rows by the softmax row sums,
  * 2 = fused with the key-split kernel forced at head_dim 96/128/256 (A/B tuning).  Same results to fp32 rounding. */
 int r4d_set_attention_fused(int32_t mode);
 
-/* f16x2 attention (ABI v5, additive): in gemm mode 2 (f16x2) r4d_gpt2_encode_* runs head_dim 128 / 256 attention on the fp16
+/* f16x2 attention (ABI v5, additive): in gemm mode 2 (f16x2) r4d_gpt2_encode_* runs head_dim 32 / 64 / 96 / 128 / 256 attention on the fp16
  * matrix cores (csrc/attention_h2.hip) -- the c_attn GEMM then writes its result as "h2 words" (uint32 per element:
  * fp16 hi | fp16 lo' << 16 of value / 4, value = hi + 2^-11 lo' to 2^-22 relative; csrc/h2.h) instead of fp32, and the attention
  * kernel consumes them without conversion.  Not used when the caller asks for the qkv tensor (out_qkv_d) and for other head
  * dims; |q|, |k|, |v| < 2^18.  r4d_set_attention_h2(0) keeps the exact-f32 attention kernels in every mode (returns the previous
  * setting; process-wide like r4d_set_gemm_split3: ranks must agree).
  * r4d_pack_h2_words_f32: x_d fp32 [n] -> words_d uint32 [n] (what the GEMM epilogue writes; for tests and external producers).
- * r4d_attention_h2_f32: r4d_attention_f32 on words: qkv_words_d [B*T, 3d] -> a_d fp32 [B*T, d]; head_dim 128 / 256 only. */
+ * r4d_attention_h2_f32: r4d_attention_f32 on words: qkv_words_d [B*T, 3d] -> a_d fp32 [B*T, d]; head_dim 32 / 64 / 96 / 128 / 256
+ * (any other head_dim, B < 1 or T < 1 is refused). */
 int r4d_set_attention_h2(int32_t on);
 /* KEY-BLOCKED K (round 5): row-major K costs every K load instruction of the attention 32 cache lines (each lane
  * its own key row, 32 bytes of each line used); in the key-blocked image -- [ceil(rows / 32)][n_head][head_dim / 8][2][32][4] uint32:
@@ -397,7 +399,8 @@ int r4d_set_encode_bf16(int32_t on);
 int r4d_get_encode_bf16(void);
 /* Causal multi-head attention on packed c_attn output qkv_d [B,T,3d] -> a_d [B,T,d] (heads merged).
  * Attention._attn + split/merge_heads, modeling_gpt2.py:140-175; scale = division by sqrt(hd) (:143).
- * scores_ws_d: device scratch of r4d_attention_workspace_bytes(B,H,T). */
+ * scores_ws_d: device scratch of r4d_attention_workspace_bytes(B,H,T).  B >= 1, 1 <= T <= 1024, head_dim a multiple of 16;
+ * anything else, or a shorter workspace, is refused before any launch. */
 size_t r4d_attention_workspace_bytes(int32_t B, int32_t n_head, int32_t T);
 int r4d_attention_f32(const float* qkv_d, int32_t B, int32_t T, int32_t n_head, int32_t d,
                       float* a_d, void* scores_ws_d, size_t ws_bytes, void* stream);

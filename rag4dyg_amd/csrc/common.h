@@ -314,7 +314,9 @@ struct RowGroups {
 };
 int launch_embed_layernorm_groups(const RowGroups& G, const float* wte, const float* wpe, int vocab, int d,
                                   const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s, bool y_lines = false);
-int launch_causal_softmax(float* S, int nbh, int T, int ld, int row_tile, hipStream_t s);
+int launch_causal_softmax(float* S, int nbh, int T, int ld, int row_tile, hipStream_t s, bool normalise = true);
+// rows of out [B*T, d] (merged heads) divided by the row sums of the unnormalised P [B*H, T, ld] (encoder.hip: attention())
+int launch_attention_rows_normalise(const float* P, float* out, int B, int T, int H, int d, int ld, hipStream_t s);
 // decode step (one new position per sequence): x = (ids ? wte[id] : emb) + wpe[pos], y = LayerNorm(x)
 int launch_embed_pos_layernorm(const int64_t* ids, const float* emb, const int32_t* pos, const float* wte,
                                const float* wpe, int vocab, int n_positions, int t_cap, int B, int d, const float* w,

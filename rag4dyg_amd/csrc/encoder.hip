@@ -61,8 +61,9 @@ static inline int tpad(int T) { return (T + 127) / 128 * 128; }
 
 // Attention._attn + split_heads/merge_heads (modeling_gpt2.py:140-175) as three launches over the packed
 // c_attn output: batched per-head Q.K^T (tiles above the diagonal skipped, logits DIVIDED by sqrt(hd) as
-// in :143), in-place causal softmax, batched P.V (K-loop trimmed to the causal range) writing straight
-// into the merged-head layout.  The B*H*T*T score block (29 MB at the worst UCI_13 batch) stays in
+// in :143), in-place causal softmax weights exp(s - max), batched P.V (K-loop trimmed to the causal range) writing
+// straight into the merged-head layout -- and a fourth, small one that divides the rows of P.V by the row sums (normalising P
+// first costs 1.4e-5 on a row of ~1000 equal weights: launch_attention_rows_normalise).  The B*H*T*T score block (29 MB at the worst UCI_13 batch) stays in
 // the 256 MB Infinity Cache between the launches.
 int g_attention_fused = -1;           // -1 auto (by head_dim), 0 three launches, 1 fused wherever instantiated
 int g_attention_h2 = 1;               // r4d_set_attention_h2: in f16x2 mode, head_dim 128 / 256 on the fp16 matrix cores (attention_h2.hip)
@@ -89,7 +90,7 @@ static int attention(const float* qkv, int B, int T, int H, int d, float* a_out,
     g.epilogue = EPI_SCALE_DIV; g.scale_div = (float)sqrt((double)hd); g.causal = CAUSAL_QK;
     int rc = launch_gemm_f32(g, s);
     if (rc) return rc;
-    rc = launch_causal_softmax(scores, B * H, T, ld, 128, s);
+    rc = launch_causal_softmax(scores, B * H, T, ld, 128, s, /*normalise=*/false);
     if (rc) return rc;
     memset(&g, 0, sizeof(g));
     g.A = scores; g.B = qkv + 2 * d; g.C = a_out;
@@ -99,7 +100,9 @@ static int attention(const float* qkv, int B, int T, int H, int d, float* a_out,
     g.sB0 = (long long)T * 3 * d; g.sB1 = hd; g.sC0 = (long long)T * d; g.sC1 = hd;
     g.a_cols = ld;
     g.epilogue = EPI_NONE; g.scale_div = 1.f; g.causal = CAUSAL_PV;
-    return launch_gemm_f32(g, s);
+    rc = launch_gemm_f32(g, s);
+    if (rc) return rc;
+    return launch_attention_rows_normalise(scores, a_out, B, T, H, d, ld, s);
 }
 
 struct Group {                 // one right-padded reference batch inside a fused launch sequence
@@ -713,6 +716,7 @@ int r4d_attention_f32(const float* qkv_d, int32_t B, int32_t T, int32_t n_head, 
     R4D_REQUIRE(qkv_d && a_d && scores_ws_d, "attention: null pointer");
     R4D_REQUIRE(n_head >= 1 && d % n_head == 0 && (d / n_head) % 16 == 0, "attention: head_dim must be a multiple of 16");
     R4D_REQUIRE(T >= 1 && T <= 1024, "attention: T=%d out of range", T);
+    R4D_REQUIRE(B >= 1, "attention: B=%d", B);       // the workspace size of B < 1 is 0: every buffer would pass the check below
     if (ws_bytes < r4d_attention_workspace_bytes(B, n_head, T)) {
         set_error("attention: workspace too small");
         return R4D_ERR_WORKSPACE;

@@ -607,7 +607,9 @@ int launch_greedy_advance(const float* logits, int B, int V, const GreedyState& 
 // row.  The reference masks with w*b - 1e4*(1-b) (modeling_gpt2.py:146) and soft-maxes all T keys (:152):
 // masked terms are exp(-1e4 - max) == 0 in fp32 whenever the row max exceeds -9896, so only keys j <= i
 // are read.  Columns i+1 .. roundup(i+1, row_tile)-1 are zero-filled: the P.V GEMM's causal K-loop
-// covers whole row tiles.
+// covers whole row tiles.  NORM = false leaves the weights exp(s - max) UNNORMALISED: the encoder's GEMM form of the
+// attention divides the rows of P.V by the row sums afterwards (attn_rows_normalise_kernel), like the fused kernels.
+template <bool NORM>
 __global__ __launch_bounds__(256) void causal_softmax_kernel(float* __restrict__ S, int nrows_total, int T, int ld,
                                                              int row_tile) {
     const int lane = threadIdx.x & 63;
@@ -636,17 +638,56 @@ __global__ __launch_bounds__(256) void causal_softmax_kernel(float* __restrict__
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
         const int j = lane + 64 * c;
-        if (j < nfill) row[j] = v[c] / s;
+        if (j < nfill) row[j] = NORM ? v[c] / s : v[c];
     }
 }
 
-int launch_causal_softmax(float* S, int nbh, int T, int ld, int row_tile, hipStream_t s) {
+int launch_causal_softmax(float* S, int nbh, int T, int ld, int row_tile, hipStream_t s, bool normalise) {
     R4D_REQUIRE(T <= 1024, "attention: T=%d exceeds n_positions cap 1024", T);
     const long long rows = (long long)nbh * T;
     ProfScope prof(PK_SOFTMAX, 4.0 * nbh * T * (double)(T + 1), s);   // bytes: causal half read + written
-    hipLaunchKernelGGL(causal_softmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, S, (int)rows, T, ld,
-                       row_tile);
+    if (normalise)
+        hipLaunchKernelGGL(causal_softmax_kernel<true>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, S, (int)rows, T, ld,
+                           row_tile);
+    else
+        hipLaunchKernelGGL(causal_softmax_kernel<false>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, S, (int)rows, T, ld,
+                           row_tile);
     R4D_CHECK_LAUNCH("causal_softmax");
+    return R4D_OK;
+}
+
+// out[(b T + i) d + h hd + 0 .. hd) /= sum_j P[z][i][0..i] (z = b H + h), one wavefront per query row: the normalisation of the
+// GEMM form of the attention, AFTER P.V.  Normalised first, a row of equal weights 1 / n is added n times one after the other in
+// the GEMM's k-loop and every addition rounds the same way (n = 994: 1.4e-5 off); exp(s - max) = 1 adds exactly.  The row sum is
+// formed in causal_softmax_kernel's own order.
+__global__ __launch_bounds__(256) void attn_rows_normalise_kernel(const float* __restrict__ P, float* __restrict__ out, int nrows_total,
+                                                                  int T, int ld, int H, int hd, int d) {
+    const int lane = threadIdx.x & 63;
+    const long long gr = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gr >= nrows_total) return;
+    const int i = (int)(gr % T);
+    const long long z = gr / T;
+    const float* row = P + z * (long long)T * ld + (long long)i * ld;
+    const int n = i + 1;
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        const int j = lane + 64 * c;
+        s += (j < n) ? row[j] : 0.f;
+    }
+    s = wave_sum(s);
+    float* dst = out + ((z / H) * T + i) * (long long)d + (z % H) * hd;
+    for (int c = lane; c < hd; c += 64) dst[c] = dst[c] / s;
+}
+
+int launch_attention_rows_normalise(const float* P, float* out, int B, int T, int H, int d, int ld, hipStream_t s) {
+    R4D_REQUIRE(P && out && B >= 1 && H >= 1 && T >= 1 && T <= 1024 && ld >= T && d % H == 0, "attention: bad normalise arguments");
+    const long long rows = (long long)B * H * T;
+    R4D_REQUIRE(rows < (1ll << 31), "attention: %lld rows exceed the grid of the row normalisation", rows);
+    ProfScope prof(PK_SOFTMAX, 2.0 * B * H * T * (double)(T + 1) + 8.0 * B * T * (double)d, s);   // bytes: causal half of P read, out read + written
+    hipLaunchKernelGGL(attn_rows_normalise_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, P, out, (int)rows, T, ld, H,
+                       d / H, d);
+    R4D_CHECK_LAUNCH("attn_rows_normalise");
     return R4D_OK;
 }
 
