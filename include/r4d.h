@@ -618,6 +618,40 @@ size_t r4d_train_attn_probs_ld(int32_t T);
 int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float* b_d, float* c_d, int32_t B, int32_t T, int32_t H,
                                     int32_t d, void* stream);
 
+/* FUSED attention of the training steps: no [T, T] block in memory (process-wide; additive ABI v6 entries;
+ * csrc/attention_train_fused.hip).  A seventh switch.  It acts only TOGETHER with r4d_set_train_attention_bf16 -- the
+ * arithmetic is that switch's: Q, K, V, dO, the probabilities and dS enter every product as bf16 (round to nearest even), one
+ * v_mfma_f32_32x32x16_bf16 per k-step, fp32 accumulation, the softmax and dS arithmetic in fp32.  NOT fp32-accurate, and NOT
+ * bit-identical to the six products: the forward rounds the UNNORMALISED probabilities exp(s - running max) and divides the
+ * accumulated O by the row sum afterwards; the backward forms P = exp(s - lse) again, from the forward's row statistics.  While both switches are on
+ *   - the forward writes att [B, T, d] and ONE fp32 log-sum-exp per (sequence, head, query), lse [B*H, T], per layer (one shared set
+ *     under activations recompute, whose re-forward leaves the forward's bits);
+ *   - the backward is three launches per batch (row sums D, dK / dV, dQ) that write this head's columns of dqkv [B, T, 3d];
+ *   - the layout holds NO P block and none of the three P-shaped scratch blocks: the three size queries shrink accordingly, and
+ *     r4d_set_train_attention (stored / recompute) changes neither a size nor a launch;
+ *   - dropout on the probabilities drops exactly the elements the unfused step drops under the same r4d_train_dropout.
+ * With this switch on and r4d_set_train_attention_bf16 off the three size queries return 0 and every training forward / backward /
+ * step entry fails with R4D_ERR_INVALID ("train-attention-fused needs train-attention-bf16") before any launch.
+ * r4d_set_train_attention_fused(0 | 1) returns R4D_OK; any other value is R4D_ERR_INVALID and changes nothing; default 0 (every
+ * launch, size and bit as without these entries).  Read like r4d_set_train_bf16: set it BEFORE the size query and keep it until the
+ * step's backward has been issued; a backward on the workspace of the most recent training forward under the other setting is
+ * refused (R4D_ERR_INVALID).  Nothing outside the training steps reads it. */
+int r4d_set_train_attention_fused(int32_t on);
+int r4d_get_train_attention_fused(void);
+/* The two launch sequences of that mode over ONE batch [B, T] with H heads, for per-op tests and tools (whatever the switches say).
+ * qkv_d [B, T, 3d], att_d / dao_d [B, T, d] merged heads, lse_d [B*H, T], dqkv_out_d [B, T, 3d]; only the T rows' own-head columns
+ * of the outputs are written, and nothing else of the inputs is read.  dropout: NULL or attn_p == 0 -> none; else the mask of
+ * element (bh, i, j) is r4d_dropout_f32's at `site`, dropout->seed / step and index_base + (bh * T + i) * r4d_train_attn_probs_ld(T) + j
+ * (index_base % 4 == 0).  The backward's workspace holds D [B*H, T] = rowsum(P o dP) (r4d_train_attn_fused_bwd_workspace_bytes; written before it
+ * is read); att_d is part of the contract (the forward's output, non-null) and is not read.  head_dim % 16 == 0 in 16 .. 256, T in 1 .. 1024, B * H <= 65535, pointers 16-byte aligned; anything else is
+ * R4D_ERR_INVALID (a short workspace: R4D_ERR_WORKSPACE) before any launch, and the size query returns 0. */
+int r4d_train_attn_fused_fwd_f32(const float* qkv_d, int32_t B, int32_t T, int32_t H, int32_t d, float* att_out_d, float* lse_out_d,
+                                 const r4d_train_dropout* dropout, uint32_t site, uint64_t index_base, void* stream);
+size_t r4d_train_attn_fused_bwd_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t d);
+int r4d_train_attn_fused_bwd_f32(const float* qkv_d, const float* att_d, const float* lse_d, const float* dao_d, int32_t B, int32_t T,
+                                 int32_t H, int32_t d, float* dqkv_out_d, const r4d_train_dropout* dropout, uint32_t site,
+                                 uint64_t index_base, void* workspace_d, size_t workspace_bytes, void* stream);
+
 /* The LM head of the training steps on plain bf16 operands (process-wide; additive ABI v6 entries; csrc/lm_head.hip on
  * csrc/gemm_b1.hip and csrc/gemm_b1tn.hip).  A third, INDEPENDENT axis beside r4d_set_train_bf16 and r4d_set_train_attention_bf16: it
  * neither reads nor sets them, and they do not read it.  NOT fp32-accurate: while on, both fp32 operands of the head's three GEMMs

@@ -190,6 +190,12 @@ PROTOTYPES = {
                                         c_size_t, _P]),
     "r4d_train_attn_probs_ld": (c_size_t, [c_int32]),
     "r4d_train_attn_product_bf16_f32": (c_int32, [c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    "r4d_set_train_attention_fused": (c_int32, [c_int32]),
+    "r4d_get_train_attention_fused": (c_int32, []),
+    "r4d_train_attn_fused_fwd_f32": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, POINTER(TrainDropoutC), c_uint32, c_uint64, _P]),
+    "r4d_train_attn_fused_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "r4d_train_attn_fused_bwd_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, POINTER(TrainDropoutC), c_uint32, c_uint64,
+                                               _P, c_size_t, _P]),
     "r4d_sumsq_accumulate_f32": (c_int32, [_P, c_int64, _P, _P]),
     "r4d_adamw_step_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int32, _P, c_float, _P]),
     "r4d_dispatch_num_branches": (c_int32, []),

@@ -45,7 +45,8 @@ enum ProfClass {
     PK_GEMM_64x64_NT, PK_GEMM_KC_128x128x32, PK_GEMM_KC_128x128x16, PK_GEMM_KC_128x64x16, PK_GEMM_KC_64x64x32, PK_GEMM_S3_128x256, PK_GEMM_S3_128x128, PK_GEMM_S3TN, PK_GEMM_H2_128x256, PK_GEMM_H2_128x128, PK_GEMM_SKINNY, PK_GEMM_SKINNY_EPI,
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
-    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_GEMM_B1H_NT, PK_GEMM_B1H_NN, PK_COUNT
+    PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_GEMM_B1H_NT, PK_GEMM_B1H_NN,
+    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -89,7 +90,8 @@ struct ProfScope {
     X(TB_FWD, "tuning:train_bf16:fwd") X(TB_DGRAD, "tuning:train_bf16:dgrad") X(TB_WGRAD, "tuning:train_bf16:wgrad") X(TB_WGRAD_FALLBACK, "tuning:train_bf16:wgrad_fallback") \
     X(TBA_NT, "tuning:train_bf16_attn:nt") X(TBA_NN, "tuning:train_bf16_attn:nn") \
     X(TBH_LOGITS, "tuning:train_head_bf16:logits") X(TBH_DGRAD, "tuning:train_head_bf16:dgrad") X(TBH_WGRAD, "tuning:train_head_bf16:wgrad") X(TBH_WGRAD_FALLBACK, "tuning:train_head_bf16:wgrad_fallback") \
-    X(TAB_FWD, "tuning:train_act_bf16:fwd") X(TAB_WGRAD, "tuning:train_act_bf16:wgrad") X(TAB_LN, "tuning:train_act_bf16:ln") X(TAB_GELU, "tuning:train_act_bf16:gelu")
+    X(TAB_FWD, "tuning:train_act_bf16:fwd") X(TAB_WGRAD, "tuning:train_act_bf16:wgrad") X(TAB_LN, "tuning:train_act_bf16:ln") X(TAB_GELU, "tuning:train_act_bf16:gelu") \
+    X(TAF_FWD, "tuning:train_attn_fused:fwd") X(TAF_ROWSUM, "tuning:train_attn_fused:rowsum") X(TAF_DKV, "tuning:train_attn_fused:dkv") X(TAF_DQ, "tuning:train_attn_fused:dq")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -244,13 +246,26 @@ static inline int emb_lg_rows(long long table_rows) {
 }
 int launch_embedding_fix_to_f32(const unsigned long long* acc, long long n, long long table_rows, float* out, hipStream_t s);
 
+// attention_train_fused.hip: Attention._attn of one batch [B, T] and its backward on the "+attn" arithmetic with no [T, T] block in
+// memory (r4d_set_train_attention_fused).  att [B, T, d] merged heads (the backward does not read it), lse / Dscr [B * H, T]; the dropout mask of element (bh, i, j)
+// is launch_dropout's at pbase + (bh T + i) ceil128(T) + j.  Shapes outside attn_train_fused_supported are refused before any launch.
+bool attn_train_fused_supported(int B, int T, int H, int d);
+size_t attn_train_fused_bwd_scratch_floats(int B, int T, int H);
+int launch_attn_train_fused_fwd(const float* qkv, int B, int T, int H, int d, float* att, float* lse, float attn_p, DropKey key,
+                                unsigned site, unsigned long long pbase, hipStream_t s);
+int launch_attn_train_fused_bwd(const float* qkv, const float* att, const float* lse, const float* dao, int B, int T, int H, int d,
+                                float* dqkv, float* Dscr, float attn_p, DropKey key, unsigned site, unsigned long long pbase, hipStream_t s);
+
 // ------------------------------------------------------------------ train.hip (the training forward / backward, shared with lm_head.hip)
-// The process-wide training switches as a value (r4d_set_train_attention, _activations, _bf16, _attention_bf16, _head_bf16, _act_bf16): every
+// The process-wide training switches as a value (r4d_set_train_attention, _activations, _bf16, _attention_bf16, _head_bf16, _act_bf16,
+// _attention_fused): every
 // entry point reads them ONCE, through train_modes(), and hands the value down; nothing below an entry point looks at a global.
 // head_bf16 is the LM head's alone (lm_head.hip): the transformer's forward and backward do not look at it.
 // act_bf16 acts only while bf16 is on: which saved activations are bf16 in memory (conv1d_route.h: train_act_bf16_block).
-struct TrainModes { int attention, activations, bf16, attn_bf16, head_bf16, act_bf16; };
+// attn_fused needs attn_bf16 (the entries refuse it alone): attention by the fused kernels, no P-shaped block.
+struct TrainModes { int attention, activations, bf16, attn_bf16, head_bf16, act_bf16, attn_fused; };
 TrainModes train_modes();
+static inline bool train_modes_ok(const TrainModes& md) { return !md.attn_fused || md.attn_bf16; }   // else: size queries 0, entries refuse
 size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts);
 // output: EITHER out_meanpool_d [sum B, d] OR out_hidden_d [rows, d] (the ln_f output); the backward takes the matching gradient
 // `sp` (nullable, one batch only): a SPLICED input (RAG generator): ids_d[0] holds -100 at the positions 2 .. 2 + r - 1, whose

@@ -522,6 +522,7 @@ int r4d_lm_ce_f32(float* logits_d, int32_t N, int32_t V, int32_t ldV, const int6
 
 size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t T, int32_t ldV) {
     if (!cfg || B <= 0 || T <= 0 || ldV <= 0 || cfg->n_embd <= 0) return 0;
+    if (!train_modes_ok(train_modes())) return 0;                 // train-attention-fused without train-attention-bf16
     return lm_layout(cfg, B, T, ldV).total * sizeof(float) + 256;
 }
 

@@ -178,6 +178,7 @@ extern "C" {
 
 size_t r4d_rag_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t Ta, int32_t ldV) {
     if (!cfg || B <= 0 || Ta <= 0 || ldV <= 0 || cfg->n_embd <= 0) return 0;
+    if (!train_modes_ok(train_modes())) return 0;                 // train-attention-fused without train-attention-bf16
     return lm_layout(cfg, B, Ta, ldV).total * sizeof(float) + 256;
 }
 

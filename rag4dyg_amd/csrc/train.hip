@@ -65,10 +65,14 @@ static int g_train_head_bf16 = 0;
 // train_act_bf16_block names (ln1 of layers >= 1, ln2, f) are kept as bf16: their producers round once, with the rounding the
 // GEMMs that read them apply while staging, so every result keeps its bits.
 static int g_train_act_bf16 = 0;
+// r4d_set_train_attention_fused: 0 attention as six products around a P-shaped block (default), 1 -- only TOGETHER with
+// g_train_attn_bf16; alone every entry refuses it -- the fused kernels of attention_train_fused.hip: no P-shaped block at all, one
+// log-sum-exp per (sequence, head, query) kept instead.  g_train_attention has no effect then.
+static int g_train_attn_fused = 0;
 // The modes as a value (common.h: TrainModes): every entry point (size queries, forward, backward, the head steps) reads the
 // globals ONCE, here, and hands the value down; nothing below an entry point looks at a global.
 TrainModes train_modes() {
-    return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16, g_train_head_bf16, g_train_act_bf16};
+    return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16, g_train_head_bf16, g_train_act_bf16, g_train_attn_fused};
 }
 // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
 static bool train_fuse_gelu() {
@@ -78,7 +82,7 @@ static bool train_fuse_gelu() {
 // The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
 // activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
 // would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
-static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0, 0, 0}, -1};
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0, 0, 0, 0}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -90,9 +94,11 @@ struct TrainLayout {
     size_t M, Ptot, pmax;
     int L, d;
     // per layer (offsets in floats)
-    std::vector<size_t> x_in, ln1, qkv, att, x_mid, ln2, pre, f, P;
+    std::vector<size_t> x_in, ln1, qkv, att, x_mid, ln2, pre, f, P, lse;
     size_t x_out, pool_scratch;
     bool recompute;                                     // no P blocks; scratch pA holds the P of the batch at hand
+    bool fused;                                         // r4d_set_train_attention_fused: no P-shaped block at all (P, pA, dP, PT); lse [M H] per layer and attD [M H] instead
+    size_t MH, attD;
     bool act_recompute;                                 // ln1 .. f (and P) of every layer are ONE shared set; x_in stays per layer
     // r4d_set_train_act_bf16 (train_act_bf16_block): the block is bf16 [M, width] -- half the floats at its offset
     bool act_on;
@@ -106,7 +112,8 @@ struct TrainLayout {
 static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int n, TrainModes md) {
     TrainLayout t;
     t.L = cfg->n_layer; t.d = cfg->n_embd;
-    t.recompute = md.attention == 1;
+    t.fused = md.attn_fused && md.attn_bf16;
+    t.recompute = md.attention == 1 && !t.fused;        // (the stored / recompute switch sizes and launches nothing while fused)
     t.act_recompute = md.activations == 1;
     t.act_on = md.bf16 && md.act_bf16;
     const size_t d = t.d;
@@ -119,6 +126,7 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
         if (pf > t.pmax) t.pmax = pf;
         pool += lnf_meanpool_scratch_floats(gs[g].B, gs[g].T, t.d);
     }
+    t.MH = t.M * cfg->n_head;
     size_t off = 0;
     auto take = [&](size_t nfloat) { const size_t o = off; off += (nfloat + 63) / 64 * 64; return o; };
     // a block that may be bf16 (two elements per float; M d / 2 is a multiple of 64 wherever a block qualifies)
@@ -129,12 +137,13 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
             // layers 1 .. L-1 share one ln1, and every layer shares the blocks behind it
             t.x_in.push_back(take(t.M * d)); t.ln1.push_back(l == 1 ? take_act(ACT_LN1, l, t.M * d) : t.ln1[1]); t.qkv.push_back(t.qkv[0]);
             t.att.push_back(t.att[0]); t.x_mid.push_back(t.x_mid[0]); t.ln2.push_back(t.ln2[0]);
-            t.pre.push_back(t.pre[0]); t.f.push_back(t.f[0]); t.P.push_back(t.P[0]);
+            t.pre.push_back(t.pre[0]); t.f.push_back(t.f[0]); t.P.push_back(t.P[0]); t.lse.push_back(t.lse[0]);
             continue;
         }
         t.x_in.push_back(take(t.M * d)); t.ln1.push_back(take_act(ACT_LN1, l, t.M * d)); t.qkv.push_back(take(t.M * 3 * d));
         t.att.push_back(take(t.M * d)); t.x_mid.push_back(take(t.M * d)); t.ln2.push_back(take_act(ACT_LN2, l, t.M * d));
-        t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take_act(ACT_F, l, t.M * 4 * d)); t.P.push_back(t.recompute ? 0 : take(t.Ptot));
+        t.pre.push_back(take(t.M * 4 * d)); t.f.push_back(take_act(ACT_F, l, t.M * 4 * d)); t.P.push_back(t.recompute || t.fused ? 0 : take(t.Ptot));
+        t.lse.push_back(t.fused ? take(t.MH) : 0);
     }
     t.x_out = take(t.M * d);
     t.pool_scratch = take(pool);
@@ -147,7 +156,8 @@ static TrainLayout layout(const r4d_gpt2_config* cfg, const TrainGroup* gs, int 
         t.xT = take(sk);
     }
     t.pA = t.recompute ? take(t.pmax) : 0;
-    t.dP = take(t.pmax); t.PT = take(t.pmax);
+    t.dP = t.fused ? 0 : take(t.pmax); t.PT = t.fused ? 0 : take(t.pmax);
+    t.attD = t.fused ? take(t.MH) : 0;
     size_t red = ln_bwd_scratch_floats((int)t.M, t.d);
     const size_t cs = colsum_scratch_floats((long long)t.M, 4 * t.d);
     if (cs > red) red = cs;
@@ -450,6 +460,39 @@ int r4d_set_train_act_bf16(int32_t on) {
 }
 int r4d_get_train_act_bf16(void) { return g_train_act_bf16; }
 
+int r4d_set_train_attention_fused(int32_t on) {
+    R4D_REQUIRE(on == 0 || on == 1, "set_train_attention_fused: %d is neither 0 (six products around a P block) nor 1 (fused kernels)", (int)on);
+    g_train_attn_fused = on;
+    return R4D_OK;
+}
+int r4d_get_train_attention_fused(void) { return g_train_attn_fused; }
+
+int r4d_train_attn_fused_fwd_f32(const float* qkv_d, int32_t B, int32_t T, int32_t H, int32_t d, float* att_out_d, float* lse_out_d,
+                                 const r4d_train_dropout* dropout, uint32_t site, uint64_t index_base, void* stream) {
+    DropCtx dc;
+    const int rc = drop_ctx(dropout, dc);
+    if (rc) return rc;
+    return launch_attn_train_fused_fwd(qkv_d, B, T, H, d, att_out_d, lse_out_d, dc.attn_p, dc.key, site, index_base, (hipStream_t)stream);
+}
+size_t r4d_train_attn_fused_bwd_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t d) {
+    return attn_train_fused_supported(B, T, H, d) ? (attn_train_fused_bwd_scratch_floats(B, T, H) + 64) * sizeof(float) : 0;
+}
+int r4d_train_attn_fused_bwd_f32(const float* qkv_d, const float* att_d, const float* lse_d, const float* dao_d, int32_t B, int32_t T,
+                                 int32_t H, int32_t d, float* dqkv_out_d, const r4d_train_dropout* dropout, uint32_t site,
+                                 uint64_t index_base, void* workspace_d, size_t workspace_bytes, void* stream) {
+    DropCtx dc;
+    const int rc = drop_ctx(dropout, dc);
+    if (rc) return rc;
+    R4D_REQUIRE(attn_train_fused_supported(B, T, H, d),
+                "train_attn_fused_bwd: bad shape B=%d T=%d H=%d d=%d (head_dim %% 16 == 0 in 16 .. 256, T in 1 .. 1024, B * H <= 65535 wanted)", B, T, H, d);
+    if (!workspace_d || workspace_bytes < r4d_train_attn_fused_bwd_workspace_bytes(B, T, H, d)) {
+        set_error("train_attn_fused_bwd: workspace %zu bytes < required %zu", workspace_bytes, r4d_train_attn_fused_bwd_workspace_bytes(B, T, H, d));
+        return R4D_ERR_WORKSPACE;
+    }
+    return launch_attn_train_fused_bwd(qkv_d, att_d, lse_d, dao_d, B, T, H, d, dqkv_out_d, (float*)workspace_d, dc.attn_p, dc.key, site,
+                                       index_base, (hipStream_t)stream);
+}
+
 size_t r4d_train_attn_probs_ld(int32_t T) { return T > 0 ? (size_t)tpad128(T) : 0; }
 
 int r4d_train_attn_product_bf16_f32(int32_t which, const float* a_d, const float* b_d, float* c_d, int32_t B, int32_t T, int32_t H,
@@ -531,6 +574,7 @@ size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_grou
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
     for (int g = 0; g < n_groups; ++g)
         if (Bs[g] <= 0 || Ts[g] <= 0) return 0;
+    if (!train_modes_ok(train_modes())) return 0;                 // train-attention-fused without train-attention-bf16
     return gpt2_train_workspace_floats(cfg, n_groups, Bs, Ts) * sizeof(float) + 256;
 }
 
@@ -600,9 +644,15 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
         if ((rc = launch_layernorm(x_in, Lw.ln_1_w, Lw.ln_1_b, M, d, cfg->ln_eps, ln1, s))) return rc;
     }
     if ((rc = conv1d(Wqkv, ln1, nullptr, M, EPI_NONE, qkv, s, fwd_ln1))) return rc;
-    for (const TrainGroup& G : gs)
-        if ((rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
-                           att + G.row0 * d, md.attn_bf16, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP))) return rc;
+    for (const TrainGroup& G : gs) {
+        if (t.fused)                                             // (row0 H: the group's first (sequence, head, query) of lse [M H])
+            rc = launch_attn_train_fused_fwd(qkv + G.row0 * 3 * d, G.B, G.T, H, d, att + G.row0 * d, ws + t.lse[l] + G.row0 * H, dc.attn_p,
+                                             dc.key, 4u * l + 0u, G.p0, s);
+        else
+            rc = attn_fwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : ws + t.P[l] + G.p0,
+                          att + G.row0 * d, md.attn_bf16, s, dc.attn_p, dc.key, 4u * l + 0u, G.p0, ws + t.dP);
+        if (rc) return rc;
+    }
     float* branch = ws + t.dy;                                   // a backward temporary, free during the forward
     if (dc.resid_p > 0.f) {                                      // x + resid_dropout(c_proj(a)), :194,229
         if ((rc = conv1d(Wo, att, nullptr, M, EPI_NONE, branch, s, fwd))) return rc;
@@ -632,6 +682,7 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
                        const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s, const SpliceIn* sp) {
     const TrainModes md = train_modes();
+    R4D_REQUIRE(train_modes_ok(md), "gpt2 train: train-attention-fused needs train-attention-bf16 (a '+attn' precision)");
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
@@ -660,6 +711,7 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
                         hipStream_t s, const SpliceIn* sp, float* d_fused) {
     const TrainModes md = train_modes();
+    R4D_REQUIRE(train_modes_ok(md), "gpt2 train backward: train-attention-fused needs train-attention-bf16 (a '+attn' precision)");
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
     if (rc) return rc;
@@ -684,6 +736,9 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     R4D_REQUIRE(!after_fwd || md.act_bf16 == g_last_fwd.modes.act_bf16,
                 "gpt2 train backward: this workspace was filled by a forward with train-act-bf16 %d, the current setting is %d",
                 g_last_fwd.modes.act_bf16, md.act_bf16);
+    R4D_REQUIRE(!after_fwd || md.attn_fused == g_last_fwd.modes.attn_fused,
+                "gpt2 train backward: this workspace was filled by a forward with train-attention-fused %d, the current setting is %d",
+                g_last_fwd.modes.attn_fused, md.attn_fused);
     const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));
@@ -744,10 +799,16 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
         }
         if (!frozen && (rc = weight_grad(att, dbr, Lg.attn_proj_w, Lg.attn_proj_b, d, d, M, d, d, xT, red, s, md.bf16))) return rc;
         if ((rc = data_grad(Wo, dbr, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                        // d(att), merged heads
-        for (const TrainGroup& G : gs)                               // stored mode: the kept P, and no block A (pA does not exist)
-            if ((rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
-                               dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, md.attn_bf16, s,
-                               dc.attn_p, dc.key, 4u * l + 0u, G.p0))) return rc;
+        for (const TrainGroup& G : gs) {                             // stored mode: the kept P, and no block A (pA does not exist)
+            if (t.fused)
+                rc = launch_attn_train_fused_bwd(qkv + G.row0 * 3 * d, att + G.row0 * d, ws + t.lse[l] + G.row0 * H, dy + G.row0 * d, G.B, G.T,
+                                                 H, d, dqkv + G.row0 * 3 * d, ws + t.attD + G.row0 * H, dc.attn_p, dc.key, 4u * l + 0u, G.p0, s);
+            else
+                rc = attn_bwd(HeadDims(G.B, G.T, H, d), qkv + G.row0 * 3 * d, t.recompute ? nullptr : ws + t.P[l] + G.p0,
+                              dy + G.row0 * d, dqkv + G.row0 * 3 * d, t.recompute ? ws + t.pA : nullptr, ws + t.dP, ws + t.PT, md.attn_bf16, s,
+                              dc.attn_p, dc.key, 4u * l + 0u, G.p0);
+            if (rc) return rc;
+        }
         if (!frozen && (rc = weight_grad(ln1, dqkv, Lg.c_attn_w, Lg.c_attn_b, d, 3 * d, M, d, 3 * d, xT, red, s, md.bf16, t.bf(ACT_LN1, l)))) return rc;
         if ((rc = data_grad(Wqkv, dqkv, M, dy, nullptr, nullptr, s, md.bf16))) return rc;                     // d(ln_1 out)
         if ((rc = launch_ln_bwd(x_in, Lw.ln_1_w, dy, dx, M, d, cfg->ln_eps, dx, Lg.ln_1_w, Lg.ln_1_b, red, 0, s))) return rc;    // dx = d(x_in)

@@ -6,6 +6,7 @@
 // models/modeling_gpt2.py:140-235 -- checked against the reference's own autograd gradients (tests/golden/g8_training_step.npz).
 #include <math.h>
 #include "common.h"
+#include "philox.h"
 
 namespace r4d {
 
@@ -308,16 +309,7 @@ __global__ __launch_bounds__(256) void meanpool_bwd_kernel(const float* __restri
 // seed, counter = (element index / 4, site, step low, step high) -- so a mask is a pure function of (seed, step, site, index):
 // nothing is stored between forward and backward (the backward regenerates it), the result does not depend on the launch
 // geometry, and the oracle restates the generator in numpy (oracle/train_ref.py philox_keep) to check forward AND gradients.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
-    }
-    return c;
-}
+// (philox4x32_10: philox.h)
 // out[i] = (resid ? resid[i] : 0) + keep(base + i) * x[i] / (1 - p), four elements (one Philox block) per thread; n, base % 4 == 0
 __global__ __launch_bounds__(256) void dropout_kernel(const float* x, const float* resid, long long n4, float* out,
                                                       unsigned threshold, float scale, DropKey key, unsigned site,
@@ -354,10 +346,7 @@ int launch_dropout(const float* x, const float* resid, long long n, float* out, 
 // transpose (dS, dS^T) and dropout + transpose (Pd^T) of the stored path and must leave ITS bits: the GEMMs behind them read
 // what they read there.  Masks: element idx = pbase + (bh * T + i) * ld + j -> Philox block idx / 4, word idx % 4 (pbase, ld
 // multiples of 4, so a block is four consecutive columns of one row and the word is j % 4), threshold / scale as launch_dropout.
-__device__ __forceinline__ uint4 attn_philox(unsigned long long c, DropKey key, unsigned site) {
-    return philox4x32_10(make_uint4((unsigned)c, site + ((unsigned)(c >> 32) << 16), key.step_lo, key.step_hi),
-                         make_uint2(key.seed_lo, key.seed_hi));
-}
+// (attn_philox: philox.h)
 
 // (a) g = mask * dP / (1 - p);  dS_ij = P_ij (g_ij - sum_k P_ik g_ik) / scale_div, IN PLACE on dP with zeros right of the diagonal
 // up to ld, and dst[bh][j][i] = dS_ij for i < T, zero for i in [T, ld) (j < T: the rows the dK GEMM reads).

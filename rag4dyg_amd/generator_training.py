@@ -95,8 +95,9 @@ class GeneratorTrainer:
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
     def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None,
-                 act_store=None):
-        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``).
+                 act_store=None, attention_kernel=None):
+        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``), as
+        is ``attention_kernel``: ``"products"`` / ``"fused"`` (None -> ``R4D_TRAIN_ATTENTION_KERNEL``; ``"fused"`` needs a ``+attn`` precision).
         ``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
         ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, beside ``precision``."""
         gnn = getattr(model, "gnn_fusion", None)
@@ -108,7 +109,7 @@ class GeneratorTrainer:
         self.model, self.freeze, self.tied = model, bool(freeze), tied
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
         self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations,
-                                  precision=precision, act_store=act_store)
+                                  precision=precision, act_store=act_store, attention_kernel=attention_kernel)
         self.head_precision = resolve_train_head_precision(head_precision)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
@@ -341,7 +342,7 @@ def evaluate(args, trainer, loader, bags):
     return float(total) / n if n else float("nan")
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None, attention_kernel=None):
     """Drop-in for ``train_generator.train`` (:141-248).  Returns (global_step, tr_loss / global_step)."""
     from .generator import get_eval_metrics_generator, load_and_cache_examples
     check_supported(args)
@@ -359,7 +360,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
         t_total = len(loader) // gas * args.num_train_epochs
     trainer = GeneratorTrainer(model, freeze=bool(getattr(args, "freeze", False)),
                                seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                               head_precision=head_precision, act_store=act_store)
+                               head_precision=head_precision, act_store=act_store, attention_kernel=attention_kernel)
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():
@@ -379,6 +380,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
           "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
     print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.enc.act_store))
+    print("  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(trainer.enc.attention_kernel))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

@@ -106,8 +106,9 @@ class LMTrainer:
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
     def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None,
-                 act_store=None):
-        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``).
+                 act_store=None, attention_kernel=None):
+        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``), as
+        is ``attention_kernel``: ``"products"`` / ``"fused"`` (None -> ``R4D_TRAIN_ATTENTION_KERNEL``; ``"fused"`` needs a ``+attn`` precision).
         ``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
         ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, an axis of its own beside ``precision``.  The
         trainer sets the head switch with the others before every size query and step call of its own."""
@@ -117,7 +118,7 @@ class LMTrainer:
                                 "this model's lm_head is a separate tensor")
         self.model = model
         self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations, precision=precision,
-                                  act_store=act_store)
+                                  act_store=act_store, attention_kernel=attention_kernel)
         self.head_precision = resolve_train_head_precision(head_precision)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
@@ -299,7 +300,7 @@ def train_epoch(model, trainer, optimizer, scheduler, train_dataloader, tr_loss,
     return global_step, tr_loss
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None, attention_kernel=None):
     """Drop-in for ``main_SimpleDyG.train`` (:200-343).  Returns (global_step, tr_loss / global_step)."""
     from .evaluation import get_eval_metrics
     if getattr(args, "fp16", False):
@@ -314,7 +315,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     else:
         t_total = len(train_dataloader) // gas * args.num_train_epochs
     trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                        head_precision=head_precision, act_store=act_store)      # every rank its own dropout masks
+                        head_precision=head_precision, act_store=act_store, attention_kernel=attention_kernel)      # every rank its own dropout masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -335,6 +336,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
           "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
     print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.enc.act_store))
+    print("  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(trainer.enc.attention_kernel))
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

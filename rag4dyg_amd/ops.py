@@ -2,6 +2,8 @@
 
 Every function requires CUDA(HIP) tensors and raises otherwise -- there is no CPU path here.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -421,6 +423,55 @@ def train_attn_product_bf16(which, a, b, c, B, T, H, d):
     check(_lib.load().r4d_train_attn_product_bf16_f32(idx, a.data_ptr(), b.data_ptr(), c.data_ptr(), int(B), int(T), int(H), int(d),
                                                       _stream()), "train_attn_product_bf16")
     return c
+
+
+def _attn_dropout_struct(dropout):
+    """None, or (attn_p, seed, step) -> the r4d_train_dropout the fused single ops read (attn_p, seed and step only)"""
+    if dropout is None:
+        return None
+    p, seed, step = dropout
+    return _lib.TrainDropoutC(0.0, float(p), 0.0, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1))
+
+
+def train_attn_fused_fwd(qkv, B, T, H, d, att=None, lse=None, dropout=None, site=0, index_base=0):
+    """The fused attention forward of ``attention_kernel="fused"`` (``r4d_train_attn_fused_fwd_f32``) over ONE [B, T] batch with H heads:
+    ``qkv`` [B, T, 3d] fp32 -> (``att`` [B, T, d] merged heads, ``lse`` [B*H, T]: one log-sum-exp per (sequence, head, query)); no
+    [T, T] block is formed in memory.  ``att`` / ``lse``: optional fp32 device tensors written in place from their FIRST element on
+    (only the T rows' own-head columns); ``dropout``: None or (attn_p, seed, step) -- the mask of element (bh, i, j) is
+    ``r4d_dropout_f32``'s at ``site`` and ``index_base + (bh * T + i) * train_attn_probs_ld(T) + j``."""
+    if att is None:
+        att = torch.empty(B, T, d, dtype=torch.float32, device=qkv.device)
+    if lse is None:
+        lse = torch.empty(B * H, T, dtype=torch.float32, device=qkv.device)
+    for t, n in ((qkv, "qkv"), (att, "att"), (lse, "lse")):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise _lib.R4DError(f"train_attn_fused_fwd: {n} must be an fp32 device tensor")
+    ds = _attn_dropout_struct(dropout)
+    check(_lib.load().r4d_train_attn_fused_fwd_f32(qkv.data_ptr(), int(B), int(T), int(H), int(d), att.data_ptr(), lse.data_ptr(),
+                                                   ctypes.byref(ds) if ds is not None else None, int(site), int(index_base), _stream()),
+          "train_attn_fused_fwd")
+    return att, lse
+
+
+def train_attn_fused_bwd(qkv, att, lse, dao, B, T, H, d, dqkv=None, dropout=None, site=0, index_base=0, workspace=None):
+    """The fused attention backward (``r4d_train_attn_fused_bwd_f32``): ``dao`` [B, T, d] (gradient of ``att``) -> ``dqkv`` [B, T, 3d],
+    from ``qkv``, the forward's ``att`` and ``lse``; three launches (row sums, dK / dV, dQ), P formed again in registers.  ``dqkv``:
+    optional fp32 device tensor written in place (only the T rows' own-head columns); ``workspace``: optional uint8 device tensor of
+    at least ``r4d_train_attn_fused_bwd_workspace_bytes`` bytes (written before it is read); ``dropout`` as in the forward."""
+    lib = _lib.load()
+    if dqkv is None:
+        dqkv = torch.empty(B, T, 3 * d, dtype=torch.float32, device=qkv.device)
+    for t, n in ((qkv, "qkv"), (att, "att"), (lse, "lse"), (dao, "dao"), (dqkv, "dqkv")):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise _lib.R4DError(f"train_attn_fused_bwd: {n} must be an fp32 device tensor")
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.r4d_train_attn_fused_bwd_workspace_bytes(int(B), int(T), int(H), int(d))), 256),
+                                dtype=torch.uint8, device=qkv.device)
+    ds = _attn_dropout_struct(dropout)
+    check(lib.r4d_train_attn_fused_bwd_f32(qkv.data_ptr(), att.data_ptr(), lse.data_ptr(), dao.data_ptr(), int(B), int(T), int(H), int(d),
+                                           dqkv.data_ptr(), ctypes.byref(ds) if ds is not None else None, int(site), int(index_base),
+                                           workspace.data_ptr(), workspace.numel(), _stream()), "train_attn_fused_bwd")
+    return dqkv
 
 
 def set_attention_fused(mode):

@@ -141,6 +141,9 @@ TRAIN_HEAD_PRECISIONS = {"fp32": 0, "bf16": 1}
 # how the bf16 LAYER axis keeps its saved activations (r4d_set_train_act_bf16: ln1 of layers >= 1, ln2 and f as bf16 in memory):
 # the same bits, a smaller workspace; meaningful only where TRAIN_PRECISIONS[precision] == 1
 TRAIN_ACT_STORES = {"fp32": 0, "bf16": 1}
+# which kernels run a block's attention (r4d_set_train_attention_fused): the six per-head products around a [B*H, T, ceil128(T)] block,
+# or the fused kernels that keep no T x T block at all (csrc/attention_train_fused.hip); "fused" needs a "+attn" precision
+TRAIN_ATTENTION_KERNELS = {"products": 0, "fused": 1}
 
 
 def _resolve(what, value, env, table, default):
@@ -196,6 +199,25 @@ def resolve_train_act_store(act_store=None):
     return _resolve("train activation store", act_store, "R4D_TRAIN_ACT_STORE", TRAIN_ACT_STORES, "fp32")
 
 
+def resolve_train_attention_kernel(attention_kernel=None):
+    """``"products"`` (a block's attention as six per-head GEMM launches around a P-shaped block, stored or recomputed) or ``"fused"``
+    (forward and backward by the fused kernels: the ``+attn`` arithmetic, no T x T block in memory, one log-sum-exp per query kept
+    instead; NOT bit-identical to ``"products"``; ``r4d_set_train_attention_fused``; the ``attention`` stored / recompute word then
+    changes neither a size nor a launch).  None -> the environment variable ``R4D_TRAIN_ATTENTION_KERNEL``, ``products`` when it is
+    unset or empty.  Anything else raises.  The pairing with ``precision`` is checked where both are known
+    (:func:`check_attention_kernel`)."""
+    return _resolve("train attention kernel", attention_kernel, "R4D_TRAIN_ATTENTION_KERNEL", TRAIN_ATTENTION_KERNELS, "products")
+
+
+def check_attention_kernel(attention_kernel, precision):
+    """``attention_kernel="fused"`` needs a ``precision`` whose attention axis is bf16: the fused kernels have that arithmetic only,
+    and the library refuses the switch alone -> ValueError here, where the names are known."""
+    if TRAIN_ATTENTION_KERNELS[attention_kernel] == 1 and TRAIN_ATTENTION_BF16[precision] != 1:
+        raise ValueError(f"train attention kernel 'fused' needs a precision with bf16 attention products ('fp32+attn' or 'bf16+attn'), "
+                         f"not {precision!r}")
+    return attention_kernel
+
+
 def check_act_store(act_store, precision):
     """``act_store="bf16"`` needs a ``precision`` whose layer axis is bf16: under ``"fp32"`` / ``"fp32+attn"`` the library
     would ignore it silently -> ValueError."""
@@ -210,12 +232,15 @@ class EncoderTrainer:
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None, act_store=None):
+    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None, act_store=None,
+                 attention_kernel=None):
         """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``);
         ``activations``: the same two words for the per-layer activations (:func:`resolve_train_activations`; None ->
         ``R4D_TRAIN_ACTIVATIONS``); ``precision``: ``"fp32"`` / ``"bf16"`` / ``"fp32+attn"`` / ``"bf16+attn"`` (:func:`resolve_train_precision`;
         None -> ``R4D_TRAIN_PRECISION``); ``act_store``: ``"fp32"`` / ``"bf16"`` (:func:`resolve_train_act_store`; None ->
-        ``R4D_TRAIN_ACT_STORE``; ``"bf16"`` needs a bf16 layer precision, ValueError otherwise).  The trainer sets the five library switches before every size query and step call of its own, so
+        ``R4D_TRAIN_ACT_STORE``; ``"bf16"`` needs a bf16 layer precision, ValueError otherwise); ``attention_kernel``: ``"products"`` /
+        ``"fused"`` (:func:`resolve_train_attention_kernel`; None -> ``R4D_TRAIN_ATTENTION_KERNEL``; ``"fused"`` needs a ``+attn``
+        precision, ValueError otherwise).  The trainer sets the six library switches before every size query and step call of its own, so
         trainers of different modes can share a process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
@@ -225,6 +250,7 @@ class EncoderTrainer:
         self.activations = resolve_train_activations(activations)
         self.precision = resolve_train_precision(precision)
         self.act_store = check_act_store(resolve_train_act_store(act_store), self.precision)
+        self.attention_kernel = check_attention_kernel(resolve_train_attention_kernel(attention_kernel), self.precision)
         self.dropout, self.seed, self.step = dropout, int(seed), 0
         self._drop_struct = None
         tr = model.transformer
@@ -334,6 +360,7 @@ class EncoderTrainer:
         _lib.load().r4d_set_train_bf16(TRAIN_PRECISIONS[self.precision])                # (returns the previous setting)
         _lib.load().r4d_set_train_attention_bf16(TRAIN_ATTENTION_BF16[self.precision])
         _lib.load().r4d_set_train_act_bf16(TRAIN_ACT_STORES[self.act_store])
+        _lib.check(_lib.load().r4d_set_train_attention_fused(TRAIN_ATTENTION_KERNELS[self.attention_kernel]), "set_train_attention_fused")
 
     set_attention_mode = select_modes        # the earlier name, kept for scripts written against it
 
@@ -627,7 +654,7 @@ def distributed_setup(args):
     return dist.get_world_size(), dist.get_rank()
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, act_store=None):
+def train(args, train_dataset, model, tokenizer, activations=None, precision=None, act_store=None, attention_kernel=None):
     """Drop-in for ``train/train_retriever.train`` (``:230-354``): AdamW on the time-decayed contrastive + InfoNCE loss, validation
     hit@3 after every epoch, best checkpoint as ``checkpoint-0`` (only once ``epoch > warmup_steps``, as upstream), last as
     ``checkpoint-1``, early stopping after ``--patience`` epochs without improvement, then the test / validation passes on
@@ -649,7 +676,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     if args.max_steps > 0:
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
     trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                             act_store=act_store)      # every rank its own masks
+                             act_store=act_store, attention_kernel=attention_kernel)      # every rank its own masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -665,6 +692,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too); "
           "no LM head in this step (R4D_TRAIN_HEAD_PRECISION is not read)".format(trainer.precision))
     print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.act_store))
+    print("  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(trainer.attention_kernel))
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

@@ -5,7 +5,7 @@ configuration) and unfrozen (tied); the per-class breakdown of ``r4d_profile_*``
 frozen step in torch autograd, fp32 on the GPU (a plain-torch GPT-2 with fused causal attention, ``oracle.generator_ref``'s GCN).  Eval mode: no
 dropout launches in either.
 
-    python tools/gen_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,reddit] [--one-step uci13] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn] [--head-precision fp32|bf16] [--act-store fp32|bf16]
+    python tools/gen_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,reddit] [--one-step uci13] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn] [--head-precision fp32|bf16] [--act-store fp32|bf16] [--attention-kernel products|fused]
 """
 import argparse
 import ctypes
@@ -129,12 +129,15 @@ def main():
                     help="arithmetic of the LM head's three GEMMs (default: R4D_TRAIN_HEAD_PRECISION, else fp32)")
     ap.add_argument("--act-store", default=None, choices=("fp32", "bf16"),
                     help="how a bf16 layer precision keeps its saved activations (default: R4D_TRAIN_ACT_STORE, else fp32)")
+    ap.add_argument("--attention-kernel", default=None, choices=("products", "fused"),
+                    help="a block's attention as six per-head products or by the fused kernels without a T x T block, which need a '+attn' "
+                         "precision (default: R4D_TRAIN_ATTENTION_KERNEL, else products)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
     if a.one_step:
         m, src, idx, tok = _setup(SHAPES[a.one_step], dev, freeze=True)
-        tr = GeneratorTrainer(m, freeze=True, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store)
+        tr = GeneratorTrainer(m, freeze=True, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store, attention_kernel=a.attention_kernel)
         bags = PreparedBags(idx, src, 7).batch(range(len(idx)), dev)
         for _ in range(2):
             tr.step(tok, bags)
@@ -147,7 +150,7 @@ def main():
         for freeze in (True, False):
             m, src, idx, tok = _setup(s, dev, freeze)
             torch.cuda.reset_peak_memory_stats()
-            tr = GeneratorTrainer(m, freeze=freeze, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store)
+            tr = GeneratorTrainer(m, freeze=freeze, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store, attention_kernel=a.attention_kernel)
             bags = PreparedBags(idx, src, 7).batch(range(len(idx)), dev)
             ms = _time(lambda: tr.step(tok, bags), a.steps, a.warmup)
             key = "frozen" if freeze else "unfrozen"

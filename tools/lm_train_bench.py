@@ -7,7 +7,7 @@ through ``r4d_lm_head_train_f32`` (ms per call and its per-class kernel times), 
 adds the chunk rows, the bytes the materialised logits alone would take next to the step's workspace, and the time of ONE sweep of
 logits GEMMs over the chunks (the GEMM the chunked head runs twice) with its share of the step.
 
-    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn] [--head-precision fp32|bf16] [--act-store fp32|bf16]
+    python tools/lm_train_bench.py [--steps 10] [--warmup 3] [--shapes uci13,wikiv2] [--attention stored|recompute] [--activations stored|recompute] [--precision fp32|bf16|fp32+attn|bf16+attn] [--head-precision fp32|bf16] [--act-store fp32|bf16] [--attention-kernel products|fused]
 """
 import argparse
 import ctypes
@@ -87,6 +87,9 @@ def main():
                     help="arithmetic of the LM head's three GEMMs (default: R4D_TRAIN_HEAD_PRECISION, else fp32)")
     ap.add_argument("--act-store", default=None, choices=("fp32", "bf16"),
                     help="how a bf16 layer precision keeps its saved activations (default: R4D_TRAIN_ACT_STORE, else fp32)")
+    ap.add_argument("--attention-kernel", default=None, choices=("products", "fused"),
+                    help="a block's attention as six per-head products or by the fused kernels without a T x T block, which need a '+attn' "
+                         "precision (default: R4D_TRAIN_ATTENTION_KERNEL, else products)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -101,7 +104,7 @@ def main():
         # eval mode: no dropout launches, so that the step and its body (timed alone below) differ by the head only
         m = m.to(dev).eval()
         torch.cuda.reset_peak_memory_stats()
-        tr = LMTrainer(m, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store)
+        tr = LMTrainer(m, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store, attention_kernel=a.attention_kernel)
         if a.one_step:
             ids = torch.randint(0, s["V"], (s["B"], a.one_step), device=dev)
             tr.step(ids)
@@ -169,7 +172,7 @@ def main():
             total_prof = sum(v["ms"] for v in prof2.values())
             head_like = {k: v for k, v in prof2.items() if v["work"] > 0}
             rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, activations=tr.enc.activations, precision=tr.enc.precision,
-                       act_store=tr.enc.act_store, head_precision=tr.head_precision, head_alone_ms=head_alone_ms,
+                       act_store=tr.enc.act_store, attention_kernel=tr.enc.attention_kernel, head_precision=tr.head_precision, head_alone_ms=head_alone_ms,
                        head_alone_classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"], work=v["work"]) for k, v in sorted(head_prof.items(), key=lambda kv: -kv[1]["ms"])},
                        launches={k: v["launches"] for k, v in sorted(prof2.items())},
                        workspace_bytes=ws_bytes, max_memory_allocated=peak, L=s["L"], H=s["H"], d=d, V=V,

@@ -6,7 +6,9 @@ stored / recompute), from the library's three size queries alone: no GPU, no all
 Rows are the padded worst case of each script (every sequence at the block size); the retriever step is its five forwards in
 one call.  Each cell is the fp32 store's size; the `bf16 store` column beside it is the same query with the layer precision bf16
 and the activation store bf16 (``r4d_set_train_bf16(1)``, ``r4d_set_train_act_bf16(1)``; DESIGN.md section 7.9: ln1 of layers >= 1,
-ln2 and f as bf16 wherever d % 256 == 0).  Vocabularies: rag4dyg_amd/synth.py (retriever flavour with [MASK], SimpleDyG / generator flavour without)."""
+ln2 and f as bf16 wherever d % 256 == 0).  The `fused` column is the fp32 store under the fused attention kernels
+(``r4d_set_train_attention_bf16(1)``, ``r4d_set_train_attention_fused(1)``; DESIGN.md section 7.10: no P-shaped block, one log-sum-exp per
+query per layer), which the attention word does not change: it stands beside the two P recompute cells.  Vocabularies: rag4dyg_amd/synth.py (retriever flavour with [MASK], SimpleDyG / generator flavour without)."""
 import ctypes
 import json
 import os
@@ -43,6 +45,7 @@ def workspace_bytes(lib, kind, L, H, d, V, batches):
 def table():
     lib = _lib.load()
     was = lib.r4d_get_train_attention(), lib.r4d_get_train_activations(), lib.r4d_get_train_bf16(), lib.r4d_get_train_act_bf16()
+    was_fused = lib.r4d_get_train_attention_bf16(), lib.r4d_get_train_attention_fused()
     out = []
     try:
         for kind, label, L, H, d, V, batches in ROWS:
@@ -56,12 +59,22 @@ def table():
                 lib.r4d_set_train_bf16(1)                       # (the layer switch alone changes no size)
                 lib.r4d_set_train_act_bf16(1)
                 rec[f"attention_{att}_activations_{act}_act_store_bf16"] = workspace_bytes(lib, kind, L, H, d, V, batches)
+                if att == "recompute":                          # (the attention_kernel="fused" cell: the attention word changes nothing)
+                    lib.r4d_set_train_bf16(0)
+                    lib.r4d_set_train_act_bf16(0)
+                    lib.r4d_set_train_attention_bf16(1)
+                    _lib.check(lib.r4d_set_train_attention_fused(1), "set_train_attention_fused")
+                    rec[f"attention_fused_activations_{act}"] = workspace_bytes(lib, kind, L, H, d, V, batches)
+                    lib.r4d_set_train_attention_fused(0)
+                    lib.r4d_set_train_attention_bf16(was_fused[0])
             out.append(rec)
     finally:
         lib.r4d_set_train_attention(was[0])
         lib.r4d_set_train_activations(was[1])
         lib.r4d_set_train_bf16(was[2])
         lib.r4d_set_train_act_bf16(was[3])
+        lib.r4d_set_train_attention_bf16(was_fused[0])
+        lib.r4d_set_train_attention_fused(was_fused[1])
     return out
 
 
@@ -72,11 +85,13 @@ def main():
             print(json.dumps(r))
         return
     print("| step | shape | P stored, activations stored | bf16 store | P recompute, activations stored | bf16 store | "
-          "P stored, activations recompute | bf16 store | P recompute, activations recompute | bf16 store |")
-    print("|---|---|---|---|---|---|---|---|---|---|")
+          "P stored, activations recompute | bf16 store | P recompute, activations recompute | bf16 store | fused, activations stored | "
+          "fused, activations recompute |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
     for r in rows:
         cells = [f"{r[k] / 1e9:.2f} GB" for att, act in MODES
                  for k in (f"attention_{att}_activations_{act}", f"attention_{att}_activations_{act}_act_store_bf16")]
+        cells += [f"{r[f'attention_fused_activations_{act}'] / 1e9:.2f} GB" for act in ("stored", "recompute")]
         print(f"| {r['step']} | {r['shape']} | " + " | ".join(cells) + " |")
 
 
