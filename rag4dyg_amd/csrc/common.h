@@ -257,23 +257,23 @@ int launch_attn_train_fused_bwd(const float* qkv, const float* att, const float*
                                 float* dqkv, float* Dscr, float attn_p, DropKey key, unsigned site, unsigned long long pbase, hipStream_t s);
 
 // ------------------------------------------------------------------ train.hip (the training forward / backward, shared with lm_head.hip)
-// The process-wide training switches as a value (r4d_set_train_attention, _activations, _bf16, _attention_bf16, _head_bf16, _act_bf16,
-// _attention_fused): every
-// entry point reads them ONCE, through train_modes(), and hands the value down; nothing below an entry point looks at a global.
+// The process-wide training switches as a value (train.hip: kTrainModes, one row per switch -- its r4d_set_train_* / r4d_get_train_*
+// pair, its setter's conventions and whether the backward guards it).  Every extern "C" entry point reads them ONCE, through
+// train_modes(), and hands the value down as an argument; nothing below an entry point looks at the global.
 // head_bf16 is the LM head's alone (lm_head.hip): the transformer's forward and backward do not look at it.
 // act_bf16 acts only while bf16 is on: which saved activations are bf16 in memory (conv1d_route.h: train_act_bf16_block).
 // attn_fused needs attn_bf16 (the entries refuse it alone): attention by the fused kernels, no P-shaped block.
 struct TrainModes { int attention, activations, bf16, attn_bf16, head_bf16, act_bf16, attn_fused; };
 TrainModes train_modes();
 static inline bool train_modes_ok(const TrainModes& md) { return !md.attn_fused || md.attn_bf16; }   // else: size queries 0, entries refuse
-size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts);
+size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts, TrainModes md);
 // output: EITHER out_meanpool_d [sum B, d] OR out_hidden_d [rows, d] (the ln_f output); the backward takes the matching gradient
 // `sp` (nullable, one batch only): a SPLICED input (RAG generator): ids_d[0] holds -100 at the positions 2 .. 2 + r - 1, whose
 // embedding rows are sp->fused [B, r, d] instead of wte rows (rag_train.hip: launch_splice_embed_ln)
 struct SpliceIn { const float* fused; int r; };
 int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
-                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s,
+                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, TrainModes md, hipStream_t s,
                        const SpliceIn* sp = nullptr);
 // `gr` == nullptr: FROZEN transformer -- no parameter gradient at all (no weight GEMM, no LayerNorm gain / shift sums, no
 // embedding scatter), only the data gradients down to the embeddings; `d_fused` must then be given.  `d_fused` (with `sp`):
@@ -281,7 +281,7 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
 int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr, int n_groups,
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
-                        hipStream_t s, const SpliceIn* sp = nullptr, float* d_fused = nullptr);
+                        TrainModes md, hipStream_t s, const SpliceIn* sp = nullptr, float* d_fused = nullptr);
 // dx[M, W.in] = epilogue(dy[M, W.out] . W^T) on the kernel dgrad_route names (train.hip): optional residual (dx = resid + ...),
 // optional fused gelu_new' (dx = (...) * gelu_new'(gelu_pre); the planes routes only).  `bf16`: TrainBf16
 int data_grad(const Conv1DW& W, const float* dy, int M, float* dx, const float* resid, const float* gelu_pre, hipStream_t s, int bf16 = 0);
@@ -295,13 +295,14 @@ int launch_splice_embed_ln(const int64_t* aug_ids, const float* fused, int r, co
 
 // ------------------------------------------------------------------ lm_head.hip (the LM head of the training steps)
 struct LMLayout { size_t train, h, logits, dh, dwte, tn, ce, total; };
-LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV);
+LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV, TrainModes md);
 // One training step through the LM head (the bodies of r4d_gpt2_lm_train_step_f32 and r4d_rag_train_step_f32 behind their
-// argument checks): forward -> head (loss, dh, dwte) -> backward -> head gradient per `head_mode` (R4D_HEAD_GRAD_*)
+// argument checks): forward -> head (loss, dh, dwte) -> backward -> head gradient per `head_mode` (R4D_HEAD_GRAD_*).  `md`: the
+// modes the export read, for the transformer's two passes and (head_bf16) the head
 int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                     const r4d_lm_head* head, int head_mode, float* head_grad, const int64_t* ids_d, const SpliceIn* sp, int B, int T,
                     float gscale, float* loss, float* d_fused, float* hidden_out, const r4d_train_dropout* dropout, void* workspace_d,
-                    size_t workspace_bytes, int head_bf16, hipStream_t s);
+                    size_t workspace_bytes, TrainModes md, hipStream_t s);
 
 // ------------------------------------------------------------------ topk.hip
 // rows x n values -> rows x k best (value, global index), canonical order; `counters_zeroed`: the caller already cleared

@@ -349,12 +349,12 @@ static size_t head_tn_floats(int N, int d, int ldV) {
     return tn;
 }
 
-LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV) {
+LMLayout lm_layout(const r4d_gpt2_config* cfg, int B, int T, int ldV, TrainModes md) {
     LMLayout t;
     const size_t N = (size_t)B * T, d = cfg->n_embd;
     size_t off = 0;
     auto take = [&](size_t n) { const size_t o = off; off += up64(n); return o; };
-    t.train = take(gpt2_train_workspace_floats(cfg, 1, &B, &T));
+    t.train = take(gpt2_train_workspace_floats(cfg, 1, &B, &T, md));
     // ldV > CE_MAX_LDV: the logits slot and the weight-gradient scratch hold ONE chunk (the full one or the shorter last one)
     // (the sizes do not depend on r4d_set_train_head_bf16: gemm_b1tn cuts its slices to the room of `tn`)
     const int C = ce_chunk_rows(ldV);
@@ -450,11 +450,11 @@ static HeadLayout head_layout(int N, int d, int ldV) {
 int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
                     const r4d_lm_head* head, int head_mode, float* head_grad, const int64_t* ids_d, const SpliceIn* sp, int B, int T,
                     float gscale, float* loss, float* d_fused, float* hidden_out, const r4d_train_dropout* dropout, void* workspace_d,
-                    size_t workspace_bytes, int head_bf16, hipStream_t s) {
+                    size_t workspace_bytes, TrainModes md, hipStream_t s) {
     const int V = cfg->vocab, ldV = head->ldV, d = cfg->n_embd, N = B * T;
     int rc = check_ce(N, V, ldV, T);
     if (rc) return rc;
-    const LMLayout t = lm_layout(cfg, B, T, ldV);
+    const LMLayout t = lm_layout(cfg, B, T, ldV, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("%s: workspace %zu bytes < required %zu", who, workspace_bytes, t.total * sizeof(float));
         return R4D_ERR_WORKSPACE;
@@ -465,12 +465,12 @@ int head_train_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_
     const int64_t* const ids[1] = {ids_d};
     const bool backward = grads || d_fused;
     const bool head_w = backward && head_mode != R4D_HEAD_GRAD_NONE;
-    if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &T, nullptr, h, dropout, ws + t.train, train_bytes, s, sp))) return rc;
+    if ((rc = gpt2_train_forward(cfg, w, 1, ids, &B, &T, nullptr, h, dropout, ws + t.train, train_bytes, md, s, sp))) return rc;
     if (hidden_out) R4D_HIP(hipMemcpyAsync(hidden_out, h, (size_t)N * d * sizeof(float), hipMemcpyDeviceToDevice, s));
     if ((rc = lm_head_train(h, N, V, d, head, ids_d, T, gscale, loss, logits, backward ? dh : nullptr, head_w ? dwte : nullptr,
-                            ws + t.tn, ws + t.ce, head_bf16, s))) return rc;
+                            ws + t.tn, ws + t.ce, md.head_bf16, s))) return rc;
     if (!backward) return R4D_OK;
-    if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &T, nullptr, dh, dropout, ws + t.train, train_bytes, s, sp, d_fused)))
+    if ((rc = gpt2_train_backward(cfg, w, grads, 1, ids, &B, &T, nullptr, dh, dropout, ws + t.train, train_bytes, md, s, sp, d_fused)))
         return rc;
     if (head_mode == R4D_HEAD_GRAD_UNTIED)
         R4D_HIP(hipMemcpyAsync(head_grad, dwte, (size_t)V * d * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -490,7 +490,7 @@ int r4d_gpt2_train_forward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt2
                                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream) {
     R4D_REQUIRE(out_hidden_d, "gpt2 train: null pointer");
     return gpt2_train_forward(cfg, w, n_groups, ids_d, Bs, Ts, nullptr, out_hidden_d, dropout, workspace_d, workspace_bytes,
-                              (hipStream_t)stream);
+                              train_modes(), (hipStream_t)stream);
 }
 
 int r4d_gpt2_train_backward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
@@ -499,7 +499,7 @@ int r4d_gpt2_train_backward_hidden_f32(const r4d_gpt2_config* cfg, const r4d_gpt
                                        void* workspace_d, size_t workspace_bytes, void* stream) {
     R4D_REQUIRE(d_hidden_d, "gpt2 train backward: null pointer");
     return gpt2_train_backward(cfg, w, grads, n_groups, ids_d, Bs, Ts, nullptr, d_hidden_d, dropout, workspace_d, workspace_bytes,
-                               (hipStream_t)stream);
+                               train_modes(), (hipStream_t)stream);
 }
 
 size_t r4d_lm_ce_workspace_bytes(int32_t N) { return N > 0 ? ce_ws_floats(N, true) * sizeof(float) : 0; }
@@ -522,8 +522,9 @@ int r4d_lm_ce_f32(float* logits_d, int32_t N, int32_t V, int32_t ldV, const int6
 
 size_t r4d_gpt2_lm_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t T, int32_t ldV) {
     if (!cfg || B <= 0 || T <= 0 || ldV <= 0 || cfg->n_embd <= 0) return 0;
-    if (!train_modes_ok(train_modes())) return 0;                 // train-attention-fused without train-attention-bf16
-    return lm_layout(cfg, B, T, ldV).total * sizeof(float) + 256;
+    const TrainModes md = train_modes();
+    if (!train_modes_ok(md)) return 0;                            // train-attention-fused without train-attention-bf16
+    return lm_layout(cfg, B, T, ldV, md).total * sizeof(float) + 256;
 }
 
 int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads,
@@ -532,9 +533,8 @@ int r4d_gpt2_lm_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weight
     R4D_REQUIRE(cfg && w && grads && grads->wte && head && head->wte_pad && ids_d && loss_d, "lm train step: null pointer");
     R4D_REQUIRE(B >= 1 && T >= 1 && head->ldV % 128 == 0 && head->ldV >= cfg->vocab,
                 "lm train step: B=%d T=%d ldV=%d (a multiple of 128 >= V=%d)", B, T, head->ldV, cfg->vocab);
-    const int head_bf16 = train_modes().head_bf16;                  // r4d_set_train_head_bf16, read here and handed down
     return head_train_step("lm train step", cfg, w, grads, head, R4D_HEAD_GRAD_TIED, nullptr, ids_d, nullptr, B, T, grad_scale, loss_d,
-                           nullptr, nullptr, dropout, workspace_d, workspace_bytes, head_bf16, (hipStream_t)stream);
+                           nullptr, nullptr, dropout, workspace_d, workspace_bytes, train_modes(), (hipStream_t)stream);
 }
 
 size_t r4d_lm_head_train_workspace_bytes(int32_t N, int32_t d, int32_t ldV) {

@@ -178,8 +178,9 @@ extern "C" {
 
 size_t r4d_rag_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B, int32_t Ta, int32_t ldV) {
     if (!cfg || B <= 0 || Ta <= 0 || ldV <= 0 || cfg->n_embd <= 0) return 0;
-    if (!train_modes_ok(train_modes())) return 0;                 // train-attention-fused without train-attention-bf16
-    return lm_layout(cfg, B, Ta, ldV).total * sizeof(float) + 256;
+    const TrainModes md = train_modes();
+    if (!train_modes_ok(md)) return 0;                            // train-attention-fused without train-attention-bf16
+    return lm_layout(cfg, B, Ta, ldV, md).total * sizeof(float) + 256;
 }
 
 int r4d_rag_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* grads, const r4d_lm_head* head,
@@ -196,9 +197,8 @@ int r4d_rag_train_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w
     R4D_REQUIRE(B >= 1 && r >= 1 && Ta >= r + 3 && head->ldV % 128 == 0 && head->ldV >= cfg->vocab,
                 "rag train step: B=%d Ta=%d r=%d ldV=%d (V=%d)", B, Ta, r, head->ldV, cfg->vocab);
     const SpliceIn sp{fused_d, r};
-    const int head_bf16 = train_modes().head_bf16;                  // r4d_set_train_head_bf16, read here and handed down
     return head_train_step("rag train step", cfg, w, grads, head, head_mode, head_grad_d, aug_ids_d, &sp, B, Ta, grad_scale, loss_d,
-                           d_fused_d, hidden_out_d, dropout, workspace_d, workspace_bytes, head_bf16, (hipStream_t)stream);
+                           d_fused_d, hidden_out_d, dropout, workspace_d, workspace_bytes, train_modes(), (hipStream_t)stream);
 }
 
 int r4d_weighted_bag_f32(const float* table_d, int32_t vocab, int32_t d, const int64_t* ids_d, const float* weights_d,

@@ -45,34 +45,49 @@ int launch_embedding_fix_to_f32(const unsigned long long* acc, long long n, long
 int launch_embedding_absmax(const float* dx, long long n, unsigned long long* acc_wte, long long table_elems, hipStream_t s);
 int launch_meanpool_bwd(const float* d_pool, long long rows, int T, int d, float* dh, hipStream_t s);
 
-// r4d_set_train_attention: 0 stored (the forward keeps P of every layer), 1 recompute (the backward forms P again with the
-// forward's two launches; no per-layer P blocks).
-static int g_train_attention = 0;
-// r4d_set_train_activations: 0 stored (the forward keeps ln1 .. f of every layer), 1 recompute (it keeps each layer's input; the
-// backward forms one layer's activations at a time again, with the forward's launches, in ONE set all layers share).
-static int g_train_activations = 0;
-// r4d_set_train_bf16: 0 the gemm mode's arithmetic (default), 1 the twelve Conv1D GEMMs of a block on plain bf16 operands
-// (gemm_b1.hip, gemm_b1tn.hip) wherever the layer carries the plane and the shape is supported.  NOT fp32-accurate.
-static int g_train_bf16 = 0;
-// r4d_set_train_attention_bf16: 0 the six per-head attention products of a block on the exact-f32 kernel (default), 1 on plain bf16
-// operands (gemm_b1h.hip).  Independent of g_train_bf16.  NOT fp32-accurate.
-static int g_train_attn_bf16 = 0;
-// r4d_set_train_head_bf16: 0 the LM head's three GEMMs on the gemm mode's kernels (default), 1 on plain bf16 operands (gemm_b1.hip,
-// gemm_b1tn.hip) wherever the head carries the plane and the shape is supported (lm_head.hip).  Independent of the two above; the
-// retriever step has no head and does not read it.  NOT fp32-accurate.
-static int g_train_head_bf16 = 0;
-// r4d_set_train_act_bf16: 0 every saved activation fp32 (default), 1 -- only while g_train_bf16 is on -- the blocks
-// train_act_bf16_block names (ln1 of layers >= 1, ln2, f) are kept as bf16: their producers round once, with the rounding the
-// GEMMs that read them apply while staging, so every result keeps its bits.
-static int g_train_act_bf16 = 0;
-// r4d_set_train_attention_fused: 0 attention as six products around a P-shaped block (default), 1 -- only TOGETHER with
-// g_train_attn_bf16; alone every entry refuses it -- the fused kernels of attention_train_fused.hip: no P-shaped block at all, one
-// log-sum-exp per (sequence, head, query) kept instead.  g_train_attention has no effect then.
-static int g_train_attn_fused = 0;
-// The modes as a value (common.h: TrainModes): every entry point (size queries, forward, backward, the head steps) reads the
-// globals ONCE, here, and hands the value down; nothing below an entry point looks at a global.
-TrainModes train_modes() {
-    return TrainModes{g_train_attention, g_train_activations, g_train_bf16, g_train_attn_bf16, g_train_head_bf16, g_train_act_bf16, g_train_attn_fused};
+// The process-wide training switches: ONE value (common.h: TrainModes) behind the fourteen r4d_set_train_* / r4d_get_train_*
+// exports, and ONE table with a row per switch.  A row carries what differs between the exports -- the name in messages, whether the
+// setter refuses a value outside 0 / 1 (`refusal`: its message, one %d) or normalises it to on != 0 (nullptr), whether it returns
+// the previous value or R4D_OK -- and whether the backward must find the switch as the forward that filled its workspace left it
+// (`guarded`: it would read another layout or run other arithmetic on the saved blocks).  A new switch is a TrainModes member and a
+// row here, its export pair below, and whatever reads it.
+static TrainModes g_modes{};
+TrainModes train_modes() { return g_modes; }
+struct TrainModeRow { int TrainModes::*field; const char* name; const char* refusal; bool returns_prev, guarded; };
+enum { TM_ATTENTION, TM_ACTIVATIONS, TM_BF16, TM_ATTN_BF16, TM_HEAD_BF16, TM_ACT_BF16, TM_ATTN_FUSED };
+static const TrainModeRow kTrainModes[] = {
+    // 0 stored (the forward keeps P of every layer), 1 recompute (the backward forms P again with the forward's two launches; no
+    // per-layer P blocks)
+    {&TrainModes::attention, "train-attention mode", "set_train_attention: mode %d is neither 0 (stored) nor 1 (recompute)", false, true},
+    // 0 stored (the forward keeps ln1 .. f of every layer), 1 recompute (it keeps each layer's input; the backward forms one layer's
+    // activations at a time again, with the forward's launches, in ONE set all layers share)
+    {&TrainModes::activations, "train-activations mode", "set_train_activations: mode %d is neither 0 (stored) nor 1 (recompute)", false, true},
+    // 0 the gemm mode's arithmetic (default), 1 the twelve Conv1D GEMMs of a block on plain bf16 operands (gemm_b1.hip, gemm_b1tn.hip)
+    // wherever the layer carries the plane and the shape is supported.  NOT fp32-accurate
+    {&TrainModes::bf16, "train-bf16", nullptr, true, true},
+    // 0 the six per-head attention products of a block on the exact-f32 kernel (default), 1 on plain bf16 operands (gemm_b1h.hip).
+    // Independent of bf16.  NOT fp32-accurate
+    {&TrainModes::attn_bf16, "train-attention-bf16", nullptr, true, true},
+    // 0 the LM head's three GEMMs on the gemm mode's kernels (default), 1 on plain bf16 operands wherever the head carries the plane
+    // and the shape is supported (lm_head.hip).  Independent of the two above; the retriever step has no head and does not read it, and
+    // no saved block depends on it: not guarded.  NOT fp32-accurate
+    {&TrainModes::head_bf16, "train-head-bf16", nullptr, true, false},
+    // 0 every saved activation fp32 (default), 1 -- only while bf16 is on -- the blocks train_act_bf16_block names (ln1 of layers >= 1,
+    // ln2, f) are kept as bf16: their producers round once, with the rounding the GEMMs that read them apply while staging, so every
+    // result keeps its bits
+    {&TrainModes::act_bf16, "train-act-bf16", "set_train_act_bf16: %d is neither 0 (fp32 activations) nor 1 (bf16 store)", true, true},
+    // 0 attention as six products around a P-shaped block (default), 1 -- only TOGETHER with attn_bf16; alone every entry refuses it
+    // (train_modes_ok) -- the fused kernels of attention_train_fused.hip: no P-shaped block at all, one log-sum-exp per (sequence, head,
+    // query) kept instead.  `attention` has no effect then
+    {&TrainModes::attn_fused, "train-attention-fused",
+     "set_train_attention_fused: %d is neither 0 (six products around a P block) nor 1 (fused kernels)", false, true},
+};
+static_assert(sizeof(kTrainModes) / sizeof(kTrainModes[0]) == TM_ATTN_FUSED + 1, "one kTrainModes row per TM_* index, in that order");
+static int set_mode(const TrainModeRow& row, int value) {
+    if (row.refusal) R4D_REQUIRE(value == 0 || value == 1, row.refusal, value);
+    const int prev = g_modes.*row.field;
+    g_modes.*row.field = value != 0;
+    return row.returns_prev ? prev : R4D_OK;
 }
 // tuning aid: R4D_TRAIN_FUSE_GELU=0 keeps the two element-wise GELU launches (read once)
 static bool train_fuse_gelu() {
@@ -82,7 +97,7 @@ static bool train_fuse_gelu() {
 // The most recent training forward: its workspace, the modes it ran under and, in activations-recompute mode, the layer whose
 // activations that workspace's shared set holds (-1: none).  It guards the backward: on that workspace under another mode it
 // would read the wrong layout -> refused; straight behind its forward it need not form the last layer's activations again.
-static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {0, 0, 0, 0, 0, 0, 0}, -1};
+static struct { const void* ws; TrainModes modes; int shared_layer; } g_last_fwd = {nullptr, {}, -1};
 
 static inline int tpad128(int T) { return (T + 127) / 128 * 128; }
 static inline int up4(long long x) { return (int)((x + 3) / 4 * 4); }
@@ -348,14 +363,15 @@ static int attn_fwd(const HeadDims& D, const float* qkv, float* P, float* out, i
 // Attention backward over one batch: dao [B,T,d] (merged heads) -> dqkv [B,T,3d].  `P`: the probabilities the forward kept, or
 // nullptr (recompute mode): they are formed again into A by the forward's two launches, the same bits.  A (recompute mode
 // only), Bs, C: scratch blocks of the batch's [B*H, T, ld] size.  The four GEMMs are the same launches in both modes; the
-// element-wise steps between them are separate launches in stored mode and the two fused row kernels, written to leave those
-// launches' bits, in recompute mode (stored mode can take the fused kernels over once they have been timed against it).
+// element-wise steps between them are separate launches in stored mode and, in recompute mode, the two row kernels that merge them
+// (`row_kernels`: launch_softmax_bwd_t, launch_dropout_transpose), written to leave those launches' bits (stored mode can take the
+// row kernels over once they have been timed against it).  Neither mode is r4d_set_train_attention_fused: that one never gets here.
 static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const float* dao, float* dqkv, float* A, float* Bs, float* C,
                     int abf, hipStream_t s, float attn_p, DropKey key, unsigned site, unsigned long long pbase) {
     const int d = D.d, BH = D.B * D.H;
     const long long n = (long long)BH * D.T * D.ld;
     const float sd = (float)sqrt((double)D.hd);                  // the logits were divided by sqrt(hd) before the softmax
-    const bool fused = P == nullptr;
+    const bool row_kernels = P == nullptr;
     int rc;
     if (!P) {
         if ((rc = attn_probs(D, qkv, A, abf, s))) return rc;
@@ -364,7 +380,7 @@ static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const f
     // dP = dO . V^T
     if ((rc = head_product(D, HP_DP, dao, qkv + 2 * d, Bs, abf, s))) return rc;
     // dS in place on Bs (through the dropout mask: d(softmax out) = mask * dP / (1 - p)), dS^T into C
-    if (fused) {
+    if (row_kernels) {
         if ((rc = launch_softmax_bwd_t(P, Bs, C, BH, D.T, D.ld, sd, attn_p, key, site, pbase, s))) return rc;
     } else {
         if (attn_p > 0.f && (rc = launch_dropout(Bs, nullptr, n, Bs, attn_p, key, site, pbase, s))) return rc;
@@ -372,11 +388,11 @@ static int attn_bwd(const HeadDims& D, const float* qkv, const float* P, const f
     }
     // dQ = dS . K,  dK = dS^T . Q
     if ((rc = head_product(D, HP_DQ, Bs, qkv + d, dqkv, abf, s))) return rc;
-    if (!fused && (rc = launch_transpose(Bs, D.T, D.T, D.ld, D.probs.s1, C, D.ld, D.probs.s1, BH, s))) return rc;
+    if (!row_kernels && (rc = launch_transpose(Bs, D.T, D.T, D.ld, D.probs.s1, C, D.ld, D.probs.s1, BH, s))) return rc;
     if ((rc = head_product(D, HP_DK, C, qkv, dqkv + d, abf, s))) return rc;
     // dV = Pd^T . dO: the probabilities the forward multiplied V with, after dropout, transposed into C (free once the dK GEMM
     // ahead in the stream has read it; Bs is free by now)
-    if (fused) {
+    if (row_kernels) {
         if ((rc = launch_dropout_transpose(P, C, BH, D.T, D.ld, attn_p, key, site, pbase, s))) return rc;
     } else {
         if (attn_p > 0.f && (rc = launch_dropout(P, nullptr, n, Bs, attn_p, key, site, pbase, s))) return rc;
@@ -417,55 +433,20 @@ int r4d_weight_grad_f32(const float* x_d, const float* dy_d, int32_t rows, int32
     return weight_grad(x_d, dy_d, dw_d, db_d, in_features, out_features, rows, in_features, out_features, skp, red, (hipStream_t)stream);
 }
 
-int r4d_set_train_attention(int32_t mode) {
-    R4D_REQUIRE(mode == 0 || mode == 1, "set_train_attention: mode %d is neither 0 (stored) nor 1 (recompute)", (int)mode);
-    g_train_attention = mode;
-    return R4D_OK;
-}
-int r4d_get_train_attention(void) { return g_train_attention; }
-
-int r4d_set_train_activations(int32_t mode) {
-    R4D_REQUIRE(mode == 0 || mode == 1, "set_train_activations: mode %d is neither 0 (stored) nor 1 (recompute)", (int)mode);
-    g_train_activations = mode;
-    return R4D_OK;
-}
-int r4d_get_train_activations(void) { return g_train_activations; }
-
-int r4d_set_train_bf16(int32_t on) {
-    const int prev = g_train_bf16;
-    g_train_bf16 = on != 0;
-    return prev;
-}
-int r4d_get_train_bf16(void) { return g_train_bf16; }
-
-int r4d_set_train_attention_bf16(int32_t on) {
-    const int prev = g_train_attn_bf16;
-    g_train_attn_bf16 = on != 0;
-    return prev;
-}
-int r4d_get_train_attention_bf16(void) { return g_train_attn_bf16; }
-
-int r4d_set_train_head_bf16(int32_t on) {
-    const int prev = g_train_head_bf16;
-    g_train_head_bf16 = on != 0;
-    return prev;
-}
-int r4d_get_train_head_bf16(void) { return g_train_head_bf16; }
-
-int r4d_set_train_act_bf16(int32_t on) {
-    R4D_REQUIRE(on == 0 || on == 1, "set_train_act_bf16: %d is neither 0 (fp32 activations) nor 1 (bf16 store)", (int)on);
-    const int prev = g_train_act_bf16;
-    g_train_act_bf16 = on;
-    return prev;
-}
-int r4d_get_train_act_bf16(void) { return g_train_act_bf16; }
-
-int r4d_set_train_attention_fused(int32_t on) {
-    R4D_REQUIRE(on == 0 || on == 1, "set_train_attention_fused: %d is neither 0 (six products around a P block) nor 1 (fused kernels)", (int)on);
-    g_train_attn_fused = on;
-    return R4D_OK;
-}
-int r4d_get_train_attention_fused(void) { return g_train_attn_fused; }
+int r4d_set_train_attention(int32_t mode) { return set_mode(kTrainModes[TM_ATTENTION], mode); }
+int r4d_get_train_attention(void) { return g_modes.attention; }
+int r4d_set_train_activations(int32_t mode) { return set_mode(kTrainModes[TM_ACTIVATIONS], mode); }
+int r4d_get_train_activations(void) { return g_modes.activations; }
+int r4d_set_train_bf16(int32_t on) { return set_mode(kTrainModes[TM_BF16], on); }
+int r4d_get_train_bf16(void) { return g_modes.bf16; }
+int r4d_set_train_attention_bf16(int32_t on) { return set_mode(kTrainModes[TM_ATTN_BF16], on); }
+int r4d_get_train_attention_bf16(void) { return g_modes.attn_bf16; }
+int r4d_set_train_head_bf16(int32_t on) { return set_mode(kTrainModes[TM_HEAD_BF16], on); }
+int r4d_get_train_head_bf16(void) { return g_modes.head_bf16; }
+int r4d_set_train_act_bf16(int32_t on) { return set_mode(kTrainModes[TM_ACT_BF16], on); }
+int r4d_get_train_act_bf16(void) { return g_modes.act_bf16; }
+int r4d_set_train_attention_fused(int32_t on) { return set_mode(kTrainModes[TM_ATTN_FUSED], on); }
+int r4d_get_train_attention_fused(void) { return g_modes.attn_fused; }
 
 int r4d_train_attn_fused_fwd_f32(const float* qkv_d, int32_t B, int32_t T, int32_t H, int32_t d, float* att_out_d, float* lse_out_d,
                                  const r4d_train_dropout* dropout, uint32_t site, uint64_t index_base, void* stream) {
@@ -574,15 +555,17 @@ size_t r4d_gpt2_train_workspace_bytes(const r4d_gpt2_config* cfg, int32_t n_grou
     if (!cfg || n_groups <= 0 || n_groups > ATT_MAXG || !Bs || !Ts) return 0;
     for (int g = 0; g < n_groups; ++g)
         if (Bs[g] <= 0 || Ts[g] <= 0) return 0;
-    if (!train_modes_ok(train_modes())) return 0;                 // train-attention-fused without train-attention-bf16
-    return gpt2_train_workspace_floats(cfg, n_groups, Bs, Ts) * sizeof(float) + 256;
+    const TrainModes md = train_modes();
+    if (!train_modes_ok(md)) return 0;                            // train-attention-fused without train-attention-bf16
+    return gpt2_train_workspace_floats(cfg, n_groups, Bs, Ts, md) * sizeof(float) + 256;
 }
 
 int r4d_gpt2_train_forward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int32_t n_groups,
                                const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d,
                                const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, void* stream) {
     R4D_REQUIRE(out_meanpool_d, "gpt2 train: null pointer");
-    return gpt2_train_forward(cfg, w, n_groups, ids_d, Bs, Ts, out_meanpool_d, nullptr, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
+    return gpt2_train_forward(cfg, w, n_groups, ids_d, Bs, Ts, out_meanpool_d, nullptr, dropout, workspace_d, workspace_bytes, train_modes(),
+                              (hipStream_t)stream);
 }
 
 int r4d_gpt2_train_backward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr,
@@ -590,17 +573,18 @@ int r4d_gpt2_train_backward_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weigh
                                 const float* d_meanpool_d, const r4d_train_dropout* dropout, void* workspace_d,
                                 size_t workspace_bytes, void* stream) {
     R4D_REQUIRE(d_meanpool_d, "gpt2 train backward: null pointer");
-    return gpt2_train_backward(cfg, w, gr, n_groups, ids_d, Bs, Ts, d_meanpool_d, nullptr, dropout, workspace_d, workspace_bytes, (hipStream_t)stream);
+    return gpt2_train_backward(cfg, w, gr, n_groups, ids_d, Bs, Ts, d_meanpool_d, nullptr, dropout, workspace_d, workspace_bytes, train_modes(),
+                               (hipStream_t)stream);
 }
 
 }  // extern "C"
 
 namespace r4d {
 
-size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts) {
+size_t gpt2_train_workspace_floats(const r4d_gpt2_config* cfg, int n_groups, const int32_t* Bs, const int32_t* Ts, TrainModes md) {
     std::vector<TrainGroup> gs((size_t)n_groups);
     for (int g = 0; g < n_groups; ++g) gs[g] = TrainGroup{nullptr, Bs[g], Ts[g], 0, 0, 0};
-    return layout(cfg, gs.data(), n_groups, train_modes()).total;
+    return layout(cfg, gs.data(), n_groups, md).total;
 }
 
 // One block of the training forward: x_in[l] -> x_in[l + 1] (x_out behind the last one), layer 0 from the token ids.
@@ -680,8 +664,8 @@ static int layer_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, 
 // The training forward; its output is EITHER the mean pool per sequence (retriever) OR the ln_f output per row (LM head)
 int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, int n_groups, const int64_t* const* ids_d,
                        const int32_t* Bs, const int32_t* Ts, float* out_meanpool_d, float* out_hidden_d,
-                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, hipStream_t s, const SpliceIn* sp) {
-    const TrainModes md = train_modes();
+                       const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes, TrainModes md, hipStream_t s,
+                       const SpliceIn* sp) {
     R4D_REQUIRE(train_modes_ok(md), "gpt2 train: train-attention-fused needs train-attention-bf16 (a '+attn' precision)");
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
@@ -709,8 +693,7 @@ int gpt2_train_forward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, in
 int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_gpt2_grads* gr, int n_groups,
                         const int64_t* const* ids_d, const int32_t* Bs, const int32_t* Ts, const float* d_meanpool_d,
                         const float* d_hidden_d, const r4d_train_dropout* dropout, void* workspace_d, size_t workspace_bytes,
-                        hipStream_t s, const SpliceIn* sp, float* d_fused) {
-    const TrainModes md = train_modes();
+                        TrainModes md, hipStream_t s, const SpliceIn* sp, float* d_fused) {
     R4D_REQUIRE(train_modes_ok(md), "gpt2 train backward: train-attention-fused needs train-attention-bf16 (a '+attn' precision)");
     std::vector<TrainGroup> gs;
     int rc = check_groups(cfg, n_groups, ids_d, Bs, Ts, gs);
@@ -721,24 +704,10 @@ int gpt2_train_backward(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
                 (gr ? gr->layers && gr->wte && gr->wpe && gr->ln_f_w && gr->ln_f_b : d_fused != nullptr),
                 "gpt2 train backward: null pointer");
     const bool after_fwd = workspace_d == g_last_fwd.ws;             // the workspace of the most recent forward
-    R4D_REQUIRE(!after_fwd || md.attention == g_last_fwd.modes.attention,
-                "gpt2 train backward: this workspace was filled by a forward in train-attention mode %d, the current mode is %d",
-                g_last_fwd.modes.attention, md.attention);
-    R4D_REQUIRE(!after_fwd || md.activations == g_last_fwd.modes.activations,
-                "gpt2 train backward: this workspace was filled by a forward in train-activations mode %d, the current mode is %d",
-                g_last_fwd.modes.activations, md.activations);
-    R4D_REQUIRE(!after_fwd || md.bf16 == g_last_fwd.modes.bf16,
-                "gpt2 train backward: this workspace was filled by a forward with train-bf16 %d, the current setting is %d",
-                g_last_fwd.modes.bf16, md.bf16);
-    R4D_REQUIRE(!after_fwd || md.attn_bf16 == g_last_fwd.modes.attn_bf16,
-                "gpt2 train backward: this workspace was filled by a forward with train-attention-bf16 %d, the current setting is %d",
-                g_last_fwd.modes.attn_bf16, md.attn_bf16);
-    R4D_REQUIRE(!after_fwd || md.act_bf16 == g_last_fwd.modes.act_bf16,
-                "gpt2 train backward: this workspace was filled by a forward with train-act-bf16 %d, the current setting is %d",
-                g_last_fwd.modes.act_bf16, md.act_bf16);
-    R4D_REQUIRE(!after_fwd || md.attn_fused == g_last_fwd.modes.attn_fused,
-                "gpt2 train backward: this workspace was filled by a forward with train-attention-fused %d, the current setting is %d",
-                g_last_fwd.modes.attn_fused, md.attn_fused);
+    for (const TrainModeRow& row : kTrainModes)
+        R4D_REQUIRE(!after_fwd || !row.guarded || md.*row.field == g_last_fwd.modes.*row.field,
+                    "gpt2 train backward: this workspace was filled by a forward with %s %d, the current value is %d", row.name,
+                    g_last_fwd.modes.*row.field, md.*row.field);
     const TrainLayout t = layout(cfg, gs.data(), n_groups, md);
     if (!workspace_d || workspace_bytes < t.total * sizeof(float)) {
         set_error("gpt2 train backward: workspace %zu bytes < required %zu", workspace_bytes, t.total * sizeof(float));

@@ -23,8 +23,7 @@ import torch
 
 from . import _lib, gpt2, ops
 from .lm_training import HeadOperand, LinearWarmupSchedule, save_checkpoint
-from .training import (TRAIN_HEAD_PRECISIONS, AdamW, EncoderTrainer, adjust_learning_rate, distributed_setup,
-                       resolve_train_head_precision)
+from .training import TRAIN_HEAD_PRECISIONS, AdamW, EncoderTrainer, adjust_learning_rate, distributed_setup
 
 
 # ------------------------------------------------------------------------------------------------ host preparation
@@ -94,12 +93,9 @@ class GeneratorTrainer:
     """One generator training micro-step on the device for a ``GPT2LMHeadModelRAG`` with ``gnn_fusion`` (one layer).  ``grads``
     maps the trainable names to views of ONE flat buffer (the clip norm is one launch, the data-parallel mean one all-reduce)."""
 
-    def __init__(self, model, freeze, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None,
-                 act_store=None, attention_kernel=None):
-        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``), as
-        is ``attention_kernel``: ``"products"`` / ``"fused"`` (None -> ``R4D_TRAIN_ATTENTION_KERNEL``; ``"fused"`` needs a ``+attn`` precision).
-        ``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
-        ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, beside ``precision``."""
+    def __init__(self, model, freeze, dropout=None, seed=0, **modes):
+        """``modes``: the mode keywords of :class:`training.EncoderTrainer` and ``head_precision`` (``training.TRAIN_MODE_AXES``), handed
+        to the encoder trainer unopened: it keeps the value (``self.modes``) and sets all seven switches."""
         gnn = getattr(model, "gnn_fusion", None)
         if gnn is None or gnn.n_layers != 1:
             raise _lib.R4DError("GeneratorTrainer: needs a one-layer gnn_fusion (graph pooling)")
@@ -108,9 +104,7 @@ class GeneratorTrainer:
             raise _lib.R4DError("GeneratorTrainer: --freeze needs the untied head of load_and_freeze_params")
         self.model, self.freeze, self.tied = model, bool(freeze), tied
         # layer copies / planes and the dropout struct, built once; no gradient buffer of its own
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, attention=attention, activations=activations,
-                                  precision=precision, act_store=act_store, attention_kernel=attention_kernel)
-        self.head_precision = resolve_train_head_precision(head_precision)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, want_grads=False, head=True, **modes)
         self.params = {n: p for n, p in model.named_parameters() if n in set(trainable_names(model, freeze))}
         offs, total = {}, 0
         for n, p in self.params.items():
@@ -132,10 +126,12 @@ class GeneratorTrainer:
         ops.range_flag(dev)
         self._refresh_head()
 
+    modes = property(lambda self: self.enc.modes)
+    head_precision = property(lambda self: self.enc.head_precision)
+
     def select_modes(self):
-        """The encoder trainer's switches and this trainer's head precision (process-wide: before every size query and step call)."""
+        """All seven switches (process-wide: before every size query and step call)."""
         self.enc.select_modes()
-        _lib.load().r4d_set_train_head_bf16(TRAIN_HEAD_PRECISIONS[self.head_precision])      # (returns the previous setting)
 
     # ---------------------------------------------------------------- derived operands
     def _current_stamp(self):
@@ -342,8 +338,9 @@ def evaluate(args, trainer, loader, bags):
     return float(total) / n if n else float("nan")
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None, attention_kernel=None):
-    """Drop-in for ``train_generator.train`` (:141-248).  Returns (global_step, tr_loss / global_step)."""
+def train(args, train_dataset, model, tokenizer, **modes):
+    """Drop-in for ``train_generator.train`` (:141-248); ``modes``: the :class:`GeneratorTrainer`'s mode keywords.  Returns
+    (global_step, tr_loss / global_step)."""
     from .generator import get_eval_metrics_generator, load_and_cache_examples
     check_supported(args)
     world, rank = distributed_setup(args)
@@ -359,8 +356,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     else:
         t_total = len(loader) // gas * args.num_train_epochs
     trainer = GeneratorTrainer(model, freeze=bool(getattr(args, "freeze", False)),
-                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                               head_precision=head_precision, act_store=act_store, attention_kernel=attention_kernel)
+                               seed=int(getattr(args, "seed", 0)) + 7919 * rank, **modes)
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():
@@ -375,12 +371,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Num Epochs = {}".format(args.num_train_epochs))
     print("  Trainable parameters = {}".format(", ".join(trainer.params)))
     print("  Total optimization steps = {}".format(t_total))
-    print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
-    print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
-          "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
-    print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.enc.act_store))
-    print("  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(trainer.enc.attention_kernel))
+    for line in trainer.modes.banner_lines():
+        print(line)
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_epoch, best_step, counter = None, None, None, 0, 0
     snapshot = lambda: {k: v.detach().clone() for k, v in model.state_dict().items()}

@@ -15,8 +15,7 @@ import os
 import torch
 
 from . import _lib, gpt2, ops
-from .training import (TRAIN_HEAD_PRECISIONS, AdamW, EncoderTrainer, distributed_setup, resolve_train_head_precision,
-                       write_checkpoint_dir)
+from .training import TRAIN_HEAD_PRECISIONS, AdamW, EncoderTrainer, distributed_setup, write_checkpoint_dir
 
 
 def padded_vocab(V):
@@ -105,21 +104,16 @@ class LMTrainer:
     the padded LM-head operand ``wte_pad`` [ldV, d] (zero rows past V) and its planes.  Every derived weight is rebuilt when the
     parameters changed since the last step (``gpt2.note_raw_parameter_write`` generation, or torch's version counter of wte)."""
 
-    def __init__(self, model, dropout=None, seed=0, attention=None, activations=None, precision=None, head_precision=None,
-                 act_store=None, attention_kernel=None):
-        """``act_store``: ``"fp32"`` / ``"bf16"``, handed to the :class:`training.EncoderTrainer` (None -> ``R4D_TRAIN_ACT_STORE``), as
-        is ``attention_kernel``: ``"products"`` / ``"fused"`` (None -> ``R4D_TRAIN_ATTENTION_KERNEL``; ``"fused"`` needs a ``+attn`` precision).
-        ``head_precision``: ``"fp32"`` / ``"bf16"`` (:func:`training.resolve_train_head_precision`; None ->
-        ``R4D_TRAIN_HEAD_PRECISION``): the LM head's three GEMMs on bf16 operands, an axis of its own beside ``precision``.  The
-        trainer sets the head switch with the others before every size query and step call of its own."""
+    def __init__(self, model, dropout=None, seed=0, **modes):
+        """``modes``: the mode keywords of :class:`training.EncoderTrainer` and ``head_precision`` (``training.TRAIN_MODE_AXES``), handed
+        to the encoder trainer unopened: it keeps the value (``self.modes``) and sets all seven switches, the head's with the others,
+        before every size query and step call."""
         head = getattr(model, "lm_head", None)
         if head is None or head.weight is not model.transformer.wte.weight:
             raise _lib.R4DError("SimpleDyG training needs lm_head tied to transformer.wte (the reference's model is always tied); "
                                 "this model's lm_head is a separate tensor")
         self.model = model
-        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, attention=attention, activations=activations, precision=precision,
-                                  act_store=act_store, attention_kernel=attention_kernel)
-        self.head_precision = resolve_train_head_precision(head_precision)
+        self.enc = EncoderTrainer(model, dropout=dropout, seed=seed, head=True, **modes)
         wte = self.enc.params["transformer.wte.weight"]
         V, d = wte.shape
         self.V, self.d, self.ldV = int(V), int(d), padded_vocab(V)
@@ -130,10 +124,12 @@ class LMTrainer:
         ops.range_flag(dev)                                     # registered: the CE kernel reports out-of-range labels there
         self.refresh()
 
+    modes = property(lambda self: self.enc.modes)
+    head_precision = property(lambda self: self.enc.head_precision)
+
     def select_modes(self):
-        """The encoder trainer's switches and this trainer's head precision (process-wide: before every size query and step call)."""
+        """All seven switches (process-wide: before every size query and step call)."""
         self.enc.select_modes()
-        _lib.load().r4d_set_train_head_bf16(TRAIN_HEAD_PRECISIONS[self.head_precision])      # (returns the previous setting)
 
     # the EncoderTrainer surface the training loop uses
     @property
@@ -300,8 +296,9 @@ def train_epoch(model, trainer, optimizer, scheduler, train_dataloader, tr_loss,
     return global_step, tr_loss
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, head_precision=None, act_store=None, attention_kernel=None):
-    """Drop-in for ``main_SimpleDyG.train`` (:200-343).  Returns (global_step, tr_loss / global_step)."""
+def train(args, train_dataset, model, tokenizer, **modes):
+    """Drop-in for ``main_SimpleDyG.train`` (:200-343); ``modes``: the :class:`LMTrainer`'s mode keywords.  Returns (global_step,
+    tr_loss / global_step)."""
     from .evaluation import get_eval_metrics
     if getattr(args, "fp16", False):
         raise NotImplementedError("SimpleDyG training: --fp16 (apex mixed precision) is not built; the path is fp32 "
@@ -314,8 +311,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
     else:
         t_total = len(train_dataloader) // gas * args.num_train_epochs
-    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                        head_precision=head_precision, act_store=act_store, attention_kernel=attention_kernel)      # every rank its own dropout masks
+    trainer = LMTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, **modes)      # every rank its own dropout masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -331,12 +327,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
     print("  Total train batch size (w. parallel, distributed & accumulation) = {}".format(args.train_batch_size * gas * world))
     print("  Gradient Accumulation steps = {}".format(gas))
-    print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.enc.attention))
-    print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.enc.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too), LM head precision = {} "
-          "(R4D_TRAIN_HEAD_PRECISION)".format(trainer.enc.precision, trainer.head_precision))
-    print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.enc.act_store))
-    print("  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(trainer.enc.attention_kernel))
+    for line in trainer.modes.banner_lines():
+        print(line)
     print("  Total optimization steps = {}".format(t_total))
     global_step, tr_loss = 0, 0.0
     best_score, best_state, best_step, counter = None, None, 0, 0

@@ -11,13 +11,17 @@ torch ops (and torch autograd) on the [5, B, d] embeddings only.  In ``model.eva
 parameter gradient equal the reference's (tests/golden/g8); in training mode dropout draws its masks from the library's
 counter-based generator (the reference's torch RNG stream cannot be reproduced), checked against the oracle given the same masks.
 """
+import collections
+import contextlib
 import ctypes
+import dataclasses
 import glob
 import math
 import os
 import random
 import re
 import shutil
+import typing
 import warnings
 
 import numpy as np
@@ -129,84 +133,112 @@ _LAYER_PARAMS = (("ln_1_w", "ln_1.weight"), ("ln_1_b", "ln_1.bias"), ("c_attn_w"
 _CONV1D = tuple((f, name) for f, name in _LAYER_PARAMS if f.endswith("_w") and not f.startswith("ln_"))
 
 
-TRAIN_ATTENTION_MODES = {"stored": 0, "recompute": 1}
-TRAIN_ACTIVATION_MODES = {"stored": 0, "recompute": 1}
-# precision name -> the layer axis (r4d_set_train_bf16: the twelve Conv1D GEMMs of a block) ...
-TRAIN_PRECISIONS = {"fp32": 0, "bf16": 1, "fp32+attn": 0, "bf16+attn": 1}
-# ... and the attention axis (r4d_set_train_attention_bf16: the six per-head products of a block); the two are independent
-TRAIN_ATTENTION_BF16 = {"fp32": 0, "bf16": 0, "fp32+attn": 1, "bf16+attn": 1}
-# the LM head's axis (r4d_set_train_head_bf16: logits, dh and dwte_head of the LM and RAG-generator steps): a table and an argument
-# of its own, independent of the two above; the retriever step has no head
-TRAIN_HEAD_PRECISIONS = {"fp32": 0, "bf16": 1}
-# how the bf16 LAYER axis keeps its saved activations (r4d_set_train_act_bf16: ln1 of layers >= 1, ln2 and f as bf16 in memory):
-# the same bits, a smaller workspace; meaningful only where TRAIN_PRECISIONS[precision] == 1
-TRAIN_ACT_STORES = {"fp32": 0, "bf16": 1}
-# which kernels run a block's attention (r4d_set_train_attention_fused): the six per-head products around a [B*H, T, ceil128(T)] block,
-# or the fused kernels that keep no T x T block at all (csrc/attention_train_fused.hip); "fused" needs a "+attn" precision
-TRAIN_ATTENTION_KERNELS = {"products": 0, "fused": 1}
+# ------------------------------------------------------------------------------------------------ the training modes
+class ModeAxis(collections.namedtuple("ModeAxis", "key env words default what head help")):
+    """One axis of the training modes: the keyword ``key`` of the trainers and ``train()`` functions (``--key-with-dashes`` in the
+    tools), the environment variable ``env`` read when the keyword is None, ``words``: word -> {library switch: value} (a switch
+    ``x`` is the pair ``r4d_set_train_x`` / ``r4d_get_train_x``), the ``default`` word when both are unset or empty, ``what`` the axis
+    is called in an error message, ``head``: the LM head's axis (the retriever step has no head: :class:`EncoderTrainer` refuses
+    the keyword and leaves the switch alone), ``help``: one line for ``--help``."""
+
+    def switch_values(self, switch):
+        """word -> value of ONE of the axis' switches (the ``TRAIN_*`` dicts below)"""
+        return {word: sets[switch] for word, sets in self.words.items()}
 
 
-def _resolve(what, value, env, table, default):
-    """``value``, or -- when it is None -- the environment variable ``env``, or ``default`` when that is unset or empty; anything
-    outside ``table`` raises."""
+# THE table of the training modes on the Python side (the library's is kTrainModes in csrc/train.hip): the resolvers, the pairing
+# checks, what a trainer selects, the banner of the train() functions and the tools' options all come from it.  The axes:
+#   attention         "stored": the forward keeps the attention probabilities of every layer; "recompute": the backward forms them again --
+#                     same bits, a smaller workspace
+#   activations       "stored": the forward keeps ln1 .. f of every layer; "recompute": it keeps each layer's input and the backward forms
+#                     one layer's activations at a time again -- same bits, a workspace that no longer grows with 16 * rows * d per layer
+#   precision         "fp32": the gemm mode's fp32-accurate arithmetic; "bf16": mixed precision, the twelve Conv1D GEMMs of every block on
+#                     bf16 operands with fp32 accumulation -- NOT fp32-accurate; master weights, gradients, AdamW, LayerNorm, softmax, GELU
+#                     and the losses stay fp32; "+attn" behind either: the six per-head attention products of every block on bf16 operands
+#                     as well (a switch of its own: "bf16" alone keeps attention in exact f32)
+#   head_precision    "fp32": the LM head's three GEMMs on the gemm mode's kernels; "bf16": logits = RN(h) . RN(wte)^T, dh = RN(dlogits) .
+#                     RN(wte), dwte = RN(dlogits)^T . RN(h) on bf16 operands with fp32 accumulation -- NOT fp32-accurate; the logits in
+#                     memory, the cross entropy and every gradient buffer stay fp32.  Composes with every precision
+#   act_store         "fp32": every saved activation fp32; "bf16": under a bf16 layer precision (check_act_store) ln1 -- layers >= 1 --, ln2
+#                     and the GELU output f are written as bf16 by their producers and read as bf16 by the GEMMs that round them anyway:
+#                     every loss, output and gradient keeps its bits, the workspace shrinks
+#   attention_kernel  "products": a block's attention as six per-head GEMM launches around a P-shaped block, stored or recomputed; "fused":
+#                     forward and backward by the fused kernels (csrc/attention_train_fused.hip) -- the "+attn" arithmetic
+#                     (check_attention_kernel), no T x T block in memory, one log-sum-exp per query kept instead; NOT bit-identical to
+#                     "products"; the attention word then changes neither a size nor a launch
+# A new mode: a row here (or a switch in a row's words), a row of kTrainModes, the declaration pair in include/r4d.h and its two
+# signatures in _lib.py (tests/test_host_train_modes.py fails on a signature that no row names).
+TRAIN_MODE_AXES = (
+    ModeAxis("attention", "R4D_TRAIN_ATTENTION", {"stored": {"attention": 0}, "recompute": {"attention": 1}}, "stored",
+             "train attention mode", False, "how the step keeps the attention probabilities"),
+    ModeAxis("activations", "R4D_TRAIN_ACTIVATIONS", {"stored": {"activations": 0}, "recompute": {"activations": 1}}, "stored",
+             "train activations mode", False, "how the step keeps the per-layer activations"),
+    ModeAxis("precision", "R4D_TRAIN_PRECISION",
+             {"fp32": {"bf16": 0, "attention_bf16": 0}, "bf16": {"bf16": 1, "attention_bf16": 0},
+              "fp32+attn": {"bf16": 0, "attention_bf16": 1}, "bf16+attn": {"bf16": 1, "attention_bf16": 1}}, "fp32",
+             "train precision", False, "arithmetic of the blocks' Conv1D GEMMs"),
+    ModeAxis("head_precision", "R4D_TRAIN_HEAD_PRECISION", {"fp32": {"head_bf16": 0}, "bf16": {"head_bf16": 1}}, "fp32",
+             "train head precision", True, "arithmetic of the LM head's three GEMMs"),
+    ModeAxis("act_store", "R4D_TRAIN_ACT_STORE", {"fp32": {"act_bf16": 0}, "bf16": {"act_bf16": 1}}, "fp32",
+             "train activation store", False, "how a bf16 layer precision keeps its saved activations"),
+    ModeAxis("attention_kernel", "R4D_TRAIN_ATTENTION_KERNEL", {"products": {"attention_fused": 0}, "fused": {"attention_fused": 1}},
+             "products", "train attention kernel", False,
+             "a block's attention as six per-head products or by the fused kernels without a T x T block, which need a '+attn' precision"),
+)
+_AXIS = {a.key: a for a in TRAIN_MODE_AXES}
+# the switches whose setter answers R4D_OK or an error (the others answer the previous value): selected through _lib.check
+_STATUS_SETTERS = ("attention", "activations", "attention_fused")
+
+TRAIN_ATTENTION_MODES = _AXIS["attention"].switch_values("attention")
+TRAIN_ACTIVATION_MODES = _AXIS["activations"].switch_values("activations")
+TRAIN_PRECISIONS = _AXIS["precision"].switch_values("bf16")                     # the layer switch of a precision word ...
+TRAIN_ATTENTION_BF16 = _AXIS["precision"].switch_values("attention_bf16")       # ... and its attention switch
+TRAIN_HEAD_PRECISIONS = _AXIS["head_precision"].switch_values("head_bf16")
+TRAIN_ACT_STORES = _AXIS["act_store"].switch_values("act_bf16")
+TRAIN_ATTENTION_KERNELS = _AXIS["attention_kernel"].switch_values("attention_fused")
+
+
+def _resolve(key, value):
+    """``value``, or -- when it is None -- the axis' environment variable, or its default when that is unset or empty; anything
+    outside the axis' words raises ValueError."""
+    axis = _AXIS[key]
     if value is None:
-        value = os.environ.get(env) or default
-    if value not in table:
-        raise ValueError(f"{what} {value!r}: expected one of {sorted(table)}")
+        value = os.environ.get(axis.env) or axis.default
+    if value not in axis.words:
+        raise ValueError(f"{axis.what} {value!r}: expected one of {sorted(axis.words)}")
     return value
 
 
 def resolve_train_attention(attention=None):
-    """``"stored"`` (the forward keeps the attention probabilities of every layer) or ``"recompute"`` (the backward forms them
-    again: same bits, a smaller workspace; ``r4d_set_train_attention``).  None -> the environment variable
-    ``R4D_TRAIN_ATTENTION``, ``stored`` when it is unset or empty.  Anything else raises."""
-    return _resolve("train attention mode", attention, "R4D_TRAIN_ATTENTION", TRAIN_ATTENTION_MODES, "stored")
+    """The ``attention`` word (TRAIN_MODE_AXES): the argument, else ``R4D_TRAIN_ATTENTION``, else ``stored``."""
+    return _resolve("attention", attention)
 
 
 def resolve_train_activations(activations=None):
-    """``"stored"`` (the forward keeps ln1 .. f of every layer) or ``"recompute"`` (it keeps each layer's input; the backward
-    forms one layer's activations at a time again: same bits, a workspace that no longer grows with 16 * rows * d per layer;
-    ``r4d_set_train_activations``).  None -> the environment variable ``R4D_TRAIN_ACTIVATIONS``, ``stored`` when it is unset or
-    empty.  Anything else raises."""
-    return _resolve("train activations mode", activations, "R4D_TRAIN_ACTIVATIONS", TRAIN_ACTIVATION_MODES, "stored")
+    """The ``activations`` word (TRAIN_MODE_AXES): the argument, else ``R4D_TRAIN_ACTIVATIONS``, else ``stored``."""
+    return _resolve("activations", activations)
 
 
 def resolve_train_precision(precision=None):
-    """``"fp32"`` (the gemm mode's fp32-accurate arithmetic) or ``"bf16"`` (mixed precision: the twelve Conv1D GEMMs of every
-    block on bf16 operands with fp32 accumulation -- NOT fp32-accurate; master weights, gradients, AdamW, LayerNorm, softmax,
-    GELU and the losses stay fp32; ``r4d_set_train_bf16``); or either of them with ``+attn`` (``"fp32+attn"``, ``"bf16+attn"``):
-    the six per-head attention products of every block on bf16 operands as well (``r4d_set_train_attention_bf16``; an independent
-    axis, ``"bf16"`` alone keeps attention in exact f32).  None -> the environment variable ``R4D_TRAIN_PRECISION``, ``fp32``
-    when it is unset or empty.  Anything else raises."""
-    return _resolve("train precision", precision, "R4D_TRAIN_PRECISION", TRAIN_PRECISIONS, "fp32")
+    """The ``precision`` word (TRAIN_MODE_AXES): the argument, else ``R4D_TRAIN_PRECISION``, else ``fp32``."""
+    return _resolve("precision", precision)
 
 
 def resolve_train_head_precision(head_precision=None):
-    """``"fp32"`` (the LM head's three GEMMs on the gemm mode's fp32-accurate kernels) or ``"bf16"`` (logits = RN(h) . RN(wte)^T,
-    dh = RN(dlogits) . RN(wte), dwte = RN(dlogits)^T . RN(h) on bf16 operands with fp32 accumulation -- NOT fp32-accurate; the
-    logits in memory, the cross entropy and every gradient buffer stay fp32; ``r4d_set_train_head_bf16``).  An axis of its own:
-    it composes with every ``precision``.  None -> the environment variable ``R4D_TRAIN_HEAD_PRECISION``, ``fp32`` when it is
-    unset or empty.  Anything else raises."""
-    return _resolve("train head precision", head_precision, "R4D_TRAIN_HEAD_PRECISION", TRAIN_HEAD_PRECISIONS, "fp32")
+    """The ``head_precision`` word (TRAIN_MODE_AXES): the argument, else ``R4D_TRAIN_HEAD_PRECISION``, else ``fp32``."""
+    return _resolve("head_precision", head_precision)
 
 
 def resolve_train_act_store(act_store=None):
-    """``"fp32"`` (every saved activation fp32) or ``"bf16"`` (under a bf16 layer precision the LayerNorm outputs ln1 -- layers
-    >= 1 -- and ln2 and the GELU output f are written as bf16 by their producers and read as bf16 by the GEMMs that round them
-    anyway: every loss, output and gradient keeps its bits, the workspace shrinks; ``r4d_set_train_act_bf16``).  None -> the
-    environment variable ``R4D_TRAIN_ACT_STORE``, ``fp32`` when it is unset or empty.  Anything else raises.  The pairing with
+    """The ``act_store`` word (TRAIN_MODE_AXES): the argument, else ``R4D_TRAIN_ACT_STORE``, else ``fp32``.  The pairing with
     ``precision`` is checked where both are known (:func:`check_act_store`)."""
-    return _resolve("train activation store", act_store, "R4D_TRAIN_ACT_STORE", TRAIN_ACT_STORES, "fp32")
+    return _resolve("act_store", act_store)
 
 
 def resolve_train_attention_kernel(attention_kernel=None):
-    """``"products"`` (a block's attention as six per-head GEMM launches around a P-shaped block, stored or recomputed) or ``"fused"``
-    (forward and backward by the fused kernels: the ``+attn`` arithmetic, no T x T block in memory, one log-sum-exp per query kept
-    instead; NOT bit-identical to ``"products"``; ``r4d_set_train_attention_fused``; the ``attention`` stored / recompute word then
-    changes neither a size nor a launch).  None -> the environment variable ``R4D_TRAIN_ATTENTION_KERNEL``, ``products`` when it is
-    unset or empty.  Anything else raises.  The pairing with ``precision`` is checked where both are known
-    (:func:`check_attention_kernel`)."""
-    return _resolve("train attention kernel", attention_kernel, "R4D_TRAIN_ATTENTION_KERNEL", TRAIN_ATTENTION_KERNELS, "products")
+    """The ``attention_kernel`` word (TRAIN_MODE_AXES): the argument, else ``R4D_TRAIN_ATTENTION_KERNEL``, else ``products``.  The
+    pairing with ``precision`` is checked where both are known (:func:`check_attention_kernel`)."""
+    return _resolve("attention_kernel", attention_kernel)
 
 
 def check_attention_kernel(attention_kernel, precision):
@@ -226,31 +258,117 @@ def check_act_store(act_store, precision):
     return act_store
 
 
+@dataclasses.dataclass(frozen=True)
+class TrainModes:
+    """One word per axis of TRAIN_MODE_AXES; ``head_precision`` is None in the value of a step without an LM head (the retriever's)."""
+    attention: str
+    activations: str
+    precision: str
+    head_precision: typing.Optional[str]
+    act_store: str
+    attention_kernel: str
+
+    @classmethod
+    def resolve(cls, head=True, **words):
+        """The value of the given keywords: per axis the argument, else its environment variable, else its default, then the two
+        pairing checks.  An unknown keyword raises TypeError -- ``head_precision`` too with ``head=False``."""
+        axes = [a for a in TRAIN_MODE_AXES if head or not a.head]
+        unknown = sorted(set(words) - {a.key for a in axes})
+        if unknown:
+            raise TypeError(f"unexpected training mode keyword {', '.join(map(repr, unknown))}: expected some of {[a.key for a in axes]}")
+        got = {a.key: _resolve(a.key, words.get(a.key)) if a in axes else None for a in TRAIN_MODE_AXES}
+        check_act_store(got["act_store"], got["precision"])
+        check_attention_kernel(got["attention_kernel"], got["precision"])
+        return cls(**got)
+
+    def record(self):
+        """{keyword: word}: what a tool reports, and what builds an equal value again (no head word in a step without a head)"""
+        return {a.key: getattr(self, a.key) for a in TRAIN_MODE_AXES if getattr(self, a.key) is not None}
+
+    def switches(self):
+        """{library switch: value} of every axis this value has a word for"""
+        return {switch: v for key, word in self.record().items() for switch, v in _AXIS[key].words[word].items()}
+
+    def select(self):
+        """Select the value in the library (process-wide switches: before every size query and step call).  A value without a head
+        word leaves the head switch alone."""
+        lib = _lib.load()
+        for switch, v in self.switches().items():
+            rc = getattr(lib, "r4d_set_train_" + switch)(v)
+            if switch in _STATUS_SETTERS:
+                _lib.check(rc, "set_train_" + switch)
+
+    def banner_lines(self):
+        """The lines on the modes that the three ``train()`` functions print"""
+        head = ("no LM head in this step (R4D_TRAIN_HEAD_PRECISION is not read)" if self.head_precision is None else
+                "LM head precision = {} (R4D_TRAIN_HEAD_PRECISION)".format(self.head_precision))
+        return ["  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(self.attention),
+                "  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(self.activations),
+                "  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too){} {}".format(
+                    self.precision, ";" if self.head_precision is None else ",", head),
+                "  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(self.act_store),
+                "  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(
+                    self.attention_kernel)]
+
+
+def _mode_word(key):
+    """A trainer's attribute ``key``: the word of its ``modes``; assigning one replaces the value (as written: no pairing check, the
+    library refuses what it cannot run)."""
+    return property(lambda self: getattr(self.modes, key),
+                    lambda self, word: setattr(self, "modes", dataclasses.replace(self.modes, **{key: word})))
+
+
+def library_modes():
+    """{switch: value} of every training switch as the library has it now (the ``r4d_get_train_*`` of every table row)"""
+    lib = _lib.load()
+    return {switch: getattr(lib, "r4d_get_train_" + switch)() for a in TRAIN_MODE_AXES for switch in next(iter(a.words.values()))}
+
+
+@contextlib.contextmanager
+def saved_library_modes():
+    """Every training switch of the library is put back on exit to what it was on entry, whatever the body set or raised"""
+    was = library_modes()
+    try:
+        yield was
+    finally:
+        lib = _lib.load()
+        for switch, v in was.items():
+            getattr(lib, "r4d_set_train_" + switch)(v)
+
+
+def add_mode_arguments(parser, head=True, keys=None):
+    """``--attention`` ... ``--attention-kernel`` on an argparse parser, one option per axis (``head=False``: none for the LM head;
+    ``keys``: these axes only); each defaults to None, i.e. to the axis' environment variable."""
+    for a in TRAIN_MODE_AXES:
+        if (head or not a.head) and (keys is None or a.key in keys):
+            parser.add_argument("--" + a.key.replace("_", "-"), default=None, choices=tuple(a.words),
+                                help=f"{a.help} (default: {a.env}, else {a.default})")
+
+
+def modes_from_args(ns):
+    """The mode keywords of a namespace parsed after :func:`add_mode_arguments`, for a trainer's ``**modes``"""
+    return {a.key: getattr(ns, a.key) for a in TRAIN_MODE_AXES if hasattr(ns, a.key)}
+
+
 class EncoderTrainer:
     """Forward-with-saved-activations and backward of the SimpleDyG encoder on the HIP kernels
     (``r4d_gpt2_train_forward_f32`` / ``r4d_gpt2_train_backward_f32``), for a ``GPT2LMHeadModelRAG`` whose parameters live
     on the GPU.  ``grads`` maps the reference's parameter names (``transformer.h.0.attn.c_attn.weight`` ...) to gradient
     tensors; ``lm_head.weight`` has none (the retriever discards the logits) unless it is the tied ``wte`` Parameter."""
 
-    def __init__(self, model, dropout=None, seed=0, want_grads=True, attention=None, activations=None, precision=None, act_store=None,
-                 attention_kernel=None):
-        """``attention``: ``"stored"`` / ``"recompute"`` (:func:`resolve_train_attention`; None -> ``R4D_TRAIN_ATTENTION``);
-        ``activations``: the same two words for the per-layer activations (:func:`resolve_train_activations`; None ->
-        ``R4D_TRAIN_ACTIVATIONS``); ``precision``: ``"fp32"`` / ``"bf16"`` / ``"fp32+attn"`` / ``"bf16+attn"`` (:func:`resolve_train_precision`;
-        None -> ``R4D_TRAIN_PRECISION``); ``act_store``: ``"fp32"`` / ``"bf16"`` (:func:`resolve_train_act_store`; None ->
-        ``R4D_TRAIN_ACT_STORE``; ``"bf16"`` needs a bf16 layer precision, ValueError otherwise); ``attention_kernel``: ``"products"`` /
-        ``"fused"`` (:func:`resolve_train_attention_kernel`; None -> ``R4D_TRAIN_ATTENTION_KERNEL``; ``"fused"`` needs a ``+attn``
-        precision, ValueError otherwise).  The trainer sets the six library switches before every size query and step call of its own, so
-        trainers of different modes can share a process.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
+    def __init__(self, model, dropout=None, seed=0, want_grads=True, head=False, **modes):
+        """``modes``: one word per axis of TRAIN_MODE_AXES -- ``attention``, ``activations``, ``precision``, ``act_store``,
+        ``attention_kernel`` (None or absent -> the axis' environment variable, then its default; :meth:`TrainModes.resolve`, which
+        also refuses ``act_store="bf16"`` without a bf16 layer precision and ``attention_kernel="fused"`` without a ``+attn`` one with a
+        ValueError).  They are kept as ``self.modes`` and readable (and assignable) as attributes of those names.  The trainer sets
+        its library switches before every size query and step call of its own, so trainers of different modes can share a process.
+        ``head=True`` (the LM and generator trainers build theirs so): ``head_precision`` is an axis too, and the head switch is set
+        with the other six.  ``want_grads=False``: no gradient buffer at all (a frozen transformer: ``grads`` / ``flat_grads`` are None and
         ``_structs`` returns no gradient struct).  ``dropout``: None -> the model config's ``embd_pdrop`` / ``attn_pdrop`` / ``resid_pdrop`` when the module is in
         training mode (``model.train()``, ``train_retriever.py:161``), the identity in eval mode; or an explicit
         (embd_p, attn_p, resid_p).  ``seed`` keys the counter-based mask generator; every forward advances its step."""
         self.model = model
-        self.attention = resolve_train_attention(attention)
-        self.activations = resolve_train_activations(activations)
-        self.precision = resolve_train_precision(precision)
-        self.act_store = check_act_store(resolve_train_act_store(act_store), self.precision)
-        self.attention_kernel = check_attention_kernel(resolve_train_attention_kernel(attention_kernel), self.precision)
+        self.modes = TrainModes.resolve(head=head, **modes)
         self.dropout, self.seed, self.step = dropout, int(seed), 0
         self._drop_struct = None
         tr = model.transformer
@@ -352,15 +470,11 @@ class EncoderTrainer:
                             self.grads["transformer.ln_f.weight"].data_ptr(), self.grads["transformer.ln_f.bias"].data_ptr(), glayers)
         return c, w, g, (layers, glayers)
 
+    attention, activations, precision, head_precision, act_store, attention_kernel = (_mode_word(a.key) for a in TRAIN_MODE_AXES)
+
     def select_modes(self):
-        """Select this trainer's attention and activations modes and its precision in the library (process-wide switches: before
-        every size query and step call)."""
-        _lib.check(_lib.load().r4d_set_train_attention(TRAIN_ATTENTION_MODES[self.attention]), "set_train_attention")
-        _lib.check(_lib.load().r4d_set_train_activations(TRAIN_ACTIVATION_MODES[self.activations]), "set_train_activations")
-        _lib.load().r4d_set_train_bf16(TRAIN_PRECISIONS[self.precision])                # (returns the previous setting)
-        _lib.load().r4d_set_train_attention_bf16(TRAIN_ATTENTION_BF16[self.precision])
-        _lib.load().r4d_set_train_act_bf16(TRAIN_ACT_STORES[self.act_store])
-        _lib.check(_lib.load().r4d_set_train_attention_fused(TRAIN_ATTENTION_KERNELS[self.attention_kernel]), "set_train_attention_fused")
+        """Select this trainer's modes in the library (process-wide switches: before every size query and step call)."""
+        self.modes.select()
 
     set_attention_mode = select_modes        # the earlier name, kept for scripts written against it (INTEGRATION.md)
 
@@ -654,8 +768,8 @@ def distributed_setup(args):
     return dist.get_world_size(), dist.get_rank()
 
 
-def train(args, train_dataset, model, tokenizer, activations=None, precision=None, act_store=None, attention_kernel=None):
-    """Drop-in for ``train/train_retriever.train`` (``:230-354``): AdamW on the time-decayed contrastive + InfoNCE loss, validation
+def train(args, train_dataset, model, tokenizer, **modes):
+    """Drop-in for ``train/train_retriever.train`` (``:230-354``; ``modes``: the :class:`EncoderTrainer`'s mode keywords): AdamW on the time-decayed contrastive + InfoNCE loss, validation
     hit@3 after every epoch, best checkpoint as ``checkpoint-0`` (only once ``epoch > warmup_steps``, as upstream), last as
     ``checkpoint-1``, early stopping after ``--patience`` epochs without improvement, then the test / validation passes on
     the best and the last weights.  Data parallel: launched under ``torch.distributed.run`` (one process per GPU) every rank
@@ -675,8 +789,7 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     gas = max(1, int(getattr(args, "gradient_accumulation_steps", 1)))
     if args.max_steps > 0:
         args.num_train_epochs = args.max_steps // max(1, len(train_dataloader) // gas) + 1
-    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, activations=activations, precision=precision,
-                             act_store=act_store, attention_kernel=attention_kernel)      # every rank its own masks
+    trainer = EncoderTrainer(model, seed=int(getattr(args, "seed", 0)) + 7919 * rank, **modes)      # every rank its own masks
     if world > 1:
         import torch.distributed as dist
         for p in trainer.params.values():                       # DistributedDataParallel's construction-time broadcast
@@ -687,12 +800,8 @@ def train(args, train_dataset, model, tokenizer, activations=None, precision=Non
     print("  Num examples = {}".format(len(train_dataset)))
     print("  Num Epochs = {}".format(args.num_train_epochs))
     print("  Instantaneous batch size per GPU = {}".format(args.per_gpu_train_batch_size))
-    print("  Attention probabilities = {} (R4D_TRAIN_ATTENTION)".format(trainer.attention))
-    print("  Layer activations = {} (R4D_TRAIN_ACTIVATIONS)".format(trainer.activations))
-    print("  Layer GEMM precision = {} (R4D_TRAIN_PRECISION; '+attn': the attention products on bf16 too); "
-          "no LM head in this step (R4D_TRAIN_HEAD_PRECISION is not read)".format(trainer.precision))
-    print("  Saved activations of the bf16 layer GEMMs = {} (R4D_TRAIN_ACT_STORE)".format(trainer.act_store))
-    print("  Attention kernels = {} (R4D_TRAIN_ATTENTION_KERNEL; 'fused': no T x T block, needs a '+attn' precision)".format(trainer.attention_kernel))
+    for line in trainer.modes.banner_lines():
+        print(line)
     all_query_time = torch.load(os.path.join("resources/", args.dataset + '_train_query_time.pt'))     # get_train_query_time.py
     all_query_time = torch.as_tensor(all_query_time).to(args.device)
     # continuing from a checkpoint directory (train_retriever.py:276; optimizer / schedule state: utils/model.py:96-102)

@@ -15,6 +15,7 @@ from contextlib import redirect_stdout
 import pytest
 import torch
 
+import _train_modes
 import test_gpu_generator_training as gen_tests
 import test_gpu_lm_training as lm_tests
 from _poison import PATTERNS, ZERO, poison, poisoned_allocations
@@ -32,12 +33,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def _switches_restored():
-    yield
-    from rag4dyg_amd import _lib
-    _lib.check(_lib.load().r4d_set_train_attention(0), "set_train_attention")
-    _lib.check(_lib.load().r4d_set_train_activations(0), "set_train_activations")
+_switches_restored = _train_modes.switches_restored(force_stored=("attention", "activations"))
 
 
 def _chunk():

@@ -12,6 +12,7 @@ import math
 import pytest
 import torch
 
+import _train_modes
 from conftest import elementwise_err, rel_err
 from test_gpu_train_attention_recompute import _assert_same_step, _batches, _bits_equal, _demb, _enc_model
 
@@ -32,12 +33,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def _both_switches_stored_afterwards():
-    yield
-    from rag4dyg_amd import _lib
-    _lib.check(_lib.load().r4d_set_train_attention(0), "set_train_attention")
-    _lib.check(_lib.load().r4d_set_train_activations(0), "set_train_activations")
+_both_switches_stored_afterwards = _train_modes.switches_restored(force_stored=("attention", "activations"))
 
 
 def _enc_trainer(m, drop, attention, activations):

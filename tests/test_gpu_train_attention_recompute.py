@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _train_modes
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -25,11 +26,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def _stored_mode_afterwards():
-    yield
-    from rag4dyg_amd import _lib
-    _lib.check(_lib.load().r4d_set_train_attention(0), "set_train_attention")
+_stored_mode_afterwards = _train_modes.switches_restored(force_stored=("attention",))
 
 
 def _tpad128(T):

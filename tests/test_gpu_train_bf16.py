@@ -7,6 +7,7 @@ Every test restores the switches it found."""
 import pytest
 import torch
 
+import _train_modes
 import _train_bf16_ref as R
 from _poison import PATTERNS, poison
 from conftest import load_state_dict_checked
@@ -28,17 +29,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def restore_switches(dev):
-    from rag4dyg_amd import _lib, ops
-    lib = _lib.load()
-    was = (lib.r4d_get_train_bf16(), lib.r4d_get_train_attention(), lib.r4d_get_train_activations(), ops.encode_precision(), ops.gemm_mode())
-    yield
-    lib.r4d_set_train_bf16(was[0])
-    lib.r4d_set_train_attention(was[1])
-    lib.r4d_set_train_activations(was[2])
-    ops.set_encode_precision(was[3])
-    ops.set_gemm_mode(was[4])
+restore_switches = _train_modes.switches_restored(ops_too=True)
 
 
 def hits(prefix=BRANCH_PREFIX):

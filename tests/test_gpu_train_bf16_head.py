@@ -11,6 +11,7 @@ import math
 import pytest
 import torch
 
+import _train_modes
 import _train_bf16_head_ref as Hd
 import _train_bf16_ref as R
 import test_gpu_train_bf16 as TB
@@ -32,20 +33,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def restore_switches(dev):
-    from rag4dyg_amd import _lib, ops
-    lib = _lib.load()
-    was = (lib.r4d_get_train_bf16(), lib.r4d_get_train_attention_bf16(), lib.r4d_get_train_head_bf16(), lib.r4d_get_train_attention(),
-           lib.r4d_get_train_activations(), ops.encode_precision(), ops.gemm_mode())
-    yield
-    lib.r4d_set_train_bf16(was[0])
-    lib.r4d_set_train_attention_bf16(was[1])
-    lib.r4d_set_train_head_bf16(was[2])
-    lib.r4d_set_train_attention(was[3])
-    lib.r4d_set_train_activations(was[4])
-    ops.set_encode_precision(was[5])
-    ops.set_gemm_mode(was[6])
+restore_switches = _train_modes.switches_restored(ops_too=True)
 
 
 def head_hits():

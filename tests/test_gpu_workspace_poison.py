@@ -62,6 +62,7 @@ import numpy as np
 import pytest
 import torch
 
+import _train_modes
 from _poison import ONE, PATTERNS, ZERO, poison, poisoned_allocations
 from conftest import load_golden
 from test_gpu_train_activation_recompute import TINY, WIDE
@@ -84,12 +85,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def _switches_restored():
-    yield
-    from rag4dyg_amd import _lib
-    _lib.check(_lib.load().r4d_set_train_attention(0), "set_train_attention")
-    _lib.check(_lib.load().r4d_set_train_activations(0), "set_train_activations")
+_switches_restored = _train_modes.switches_restored(force_stored=("attention", "activations"))
 
 
 def _stream():

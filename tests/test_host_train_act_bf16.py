@@ -19,14 +19,9 @@ NOTHING = [(1, 256, [(1, 31)]), (2, 64, [(3, 40)])]                        # M =
 
 @pytest.fixture()
 def lib():
-    from rag4dyg_amd import _lib
-    lib = _lib.load()
-    was = (lib.r4d_get_train_attention(), lib.r4d_get_train_activations(), lib.r4d_get_train_bf16(), lib.r4d_get_train_act_bf16())
-    yield lib
-    lib.r4d_set_train_attention(was[0])
-    lib.r4d_set_train_activations(was[1])
-    lib.r4d_set_train_bf16(was[2])
-    lib.r4d_set_train_act_bf16(was[3])
+    from rag4dyg_amd import _lib, training
+    with training.saved_library_modes():
+        yield _lib.load()
 
 
 def expected_saving(L, d, M, act_recompute):
@@ -119,12 +114,12 @@ def test_a_trainer_refuses_the_bf16_store_under_an_fp32_layer_precision(monkeypa
     monkeypatch.setenv("R4D_TRAIN_ACT_STORE", "bf16")
     with pytest.raises(ValueError, match="bf16 layer precision"):
         training.EncoderTrainer(Model(), precision="fp32")
-    import inspect
+    from _train_modes import takes_mode_keyword
     for cls in (training.EncoderTrainer, LMTrainer, GeneratorTrainer):
-        assert "act_store" in inspect.signature(cls.__init__).parameters, cls
+        assert takes_mode_keyword(cls.__init__, "act_store"), cls
     for fn in (training.train, __import__("rag4dyg_amd.lm_training", fromlist=["train"]).train,
                __import__("rag4dyg_amd.generator_training", fromlist=["train"]).train):
-        assert "act_store" in inspect.signature(fn).parameters, fn
+        assert takes_mode_keyword(fn, "act_store"), fn
 
 
 @pytest.mark.parametrize("L,d,groups", SHAPES + [NOTHING[0]], ids=lambda v: str(v).replace(" ", ""))

@@ -13,18 +13,16 @@ from test_host_train_attention_recompute import CASES, _cfg, _retriever_bytes
 
 NEW_SYMBOLS = ("r4d_set_train_attention_fused", "r4d_get_train_attention_fused", "r4d_train_attn_fused_fwd_f32",
                "r4d_train_attn_fused_bwd_workspace_bytes", "r4d_train_attn_fused_bwd_f32")
-SETTERS = ("attention", "activations", "bf16", "attention_bf16", "act_bf16", "attention_fused")
 
 
 @pytest.fixture()
 def lib():
     """the library with every training switch as the test found it afterwards"""
+    from rag4dyg_amd import training
     lib = _lib.load()
-    was = {s: getattr(lib, "r4d_get_train_" + s)() for s in SETTERS}
-    assert was["attention_fused"] == 0, "a test before this one left the fused switch on"
-    yield lib
-    for s, v in was.items():
-        getattr(lib, "r4d_set_train_" + s)(v)
+    with training.saved_library_modes() as was:
+        assert was["attention_fused"] == 0, "a test before this one left the fused switch on"
+        yield lib
     assert lib.r4d_get_train_attention_fused() == 0
 
 

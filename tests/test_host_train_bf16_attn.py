@@ -81,9 +81,9 @@ def test_fp16_is_still_refused_whatever_the_precision():
 
 
 def test_tools_take_the_new_names():
+    from _train_modes import tool_mode_choices
     for tool in ("bench_components.py", "lm_train_bench.py", "gen_train_bench.py"):
-        text = open(os.path.join(REPO, "tools", tool)).read()
-        assert '"fp32", "bf16", "fp32+attn", "bf16+attn"' in text, tool
+        assert tool_mode_choices(tool, "--precision")[1] == ("fp32", "bf16", "fp32+attn", "bf16+attn"), tool
 
 
 def test_emulation_patches_attn_core_and_restores_it():

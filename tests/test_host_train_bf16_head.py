@@ -153,9 +153,13 @@ def test_fp16_is_still_refused_whatever_the_head_precision():
 
 
 def test_tools_take_the_head_precision():
+    import argparse
+    from _train_modes import tool_mode_choices
+    from rag4dyg_amd import training
     for tool in ("lm_train_bench.py", "gen_train_bench.py"):
-        text = open(os.path.join(REPO, "tools", tool)).read()
-        assert '"--head-precision"' in text and 'choices=("fp32", "bf16")' in text and "head_precision=a.head_precision" in text, tool
+        text, words = tool_mode_choices(tool, "--head-precision")
+        assert words == ("fp32", "bf16") and "**training.modes_from_args(a)" in text, tool
+    assert training.modes_from_args(argparse.Namespace(head_precision="bf16", steps=3)) == {"head_precision": "bf16"}
 
 
 def test_head_function_agrees_with_float64_autograd_of_the_rounded_operands():

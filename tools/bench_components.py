@@ -408,12 +408,14 @@ print(json.dumps({"rows": rows, "cols": len(lists), "seconds": el}))
 """
 
 
-def training(attention=None, activations=None, precision=None, attention_kernel=None):
-    """(``--attention-kernel products|fused``: the six per-head products or the fused kernels without a T x T block, ``EncoderTrainer(attention_kernel=)``;
-    ``--attention stored|recompute``: how the step keeps the attention probabilities, ``EncoderTrainer(attention=)``;
-    ``--activations stored|recompute``: the same for the per-layer activations; ``--precision fp32|bf16|fp32+attn|bf16+attn``: the arithmetic of the
-    blocks' Conv1D GEMMs, ``EncoderTrainer(precision=)``; the line reports the three modes, the trainer's
-    workspace bytes and torch's peak allocated bytes.)  SURVEY 8f-4: one retriever training iteration (five forwards with saved activations, losses, encoder backward, clip,
+TRAINING_MODE_KEYS = ("attention", "activations", "precision", "attention_kernel")      # the axes of training.TRAIN_MODE_AXES this entry takes
+
+
+def training(**modes):
+    """(``--attention stored|recompute``, ``--activations stored|recompute``, ``--precision fp32|bf16|fp32+attn|bf16+attn``,
+    ``--attention-kernel products|fused``: the ``EncoderTrainer``'s mode keywords of those names, words and meanings in
+    ``rag4dyg_amd.training.TRAIN_MODE_AXES``; the line reports the four words, the trainer's workspace bytes and torch's peak
+    allocated bytes.)  SURVEY 8f-4: one retriever training iteration (five forwards with saved activations, losses, encoder backward, clip,
     AdamW) at the UCI_13 script's shape (L4 H2 d512, batch 64: scripts/train_retriever/train_retriever_UCI_13.sh:8-12) on
     synthetic UCI_13-length sequences.  flop = 3 x the forward's algorithmic encoder flop (forward + dX + dW) of the five
     padded batches; wall clock includes the host side of the step (aug, loss autograd over [5, B, d], ~40 optimizer launches)."""
@@ -443,7 +445,7 @@ def training(attention=None, activations=None, precision=None, attention_kernel=
     torch.cuda.reset_peak_memory_stats()
     for mode in ("warm", "eval", "train"):               # "train": model.train(), dropout 0.1 at the four sites like the reference
         m.train(mode == "train")
-        trainer = tr.EncoderTrainer(m, seed=42, attention=attention, activations=activations, precision=precision, attention_kernel=attention_kernel)
+        trainer = tr.EncoderTrainer(m, seed=42, **modes)
         opt = tr.AdamW(trainer.params, trainer.grads, lr=1e-5, eps=1e-8, weight_decay=0.0, flat_grads=trainer.flat_grads)
         random.seed(0)
         for b in batches[:2]:
@@ -473,7 +475,7 @@ def training(attention=None, activations=None, precision=None, attention_kernel=
          ms_per_step_dropout_off=round(1e3 * wall["eval"] / n, 3),
          forward_ms=round(ev[0].elapsed_time(ev[1]), 3), backward_ms=round(ev[1].elapsed_time(ev[2]), 3),
          optimizer_ms=round(ev[2].elapsed_time(ev[3]), 3), padded_T=[int(x.shape[1]) for x in b[:3]],
-         attention=trainer.attention, activations=trainer.activations, precision=trainer.precision, attention_kernel=trainer.attention_kernel, workspace_bytes=int(trainer._ws.numel()),
+         **{k: getattr(trainer, k) for k in TRAINING_MODE_KEYS}, workspace_bytes=int(trainer._ws.numel()),
          max_memory_allocated=int(torch.cuda.max_memory_allocated()))
 
 
@@ -525,13 +527,14 @@ def jaccard_cpu_all_cores():
 
 
 if __name__ == "__main__":
-    for flag, words in (("--attention", ("stored", "recompute")), ("--activations", ("stored", "recompute")),
-                        ("--precision", ("fp32", "bf16", "fp32+attn", "bf16+attn")), ("--attention-kernel", ("products", "fused"))):      # training entry only
-        if flag in sys.argv:
+    from rag4dyg_amd.training import TRAIN_MODE_AXES
+    for axis in TRAIN_MODE_AXES:                                                  # training entry only
+        flag = "--" + axis.key.replace("_", "-")
+        if axis.key in TRAINING_MODE_KEYS and flag in sys.argv:
             i = sys.argv.index(flag)
-            if sys.argv[i + 1] not in words:
-                sys.exit(f"{flag}: {' or '.join(words)}")
-            training = functools.partial(training, **{flag[2:].replace("-", "_"): sys.argv[i + 1]})
+            if sys.argv[i + 1] not in axis.words:
+                sys.exit(f"{flag}: {' or '.join(axis.words)}")
+            training = functools.partial(training, **{axis.key: sys.argv[i + 1]})
             del sys.argv[i:i + 2]
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):
         {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "generator": generator,

@@ -111,7 +111,7 @@ def _torch_step(m, src, idx, tok, H, L):
 
 
 def main():
-    from rag4dyg_amd import _lib, ops
+    from rag4dyg_amd import _lib, ops, training
     from rag4dyg_amd.generator_training import GeneratorTrainer, PreparedBags
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -119,25 +119,13 @@ def main():
     ap.add_argument("--shapes", default="uci13,reddit")
     ap.add_argument("--one-step", default="", metavar="SHAPE",
                     help="one warm-up and ONE timed frozen step at SHAPE, print nothing else (for a kernel trace)")
-    ap.add_argument("--attention", default=None, choices=("stored", "recompute"),
-                    help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
-    ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
-                    help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
-    ap.add_argument("--precision", default=None, choices=("fp32", "bf16", "fp32+attn", "bf16+attn"),
-                    help="arithmetic of the blocks' Conv1D GEMMs (default: R4D_TRAIN_PRECISION, else fp32)")
-    ap.add_argument("--head-precision", default=None, choices=("fp32", "bf16"),
-                    help="arithmetic of the LM head's three GEMMs (default: R4D_TRAIN_HEAD_PRECISION, else fp32)")
-    ap.add_argument("--act-store", default=None, choices=("fp32", "bf16"),
-                    help="how a bf16 layer precision keeps its saved activations (default: R4D_TRAIN_ACT_STORE, else fp32)")
-    ap.add_argument("--attention-kernel", default=None, choices=("products", "fused"),
-                    help="a block's attention as six per-head products or by the fused kernels without a T x T block, which need a '+attn' "
-                         "precision (default: R4D_TRAIN_ATTENTION_KERNEL, else products)")
+    training.add_mode_arguments(ap)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
     if a.one_step:
         m, src, idx, tok = _setup(SHAPES[a.one_step], dev, freeze=True)
-        tr = GeneratorTrainer(m, freeze=True, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store, attention_kernel=a.attention_kernel)
+        tr = GeneratorTrainer(m, freeze=True, **training.modes_from_args(a))
         bags = PreparedBags(idx, src, 7).batch(range(len(idx)), dev)
         for _ in range(2):
             tr.step(tok, bags)
@@ -150,7 +138,7 @@ def main():
         for freeze in (True, False):
             m, src, idx, tok = _setup(s, dev, freeze)
             torch.cuda.reset_peak_memory_stats()
-            tr = GeneratorTrainer(m, freeze=freeze, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store, attention_kernel=a.attention_kernel)
+            tr = GeneratorTrainer(m, freeze=freeze, **training.modes_from_args(a))
             bags = PreparedBags(idx, src, 7).batch(range(len(idx)), dev)
             ms = _time(lambda: tr.step(tok, bags), a.steps, a.warmup)
             key = "frozen" if freeze else "unfrozen"
@@ -158,8 +146,7 @@ def main():
             rec[key + "_tokens_per_s"] = round(tokens / (ms / 1e3), 1)
             rec[key + "_workspace_bytes"] = int(tr._ws.numel())
             rec[key + "_max_memory_allocated"] = int(torch.cuda.max_memory_allocated())      # model, trainer and the timed steps
-            rec["attention"], rec["activations"], rec["precision"] = tr.enc.attention, tr.enc.activations, tr.enc.precision
-            rec["head_precision"] = tr.head_precision
+            rec.update(tr.modes.record())
             if freeze:
                 lib.r4d_profile_enable(1)
                 tr.step(tok, bags)

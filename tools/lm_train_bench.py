@@ -68,7 +68,7 @@ def _logits_sweep(tr, h):
 
 def main():
     from oracle import gpt2_ref
-    from rag4dyg_amd import _lib, ops
+    from rag4dyg_amd import _lib, ops, training
     from rag4dyg_amd.gpt2 import GPT2Config, GPT2LMHeadModel
     from rag4dyg_amd.lm_training import LMTrainer
     ap = argparse.ArgumentParser()
@@ -77,19 +77,7 @@ def main():
     ap.add_argument("--shapes", default="uci13,wikiv2")
     ap.add_argument("--one-step", type=int, default=0, metavar="T",
                     help="run one warm-up and ONE timed step at T of the first shape, print nothing else (for a kernel trace)")
-    ap.add_argument("--attention", default=None, choices=("stored", "recompute"),
-                    help="how the step keeps the attention probabilities (default: R4D_TRAIN_ATTENTION, else stored)")
-    ap.add_argument("--activations", default=None, choices=("stored", "recompute"),
-                    help="how the step keeps the per-layer activations (default: R4D_TRAIN_ACTIVATIONS, else stored)")
-    ap.add_argument("--precision", default=None, choices=("fp32", "bf16", "fp32+attn", "bf16+attn"),
-                    help="arithmetic of the blocks' Conv1D GEMMs (default: R4D_TRAIN_PRECISION, else fp32)")
-    ap.add_argument("--head-precision", default=None, choices=("fp32", "bf16"),
-                    help="arithmetic of the LM head's three GEMMs (default: R4D_TRAIN_HEAD_PRECISION, else fp32)")
-    ap.add_argument("--act-store", default=None, choices=("fp32", "bf16"),
-                    help="how a bf16 layer precision keeps its saved activations (default: R4D_TRAIN_ACT_STORE, else fp32)")
-    ap.add_argument("--attention-kernel", default=None, choices=("products", "fused"),
-                    help="a block's attention as six per-head products or by the fused kernels without a T x T block, which need a '+attn' "
-                         "precision (default: R4D_TRAIN_ATTENTION_KERNEL, else products)")
+    training.add_mode_arguments(ap)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -104,7 +92,7 @@ def main():
         # eval mode: no dropout launches, so that the step and its body (timed alone below) differ by the head only
         m = m.to(dev).eval()
         torch.cuda.reset_peak_memory_stats()
-        tr = LMTrainer(m, attention=a.attention, activations=a.activations, precision=a.precision, head_precision=a.head_precision, act_store=a.act_store, attention_kernel=a.attention_kernel)
+        tr = LMTrainer(m, **training.modes_from_args(a))
         if a.one_step:
             ids = torch.randint(0, s["V"], (s["B"], a.one_step), device=dev)
             tr.step(ids)
@@ -171,8 +159,7 @@ def main():
             lib.r4d_profile_enable(0)
             total_prof = sum(v["ms"] for v in prof2.values())
             head_like = {k: v for k, v in prof2.items() if v["work"] > 0}
-            rec = dict(shape=name, mode=ops.gemm_mode(), attention=tr.enc.attention, activations=tr.enc.activations, precision=tr.enc.precision,
-                       act_store=tr.enc.act_store, attention_kernel=tr.enc.attention_kernel, head_precision=tr.head_precision, head_alone_ms=head_alone_ms,
+            rec = dict(shape=name, mode=ops.gemm_mode(), **tr.modes.record(), head_alone_ms=head_alone_ms,
                        head_alone_classes={k: dict(ms=round(v["ms"], 4), launches=v["launches"], work=v["work"]) for k, v in sorted(head_prof.items(), key=lambda kv: -kv[1]["ms"])},
                        launches={k: v["launches"] for k, v in sorted(prof2.items())},
                        workspace_bytes=ws_bytes, max_memory_allocated=peak, L=s["L"], H=s["H"], d=d, V=V,

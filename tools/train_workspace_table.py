@@ -4,11 +4,12 @@ stored / recompute), from the library's three size queries alone: no GPU, no all
     python tools/train_workspace_table.py [--json]
 
 Rows are the padded worst case of each script (every sequence at the block size); the retriever step is its five forwards in
-one call.  Each cell is the fp32 store's size; the `bf16 store` column beside it is the same query with the layer precision bf16
-and the activation store bf16 (``r4d_set_train_bf16(1)``, ``r4d_set_train_act_bf16(1)``; DESIGN.md section 7.9: ln1 of layers >= 1,
-ln2 and f as bf16 wherever d % 256 == 0).  The `fused` column is the fp32 store under the fused attention kernels
-(``r4d_set_train_attention_bf16(1)``, ``r4d_set_train_attention_fused(1)``; DESIGN.md section 7.10: no P-shaped block, one log-sum-exp per
-query per layer), which the attention word does not change: it stands beside the two P recompute cells.  Vocabularies: rag4dyg_amd/synth.py (retriever flavour with [MASK], SimpleDyG / generator flavour without)."""
+one call.  Each cell is the fp32 store's size; the `bf16 store` column beside it is the same query with ``precision="bf16"``,
+``act_store="bf16"`` (ln1 of layers >= 1, ln2 and f as bf16 wherever d % 256 == 0).  The `fused` column is the
+fp32 store under ``precision="fp32+attn"``, ``attention_kernel="fused"`` (no P-shaped block, one log-sum-exp
+per query per layer), which the attention word does not change: it stands beside the two P recompute cells.  The words are those of
+``rag4dyg_amd.training.TRAIN_MODE_AXES``, selected through ``TrainModes.select()``; the library's switches are put back afterwards.
+Vocabularies: rag4dyg_amd/synth.py (retriever flavour with [MASK], SimpleDyG / generator flavour without)."""
 import ctypes
 import json
 import os
@@ -18,6 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from rag4dyg_amd import _lib, synth                                            # noqa: E402
 from rag4dyg_amd.lm_training import padded_vocab                               # noqa: E402
+from rag4dyg_amd.training import TrainModes, saved_library_modes              # noqa: E402
 
 # (kind, label, L, H, d, vocab, batches)
 ROWS = [("retriever", "UCI_13 L4 H2 d512 5x(64, 512)", 4, 2, 512, synth.UCI_13.vocab, [(64, 512)] * 5),
@@ -27,7 +29,11 @@ ROWS = [("retriever", "UCI_13 L4 H2 d512 5x(64, 512)", 4, 2, 512, synth.UCI_13.v
         ("lm", "hepth L12 H2 d256 (32, 512)", 12, 2, 256, synth.HEPTH.vocab_generator, [(32, 512)]),
         ("generator", "UCI_13 L6 H8 d768 (32, 513)", 6, 8, 768, synth.UCI_13.vocab_generator, [(32, 513)])]
 MODES = [("stored", "stored"), ("recompute", "stored"), ("stored", "recompute"), ("recompute", "recompute")]   # (attention, activations)
-WORD = {"stored": 0, "recompute": 1}
+# the cells of one (attention, activations) pair, as words of training.TRAIN_MODE_AXES (every axis named: the environment has no say):
+# key suffix -> words; the attention_kernel="fused" cell stands beside "recompute" only (the attention word changes nothing there)
+BASE = dict(precision="fp32", head_precision="fp32", act_store="fp32", attention_kernel="products")
+CELLS = {"": BASE, "_act_store_bf16": dict(BASE, precision="bf16", act_store="bf16")}       # (the layer switch alone changes no size)
+FUSED = dict(BASE, precision="fp32+attn", attention_kernel="fused")
 
 
 def workspace_bytes(lib, kind, L, H, d, V, batches):
@@ -44,37 +50,20 @@ def workspace_bytes(lib, kind, L, H, d, V, batches):
 
 def table():
     lib = _lib.load()
-    was = lib.r4d_get_train_attention(), lib.r4d_get_train_activations(), lib.r4d_get_train_bf16(), lib.r4d_get_train_act_bf16()
-    was_fused = lib.r4d_get_train_attention_bf16(), lib.r4d_get_train_attention_fused()
     out = []
-    try:
+    with saved_library_modes():
         for kind, label, L, H, d, V, batches in ROWS:
             rec = dict(step=kind, shape=label)
+
+            def cell(**words):
+                TrainModes.resolve(**words).select()
+                return workspace_bytes(lib, kind, L, H, d, V, batches)
             for att, act in MODES:
-                _lib.check(lib.r4d_set_train_attention(WORD[att]), "set_train_attention")
-                _lib.check(lib.r4d_set_train_activations(WORD[act]), "set_train_activations")
-                lib.r4d_set_train_bf16(0)
-                lib.r4d_set_train_act_bf16(0)
-                rec[f"attention_{att}_activations_{act}"] = workspace_bytes(lib, kind, L, H, d, V, batches)
-                lib.r4d_set_train_bf16(1)                       # (the layer switch alone changes no size)
-                lib.r4d_set_train_act_bf16(1)
-                rec[f"attention_{att}_activations_{act}_act_store_bf16"] = workspace_bytes(lib, kind, L, H, d, V, batches)
-                if att == "recompute":                          # (the attention_kernel="fused" cell: the attention word changes nothing)
-                    lib.r4d_set_train_bf16(0)
-                    lib.r4d_set_train_act_bf16(0)
-                    lib.r4d_set_train_attention_bf16(1)
-                    _lib.check(lib.r4d_set_train_attention_fused(1), "set_train_attention_fused")
-                    rec[f"attention_fused_activations_{act}"] = workspace_bytes(lib, kind, L, H, d, V, batches)
-                    lib.r4d_set_train_attention_fused(0)
-                    lib.r4d_set_train_attention_bf16(was_fused[0])
+                for suffix, words in CELLS.items():
+                    rec[f"attention_{att}_activations_{act}{suffix}"] = cell(attention=att, activations=act, **words)
+                if att == "recompute":
+                    rec[f"attention_fused_activations_{act}"] = cell(attention=att, activations=act, **FUSED)
             out.append(rec)
-    finally:
-        lib.r4d_set_train_attention(was[0])
-        lib.r4d_set_train_activations(was[1])
-        lib.r4d_set_train_bf16(was[2])
-        lib.r4d_set_train_act_bf16(was[3])
-        lib.r4d_set_train_attention_bf16(was_fused[0])
-        lib.r4d_set_train_attention_fused(was_fused[1])
     return out
 
 
