@@ -397,6 +397,32 @@ int r4d_conv1d_bf16_f32(const float* x_d, const uint16_t* w_bf16_d /* [N][K] */,
                         int32_t M, int32_t K, int32_t N, int32_t epilogue, float* y_d, void* stream);
 int r4d_set_encode_bf16(int32_t on);
 int r4d_get_encode_bf16(void);
+/*
+ * bf16 ATTENTION for the encoder forward under r4d_set_encode_bf16 (additive ABI v6 entries; csrc/attention_b1.hip).  NOT
+ * fp32-accurate.  Per (sequence, head): q, k and v are rounded to bf16 (round to nearest even, v_cvt_pk_bf16_f32: the rounding of
+ * r4d_conv1d_bf16_f32); S = q . k^T on ONE v_mfma_f32_32x32x16_bf16 per 16 k with fp32 accumulation, divided by sqrt(hd) in fp32;
+ * the causal mask is by selection (a key right of the diagonal or at / past T contributes p = 0 exactly, whatever memory holds);
+ * the online softmax is fp32; the UNNORMALISED p = exp(s - m) enters P . V rounded to bf16 while the row sum adds the unrounded
+ * fp32 p; O is accumulated in fp32 and divided by the row sum at the end.  A (sequence, head)'s bits depend on its own operands
+ * alone: not on the launch it travels in, on its neighbours, or on what lies past T.
+ * r4d_set_encode_attention_bf16(on != 0) returns the previous setting; default 0; process-wide.  The switch is read by the
+ * encoder entries only (those r4d_set_encode_bf16 names) and ONLY WHILE r4d_set_encode_bf16 is on: alone it changes nothing.
+ * While both are on, a block whose c_attn runs on the plain-bf16 GEMM takes its attention on this kernel: c_attn writes RN(q|k|v) as
+ * bf16 [M, 3d] (fp32 as before where the caller asked for qkv: the kernel then rounds while staging -- the same bits), the
+ * attention writes RN(O) as bf16 [M, d] and attn.c_proj reads that.  Both fit the fp32 buffers of the workspace: no size query
+ * changes.  Where the kernel does not serve a shape the block takes the route of r4d_set_encode_bf16 alone: through these entries
+ * that is a head dim above 256 (a head dim off the multiples of 16, and more than 65,535 sequences in one launch, are refused by
+ * the entries themselves whatever the switches say).  r4d_get_encode_attention_bf16 reads the switch.
+ * r4d_attention_bf16_groups: the kernel alone over n_groups (1 .. 16) batches in ONE launch: batch g = Bs[g] sequences of Ts[g]
+ * tokens whose first token row is row0s[g] of qkv_d [rows, 3d] / a_d [rows, d].  qkv_is_bf16 / out_is_bf16: the element type behind
+ * the pointers (0 fp32, 1 bf16 bits).  head_dim = d / n_head a multiple of 16 in 16 .. 256, 1 <= T <= 1024, at most 65,535
+ * sequences, both pointers 16-byte aligned; anything else is refused before any launch (R4D_ERR_INVALID).  Only the batches' own
+ * rows of a_d are written.
+ */
+int r4d_set_encode_attention_bf16(int32_t on);
+int r4d_get_encode_attention_bf16(void);
+int r4d_attention_bf16_groups(const void* qkv_d, int32_t qkv_is_bf16, int32_t n_groups, const int32_t* Bs, const int32_t* Ts,
+                              const int64_t* row0s, int32_t n_head, int32_t d, void* a_d, int32_t out_is_bf16, void* stream);
 /* Causal multi-head attention on packed c_attn output qkv_d [B,T,3d] -> a_d [B,T,d] (heads merged).
  * Attention._attn + split/merge_heads, modeling_gpt2.py:140-175; scale = division by sqrt(hd) (:143).
  * scores_ws_d: device scratch of r4d_attention_workspace_bytes(B,H,T).  B >= 1, 1 <= T <= 1024, head_dim a multiple of 16;

@@ -111,6 +111,10 @@ PROTOTYPES = {
     "r4d_conv1d_bf16_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "r4d_set_encode_bf16": (c_int32, [c_int32]),
     "r4d_get_encode_bf16": (c_int32, []),
+    "r4d_set_encode_attention_bf16": (c_int32, [c_int32]),
+    "r4d_get_encode_attention_bf16": (c_int32, []),
+    "r4d_attention_bf16_groups": (c_int32, [_P, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), c_int32, c_int32,
+                                            _P, c_int32, _P]),
     "r4d_attention_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "r4d_attention_f32": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),
     "r4d_normalize_rows_f32": (c_int32, [_P, c_int32, c_int32, _P, _P]),

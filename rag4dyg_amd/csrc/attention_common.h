@@ -1,4 +1,5 @@
-// What attention_fused.hip and attention_h2.hip share.
+// What attention_fused.hip and attention_h2.hip share; attention_b1.hip takes the group table, the 1-D work mapping (at 128-query
+// tiles) and the grid from here and writes its own K / V descriptors beside ATTN_KV_RSRC (whose byte ranges are 4-byte elements).
 //
 // Device part: TEXT, not functions.  The pieces below are macros over the including kernel's own locals, in the idiom of
 // gemm_epilogue_rowmajor.h / gemm_tn_tail.h: written as a __forceinline__ function that fills a small struct, the 1-D work mapping
@@ -23,7 +24,9 @@ namespace r4d {
 // before: 970 MB per launch against 290 MB of qkv + out, L2 hit rate 22 %, i.e. the kernel ran at the HBM limit).  Long (late)
 // query tiles go first.  Declares qt, h, seq, gi, T, q0 and rowb (the first token row of the sequence); workgroups past the last
 // pair or past their sequence's end return.  (attn_fused_kernel's 3-D grid is a different mapping and keeps its own text.)
-#define ATTN_TILE_1D(G_, H_, ntq_)                                                                                  \
+// QT_: the queries of a tile -- 32 in the kernels of attention_fused.hip / attention_h2.hip, 128 in attention_b1.hip.
+#define ATTN_TILE_1D(G_, H_, ntq_) ATTN_TILE_1D_Q(G_, H_, ntq_, 32)
+#define ATTN_TILE_1D_Q(G_, H_, ntq_, QT_)                                                                           \
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;                                                         \
     const int pair = (slot / ntq_) * 8 + xcd;           /* (sequence, head) index */                                \
     if (pair >= G_.seq_prefix[G_.n] * H_) return;                                                                   \
@@ -31,7 +34,7 @@ namespace r4d {
     int gi = 0;                                                                                                     \
     while (gi + 1 < G_.n && seq >= G_.seq_prefix[gi + 1]) ++gi;                                                     \
     const int T = G_.T[gi];                                                                                         \
-    const int q0 = qt * 32;                                                                                         \
+    const int q0 = qt * QT_;                                                                                        \
     if (q0 >= T) return;                                /* ntq covers the longest batch */                          \
     const long long rowb = G_.row0[gi] + (long long)(seq - G_.seq_prefix[gi]) * T;
 
@@ -164,9 +167,9 @@ static inline int attn_groups_fill(const char* prefix, int n, const int* Bs, con
 }
 
 // Workgroups of the 1-D mapping (ATTN_TILE_1D): the (sequence, head) pairs rounded up to the 8 XCDs, times ntq = query tiles of
-// the longest batch.
-static inline int attn_grid_1d(const char* prefix, const AttnGroups& G, int H, int Tmax, int& ntq, unsigned& grid) {
-    ntq = cdiv(Tmax, 32);
+// the longest batch (tiles of `qtile` queries).
+static inline int attn_grid_1d(const char* prefix, const AttnGroups& G, int H, int Tmax, int& ntq, unsigned& grid, int qtile = 32) {
+    ntq = cdiv(Tmax, qtile);
     const long long pairs8 = ((long long)G.seq_prefix[G.n] * H + 7) / 8;
     R4D_REQUIRE(pairs8 * 8 * ntq < (1ll << 31), "%s: grid too large", prefix);
     grid = (unsigned)(pairs8 * 8 * ntq);

@@ -46,7 +46,7 @@ enum ProfClass {
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
     PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_GEMM_B1H_NT, PK_GEMM_B1H_NN,
-    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_COUNT
+    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_ATTN_B1, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -91,7 +91,8 @@ struct ProfScope {
     X(TBA_NT, "tuning:train_bf16_attn:nt") X(TBA_NN, "tuning:train_bf16_attn:nn") \
     X(TBH_LOGITS, "tuning:train_head_bf16:logits") X(TBH_DGRAD, "tuning:train_head_bf16:dgrad") X(TBH_WGRAD, "tuning:train_head_bf16:wgrad") X(TBH_WGRAD_FALLBACK, "tuning:train_head_bf16:wgrad_fallback") \
     X(TAB_FWD, "tuning:train_act_bf16:fwd") X(TAB_WGRAD, "tuning:train_act_bf16:wgrad") X(TAB_LN, "tuning:train_act_bf16:ln") X(TAB_GELU, "tuning:train_act_bf16:gelu") \
-    X(TAF_FWD, "tuning:train_attn_fused:fwd") X(TAF_ROWSUM, "tuning:train_attn_fused:rowsum") X(TAF_DKV, "tuning:train_attn_fused:dkv") X(TAF_DQ, "tuning:train_attn_fused:dq")
+    X(TAF_FWD, "tuning:train_attn_fused:fwd") X(TAF_ROWSUM, "tuning:train_attn_fused:rowsum") X(TAF_DKV, "tuning:train_attn_fused:dkv") X(TAF_DQ, "tuning:train_attn_fused:dq") \
+    X(EBA_BF16, "tuning:encode_bf16_attn:bf16 qkv") X(EBA_F32, "tuning:encode_bf16_attn:fp32 qkv, rounded while staged") X(EBA_FALLBACK, "tuning:encode_bf16_attn:fallback to the exact-f32 attention")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -374,6 +375,13 @@ int launch_attention_fused(const float* qkv, int B, int T, int H, int d, float* 
 int launch_attention_fused_groups(const float* qkv, int n, const int* Bs, const int* Ts, const long long* row0s, int H,
                                   int d, float* out, hipStream_t s);
 extern int g_attention_variant;
+// attention_b1.hip: the encoder's opt-in bf16 attention (r4d_set_encode_attention_bf16; NOT fp32-accurate): the groups of one launch
+// as launch_attention_fused_groups takes them; qkv fp32 or bf16 [rows, 3d], out fp32 or bf16 [rows, d].  Shapes outside
+// attention_b1_supported (head_dim % 16, 16 .. 256) and launches of more than 65,535 sequences are refused before any launch
+bool attention_b1_supported(int H, int d);
+int launch_attention_b1_groups(const void* qkv, bool qkv_bf16, int n, const int* Bs, const int* Ts, const long long* row0s, int H, int d,
+                               void* out, bool out_bf16, hipStream_t s);
+extern int g_encode_attn_bf16;       // r4d_set_encode_attention_bf16: read by the encoder entries, only while g_encode_bf16 is on
 extern int g_attention_fused;        // -1 auto (default), 1 fused, 0 three-launch GEMM form (r4d_set_attention_fused)
 // Layer 0's repeated pad rows (encoder.hip: encode_impl).  The layer-0 c_attn row depends on (token, position) only,
 // so 32-row blocks (by GLOBAL row index, as in the key-blocked image) whose rows all carry one candidate token c are dropped from

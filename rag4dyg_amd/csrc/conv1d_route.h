@@ -16,7 +16,10 @@ enum GemmEpilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_SCALE_DIV 
                     EPI_H2WORDS = 7,
                     // gemm_b1 only (training, r4d_set_train_act_bf16): GELU_KEEP whose gelu(v) leaves as bf16 [M, N] (RNE; ldc in bf16 elements);
                     // the pre-activation stays fp32.  Appended: route conditions compare against EPI_RESIDUAL's ordering
-                    EPI_GELU_KEEP_BF16 = 8 };
+                    EPI_GELU_KEEP_BF16 = 8,
+                    // gemm_b1 only (encoder, r4d_set_encode_attention_bf16): EPI_NONE whose result leaves as bf16 [M, N] (RNE; ldc in bf16
+                    // elements): c_attn's q | k | v for attention_b1.hip, which rounds the fp32 form by the same rule while staging
+                    EPI_NONE_BF16 = 9 };
 
 extern int g_gemm_split3;             // Conv1D arithmetic (r4d_set_gemm_split3): 0 exact-f32 MFMA, 1 bf16x3 planes, 2 f16x2 planes (bf16x3 where a layer carries no f16 planes)
 

@@ -18,6 +18,7 @@ void set_error(const char* fmt, ...) {
 
 int g_gemm_split3 = 1;                // r4d_set_gemm_split3: 0 exact f32, 1 bf16x3, 2 f16x2
 int g_encode_bf16 = 0;                // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs in plain bf16 (gemm_b1.hip), whatever the mode above
+int g_encode_attn_bf16 = 0;           // r4d_set_encode_attention_bf16: ... and their attention on bf16 operands (attention_b1.hip); read only while the switch above is on
 
 int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts) {
     const int K = W.in, N = W.out;
@@ -204,6 +205,12 @@ int r4d_set_encode_bf16(int32_t on) {
     return prev;
 }
 int r4d_get_encode_bf16(void) { return g_encode_bf16; }
+int r4d_set_encode_attention_bf16(int32_t on) {
+    const int prev = g_encode_attn_bf16;
+    g_encode_attn_bf16 = on != 0;
+    return prev;
+}
+int r4d_get_encode_attention_bf16(void) { return g_encode_attn_bf16; }
 int r4d_set_range_flag(uint32_t* flag_d) { g_range_flag = flag_d; return R4D_OK; }
 int r4d_set_attention_kblk(int32_t on) {
     const int prev = g_attention_kblk < 0 ? 1 : g_attention_kblk;
@@ -332,6 +339,20 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
             if (nseq > 65535) words = false;
         }
+        // bf16 precision with the attention switch ("bf16+attn"): the attention on bf16 operands (attention_b1.hip) wherever that kernel
+        // serves the shape, else this block takes the route of "bf16" alone (counted).  bf16 BETWEEN producer and consumer where
+        // nothing else reads the fp32 form: c_attn on gemm_b1 writes RN(q | k | v) as bf16 [M, 3d] unless the caller asked for qkv
+        // (then fp32 as before, and the kernel rounds while staging: the same bits), the attention writes RN(O) as bf16 [M, d]
+        // where attn.c_proj is on gemm_b1, which reads it as its bf16 A operand.  Both fit the fp32 buffers.
+        const bool want_battn = g_encode_bf16 && g_encode_attn_bf16;
+        bool battn = want_battn && attention_b1_supported(H, d);
+        for (int g0 = 0; g0 < n_groups && battn; g0 += ATT_MAXG) {
+            attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
+            if (nseq > 65535) battn = false;
+        }
+        if (want_battn && !battn) R4D_BRANCH(EBA_FALLBACK);
+        const bool qkv_b = battn && !out_qkv_d && conv1d_route(Wqkv, M, EPI_NONE, false, BF16_ENCODE) == ROUTE_B1;
+        const bool att_b = battn && conv1d_route(Wo, M, EPI_RESIDUAL, false, BF16_ENCODE) == ROUTE_B1;
         // ... and its K third as the key-blocked image the head_dim 128 / 256 kernel loads by whole cache lines (attention_h2.hip)
         if (g_attention_kblk < 0) { const char* e = getenv("R4D_ATT_KBLK"); g_attention_kblk = e ? atoi(e) != 0 : 1; }
         const bool kblk = words && lines && g_attention_kblk && (d / H) % 32 == 0;      // every head_dim attention_h2.hip serves
@@ -382,12 +403,19 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             if ((rc = launch_gemm_h2p_rowmap(a, ln_lines, pr, pb, s))) return rc;
             rc = launch_pad_rows_fill(pr, pb, reinterpret_cast<unsigned*>(qkv), ws.kblk, d, s);
         } else if (lines) rc = conv1d_lines(Wqkv, ln_lines, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s, kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
+        else if (qkv_b) rc = launch_gemm_b1(s3_args(ws.ln, Wqkv.w3, Wqkv.b, nullptr, M, d, 3 * d, EPI_NONE_BF16, qkv), s);
         else rc = conv1d(Wqkv, ws.ln, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, s, enc);
         if (rc) return rc;
         // ... and with them the attention output: attn_h2_kernel writes its merged-head rows as lines for attn.c_proj
         const bool att_lines = words && lines && Wo.h2 && gemm_h2p_supported(M, d, d);
         bool fused_done = false;
-        if (words) {
+        if (battn) {
+            fused_done = true;
+            for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {
+                const int n = attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
+                if ((rc = launch_attention_b1_groups(qkv, qkv_b, n, Bs, Ts, r0, H, d, ws.att, att_b, s))) return rc;
+            }
+        } else if (words) {
             fused_done = true;
             for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {
                 const int n = attn_chunk(groups, g0, n_groups, Bs, Ts, r0, &nseq);
@@ -411,7 +439,11 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             }
         }
         if (att_lines) rc = conv1d_lines(Wo, reinterpret_cast<const unsigned short*>(ws.att), ws.x, M, EPI_RESIDUAL, ws.x, false, s);
-        else rc = conv1d(Wo, ws.att, ws.x, M, EPI_RESIDUAL, ws.x, s, enc);
+        else if (att_b) {
+            S3Args a = s3_args(ws.att, Wo.w3, Wo.b, ws.x, M, d, d, EPI_RESIDUAL, ws.x);
+            a.a_bf16 = 1;
+            rc = launch_gemm_b1(a, s);
+        } else rc = conv1d(Wo, ws.att, ws.x, M, EPI_RESIDUAL, ws.x, s, enc);
         if (rc) return rc;
         if (lines) {
             if ((rc = launch_layernorm_lines(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ln_lines, s))) return rc;

@@ -198,7 +198,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
 // ---------------------------------------------------------------------------------------------- host side
 // what the encoder forward uses, and the two kinds of the training step (c_fc forward with the kept pre-activation; the mlp
 // c_proj data gradient times gelu_new'(pre))
-#define B1_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_GRAD)
+// (EPI_NONE_BF16: c_attn of the encoder's "bf16+attn" precision)
+#define B1_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_GRAD) X(L, EPI_NONE_BF16)
 // with a bf16 A operand: the training forward's three consumers of a bf16 block (c_attn, c_fc, mlp c_proj)
 #define B1_KINDS_ABF(X, L) X(L, EPI_NONE) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_KEEP_BF16)
 template <int BM, int BN, int WGM, int WGN>
@@ -230,7 +231,7 @@ int launch_gemm_b1(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.lda % 4 == 0 && ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.planes % 16) == 0, "gemm_b1: alignment");
     R4D_REQUIRE((a.epilogue != EPI_RESIDUAL && a.epilogue != EPI_GELU_KEEP && a.epilogue != EPI_GELU_GRAD && a.epilogue != EPI_GELU_KEEP_BF16) || a.resid, "gemm_b1: epilogue %d needs the second buffer", a.epilogue);
     R4D_REQUIRE(!a.a_bf16 || a.lda % 8 == 0, "gemm_b1: a bf16 A operand wants lda %% 8 == 0 (lda=%d)", a.lda);
-    R4D_REQUIRE(a.epilogue != EPI_GELU_KEEP_BF16 || (a.N % 2 == 0 && a.ldc % 2 == 0 && ((uintptr_t)a.C % 4) == 0), "gemm_b1: the bf16 output wants even N and ldc");
+    R4D_REQUIRE((a.epilogue != EPI_GELU_KEEP_BF16 && a.epilogue != EPI_NONE_BF16) || (a.N % 2 == 0 && a.ldc % 2 == 0 && ((uintptr_t)a.C % 4) == 0), "gemm_b1: the bf16 output wants even N and ldc");
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("R4D_GEMM_B1_TILE"); forced = e ? atoi(e) : -1; }   // tuning aid: 0 / 1 forces a tile
     const int t = (forced == 0 || forced == 1) ? forced : pick_tile_128(a.M, a.N);

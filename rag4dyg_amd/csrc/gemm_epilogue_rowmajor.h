@@ -42,8 +42,9 @@
 {
     static_assert(EPI != EPI_H2WORDS || EPILOGUE_PAIR_WORDS, "the h2-word output forms its two words from the pair");
     // the second buffer is read (residual; training backward: the pre-activation) or written (training forward: the pre-activation)
-    // GELU_KEEP_BF16 (gemm_b1 only): GELU_KEEP whose C is bf16 [M, N] -- ldc counts bf16 elements, N and ldc are even
-    constexpr bool KEEPS = EPI == EPI_GELU_KEEP || EPI == EPI_GELU_KEEP_BF16, C_BF16 = EPI == EPI_GELU_KEEP_BF16;
+    // GELU_KEEP_BF16 (gemm_b1 only): GELU_KEEP whose C is bf16 [M, N] -- ldc counts bf16 elements, N and ldc are even; NONE_BF16
+    // (gemm_b1 only): the plain result as bf16 in the same way
+    constexpr bool KEEPS = EPI == EPI_GELU_KEEP || EPI == EPI_GELU_KEEP_BF16, C_BF16 = EPI == EPI_GELU_KEEP_BF16 || EPI == EPI_NONE_BF16;
     constexpr bool USES_R = EPI == EPI_RESIDUAL || KEEPS || EPI == EPI_GELU_GRAD;
     constexpr bool LOADS_R = EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD;
     constexpr int C_SZ = C_BF16 ? 2 : 4;

@@ -277,7 +277,7 @@ class GPT2Model(_PreTrained):
         return self._derived("w3", w, lambda: ops.split3_planes(w.detach())).data_ptr()
 
     def _b1(self, w):
-        """The ONE bf16 plane [out,in] of a static Conv1D weight (``ops.bf16_plane``) for ``ops.encode_precision() == "bf16"``;
+        """The ONE bf16 plane [out,in] of a static Conv1D weight (``ops.bf16_plane``) for ``ops.encode_precision()`` "bf16" / "bf16+attn";
         None when the shape has no kernel."""
         if w.shape[0] % 32 != 0:
             return None
@@ -313,7 +313,7 @@ class GPT2Model(_PreTrained):
             ws4 = (blk.attn.c_attn.weight, blk.attn.c_proj.weight, blk.mlp.c_fc.weight, blk.mlp.c_proj.weight)
             h2 = [self._h2(w) for w in ws4]                                       # f16x2 mode only (None otherwise / out of fp16 range)
             w3 = [self._w3(w) if h is None else None for w, h in zip(ws4, h2)]    # bf16x3 planes: that mode, or the f16x2 fallback
-            if not decode and ops.encode_precision() == "bf16":                   # bf16 encode reads plane 0 only: where no planes
+            if not decode and ops.encode_precision() != "fp32":                   # bf16 encode reads plane 0 only: where no planes
                 w3 = [p3 if p3 is not None else self._b1(w) for w, p3 in zip(ws4, w3)]     # go today, that one plane goes
             layers[i] = _lib.GPT2LayerC(p(blk.ln_1.weight), p(blk.ln_1.bias), p(blk.attn.c_attn.weight),
                                         p(blk.attn.c_attn.bias), p(blk.attn.c_proj.weight), p(blk.attn.c_proj.bias),
@@ -335,11 +335,11 @@ class GPT2Model(_PreTrained):
         """Run ``thunk()`` (one or more ``encode*`` calls) under the range guard (``include/r4d.h``, ABI v6): ONE read of the device
         word afterwards; a non-finite hidden state in gemm mode "f16x2" (an activation beyond fp16's exponent range) re-runs the thunk
         once under "bf16x3" with a RuntimeWarning, and ``R4DError`` if it comes up again or in any other mode.  Under
-        ``ops.encode_precision() == "bf16"`` there is no re-run: bf16 has fp32's exponent range, a non-finite hidden state is an error."""
+        ``ops.encode_precision()`` "bf16" / "bf16+attn" there is no re-run: bf16 has fp32's exponent range, a non-finite hidden state is an error."""
         ops.range_flag(device).zero_()
         out = thunk()
         flag = ops.take_range_flag()
-        if flag & ops.RANGE_NONFINITE_HIDDEN and ops.gemm_mode() == "f16x2" and ops.encode_precision() != "bf16":
+        if flag & ops.RANGE_NONFINITE_HIDDEN and ops.gemm_mode() == "f16x2" and ops.encode_precision() == "fp32":
             import warnings
             warnings.warn(f"rag4dyg_amd: an activation left the fp16 range of the f16x2 arithmetic (non-finite hidden state); "
                           f"re-running {what} with the bf16x3 GEMMs", RuntimeWarning, stacklevel=3)

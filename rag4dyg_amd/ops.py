@@ -231,12 +231,12 @@ def conv1d_s3(x, planes, bias, epilogue="none", residual=None):
     return y
 
 
-_ENCODE_PRECISIONS = {"fp32": 0, "bf16": 1}
+_ENCODE_PRECISIONS = {"fp32": (0, 0), "bf16": (1, 0), "bf16+attn": (1, 1)}     # word -> (r4d_set_encode_bf16, r4d_set_encode_attention_bf16)
 _ENCODE_PRECISION = None
 
 
 def resolve_encode_precision(precision=None):
-    """``"fp32"`` or ``"bf16"``.  None -> the environment variable ``R4D_ENCODE_PRECISION``, ``fp32`` when it is unset or empty.
+    """``"fp32"``, ``"bf16"`` or ``"bf16+attn"``.  None -> the environment variable ``R4D_ENCODE_PRECISION``, ``fp32`` when it is unset or empty.
     Anything else raises."""
     if precision is None:
         import os
@@ -251,6 +251,10 @@ def encode_precision():
     ``retrieval.encode_batches``): ``"fp32"`` (default) -- the fp32-accurate arithmetic :func:`gemm_mode` names; ``"bf16"`` -- both
     operands rounded to bf16, one matrix-core product per fp32 product (``csrc/gemm_b1.hip``).  "bf16" is NOT fp32-accurate
     (DESIGN.md 7): retrieval under it is approximate, and greedy decoding prefills in bf16 while the cached step stays fp32.
+    ``"bf16+attn"`` -- the "bf16" arithmetic with the encoder's attention on bf16 operands as well (``csrc/attention_b1.hip``: q, k,
+    v and the unnormalised probabilities rounded to bf16, one matrix-core product per product, fp32 softmax and accumulation;
+    q | k | v and the attention output travel as bf16 between their producers and consumers); where that kernel does not serve a
+    shape the block takes the "bf16" route.
     ``R4D_ENCODE_PRECISION=bf16`` (read once, at the first call) or :func:`set_encode_precision` select it.  Process-wide: the
     ranks of a sharded job must agree."""
     if _ENCODE_PRECISION is None:
@@ -259,13 +263,15 @@ def encode_precision():
 
 
 def set_encode_precision(precision):
-    """Select :func:`encode_precision` ("fp32" | "bf16"; anything else raises ValueError and changes nothing).  Returns the
-    previous setting."""
+    """Select :func:`encode_precision` ("fp32" | "bf16" | "bf16+attn"; anything else raises ValueError and changes nothing).
+    Returns the previous setting."""
     global _ENCODE_PRECISION
     if precision not in _ENCODE_PRECISIONS:
         raise ValueError(f"encode precision {precision!r}: expected one of {sorted(_ENCODE_PRECISIONS)}")
     prev = _ENCODE_PRECISION if _ENCODE_PRECISION is not None else resolve_encode_precision()
-    _lib.load().r4d_set_encode_bf16(_ENCODE_PRECISIONS[precision])
+    gemms, attn = _ENCODE_PRECISIONS[precision]
+    _lib.load().r4d_set_encode_bf16(gemms)
+    _lib.load().r4d_set_encode_attention_bf16(attn)
     _ENCODE_PRECISION = precision
     return prev
 
@@ -290,6 +296,33 @@ def conv1d_bf16(x, w_bf16, bias, epilogue="none", residual=None):
     check(_lib.load().r4d_conv1d_bf16_f32(_dev(x, torch.float32, "x"), _dev(w_bf16, torch.int16, "w_bf16"), bp, rp, M, K, N, epi,
                                           y.data_ptr(), _stream()), "conv1d_bf16")
     return y
+
+
+def attention_bf16(qkv, groups, n_head, out_bf16=None):
+    """The encoder attention of ``encode_precision() == "bf16+attn"`` alone (``r4d_attention_bf16_groups``; NOT fp32-accurate) over
+    ``groups`` = [(B, T), ...] (at most 16) in ONE launch: batch g's B * T token rows follow batch g - 1's in ``qkv`` [rows, 3d]
+    (torch.float32, or torch.bfloat16 as c_attn writes it under the word) -> [rows, d] merged heads, torch.bfloat16 when
+    ``out_bf16`` (default: as ``qkv``), else torch.float32.  head_dim = d / n_head a multiple of 16 in 16 .. 256, T <= 1024."""
+    if not qkv.is_cuda or qkv.dtype not in (torch.float32, torch.bfloat16) or not qkv.is_contiguous() or qkv.dim() != 2:
+        raise _lib.R4DError("attention_bf16: qkv must be a contiguous 2-D fp32 or bf16 device tensor [rows, 3d]")
+    in_bf16 = qkv.dtype == torch.bfloat16
+    out_bf16 = in_bf16 if out_bf16 is None else bool(out_bf16)
+    rows, d3 = qkv.shape
+    d = d3 // 3
+    n = len(groups)
+    if n < 1 or d3 % 3 or sum(int(B) * int(T) for B, T in groups) != rows or any(int(B) < 1 or int(T) < 1 for B, T in groups):
+        raise _lib.R4DError(f"attention_bf16: groups {list(groups)} do not tile the {rows} rows of qkv [rows, 3d]")
+    Bs = (ctypes.c_int32 * n)(*[int(B) for B, _ in groups])
+    Ts = (ctypes.c_int32 * n)(*[int(T) for _, T in groups])
+    r0, acc = [], 0
+    for B, T in groups:
+        r0.append(acc)
+        acc += int(B) * int(T)
+    row0s = (ctypes.c_int64 * n)(*r0)
+    out = torch.empty(rows, d, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=qkv.device)
+    check(_lib.load().r4d_attention_bf16_groups(qkv.data_ptr(), int(in_bf16), n, Bs, Ts, row0s, int(n_head), d, out.data_ptr(), int(out_bf16),
+                                                _stream()), "attention_bf16")
+    return out
 
 
 def conv1d_bf16_keep(x, w_bf16, bias):

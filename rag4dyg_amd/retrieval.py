@@ -50,7 +50,7 @@ def encode_batches(model, batches, max_rows=MAX_FUSED_ROWS, check=True):
     group ONE read of the device's range word.  If a non-finite hidden state came up in gemm mode "f16x2" (an activation beyond
     fp16's exponent range) the WHOLE call is re-run once under "bf16x3" -- fp32's range, the same accuracy -- with a warning;
     if it comes up again, or in any other mode, ``R4DError``: NaN embeddings are never returned.  No re-run under
-    ``ops.encode_precision() == "bf16"`` (bf16 has fp32's exponent range: a non-finite hidden state is an error there)."""
+    ``ops.encode_precision()`` "bf16" / "bf16+attn" (bf16 has fp32's exponent range: a non-finite hidden state is an error there)."""
     flag_word = ops.range_flag(batches[0].device if batches else None)
     if check:
         flag_word.zero_()                                             # (somebody else's unread bits are not this call's)
@@ -58,7 +58,7 @@ def encode_batches(model, batches, max_rows=MAX_FUSED_ROWS, check=True):
     if not check:
         return emb
     flag = ops.take_range_flag()
-    if flag & ops.RANGE_NONFINITE_HIDDEN and ops.gemm_mode() == "f16x2" and ops.encode_precision() != "bf16":
+    if flag & ops.RANGE_NONFINITE_HIDDEN and ops.gemm_mode() == "f16x2" and ops.encode_precision() == "fp32":
         import warnings
         warnings.warn("rag4dyg_amd: an activation left the fp16 range of the f16x2 arithmetic (non-finite hidden state); "
                       "re-encoding this call with the bf16x3 GEMMs", RuntimeWarning, stacklevel=2)

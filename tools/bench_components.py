@@ -5,7 +5,10 @@
   jaccard   f64 Jaccard matrices: real hepth/11 sets (golden fixture) and a synthetic 20k x 20k scale-up
   pool      pool-encode sequences/s (reference batching, fused groups)
   encode_precision   the bench step's encode, val-mode greedy decode and the real-data top-10 lists under
-            ops.set_encode_precision("bf16") beside the f16x2 and bf16x3 arithmetics (alternated in one process)
+            ops.set_encode_precision("bf16") and ("bf16+attn") beside the f16x2 and bf16x3 arithmetics (alternated in one
+            process); the attention kernels of the two words alone at head dims 64 .. 256
+  encode_step_trace WORD [SHAPE]   12 encode steps under one precision word and nothing else: the program of a
+            ``rocprofv3 --kernel-trace --stats -- python tools/bench_components.py encode_step_trace bf16+attn`` run
 Each line: achieved = algorithmic bytes / HIP-event time of the kernel class (r4d_profile_* hooks), peak 8 TB/s.
 CPU baselines: oracle single-thread python-set Jaccard (as retrieval_data_annotation.py:36-41) on a bounded sample.
 """
@@ -184,7 +187,9 @@ def encode_precision():
     events around 10 steps behind 2 warm-up steps, the arms alternated over 5 rounds; with the per-class launch times of one arm;
     (b) val-mode greedy decode (SimpleDyG loop, 11 tokens per prompt, batches of 32) at the UCI_13 generator model L6 H8 d768:
     tokens/s, wall clock around a synchronised batch loop;
-    (c) recorded, not gated: the bf16 top-10 lists on the real UCI_13 (G4) and wikiv2 (G12) fixtures against the golden lists."""
+    (c) recorded, not gated: the bf16 top-10 lists on the real UCI_13 (G4) and wikiv2 (G12) fixtures against the golden lists;
+    (d) the attention kernels alone (``attention_alone``).
+    The "bf16+attn" arm's baseline is the "bf16" arm of the SAME run: the third word touches neither its kernels nor its routing."""
     import statistics
     from bench import build_model
     from oracle import gpt2_ref
@@ -192,7 +197,7 @@ def encode_precision():
     from rag4dyg_amd.gpt2 import GPT2Config, GPT2LMHeadModel, GPT2LMHeadModelRAG
     from rag4dyg_amd.retrieval import PoolIndex, encode_batches, right_pad_batches
     was = (ops.encode_precision(), ops.gemm_mode())
-    arms = {"bf16": ("bf16", "f16x2"), "f16x2": ("fp32", "f16x2"), "bf16x3": ("fp32", "bf16x3")}
+    arms = {"bf16": ("bf16", "f16x2"), "bf16+attn": ("bf16+attn", "f16x2"), "f16x2": ("fp32", "f16x2"), "bf16x3": ("fp32", "bf16x3")}
     med = lambda v: statistics.median(v)
     try:
         for name in ("UCI_13", "wikiv2"):
@@ -216,10 +221,16 @@ def encode_precision():
             ms = {n: [1e3 / r for r in v] for n, v in rates.items()}
             ops.set_encode_precision("bf16"); ops.set_gemm_mode("f16x2")
             _wall, classes = profile(lambda: m.encode_groups_meanpool(groups[2]), 5)
+            ops.set_encode_precision("bf16+attn")
+            _wall, classes_attn = profile(lambda: m.encode_groups_meanpool(groups[2]), 5)
+            share = lambda cl, k: round(cl[k]["us"] * cl[k]["launches"] / sum(v["us"] * v["launches"] for v in cl.values()), 4) if k in cl else None
             emit(component="encode_step", shape=name, batches_per_step=8, mean_token_rows_per_step=round(rows),
                  ms_per_step={n: round(med(v), 3) for n, v in ms.items()}, ms_min_max={n: [round(min(v), 3), round(max(v), 3)] for n, v in ms.items()},
                  bf16_over_f16x2=round(med(ms["bf16"]) / med(ms["f16x2"]), 3), bf16_over_bf16x3=round(med(ms["bf16"]) / med(ms["bf16x3"]), 3),
-                 bf16_arm_classes={k: dict(us=round(v["us"], 1), launches=v["launches"]) for k, v in classes.items()})
+                 bf16attn_over_bf16=round(med(ms["bf16+attn"]) / med(ms["bf16"]), 3),
+                 attention_share_of_kernel_time={"bf16": share(classes, "attn_fused"), "bf16+attn": share(classes_attn, "attn_b1")},
+                 bf16_arm_classes={k: dict(us=round(v["us"], 1), launches=v["launches"]) for k, v in classes.items()},
+                 bf16attn_arm_classes={k: dict(us=round(v["us"], 1), launches=v["launches"]) for k, v in classes_attn.items()})
         # (b) val-mode decode
         shape = synth.SHAPES["UCI_13"]
         L, H, d, V = 6, 8, 768, shape.vocab
@@ -267,8 +278,59 @@ def encode_precision():
                 res[n] = dict(mean_overlap_of_10=round(float(np.mean(inter)), 3), min_overlap=int(min(inter)),
                               lists_identical=round(float((idx == ref10).all(axis=1).mean()), 4), top1_identical=round(float((idx[:, 0] == ref10[:, 0]).mean()), 4))
             emit(component="retrieval_top10_vs_golden", fixture=fixture, queries=int(ref10.shape[0]), pool=int(len(k["pool_off"]) - 1), **res)
+        attention_alone()
     finally:
         ops.set_encode_precision(was[0]); ops.set_gemm_mode(was[1])
+
+
+def attention_alone():
+    """The encoder attention of ONE layer alone: one batch of 256 sequences of T tokens in ONE launch per arm, d = 512 (768 at head
+    dim 96) -- the exact-f32 kernel the "bf16" word runs (``ops.attention``: ``launch_attention_fused``, the grouped launch with one
+    group) against ``ops.attention_bf16`` on fp32 and on bf16 qkv; device events around 20 calls behind 3 warm-ups, the arms
+    alternated over 5 rounds, medians."""
+    import statistics
+    g = torch.Generator().manual_seed(0)
+    for hd in (64, 96, 128, 256):
+        d = 768 if hd == 96 else 512
+        H = d // hd
+        for T in (128, 340):
+            B = 256
+            qkv = torch.randn(B * T, 3 * d, generator=g).to(dev)
+            qbf = qkv.bfloat16()
+            q3 = qkv.view(B, T, 3 * d)
+            arms = {"exact_f32": lambda: ops.attention(q3, H), "bf16_attn_fp32_qkv": lambda: ops.attention_bf16(qkv, [(B, T)], H, out_bf16=True),
+                    "bf16_attn_bf16_qkv": lambda: ops.attention_bf16(qbf, [(B, T)], H)}
+            us = {n: [] for n in arms}
+            for _ in range(5):
+                for n, fn in arms.items():
+                    for _w in range(3):
+                        fn()
+                    torch.cuda.synchronize()
+                    a, b_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _r in range(20):
+                        fn()
+                    b_.record(); torch.cuda.synchronize()
+                    us[n].append(a.elapsed_time(b_) * 1e3 / 20)
+            med = {n: round(statistics.median(v), 1) for n, v in us.items()}
+            emit(component="attention_alone", head_dim=hd, d=d, H=H, T_longest=T, sequences=B, token_rows=B * T, us_per_layer=med,
+                 us_min_max={n: [round(min(v), 1), round(max(v), 1)] for n, v in us.items()},
+                 bf16_qkv_over_exact=round(med["bf16_attn_bf16_qkv"] / med["exact_f32"], 3),
+                 fp32_qkv_over_exact=round(med["bf16_attn_fp32_qkv"] / med["exact_f32"], 3))
+
+
+def encode_step_trace(word="bf16", shape_name="UCI_13"):
+    """12 encode steps of the bench shape under ``word`` (gemm mode f16x2), nothing else on the device: for a kernel trace."""
+    from bench import build_model
+    from rag4dyg_amd.retrieval import right_pad_batches
+    shape = synth.SHAPES[shape_name]
+    m = build_model(shape, dev)
+    qb = right_pad_batches(synth.sequences(shape, 32 * 96, "query", seed=9000), 32, shape.pad_id, dev)
+    ops.set_encode_precision(word); ops.set_gemm_mode("f16x2")
+    for i in range(0, len(qb), 8):
+        m.encode_groups_meanpool(qb[i:i + 8])
+    torch.cuda.synchronize()
+    emit(component="encode_step_trace", word=word, shape=shape_name, steps=len(qb) // 8)
 
 
 def generator(shape_name="UCI_13", L=6, H=8, d=768, topk=7, pool_n=512):
@@ -536,6 +598,9 @@ if __name__ == "__main__":
                 sys.exit(f"{flag}: {' or '.join(axis.words)}")
             training = functools.partial(training, **{axis.key: sys.argv[i + 1]})
             del sys.argv[i:i + 2]
+    if sys.argv[1:2] == ["encode_step_trace"]:                                    # takes its word (and shape) as arguments
+        encode_step_trace(*sys.argv[2:4])
+        sys.exit(0)
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):
-        {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "generator": generator,
+        {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "attention_alone": attention_alone, "encode_step_trace": encode_step_trace, "generator": generator,
          "generator_reddit": generator_reddit, "simpledyg": simpledyg_eval, "training": training, "training_cpu": training_cpu}[part]()
