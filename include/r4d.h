@@ -443,20 +443,29 @@ size_t r4d_score_topk_workspace_bytes(int32_t Q, int32_t N, int32_t k);
  * S = (q_hat @ pool_hat^T + 1) / 2 over one pool shard, then per-row top-k with the canonical order
  * (score descending, pool index ascending).
  *   q_hat_d [Q,d], pool_hat_d [N,d] row-normalised;  index_offset = global index of shard row 0
- *   out_val_d f32 [Q,k], out_idx_d int64 [Q,k] (global indices)        (k <= 64, k <= N)
+ *   out_val_d f32 [Q,k], out_idx_d int64 [Q,k] (global indices)        (k <= r4d_topk_max_k() = 2048, k <= N)
+ * The scoring does not depend on k; beyond k = 64 the selection is r4d_topk_f32's second path (below).
  *   out_scores_d f32 [Q,N] full score rows (file-compat mode) or NULL
  */
 int r4d_score_topk_f32(const float* q_hat_d, const float* pool_hat_d, int32_t Q, int32_t N, int32_t d,
                        int32_t k, int64_t index_offset, float* out_val_d, int64_t* out_idx_d,
                        float* out_scores_d, void* workspace_d, size_t workspace_bytes, void* stream);
 /* Per-row top-k of an f32 matrix with the same canonical order (e.g. the ground-truth top-3 of the float32
- * Jaccard rows, train_retriever.py:461-462).  rows <= 65535.  One launch for n <= 16384 * 1024 / k. */
+ * Jaccard rows, train_retriever.py:461-462).  rows <= 65535, k <= min(r4d_topk_max_k(), n).
+ * k <= 64: one launch for n <= 16384 * 1024 / k.  64 < k <= 2048: a workgroup per 16384 columns selects its k best by radix
+ * select and sorts them (one launch), longer rows repeat that over the candidates -- no cross-workgroup hand-off.  The result is
+ * the same at every k: values as order-preserving keys (NaN -> -inf, -0.0 -> +0.0), key descending, column ascending, the first
+ * k; a NaN is reported as -inf.  A workspace size never shrinks from k = 64 to k = 65. */
+int r4d_topk_max_k(void);                     /* 2048: the largest k of the three f32 entries (r4d_topk_f64: 64) */
 size_t r4d_topk_f32_workspace_bytes(int32_t rows, int32_t n, int32_t k);
 int r4d_topk_f32(const float* m_d, int32_t rows, int32_t n, int32_t k, float* out_val_d, int64_t* out_idx_d,
                  void* workspace_d, size_t workspace_bytes, void* stream);
 /* Merge G per-shard candidate lists (after the RCCL all-gather): vals_d [G,Q,k], idx_d [G,Q,k]
  * -> out [Q,k], same canonical order; result == single-GPU top-k by construction.  Shards in ascending order of
- * their index ranges (rank order), every list sorted by (value desc, index asc) as r4d_score_topk_f32 emits them. */
+ * their index ranges (rank order), every list sorted by (value desc, index asc) as r4d_score_topk_f32 emits them.
+ * k <= r4d_topk_max_k(), Q <= 65535, G * k <= 2^30.  A shard shorter than k pads its list with (-inf, INT64_MAX); a pad is an
+ * ordinary candidate at its list position (it can only surface where fewer than k real candidates exist).  k > 64 takes the
+ * gathered lists through r4d_topk_f32's second path. */
 size_t r4d_merge_topk_workspace_bytes(int32_t G, int32_t Q, int32_t k);
 int r4d_merge_topk_f32(const float* vals_d, const int64_t* idx_d, int32_t G, int32_t Q, int32_t k,
                        float* out_val_d, int64_t* out_idx_d, void* workspace_d, size_t workspace_bytes, void* stream);

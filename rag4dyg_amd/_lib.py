@@ -121,6 +121,7 @@ PROTOTYPES = {
     "r4d_score_topk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "r4d_score_topk_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P, _P,
                                      c_size_t, _P]),
+    "r4d_topk_max_k": (c_int32, []),
     "r4d_topk_f32_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "r4d_topk_f32": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "r4d_merge_topk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),

@@ -80,6 +80,7 @@ struct ProfScope {
     X(SCAN_SHORT, "scan:short shard (even rows, two tiles in flight)") X(SCAN_DMA, "scan:short shard, LDS-DMA staged") X(SCAN_RING, "scan:long shard, LDS-DMA ring") X(SCAN_GEMM, "scan:tiled GEMM (Q > 64 or other d)") X(SCAN_TILED, "scan:128x256 tiles in the scan kernels' arithmetic (Q >= 64)") X(SCAN_BF16X3, "scan:bf16x3 operands") X(SCAN_F32, "scan:exact-f32 operands")  \
     X(TOPK_ONE_WG, "topk:one workgroup per row") X(TOPK_TICKET, "topk:cross-workgroup ticket merge")                      \
     X(TOPK_MULTI, "topk:second launch over candidates") X(TOPK_F64, "topk:f64 rows")                                      \
+    X(TOPKL_ONE, "tuning:topk_large:one level") X(TOPKL_MULTI, "tuning:topk_large:several levels") X(TOPKL_MERGE, "tuning:topk_large:merge route") \
     X(EMBED_LN4, "embed+layernorm:16-byte lanes") X(EMBED_GENERIC, "embed+layernorm:generic") X(LN4_2, "layernorm:ln4<2>") X(LN4_4, "layernorm:ln4<4>") X(LN4_8, "layernorm:ln4<8>") X(LN_GENERIC, "layernorm:generic") \
     X(LNF_8, "lnf_meanpool:<8>") X(LNF_16, "lnf_meanpool:<16>") X(LNF_32, "lnf_meanpool:<32>")                             \
     X(DEC_ATT_32, "decode_attention:<32>") X(DEC_ATT_64, "decode_attention:<64>")                                         \
@@ -312,6 +313,14 @@ template <typename T> size_t topk_ws_bytes(int rows, int n, int k);
 template <typename T>
 int topk_rows(const T* vals, const long long* idx_in, int rows, int n, long long ld, int k, long long index_offset, T* out_v,
               long long* out_i, void* ws, size_t ws_bytes, bool counters_zeroed, hipStream_t s);
+
+// ------------------------------------------------------------------ topk_large.hip
+// f32 rows at 64 < k <= TOPK_MAX_K (radix select + LDS sort per 16384 list positions, one launch per level); topk_rows<float> and
+// topk_ws_bytes<float> route here, no other caller
+constexpr int TOPK_MAX_K = 2048;
+size_t topk_large_ws_bytes(int rows, int n, int k);
+int topk_large_rows(const float* vals, const long long* idx_in, int rows, int n, long long ld, int k, long long index_offset,
+                    float* out_v, long long* out_i, void* ws, hipStream_t s);
 
 // ------------------------------------------------------------------ encoder_ops.hip
 int launch_layernorm(const float* x, const float* w, const float* b, int rows, int d, float eps, float* y,

@@ -679,7 +679,7 @@ int r4d_score_topk_f32(const float* q_hat_d, const float* pool_hat_d, int32_t Q,
                        void* workspace_d, size_t workspace_bytes, void* stream) {
     R4D_REQUIRE(q_hat_d && pool_hat_d && out_val_d && out_idx_d, "score_topk: null pointer");
     R4D_REQUIRE(Q >= 1 && Q <= 65535 && N >= 1 && d >= 4 && d % 4 == 0, "score_topk: bad shape Q=%d N=%d d=%d", Q, N, d);
-    R4D_REQUIRE(k >= 1 && k <= 64 && k <= N, "score_topk: k=%d must be in [1, min(64, N=%d)]", k, N);
+    R4D_REQUIRE(k >= 1 && k <= TOPK_MAX_K && k <= N, "score_topk: k=%d must be in [1, min(%d, N=%d)]", k, TOPK_MAX_K, N);
     if (!workspace_d || workspace_bytes < r4d_score_topk_workspace_bytes(Q, N, k)) {
         set_error("score_topk: workspace too small");
         return R4D_ERR_WORKSPACE;

@@ -15,36 +15,9 @@
 #include <string.h>
 #include <stdlib.h>
 #include "common.h"
+#include "topk_key.h"      // KeyOf: order-preserving keys (NaN -> -inf, -0.0 -> +0.0; key 0 = padding)
 
 namespace r4d {
-
-// ------------------------------------------------------------------------------------ order-preserving keys
-template <typename T> struct KeyOf;
-template <> struct KeyOf<float> {
-    typedef uint32_t K;
-    static __device__ __forceinline__ K make(float x) {           // larger value <=> larger key; NaN sorts with -inf
-        x = (x == x) ? x + 0.0f : -INFINITY;                       // -0.0 + 0.0 == +0.0
-        const uint32_t b = __builtin_bit_cast(uint32_t, x);
-        return b ^ (uint32_t)(((int32_t)b >> 31) | (int32_t)0x80000000);
-    }
-    static __device__ __forceinline__ float value(K k) {
-        const uint32_t b = k ^ ((k & 0x80000000u) ? 0x80000000u : 0xffffffffu);
-        return __builtin_bit_cast(float, b);
-    }
-};
-template <> struct KeyOf<double> {
-    typedef uint64_t K;
-    static __device__ __forceinline__ K make(double x) {
-        x = (x == x) ? x + 0.0 : -(double)INFINITY;
-        const uint64_t b = __builtin_bit_cast(uint64_t, x);
-        return b ^ (uint64_t)(((int64_t)b >> 63) | (int64_t)0x8000000000000000ull);
-    }
-    static __device__ __forceinline__ double value(K k) {
-        const uint64_t b = k ^ ((k >> 63) ? 0x8000000000000000ull : 0xffffffffffffffffull);
-        return __builtin_bit_cast(double, b);
-    }
-};
-// Key 0 is below every real key (the smallest real key is that of -inf): it marks padding and consumed slots.
 
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
@@ -359,6 +332,7 @@ static inline int pick_waves(long long nseg, int k) {
 
 template <typename T>
 size_t topk_ws_bytes(int rows, int n, int k) {
+    if (sizeof(T) == 4 && k > MAXK) return topk_large_ws_bytes(rows, n, k);
     size_t total = align_up((size_t)rows * sizeof(unsigned), 256);          // ticket counters
     long long cur = n;
     while (true) {
@@ -380,12 +354,16 @@ template size_t topk_ws_bytes<double>(int, int, int);
 template <typename T>
 int topk_rows(const T* vals, const long long* idx_in, int rows, int n, long long ld, int k, long long index_offset,
               T* out_v, long long* out_i, void* ws, size_t ws_bytes, bool counters_zeroed, hipStream_t s) {
-    R4D_REQUIRE(k >= 1 && k <= MAXK && k <= n, "topk: k=%d must be in [1, min(64, n=%d)]", k, n);
+    constexpr int kmax = sizeof(T) == 4 ? TOPK_MAX_K : MAXK;                      // beyond MAXK: topk_large.hip, f32 rows only
+    R4D_REQUIRE(k >= 1 && k <= kmax && k <= n, "topk: k=%d must be in [1, min(%d, n=%d)]", k, kmax, n);
     R4D_REQUIRE(rows >= 1 && rows <= 65535, "topk: rows=%d outside [1, 65535]", rows);
     R4D_REQUIRE(n <= (1 << 30), "topk: n=%d exceeds 2^30 columns", n);          // 32-bit column arithmetic incl. the padded tail
     if (!ws || ws_bytes < topk_ws_bytes<T>(rows, n, k)) {
         set_error("topk: workspace too small");
         return R4D_ERR_WORKSPACE;
+    }
+    if constexpr (sizeof(T) == 4) {
+        if (k > MAXK) return topk_large_rows(vals, idx_in, rows, n, ld, k, index_offset, out_v, out_i, ws, s);
     }
     unsigned* counters = (unsigned*)ws;
     char* wp = (char*)ws + align_up((size_t)rows * sizeof(unsigned), 256);
@@ -648,17 +626,18 @@ int r4d_topk_f32(const float* m_d, int32_t rows, int32_t n, int32_t k, float* ou
 
 size_t r4d_merge_topk_workspace_bytes(int32_t G, int32_t Q, int32_t k) {
     if (G <= 0 || Q <= 0 || k <= 0) return 0;
-    if ((long long)G * k <= 1024) return 256;
+    if ((long long)G * k <= 1024 && k <= MAXK) return 256;
     return align_up((size_t)G * Q * k * 4, 256) + align_up((size_t)G * Q * k * 8, 256) + topk_ws_bytes<float>(Q, G * k, k);
 }
 
 int r4d_merge_topk_f32(const float* vals_d, const int64_t* idx_d, int32_t G, int32_t Q, int32_t k, float* out_val_d,
                        int64_t* out_idx_d, void* workspace_d, size_t workspace_bytes, void* stream) {
     R4D_REQUIRE(vals_d && idx_d && out_val_d && out_idx_d, "merge_topk: null pointer");
-    R4D_REQUIRE(G >= 1 && Q >= 1 && Q <= 65535 && k >= 1 && k <= MAXK, "merge_topk: G=%d Q=%d k=%d out of range", G, Q, k);
+    R4D_REQUIRE(G >= 1 && Q >= 1 && Q <= 65535 && k >= 1 && k <= TOPK_MAX_K && (long long)G * k <= (1 << 30),
+                "merge_topk: G=%d Q=%d k=%d out of range (Q <= 65535, k <= %d, G * k <= 2^30)", G, Q, k, TOPK_MAX_K);
     hipStream_t s = (hipStream_t)stream;
     const long long tot = (long long)G * Q * k;
-    if ((long long)G * k <= 1024) {
+    if ((long long)G * k <= 1024 && k <= MAXK) {
         ProfScope prof(PK_MERGE_TOPK, 24.0 * tot, s);
         hipLaunchKernelGGL(merge_topk_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, s, vals_d, (const long long*)idx_d, G, Q, k,
                            out_val_d, (long long*)out_idx_d);
@@ -669,6 +648,7 @@ int r4d_merge_topk_f32(const float* vals_d, const int64_t* idx_d, int32_t G, int
         set_error("merge_topk: workspace too small");
         return R4D_ERR_WORKSPACE;
     }
+    if (k > MAXK) R4D_BRANCH(TOPKL_MERGE);                      // any G: the one-wavefront merge hands back 64 at the most
     float* cv = (float*)workspace_d;
     long long* ci = (long long*)((char*)workspace_d + align_up((size_t)tot * 4, 256));
     char* ws = (char*)ci + align_up((size_t)tot * 8, 256);
@@ -693,6 +673,8 @@ int r4d_argsort_desc_f64(const double* scores_d, int32_t rows, int32_t n, int32_
                          size_t workspace_bytes, void* stream) {
     return argsort_desc<double>(scores_d, rows, n, perm_d, workspace_d, workspace_bytes, (hipStream_t)stream);
 }
+
+int r4d_topk_max_k(void) { return TOPK_MAX_K; }
 
 size_t r4d_topk_f64_workspace_bytes(int32_t rows, int32_t n, int32_t k) {
     if (rows <= 0 || n <= 0 || k <= 0) return 0;

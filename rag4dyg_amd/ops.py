@@ -670,8 +670,18 @@ def score_topk(q_hat, pool_hat, k, index_offset=0, want_scores=False):
     return vals, idx, scores
 
 
+def __getattr__(name):
+    # ops.TOPK_MAX_K: the largest k of topk_f32 / score_topk / merge_topk (2048; topk_f64: 64).  Read from the library on first
+    # use, so that importing this module does not need the library.
+    if name == "TOPK_MAX_K":
+        globals()["TOPK_MAX_K"] = int(_lib.load().r4d_topk_max_k())
+        return globals()["TOPK_MAX_K"]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def topk_f32(m, k):
-    """Canonical per-row top-k of an f32 matrix -> (vals [rows,k], idx int64 [rows,k])."""
+    """Canonical per-row top-k of an f32 matrix -> (vals [rows,k], idx int64 [rows,k]); k <= min(TOPK_MAX_K, n).  Values are
+    ordered as keys (NaN -> -inf, -0.0 -> +0.0), ties by ascending column; beyond k = 64 the library selects by radix select."""
     rows, n = m.shape
     lib = _lib.load()
     ws = workspace(lib.r4d_topk_f32_workspace_bytes(rows, n, k), m.device, "topk32")

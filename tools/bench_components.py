@@ -7,6 +7,8 @@
   encode_precision   the bench step's encode, val-mode greedy decode and the real-data top-10 lists under
             ops.set_encode_precision("bf16") and ("bf16+attn") beside the f16x2 and bf16x3 arithmetics (alternated in one
             process); the attention kernels of the two words alone at head dims 64 .. 256
+  topk_large   top-100 / top-1024 of 256 x 100k, 32 x 100k and 2,048 x 12,512 score rows: the radix-select path, the argsort route
+            to the same lists, and the k = 64 launch, alternated in one process
   encode_step_trace WORD [SHAPE]   12 encode steps under one precision word and nothing else: the program of a
             ``rocprofv3 --kernel-trace --stats -- python tools/bench_components.py encode_step_trace bf16+attn`` run
 Each line: achieved = algorithmic bytes / HIP-event time of the kernel class (r4d_profile_* hooks), peak 8 TB/s.
@@ -113,6 +115,36 @@ def topk():
         for k in (1, 10, 64):
             gw = graph_wall(lambda: ops.topk_f32(S, k))
             emit(component="topk", rows=32, n=n, k=k, gpu_wall_us=round(gw * 1e6, 2))
+
+
+def topk_large():
+    """Top-k beyond 64 per row (csrc/topk_large.hip) against the only other route to the same lists -- the full-row ranking
+    ``ops.argsort_desc`` sliced to k plus the value gather -- with the k = 64 launch of the same rows as a scale.  HIP events
+    around ``reps`` back-to-back calls after a warm-up, the three arms alternated over 5 rounds in one process, medians; the two
+    routes' lists are compared before anything is timed."""
+    import statistics
+    for rows, n in ((256, 100000), (32, 100000), (2048, 12512)):
+        S = torch.rand(rows, n, generator=torch.Generator().manual_seed(rows + n)).to(dev)
+        for k in (100, 1024):
+            def by_argsort():
+                perm = ops.argsort_desc(S)[:, :k].long()
+                return torch.gather(S, 1, perm), perm
+            arms = {"topk_large": (lambda: ops.topk_f32(S, k), 20), "argsort_slice": (by_argsort, 3), "topk_k64": (lambda: ops.topk_f32(S, 64), 20)}
+            a, b_ = arms["topk_large"][0](), by_argsort()
+            assert torch.equal(a[0], b_[0]) and torch.equal(a[1], b_[1]), (rows, n, k)
+            us = {name: [] for name in arms}
+            for _ in range(5):
+                for name, (fn, reps) in arms.items():
+                    fn(); torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _r in range(reps):
+                        fn()
+                    e1.record(); torch.cuda.synchronize()
+                    us[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+            med = {name: round(statistics.median(v), 1) for name, v in us.items()}
+            emit(component="topk_large", rows=rows, n=n, k=k, us=med, spread_us={name: [round(min(v), 1), round(max(v), 1)] for name, v in us.items()},
+                 speedup_over_argsort=round(med["argsort_slice"] / med["topk_large"], 1), lists_equal=True)
 
 
 def jaccard():
@@ -602,5 +634,5 @@ if __name__ == "__main__":
         encode_step_trace(*sys.argv[2:4])
         sys.exit(0)
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):
-        {"scan": scan, "topk": topk, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "attention_alone": attention_alone, "encode_step_trace": encode_step_trace, "generator": generator,
+        {"scan": scan, "topk": topk, "topk_large": topk_large, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "attention_alone": attention_alone, "encode_step_trace": encode_step_trace, "generator": generator,
          "generator_reddit": generator_reddit, "simpledyg": simpledyg_eval, "training": training, "training_cpu": training_cpu}[part]()
