@@ -423,6 +423,22 @@ int r4d_set_encode_attention_bf16(int32_t on);
 int r4d_get_encode_attention_bf16(void);
 int r4d_attention_bf16_groups(const void* qkv_d, int32_t qkv_is_bf16, int32_t n_groups, const int32_t* Bs, const int32_t* Ts,
                               const int64_t* row0s, int32_t n_head, int32_t d, void* a_d, int32_t out_is_bf16, void* stream);
+/*
+ * bf16 STORE of the activations for the encoder forward under r4d_set_encode_bf16 (additive ABI v6 entries).  Changes NO output bit:
+ * the plain-bf16 GEMM rounds its fp32 A operand to bf16 while staging it (round to nearest even, v_cvt_pk_bf16_f32); with this
+ * switch the same rounding is applied ONCE where the activation is produced and the GEMM reads the bf16 rows as they are.
+ * r4d_set_encode_act_bf16(on != 0) returns the previous setting; default 0; process-wide.  The switch is read by the encoder
+ * entries only (those r4d_set_encode_bf16 names) and ONLY WHILE r4d_set_encode_bf16 is on: alone it changes nothing.  While both
+ * are on, each of a block's three buffers is decided on its own: ln1 (every layer; layer 0's leaves the fused embedding kernel) is
+ * bf16 [M, d] where c_attn runs on the plain-bf16 GEMM, ln2 [M, d] where c_fc does, the GELU output f [M, 4d] where c_fc AND
+ * mlp.c_proj do (c_fc then writes RN(gelu_new(v)) and nothing else) -- and n_embd % 256 == 0 (the producers' 16-byte stores).  Any
+ * other buffer stays fp32 and its launches are those of the switch off.  With r4d_set_encode_attention_bf16 on as well, c_attn
+ * reads bf16 ln1 and writes bf16 q | k | v (fp32 where the caller asked for qkv, as before).  The bf16 rows occupy the first half of
+ * the workspace's fp32 buffers and nothing reads the other half: no size query changes.  r4d_get_encode_act_bf16 reads the switch.
+ * The kernels alone: r4d_layernorm_bf16_f32 and r4d_conv1d_bf16_act_f32 (kinds 3 and 4), further down.
+ */
+int r4d_set_encode_act_bf16(int32_t on);
+int r4d_get_encode_act_bf16(void);
 /* Causal multi-head attention on packed c_attn output qkv_d [B,T,3d] -> a_d [B,T,d] (heads merged).
  * Attention._attn + split/merge_heads, modeling_gpt2.py:140-175; scale = division by sqrt(hd) (:143).
  * scores_ws_d: device scratch of r4d_attention_workspace_bytes(B,H,T).  B >= 1, 1 <= T <= 1024, head_dim a multiple of 16;
@@ -733,6 +749,8 @@ int r4d_get_train_act_bf16(void);
  * r4d_layernorm_bf16_f32: y_bf16_d [rows, d] = RN(LayerNorm(x)) with r4d_layernorm_f32's statistics; d % 256 == 0, 16-byte aligned.
  * r4d_conv1d_bf16_act_f32: r4d_conv1d_bf16_f32 on x_bf16_d [M, K] bf16 (K % 32 == 0).  kind 0: y_d f32 [M,N]; 1: y_d = second_d + ...;
  *   2: second_d f32 [M,N] <- the pre-activation, y_d bf16 [M,N] <- RN(gelu_new(pre)) (N even).
+ *   The encoder's r4d_set_encode_act_bf16 adds two kinds without a second buffer (second_d ignored), N even:
+ *   3: y_d bf16 [M,N] <- RN(gelu_new(v)), no pre-activation kept (c_fc); 4: y_d bf16 [M,N] <- RN(v) (c_attn under bf16 attention).
  * r4d_weight_grad_bf16_act_f32: r4d_weight_grad_bf16_f32 on x_bf16_d [rows, in] bf16 with row stride ldx (bf16 elements, a multiple
  *   of 8); the same workspace (r4d_weight_grad_bf16_workspace_bytes). */
 int r4d_layernorm_bf16_f32(const float* x_d, const float* w_d, const float* b_d, int32_t rows, int32_t d, float eps,

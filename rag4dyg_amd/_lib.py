@@ -113,6 +113,8 @@ PROTOTYPES = {
     "r4d_get_encode_bf16": (c_int32, []),
     "r4d_set_encode_attention_bf16": (c_int32, [c_int32]),
     "r4d_get_encode_attention_bf16": (c_int32, []),
+    "r4d_set_encode_act_bf16": (c_int32, [c_int32]),
+    "r4d_get_encode_act_bf16": (c_int32, []),
     "r4d_attention_bf16_groups": (c_int32, [_P, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), c_int32, c_int32,
                                             _P, c_int32, _P]),
     "r4d_attention_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),

@@ -93,7 +93,8 @@ struct ProfScope {
     X(TBH_LOGITS, "tuning:train_head_bf16:logits") X(TBH_DGRAD, "tuning:train_head_bf16:dgrad") X(TBH_WGRAD, "tuning:train_head_bf16:wgrad") X(TBH_WGRAD_FALLBACK, "tuning:train_head_bf16:wgrad_fallback") \
     X(TAB_FWD, "tuning:train_act_bf16:fwd") X(TAB_WGRAD, "tuning:train_act_bf16:wgrad") X(TAB_LN, "tuning:train_act_bf16:ln") X(TAB_GELU, "tuning:train_act_bf16:gelu") \
     X(TAF_FWD, "tuning:train_attn_fused:fwd") X(TAF_ROWSUM, "tuning:train_attn_fused:rowsum") X(TAF_DKV, "tuning:train_attn_fused:dkv") X(TAF_DQ, "tuning:train_attn_fused:dq") \
-    X(EBA_BF16, "tuning:encode_bf16_attn:bf16 qkv") X(EBA_F32, "tuning:encode_bf16_attn:fp32 qkv, rounded while staged") X(EBA_FALLBACK, "tuning:encode_bf16_attn:fallback to the exact-f32 attention")
+    X(EBA_BF16, "tuning:encode_bf16_attn:bf16 qkv") X(EBA_F32, "tuning:encode_bf16_attn:fp32 qkv, rounded while staged") X(EBA_FALLBACK, "tuning:encode_bf16_attn:fallback to the exact-f32 attention") \
+    X(EAB_LN1, "tuning:encode_act_bf16:ln1") X(EAB_LN2, "tuning:encode_act_bf16:ln2") X(EAB_F, "tuning:encode_act_bf16:f") X(EAB_KEPT_F32, "tuning:encode_act_bf16:kept fp32")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -187,6 +188,7 @@ int launch_split2_lines(const float* x, long long rows, int K, unsigned short* l
 // plane [N][K] (plane 0 of the bf16x3 planes); the bf16x3 kernel's shape contract; epilogues none / GELU / residual
 // (training, r4d_set_train_bf16: also GELU_KEEP and GELU_GRAD).  a.a_bf16 (r4d_set_train_act_bf16): A is already bf16 in memory -- the
 // same operand bits, one 16-byte load per item and no rounding; epilogues none / residual / GELU_KEEP / GELU_KEEP_BF16 (C as bf16)
+// and, for the encoder (r4d_set_encode_act_bf16), GELU / GELU_BF16 / NONE_BF16
 int launch_gemm_b1(const S3Args& a, hipStream_t stream);
 // gemm_b1tn.hip: out[I,J] (one slice) or partials [S][I][J] <- RN_bf16(X[M,I])^T . RN_bf16(dY[M,J]) over S slices of the M rows,
 // db_out (nullable) [J] or [S][J] <- column sums of the unrounded dY; gemm_s3tn's shape contract
@@ -339,7 +341,8 @@ struct RowGroups {
     const float* emb[ATT_MAXG];
 };
 int launch_embed_layernorm_groups(const RowGroups& G, const float* wte, const float* wpe, int vocab, int d,
-                                  const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s, bool y_lines = false);
+                                  const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s, bool y_lines = false,
+                                  bool y_bf16 = false);
 int launch_causal_softmax(float* S, int nbh, int T, int ld, int row_tile, hipStream_t s, bool normalise = true);
 // rows of out [B*T, d] (merged heads) divided by the row sums of the unnormalised P [B*H, T, ld] (encoder.hip: attention())
 int launch_attention_rows_normalise(const float* P, float* out, int B, int T, int H, int d, int ld, hipStream_t s);
@@ -391,6 +394,7 @@ bool attention_b1_supported(int H, int d);
 int launch_attention_b1_groups(const void* qkv, bool qkv_bf16, int n, const int* Bs, const int* Ts, const long long* row0s, int H, int d,
                                void* out, bool out_bf16, hipStream_t s);
 extern int g_encode_attn_bf16;       // r4d_set_encode_attention_bf16: read by the encoder entries, only while g_encode_bf16 is on
+extern int g_encode_act_bf16;        // r4d_set_encode_act_bf16: read by the encoder entries, only while g_encode_bf16 is on
 extern int g_attention_fused;        // -1 auto (default), 1 fused, 0 three-launch GEMM form (r4d_set_attention_fused)
 // Layer 0's repeated pad rows (encoder.hip: encode_impl).  The layer-0 c_attn row depends on (token, position) only,
 // so 32-row blocks (by GLOBAL row index, as in the key-blocked image) whose rows all carry one candidate token c are dropped from

@@ -19,7 +19,10 @@ enum GemmEpilogue { EPI_NONE = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_SCALE_DIV 
                     EPI_GELU_KEEP_BF16 = 8,
                     // gemm_b1 only (encoder, r4d_set_encode_attention_bf16): EPI_NONE whose result leaves as bf16 [M, N] (RNE; ldc in bf16
                     // elements): c_attn's q | k | v for attention_b1.hip, which rounds the fp32 form by the same rule while staging
-                    EPI_NONE_BF16 = 9 };
+                    EPI_NONE_BF16 = 9,
+                    // gemm_b1 only (encoder, r4d_set_encode_act_bf16): EPI_GELU whose gelu(v) leaves as bf16 [M, N] (RNE; ldc in bf16
+                    // elements) and nothing else: c_fc's f for mlp.c_proj, which rounds the fp32 form by the same rule while staging
+                    EPI_GELU_BF16 = 10 };
 
 extern int g_gemm_split3;             // Conv1D arithmetic (r4d_set_gemm_split3): 0 exact-f32 MFMA, 1 bf16x3 planes, 2 f16x2 planes (bf16x3 where a layer carries no f16 planes)
 
@@ -122,6 +125,21 @@ static inline GemmRoute conv1d_route(const Conv1DW& W, int M, int epilogue, bool
 static inline bool conv1d_fuses_gelu_keep(const Conv1DW& W, int M, int bf16) {
     const GemmRoute r = conv1d_route(W, M, EPI_GELU_KEEP, false, bf16);
     return r == ROUTE_B1 || r == ROUTE_S3 || (r == ROUTE_H2 && W.w3 && gemm_s3_supported(M, W.in, W.out));
+}
+// The activations a bf16 encoder forward may keep as bf16 [M, width] between producer and consumer (r4d_set_encode_act_bf16; DESIGN.md
+// 7 item 13): a block's ln1 (every layer: the fused embedding kernel has a bf16 output), its ln2 and its f -- train_act_bf16_block's
+// three (above), decided per buffer.  ONE rule on shapes and plane presence: both switches on (`on`), the producers' 16-byte bf16
+// stores (d % 256 == 0), and every GEMM that touches the buffer on the plain-bf16 kernel: ln1's consumer c_attn, ln2's consumer
+// c_fc, f's producer c_fc and its consumer mlp.c_proj.  Otherwise that buffer stays fp32 and the launches are those of the switch off
+static inline bool encode_act_bf16_block(int which, bool on, const Conv1DW& Wqkv, const Conv1DW& Wfc, const Conv1DW& Wp, int M, int d) {
+    if (!on || d <= 0 || d % 256 != 0) return false;
+    const bool fc = conv1d_route(Wfc, M, EPI_GELU, false, BF16_ENCODE) == ROUTE_B1;
+    switch (which) {
+        case ACT_LN1: return conv1d_route(Wqkv, M, EPI_NONE, false, BF16_ENCODE) == ROUTE_B1;
+        case ACT_LN2: return fc;
+        case ACT_F: return fc && conv1d_route(Wp, M, EPI_RESIDUAL, false, BF16_ENCODE) == ROUTE_B1;
+        default: return false;
+    }
 }
 // dx[M, in] = dy[M, out] . W^T.  A Conv1D reads w [in, out] as the k-contiguous operand (b_trans = 1); the LM head (no `w`) reads
 // its table [out, in] as a row-major one (b_trans = 0) and never takes the LAYERS' plain bf16: only its own switch

@@ -19,6 +19,7 @@ void set_error(const char* fmt, ...) {
 int g_gemm_split3 = 1;                // r4d_set_gemm_split3: 0 exact f32, 1 bf16x3, 2 f16x2
 int g_encode_bf16 = 0;                // r4d_set_encode_bf16: the encoder calls' Conv1D GEMMs in plain bf16 (gemm_b1.hip), whatever the mode above
 int g_encode_attn_bf16 = 0;           // r4d_set_encode_attention_bf16: ... and their attention on bf16 operands (attention_b1.hip); read only while the switch above is on
+int g_encode_act_bf16 = 0;            // r4d_set_encode_act_bf16: ... and ln1 / ln2 / f as bf16 between producer and consumer; read only while r4d_set_encode_bf16 is on
 
 int conv1d(const Conv1DW& W, const float* x, const float* resid, int M, int epilogue, float* y, hipStream_t s, const Conv1DOpts& opts) {
     const int K = W.in, N = W.out;
@@ -211,6 +212,12 @@ int r4d_set_encode_attention_bf16(int32_t on) {
     return prev;
 }
 int r4d_get_encode_attention_bf16(void) { return g_encode_attn_bf16; }
+int r4d_set_encode_act_bf16(int32_t on) {
+    const int prev = g_encode_act_bf16;
+    g_encode_act_bf16 = on != 0;
+    return prev;
+}
+int r4d_get_encode_act_bf16(void) { return g_encode_act_bf16; }
 int r4d_set_range_flag(uint32_t* flag_d) { g_range_flag = flag_d; return R4D_OK; }
 int r4d_set_attention_kblk(int32_t on) {
     const int prev = g_attention_kblk < 0 ? 1 : g_attention_kblk;
@@ -323,7 +330,8 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         // f16x2 mode, round 5: the LayerNorms write their rows as f16x2 LINES, the c_fc GELU epilogue too, and c_attn / c_fc /
         // mlp.c_proj take them through LDS-DMA (gemm_h2p.hip) -- the values of the register-staged gemm_h2 path, bit for bit
         // (r4d_set_gemm_h2p(0) keeps that one); the buffers keep their size (4 bytes per element either way)
-        // (bf16 precision takes the structure of the bf16x3 path: fp32 activations, exact-f32 attention, no lines or h2 words)
+        // (bf16 precision takes the structure of the bf16x3 path: fp32 activations, exact-f32 attention, no lines or h2 words;
+        //  its own switches move the attention and the activations to bf16 below)
         const bool lines = !g_encode_bf16 && g_gemm_split3 == 2 && g_gemm_h2p && Wqkv.h2 && Wfc.h2 && Wp.h2 && layernorm_lines_supported(d) &&
                            gemm_h2p_supported(M, d, 3 * d) && gemm_h2p_supported(M, d, 4 * d) && gemm_h2p_supported(M, 4 * d, d);
         unsigned short* ln_lines = reinterpret_cast<unsigned short*>(ws.ln);
@@ -353,6 +361,18 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
         if (want_battn && !battn) R4D_BRANCH(EBA_FALLBACK);
         const bool qkv_b = battn && !out_qkv_d && conv1d_route(Wqkv, M, EPI_NONE, false, BF16_ENCODE) == ROUTE_B1;
         const bool att_b = battn && conv1d_route(Wo, M, EPI_RESIDUAL, false, BF16_ENCODE) == ROUTE_B1;
+        // bf16 precision with the activation switch (r4d_set_encode_act_bf16): ln1, ln2 and f are rounded ONCE where they are produced and
+        // travel as bf16 [M, width] in the first half of ws.ln / ws.fc to a gemm_b1 that reads them as its bf16 A operand -- the bits it
+        // would have rounded while staging the fp32 form.  Per buffer (conv1d_route.h: encode_act_bf16_block), counted
+        const bool want_act = g_encode_bf16 && g_encode_act_bf16;
+        const bool ln1_b = encode_act_bf16_block(ACT_LN1, want_act, Wqkv, Wfc, Wp, M, d), ln2_b = encode_act_bf16_block(ACT_LN2, want_act, Wqkv, Wfc, Wp, M, d),
+                   f_b = encode_act_bf16_block(ACT_F, want_act, Wqkv, Wfc, Wp, M, d);
+        if (want_act) {
+            if (ln1_b) R4D_BRANCH(EAB_LN1); else R4D_BRANCH(EAB_KEPT_F32);
+            if (ln2_b) R4D_BRANCH(EAB_LN2); else R4D_BRANCH(EAB_KEPT_F32);
+            if (f_b) R4D_BRANCH(EAB_F); else R4D_BRANCH(EAB_KEPT_F32);
+        }
+        unsigned short* ln_b16 = reinterpret_cast<unsigned short*>(ws.ln);
         // ... and its K third as the key-blocked image the head_dim 128 / 256 kernel loads by whole cache lines (attention_h2.hip)
         if (g_attention_kblk < 0) { const char* e = getenv("R4D_ATT_KBLK"); g_attention_kblk = e ? atoi(e) != 0 : 1; }
         const bool kblk = words && lines && g_attention_kblk && (d / H) % 32 == 0;      // every head_dim attention_h2.hip serves
@@ -373,7 +393,7 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
                 const RowGroups R = row_groups(groups, g0, n_groups);
                 const size_t r0 = groups[g0].row0;
                 rc = launch_embed_layernorm_groups(R, w->wte, w->wpe, cfg->vocab, d, L.ln_1_w, L.ln_1_b, cfg->ln_eps,
-                                                   ws.x + r0 * d, ws.ln + r0 * d, s, lines);
+                                                   ws.x + r0 * d, ln1_b ? reinterpret_cast<float*>(ln_b16 + r0 * d) : ws.ln + r0 * d, s, lines, ln1_b);
                 if (rc) return rc;
             }
             if (pad0) {                                                   // the table: one sequence of Tmax positions, every id = c
@@ -383,6 +403,7 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
                                                         ws.x + (size_t)pr.Mp * d, ws.ln + (size_t)pr.Mp * d, s, lines))) return rc;
             }
         } else if ((rc = lines ? launch_layernorm_lines(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ln_lines, s)
+                       : ln1_b ? launch_layernorm_bf16(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ln_b16, s)
                                : launch_layernorm(ws.x, L.ln_1_w, L.ln_1_b, M, d, cfg->ln_eps, ws.ln, s))) {
             return rc;
         }
@@ -403,7 +424,11 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             if ((rc = launch_gemm_h2p_rowmap(a, ln_lines, pr, pb, s))) return rc;
             rc = launch_pad_rows_fill(pr, pb, reinterpret_cast<unsigned*>(qkv), ws.kblk, d, s);
         } else if (lines) rc = conv1d_lines(Wqkv, ln_lines, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, false, s, kblk ? ws.kblk : nullptr, kblk ? d / H : 0);
-        else if (qkv_b) rc = launch_gemm_b1(s3_args(ws.ln, Wqkv.w3, Wqkv.b, nullptr, M, d, 3 * d, EPI_NONE_BF16, qkv), s);
+        else if (qkv_b || ln1_b) {          // (ln1_b: c_attn is on gemm_b1 by the rule)
+            S3Args a = s3_args(ws.ln, Wqkv.w3, Wqkv.b, nullptr, M, d, 3 * d, qkv_b ? EPI_NONE_BF16 : EPI_NONE, qkv);
+            a.a_bf16 = ln1_b;
+            rc = launch_gemm_b1(a, s);
+        }
         else rc = conv1d(Wqkv, ws.ln, nullptr, M, words ? EPI_H2WORDS : EPI_NONE, qkv, s, enc);
         if (rc) return rc;
         // ... and with them the attention output: attn_h2_kernel writes its merged-head rows as lines for attn.c_proj
@@ -451,9 +476,20 @@ static int encode_impl(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, co
             if ((rc = conv1d_lines(Wp, fc_lines, ws.x, M, EPI_RESIDUAL, ws.x, false, s))) return rc;
             continue;
         }
-        if ((rc = launch_layernorm(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ws.ln, s))) return rc;
-        if ((rc = conv1d(Wfc, ws.ln, nullptr, M, EPI_GELU, ws.fc, s, enc))) return rc;
-        if ((rc = conv1d(Wp, ws.fc, ws.x, M, EPI_RESIDUAL, ws.x, s, enc))) return rc;
+        if ((rc = ln2_b ? launch_layernorm_bf16(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ln_b16, s)
+                        : launch_layernorm(ws.x, L.ln_2_w, L.ln_2_b, M, d, cfg->ln_eps, ws.ln, s))) return rc;
+        if (ln2_b) {                        // (c_fc is on gemm_b1 by the rule; f_b implies ln2_b)
+            S3Args a = s3_args(ws.ln, Wfc.w3, Wfc.b, nullptr, M, d, 4 * d, f_b ? EPI_GELU_BF16 : EPI_GELU, ws.fc);
+            a.a_bf16 = 1;
+            rc = launch_gemm_b1(a, s);
+        } else rc = conv1d(Wfc, ws.ln, nullptr, M, EPI_GELU, ws.fc, s, enc);
+        if (rc) return rc;
+        if (f_b) {
+            S3Args a = s3_args(ws.fc, Wp.w3, Wp.b, ws.x, M, 4 * d, d, EPI_RESIDUAL, ws.x);
+            a.a_bf16 = 1;
+            rc = launch_gemm_b1(a, s);
+        } else rc = conv1d(Wp, ws.fc, ws.x, M, EPI_RESIDUAL, ws.x, s, enc);
+        if (rc) return rc;
     }
     size_t part0 = 0;                                                   // scratch offset of the launch's first batch
     for (int g0 = 0; g0 < n_groups; g0 += ATT_MAXG) {

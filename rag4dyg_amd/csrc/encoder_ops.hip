@@ -250,7 +250,8 @@ __global__ __launch_bounds__(256) void embed_ln_groups_kernel(const RowTable G, 
 
 // the same with 16-byte lanes (d % 256 == 0, every pointer 16-byte aligned): a quarter of the memory instructions of the 4-byte form,
 // which held this write-bound kernel at 2.5 TB/s (ln4_kernel's layout and reduction order)
-template <int NQ, bool LINES = false>
+// BF16 (encoder, r4d_set_encode_act_bf16): y as bf16 [rows, d] -- the fp32 form's row arithmetic, ln4_kernel<NQ, false, true>'s store; x stays fp32
+template <int NQ, bool LINES = false, bool BF16 = false>
 __global__ __launch_bounds__(256) void embed_ln4_groups_kernel(const RowTable G, const RowInputs in,
                                                                const float* __restrict__ wte, const float* __restrict__ wpe,
                                                                int vocab, int d, const float* __restrict__ w,
@@ -298,6 +299,29 @@ __global__ __launch_bounds__(256) void embed_ln4_groups_kernel(const RowTable G,
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
     const float rstd = rsqrtf(wave_sum(q) / (float)d + eps);
+    if constexpr (BF16) {
+        static_assert(NQ % 2 == 0 && !LINES, "quads in pairs");
+        unsigned short* yb = reinterpret_cast<unsigned short*>(y_out) + row * d;
+        const bool odd = lane & 1;
+        const float4* w4 = reinterpret_cast<const float4*>(w);
+        const float4* b4 = reinterpret_cast<const float4*>(b);
+#pragma unroll
+        for (int i = 0; i < NQ; i += 2)
+            if (i < nq) {                                              // (wave-uniform)
+                const bool two = i + 1 < nq;
+                const float4 ya = ln4_out(v[i], mean, rstd, w4[lane + 64 * i], b4[lane + 64 * i]);
+                const unsigned a0 = ln_cvt_pk_bf16(ya.x, ya.y), a1 = ln_cvt_pk_bf16(ya.z, ya.w);
+                unsigned b0 = 0u, b1 = 0u;
+                if (two) {
+                    const float4 y2 = ln4_out(v[i + 1], mean, rstd, w4[lane + 64 * (i + 1)], b4[lane + 64 * (i + 1)]);
+                    b0 = ln_cvt_pk_bf16(y2.x, y2.y); b1 = ln_cvt_pk_bf16(y2.z, y2.w);
+                }
+                const unsigned r0 = lane_swap1(odd ? a0 : b0), r1 = lane_swap1(odd ? a1 : b1);
+                if (!odd) *reinterpret_cast<uint4*>(yb + 4 * lane + 256 * i) = make_uint4(a0, a1, r0, r1);
+                else if (two) *reinterpret_cast<uint4*>(yb + 4 * (lane - 1) + 256 * (i + 1)) = make_uint4(r0, r1, b0, b1);
+            }
+        return;
+    }
     float4* yr = reinterpret_cast<float4*>(y_out + row * d) + lane;
 #pragma unroll
     for (int i = 0; i < NQ; ++i)
@@ -311,7 +335,8 @@ __global__ __launch_bounds__(256) void embed_ln4_groups_kernel(const RowTable G,
 }
 
 int launch_embed_layernorm_groups(const RowGroups& G, const float* wte, const float* wpe, int vocab, int d,
-                                  const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s, bool y_lines) {
+                                  const float* w, const float* b, float eps, float* x_out, float* y_out, hipStream_t s, bool y_lines,
+                                  bool y_bf16) {
     R4D_REQUIRE(d % 64 == 0 && d <= 64 * MAXV, "embed: d=%d must be a multiple of 64 and <= %d", d, 64 * MAXV);
     R4D_REQUIRE(G.n >= 1 && G.n <= ATT_MAXG, "embed: %d batches per launch (max %d)", G.n, ATT_MAXG);
     const RowTable t = make_table(G);
@@ -330,6 +355,15 @@ int launch_embed_layernorm_groups(const RowGroups& G, const float* wte, const fl
         if (d <= 512) hipLaunchKernelGGL((embed_ln4_groups_kernel<2, true>), grid, dim3(256), 0, s, t, in, wte, wpe, vocab, d, w, b, eps, x_out, y_out);
         else if (d <= 1024) hipLaunchKernelGGL((embed_ln4_groups_kernel<4, true>), grid, dim3(256), 0, s, t, in, wte, wpe, vocab, d, w, b, eps, x_out, y_out);
         else hipLaunchKernelGGL((embed_ln4_groups_kernel<8, true>), grid, dim3(256), 0, s, t, in, wte, wpe, vocab, d, w, b, eps, x_out, y_out);
+        R4D_CHECK_LAUNCH("embed_layernorm");
+        return R4D_OK;
+    }
+    if (y_bf16) {                                                // y as bf16 [rows, d] behind the pointer (r4d_set_encode_act_bf16; the caller checked d % 256 == 0)
+        R4D_REQUIRE(vec, "embed: bf16 output needs d %% 256 == 0 and 16-byte aligned pointers");
+        R4D_BRANCH(EMBED_LN4);
+        if (d <= 512) hipLaunchKernelGGL((embed_ln4_groups_kernel<2, false, true>), grid, dim3(256), 0, s, t, in, wte, wpe, vocab, d, w, b, eps, x_out, y_out);
+        else if (d <= 1024) hipLaunchKernelGGL((embed_ln4_groups_kernel<4, false, true>), grid, dim3(256), 0, s, t, in, wte, wpe, vocab, d, w, b, eps, x_out, y_out);
+        else hipLaunchKernelGGL((embed_ln4_groups_kernel<8, false, true>), grid, dim3(256), 0, s, t, in, wte, wpe, vocab, d, w, b, eps, x_out, y_out);
         R4D_CHECK_LAUNCH("embed_layernorm");
         return R4D_OK;
     }

@@ -32,6 +32,7 @@ struct B1Shape { int M, N, K, lda, ldc, ldr; };
 // ABF (training, r4d_set_train_act_bf16): A is bf16 [M, lda] in memory -- the bits its producer rounded once (the same RNE) -- behind
 // the float pointer: an item is ONE 16-byte load of eight bf16 where the fp32 form has two loads of four floats and four
 // conversions; the same LDS image, k order, MFMA sequence and epilogues.  The descriptor's range is the bf16 block's own length.
+// (The encoder under r4d_set_encode_act_bf16 reads ln1, ln2 and the GELU output this way, and the attention output under "bf16+attn".)
 template <int BM, int BN, int WGM, int WGN, int EPI, bool ABF = false>
 __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD) && BN == 256) ? 2 : 4) void gemm_b1_kernel(
     const float* __restrict__ Ag, const unsigned short* __restrict__ Bp, float* __restrict__ Cg,
@@ -201,7 +202,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, ((EPI == EPI_RESIDUAL || EPI == EPI
 // (EPI_NONE_BF16: c_attn of the encoder's "bf16+attn" precision)
 #define B1_KINDS(X, L) X(L, EPI_NONE) X(L, EPI_GELU) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_GRAD) X(L, EPI_NONE_BF16)
 // with a bf16 A operand: the training forward's three consumers of a bf16 block (c_attn, c_fc, mlp c_proj)
-#define B1_KINDS_ABF(X, L) X(L, EPI_NONE) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_KEEP_BF16)
+// (the encoder's r4d_set_encode_act_bf16: c_fc as EPI_GELU_BF16 -- EPI_GELU where mlp.c_proj keeps fp32 -- and c_attn as EPI_NONE_BF16
+// under "bf16+attn")
+#define B1_KINDS_ABF(X, L) X(L, EPI_NONE) X(L, EPI_RESIDUAL) X(L, EPI_GELU_KEEP) X(L, EPI_GELU_KEEP_BF16) X(L, EPI_GELU) X(L, EPI_GELU_BF16) X(L, EPI_NONE_BF16)
 template <int BM, int BN, int WGM, int WGN>
 static int launch_b1(const S3Args& a, hipStream_t stream) {
     const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
@@ -231,7 +234,7 @@ int launch_gemm_b1(const S3Args& a, hipStream_t stream) {
     R4D_REQUIRE(a.lda % 4 == 0 && ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.planes % 16) == 0, "gemm_b1: alignment");
     R4D_REQUIRE((a.epilogue != EPI_RESIDUAL && a.epilogue != EPI_GELU_KEEP && a.epilogue != EPI_GELU_GRAD && a.epilogue != EPI_GELU_KEEP_BF16) || a.resid, "gemm_b1: epilogue %d needs the second buffer", a.epilogue);
     R4D_REQUIRE(!a.a_bf16 || a.lda % 8 == 0, "gemm_b1: a bf16 A operand wants lda %% 8 == 0 (lda=%d)", a.lda);
-    R4D_REQUIRE((a.epilogue != EPI_GELU_KEEP_BF16 && a.epilogue != EPI_NONE_BF16) || (a.N % 2 == 0 && a.ldc % 2 == 0 && ((uintptr_t)a.C % 4) == 0), "gemm_b1: the bf16 output wants even N and ldc");
+    R4D_REQUIRE((a.epilogue != EPI_GELU_KEEP_BF16 && a.epilogue != EPI_NONE_BF16 && a.epilogue != EPI_GELU_BF16) || (a.N % 2 == 0 && a.ldc % 2 == 0 && ((uintptr_t)a.C % 4) == 0), "gemm_b1: the bf16 output wants even N and ldc");
     static int forced = -2;
     if (forced == -2) { const char* e = getenv("R4D_GEMM_B1_TILE"); forced = e ? atoi(e) : -1; }   // tuning aid: 0 / 1 forces a tile
     const int t = (forced == 0 || forced == 1) ? forced : pick_tile_128(a.M, a.N);
@@ -254,10 +257,11 @@ int r4d_conv1d_bf16_f32(const float* x_d, const uint16_t* w_bf16_d, const float*
 
 int r4d_conv1d_bf16_act_f32(const uint16_t* x_bf16_d, const uint16_t* w_bf16_d, const float* bias_d, int32_t M, int32_t K, int32_t N,
                             int32_t kind, float* second_d, void* y_d, void* stream) {
-    R4D_REQUIRE(kind >= 0 && kind <= 2, "conv1d_bf16_act: kind %d not in {0 none, 1 residual, 2 gelu-keep with a bf16 output}", kind);
-    R4D_REQUIRE(kind == 0 || (second_d && (void*)second_d != y_d), "conv1d_bf16_act: kind %d needs the second buffer", kind);
-    S3Args a = s3_args(reinterpret_cast<const float*>(x_bf16_d), w_bf16_d, bias_d, kind ? second_d : nullptr, M, K, N,
-                       kind == 2 ? EPI_GELU_KEEP_BF16 : kind == 1 ? EPI_RESIDUAL : EPI_NONE, (float*)y_d);
+    R4D_REQUIRE(kind >= 0 && kind <= 4, "conv1d_bf16_act: kind %d not in {0 none, 1 residual, 2 gelu-keep with a bf16 output, 3 gelu as bf16, 4 none as bf16}", kind);
+    const bool two = kind == 1 || kind == 2;
+    R4D_REQUIRE(!two || (second_d && (void*)second_d != y_d), "conv1d_bf16_act: kind %d needs the second buffer", kind);
+    static const int epilogues[5] = {EPI_NONE, EPI_RESIDUAL, EPI_GELU_KEEP_BF16, EPI_GELU_BF16, EPI_NONE_BF16};
+    S3Args a = s3_args(reinterpret_cast<const float*>(x_bf16_d), w_bf16_d, bias_d, two ? second_d : nullptr, M, K, N, epilogues[kind], (float*)y_d);
     a.a_bf16 = 1;
     return launch_gemm_b1(a, (hipStream_t)stream);
 }

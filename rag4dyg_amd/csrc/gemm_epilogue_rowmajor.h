@@ -42,9 +42,10 @@
 {
     static_assert(EPI != EPI_H2WORDS || EPILOGUE_PAIR_WORDS, "the h2-word output forms its two words from the pair");
     // the second buffer is read (residual; training backward: the pre-activation) or written (training forward: the pre-activation)
-    // GELU_KEEP_BF16 (gemm_b1 only): GELU_KEEP whose C is bf16 [M, N] -- ldc counts bf16 elements, N and ldc are even; NONE_BF16
-    // (gemm_b1 only): the plain result as bf16 in the same way
-    constexpr bool KEEPS = EPI == EPI_GELU_KEEP || EPI == EPI_GELU_KEEP_BF16, C_BF16 = EPI == EPI_GELU_KEEP_BF16 || EPI == EPI_NONE_BF16;
+    // GELU_KEEP_BF16 (gemm_b1 only): GELU_KEEP whose C is bf16 [M, N] -- ldc counts bf16 elements, N and ldc are even; NONE_BF16 and
+    // GELU_BF16 (gemm_b1 only): the plain result / gelu(v) as bf16 in the same way, no second buffer
+    constexpr bool KEEPS = EPI == EPI_GELU_KEEP || EPI == EPI_GELU_KEEP_BF16, GELUS = EPI == EPI_GELU || EPI == EPI_GELU_BF16 || KEEPS;
+    constexpr bool C_BF16 = EPI == EPI_GELU_KEEP_BF16 || EPI == EPI_NONE_BF16 || EPI == EPI_GELU_BF16;
     constexpr bool USES_R = EPI == EPI_RESIDUAL || KEEPS || EPI == EPI_GELU_GRAD;
     constexpr bool LOADS_R = EPI == EPI_RESIDUAL || EPI == EPI_GELU_GRAD;
     constexpr int C_SZ = C_BF16 ? 2 : 4;
@@ -86,7 +87,7 @@
                                                                   ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr + j * 32) * 4, 0);
                         }
                     }
-                    if (EPI == EPI_GELU || KEEPS) v2 = gelu_new2(v2);
+                    if (GELUS) v2 = gelu_new2(v2);
                     else if (EPI == EPI_RESIDUAL) { v2.x += res[r2]; v2.y += res[r2 + 1]; }
                     else if (EPI == EPI_GELU_GRAD) { v2.x *= gelu_new_grad(res[r2]); v2.y *= gelu_new_grad(res[r2 + 1]); }
 #ifdef EPILOGUE_SCALE_DIVISOR
@@ -141,7 +142,7 @@
                     float v = EPILOGUE_VALUE(i, j, r) + bias;
                     if (!EPILOGUE_EDGE_PRELOAD && LOADS_R) res[r] = residg[(long long)min(row, g.M - 1) * g.ldr + colc];
                     if (KEEPS && row < g.M && col_ok) const_cast<float*>(residg)[(long long)row * g.ldr + col] = v;
-                    if (EPI == EPI_GELU || KEEPS) v = gelu_new1(v);
+                    if (GELUS) v = gelu_new1(v);
                     else if (EPI == EPI_RESIDUAL) v += res[r];
                     else if (EPI == EPI_GELU_GRAD) v *= gelu_new_grad(res[r]);
 #ifdef EPILOGUE_SCALE_DIVISOR

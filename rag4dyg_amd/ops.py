@@ -256,9 +256,11 @@ def encode_precision():
     q | k | v and the attention output travel as bf16 between their producers and consumers); where that kernel does not serve a
     shape the block takes the "bf16" route.
     ``R4D_ENCODE_PRECISION=bf16`` (read once, at the first call) or :func:`set_encode_precision` select it.  Process-wide: the
-    ranks of a sharded job must agree."""
+    ranks of a sharded job must agree.  (The first call also resolves :func:`encode_act_store`, which applies to the same entries.)"""
     if _ENCODE_PRECISION is None:
         set_encode_precision(resolve_encode_precision())
+    if _ENCODE_ACT_STORE is None:
+        encode_act_store()
     return _ENCODE_PRECISION
 
 
@@ -273,6 +275,45 @@ def set_encode_precision(precision):
     _lib.load().r4d_set_encode_bf16(gemms)
     _lib.load().r4d_set_encode_attention_bf16(attn)
     _ENCODE_PRECISION = precision
+    return prev
+
+
+_ENCODE_ACT_STORES = {"fp32": 0, "bf16": 1}                                     # word -> r4d_set_encode_act_bf16
+_ENCODE_ACT_STORE = None
+
+
+def resolve_encode_act_store(store=None):
+    """``"fp32"`` or ``"bf16"``.  None -> the environment variable ``R4D_ENCODE_ACT_STORE``, ``fp32`` when it is unset or empty.
+    Anything else raises."""
+    if store is None:
+        import os
+        store = os.environ.get("R4D_ENCODE_ACT_STORE") or "fp32"
+    if store not in _ENCODE_ACT_STORES:
+        raise ValueError(f"encode activation store {store!r}: expected one of {sorted(_ENCODE_ACT_STORES)}")
+    return store
+
+
+def encode_act_store():
+    """How the encoder FORWARD under ``encode_precision()`` "bf16" / "bf16+attn" keeps a block's ln1, ln2 and GELU output between
+    producer and consumer: ``"fp32"`` (default) -- fp32 rows that the bf16 GEMM rounds while staging; ``"bf16"`` -- rounded once where
+    they are produced and stored as bf16 rows the GEMM reads as they are (``r4d_set_encode_act_bf16``): half the bytes, the SAME
+    output bits.  Per buffer, where its GEMMs run on the bf16 kernel and n_embd % 256 == 0; elsewhere that buffer stays fp32.
+    Applies exactly where the precision word applies and does nothing under ``"fp32"`` precision.
+    ``R4D_ENCODE_ACT_STORE=bf16`` (read once, at the first call) or :func:`set_encode_act_store` select it.  Process-wide."""
+    if _ENCODE_ACT_STORE is None:
+        set_encode_act_store(resolve_encode_act_store())
+    return _ENCODE_ACT_STORE
+
+
+def set_encode_act_store(store):
+    """Select :func:`encode_act_store` ("fp32" | "bf16"; anything else raises ValueError and changes nothing).  Returns the
+    previous setting."""
+    global _ENCODE_ACT_STORE
+    if store not in _ENCODE_ACT_STORES:
+        raise ValueError(f"encode activation store {store!r}: expected one of {sorted(_ENCODE_ACT_STORES)}")
+    prev = _ENCODE_ACT_STORE if _ENCODE_ACT_STORE is not None else resolve_encode_act_store()
+    _lib.load().r4d_set_encode_act_bf16(_ENCODE_ACT_STORES[store])
+    _ENCODE_ACT_STORE = store
     return prev
 
 
@@ -392,12 +433,13 @@ def layernorm_bf16(x, w, b, eps=1e-5):
 def conv1d_bf16_act(x_bf16, w_bf16, bias, epilogue="none", residual=None):
     """:func:`conv1d_bf16` / :func:`conv1d_bf16_keep` on an activation that is ALREADY bf16 in memory (``x_bf16`` torch.bfloat16
     [M, K]): the same operand bits, so the same result bits as on the fp32 activation it was rounded from.  ``epilogue``: "none" ->
-    y fp32; "residual" -> y = residual + ...; "gelu_keep" -> (pre fp32, y torch.bfloat16 = RN(gelu_new(pre)))."""
+    y fp32; "residual" -> y = residual + ...; "gelu_keep" -> (pre fp32, y torch.bfloat16 = RN(gelu_new(pre))); the encoder's
+    (:func:`encode_act_store`) "gelu" -> y torch.bfloat16 = RN(gelu_new(v)), no pre-activation kept; "none_bf16" -> y torch.bfloat16 = RN(v)."""
     N, K = w_bf16.shape
     M = x_bf16.numel() // K
-    kind = {"none": 0, "residual": 1, "gelu_keep": 2}[epilogue]
+    kind = {"none": 0, "residual": 1, "gelu_keep": 2, "gelu": 3, "none_bf16": 4}[epilogue]
     dev = x_bf16.device
-    y = torch.empty(x_bf16.shape[:-1] + (N,), dtype=torch.bfloat16 if kind == 2 else torch.float32, device=dev)
+    y = torch.empty(x_bf16.shape[:-1] + (N,), dtype=torch.bfloat16 if kind >= 2 else torch.float32, device=dev)
     second = None
     if kind == 1:
         second = residual

@@ -202,12 +202,12 @@ def pool():
 
 
 def _alternate(arms, run, rounds=5):
-    """``arms``: name -> (encode precision, gemm mode); ``run()`` -> (seconds of device time, units of work).  Every arm in every
-    round, round after round; -> name -> list of rates."""
+    """``arms``: name -> (encode precision, gemm mode[, encode activation store, default "fp32"]); ``run()`` -> (seconds of device
+    time, units of work).  Every arm in every round, round after round; -> name -> list of rates."""
     out = {n: [] for n in arms}
     for _ in range(rounds):
-        for n, (prec, mode) in arms.items():
-            ops.set_encode_precision(prec); ops.set_gemm_mode(mode)
+        for n, (prec, mode, *store) in arms.items():
+            ops.set_encode_precision(prec); ops.set_gemm_mode(mode); ops.set_encode_act_store(store[0] if store else "fp32")
             el, work = run()
             out[n].append(work / el)
     return out
@@ -221,15 +221,18 @@ def encode_precision():
     tokens/s, wall clock around a synchronised batch loop;
     (c) recorded, not gated: the bf16 top-10 lists on the real UCI_13 (G4) and wikiv2 (G12) fixtures against the golden lists;
     (d) the attention kernels alone (``attention_alone``).
-    The "bf16+attn" arm's baseline is the "bf16" arm of the SAME run: the third word touches neither its kernels nor its routing."""
+    The "bf16+attn" arm's baseline is the "bf16" arm of the SAME run: the third word touches neither its kernels nor its routing.
+    The arms "bf16 | act" and "bf16+attn | act" are those two words with ``ops.set_encode_act_store("bf16")`` (ln1 / ln2 / the GELU
+    output stored as bf16: the same bits); THEIR baseline is the same word's store-off arm of the same run, in (a) and (b)."""
     import statistics
     from bench import build_model
     from oracle import gpt2_ref
     from rag4dyg_amd.evaluation import greedy_decode_batch
     from rag4dyg_amd.gpt2 import GPT2Config, GPT2LMHeadModel, GPT2LMHeadModelRAG
     from rag4dyg_amd.retrieval import PoolIndex, encode_batches, right_pad_batches
-    was = (ops.encode_precision(), ops.gemm_mode())
-    arms = {"bf16": ("bf16", "f16x2"), "bf16+attn": ("bf16+attn", "f16x2"), "f16x2": ("fp32", "f16x2"), "bf16x3": ("fp32", "bf16x3")}
+    was = (ops.encode_precision(), ops.gemm_mode(), ops.encode_act_store())
+    arms = {"bf16": ("bf16", "f16x2"), "bf16 | act": ("bf16", "f16x2", "bf16"), "bf16+attn": ("bf16+attn", "f16x2"),
+            "bf16+attn | act": ("bf16+attn", "f16x2", "bf16"), "f16x2": ("fp32", "f16x2"), "bf16x3": ("fp32", "bf16x3")}
     med = lambda v: statistics.median(v)
     try:
         for name in ("UCI_13", "wikiv2"):
@@ -251,7 +254,7 @@ def encode_precision():
                 return a.elapsed_time(b) * 1e-3, 10.0
             rates = _alternate(arms, run)
             ms = {n: [1e3 / r for r in v] for n, v in rates.items()}
-            ops.set_encode_precision("bf16"); ops.set_gemm_mode("f16x2")
+            ops.set_encode_precision("bf16"); ops.set_gemm_mode("f16x2"); ops.set_encode_act_store("fp32")
             _wall, classes = profile(lambda: m.encode_groups_meanpool(groups[2]), 5)
             ops.set_encode_precision("bf16+attn")
             _wall, classes_attn = profile(lambda: m.encode_groups_meanpool(groups[2]), 5)
@@ -260,6 +263,7 @@ def encode_precision():
                  ms_per_step={n: round(med(v), 3) for n, v in ms.items()}, ms_min_max={n: [round(min(v), 3), round(max(v), 3)] for n, v in ms.items()},
                  bf16_over_f16x2=round(med(ms["bf16"]) / med(ms["f16x2"]), 3), bf16_over_bf16x3=round(med(ms["bf16"]) / med(ms["bf16x3"]), 3),
                  bf16attn_over_bf16=round(med(ms["bf16+attn"]) / med(ms["bf16"]), 3),
+                 act_over_off={n: round(med(ms[n + " | act"]) / med(ms[n]), 3) for n in ("bf16", "bf16+attn")},
                  attention_share_of_kernel_time={"bf16": share(classes, "attn_fused"), "bf16+attn": share(classes_attn, "attn_b1")},
                  bf16_arm_classes={k: dict(us=round(v["us"], 1), launches=v["launches"]) for k, v in classes.items()},
                  bf16attn_arm_classes={k: dict(us=round(v["us"], 1), launches=v["launches"]) for k, v in classes_attn.items()})
@@ -285,7 +289,8 @@ def encode_precision():
         tps = _alternate(arms, run_decode, rounds=3)
         emit(component="val_decode", shape="UCI_13", model=f"L{L} H{H} d{d} V{V}", prompts=len(prompts), batch=32,
              mean_prompt_len=round(float(np.mean([len(p) for p in prompts])), 1),
-             tokens_per_s={n: round(med(v), 1) for n, v in tps.items()}, tokens_per_s_min_max={n: [round(min(v), 1), round(max(v), 1)] for n, v in tps.items()})
+             tokens_per_s={n: round(med(v), 1) for n, v in tps.items()},
+             act_over_off={n: round(med(tps[n + " | act"]) / med(tps[n]), 3) for n in ("bf16", "bf16+attn")}, tokens_per_s_min_max={n: [round(min(v), 1), round(max(v), 1)] for n, v in tps.items()})
         # (c) real-data retrieval under bf16 against the golden top-10 lists
         gold = os.path.join(REPO, "tests", "golden")
         unrag = lambda flat, off: [flat[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)]
@@ -301,7 +306,10 @@ def encode_precision():
             m = m.to(dev).eval()
             pad = int(k["pad_id"])
             res = {}
-            for n, (prec, mode) in arms.items():
+            ops.set_encode_act_store("fp32")
+            for n, (prec, mode, *store) in arms.items():
+                if store:                                                # the same bits as the store-off arm (tests/test_gpu_encode_bf16_act.py)
+                    continue
                 ops.set_encode_precision(prec); ops.set_gemm_mode(mode)
                 pool = encode_batches(m, right_pad_batches(unrag(k["pool_flat"], k["pool_off"]), 32, pad, dev))
                 q = encode_batches(m, right_pad_batches(unrag(k["test_flat"], k["test_off"]), 32, pad, dev))
@@ -312,7 +320,7 @@ def encode_precision():
             emit(component="retrieval_top10_vs_golden", fixture=fixture, queries=int(ref10.shape[0]), pool=int(len(k["pool_off"]) - 1), **res)
         attention_alone()
     finally:
-        ops.set_encode_precision(was[0]); ops.set_gemm_mode(was[1])
+        ops.set_encode_precision(was[0]); ops.set_gemm_mode(was[1]); ops.set_encode_act_store(was[2])
 
 
 def attention_alone():
@@ -351,18 +359,19 @@ def attention_alone():
                  fp32_qkv_over_exact=round(med["bf16_attn_fp32_qkv"] / med["exact_f32"], 3))
 
 
-def encode_step_trace(word="bf16", shape_name="UCI_13"):
-    """12 encode steps of the bench shape under ``word`` (gemm mode f16x2), nothing else on the device: for a kernel trace."""
+def encode_step_trace(word="bf16", shape_name="UCI_13", store="fp32"):
+    """12 encode steps of the bench shape under ``word`` (gemm mode f16x2) and the activation ``store``, nothing else on the
+    device: for a kernel trace."""
     from bench import build_model
     from rag4dyg_amd.retrieval import right_pad_batches
     shape = synth.SHAPES[shape_name]
     m = build_model(shape, dev)
     qb = right_pad_batches(synth.sequences(shape, 32 * 96, "query", seed=9000), 32, shape.pad_id, dev)
-    ops.set_encode_precision(word); ops.set_gemm_mode("f16x2")
+    ops.set_encode_precision(word); ops.set_gemm_mode("f16x2"); ops.set_encode_act_store(store)
     for i in range(0, len(qb), 8):
         m.encode_groups_meanpool(qb[i:i + 8])
     torch.cuda.synchronize()
-    emit(component="encode_step_trace", word=word, shape=shape_name, steps=len(qb) // 8)
+    emit(component="encode_step_trace", word=word, store=store, shape=shape_name, steps=len(qb) // 8)
 
 
 def generator(shape_name="UCI_13", L=6, H=8, d=768, topk=7, pool_n=512):
@@ -631,7 +640,7 @@ if __name__ == "__main__":
             training = functools.partial(training, **{axis.key: sys.argv[i + 1]})
             del sys.argv[i:i + 2]
     if sys.argv[1:2] == ["encode_step_trace"]:                                    # takes its word (and shape) as arguments
-        encode_step_trace(*sys.argv[2:4])
+        encode_step_trace(*sys.argv[2:5])
         sys.exit(0)
     for part in (sys.argv[1:] or ["scan", "topk", "jaccard", "jaccard_cpu", "pool", "generator", "generator_reddit", "simpledyg", "training", "training_cpu"]):
         {"scan": scan, "topk": topk, "topk_large": topk_large, "jaccard": jaccard, "jaccard_cpu": jaccard_cpu_all_cores, "pool": pool, "encode_precision": encode_precision, "attention_alone": attention_alone, "encode_step_trace": encode_step_trace, "generator": generator,
