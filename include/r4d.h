@@ -375,6 +375,26 @@ int r4d_conv1d_h2_f32(const float* x_d, const uint16_t* planes_d, const float* b
  * r4d_gpt2_layer's c_attn_wTg / c_attn_lnc (with ln_1) and c_fc_wTg / c_fc_lnc (with ln_2).  Once per checkpoint. */
 int r4d_fold_layernorm_f32(const float* wT_d, const float* ln_w_d, const float* ln_b_d, int32_t N, int32_t K, float* wTg_d,
                            float* lnc_d, void* stream);
+/* The weight-stream GEMM of the cached decode step and of the greedy loop's LM head, alone (additive ABI v6 entries;
+ * csrc/gemm_skinny.hip): y[M,N] = epilogue(x'[M,K] . wT[N,K]^T + bias), 1 <= M <= 32 rows, K a multiple of 256, N >= 1, wT_d the
+ * k-contiguous weight; epilogue as r4d_conv1d_f32 (residual_d with epilogue 2 and only with it; y_d may be residual_d).  The entry
+ * launches what the decode step launches for the same arguments -- the kernel form follows K, N and the tuning word R4D_SKINNY16
+ *  -- and adds no route.
+ *   x' = x, or LayerNorm(x) in one of two forms, both for K = 512 or 768 only: ln_w_d / ln_b_d [K] (both or neither) -- the
+ *   LayerNorm is formed in the launch; ln_fold_d [2][N] -- wT_d is the FOLDED weight and ln_fold_d its column constants, both from
+ *   r4d_fold_layernorm_f32 (16-column kernels only: refused under R4D_SKINNY16=0).  The two forms exclude each other; a folded
+ *   LayerNorm may carry a residual.
+ *   workspace_d: r4d_conv1d_skinny_workspace_bytes(K, N) = 4 * (ceil(K / 256) * 32 * N + 256) bytes (0 for an unsupported K or N).  Its
+ *   first 256 words are the split-K tickets: counters_zeroed = 0 -- the entry clears them where the chosen form reads them;
+ *   counters_zeroed != 0 -- the caller promises that they are zero (a completed launch leaves them zero).  Nothing else in the
+ *   workspace is read before it is written.
+ * Only rows 0 .. M-1 of y_d are written.  x_d, wT_d, ln_w_d and ln_b_d 16-byte aligned.  R4D_ERR_INVALID for anything else above,
+ * R4D_ERR_WORKSPACE for a short workspace; nothing is launched in either case. */
+size_t r4d_conv1d_skinny_workspace_bytes(int32_t K, int32_t N);
+int r4d_conv1d_skinny_f32(const float* x_d, const float* wT_d /* [N,K] */, const float* bias_d, const float* residual_d, int32_t M,
+                          int32_t K, int32_t N, int32_t epilogue, const float* ln_w_d, const float* ln_b_d, float ln_eps,
+                          const float* ln_fold_d, int32_t counters_zeroed, float* y_d, void* workspace_d, size_t workspace_bytes,
+                          void* stream);
 int r4d_set_gemm_split3(int32_t mode);
 int r4d_get_gemm_split3(void);
 /*

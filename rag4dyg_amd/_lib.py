@@ -106,6 +106,9 @@ PROTOTYPES = {
     "r4d_split2_planes_f16": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P]),
     "r4d_conv1d_h2_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "r4d_fold_layernorm_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, _P, _P, _P]),
+    "r4d_conv1d_skinny_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "r4d_conv1d_skinny_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_float, _P, c_int32, _P, _P,
+                                        c_size_t, _P]),
     "r4d_set_gemm_split3": (c_int32, [c_int32]),
     "r4d_get_gemm_split3": (c_int32, []),
     "r4d_conv1d_bf16_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),

@@ -197,6 +197,31 @@ int r4d_fold_layernorm_f32(const float* wT_d, const float* ln_w_d, const float* 
                            float* lnc_d, void* stream) {
     return launch_fold_layernorm(wT_d, ln_w_d, ln_b_d, N, K, wTg_d, lnc_d, (hipStream_t)stream);
 }
+// The decode step's weight-stream GEMM alone (gemm_skinny.hip): every check that launch_gemm_skinny leaves to its callers,
+// then launch_gemm_skinny itself -- the same kernels, chosen the same way
+size_t r4d_conv1d_skinny_workspace_bytes(int32_t K, int32_t N) {
+    return gemm_skinny_supported(1, K, N) ? sizeof(float) * gemm_skinny_scratch_floats(K, N) : 0;
+}
+int r4d_conv1d_skinny_f32(const float* x_d, const float* wT_d, const float* bias_d, const float* residual_d, int32_t M, int32_t K,
+                          int32_t N, int32_t epilogue, const float* ln_w_d, const float* ln_b_d, float ln_eps, const float* ln_fold_d,
+                          int32_t counters_zeroed, float* y_d, void* workspace_d, size_t workspace_bytes, void* stream) {
+    R4D_REQUIRE(gemm_skinny_supported(M, K, N), "conv1d_skinny: unsupported shape M=%d K=%d N=%d (1 <= M <= 32, K a multiple of 256, N >= 1)",
+                M, K, N);
+    R4D_REQUIRE(x_d && wT_d && y_d && workspace_d, "conv1d_skinny: null pointer");
+    R4D_REQUIRE(((uintptr_t)x_d % 16) == 0 && ((uintptr_t)wT_d % 16) == 0, "conv1d_skinny: x and wT must be 16-byte aligned");
+    R4D_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU || epilogue == EPI_RESIDUAL, "conv1d_skinny: epilogue=%d", epilogue);
+    R4D_REQUIRE((epilogue == EPI_RESIDUAL) == (residual_d != nullptr), "conv1d_skinny: a residual goes with epilogue 2 and only with it");
+    R4D_REQUIRE((ln_w_d != nullptr) == (ln_b_d != nullptr), "conv1d_skinny: ln_w and ln_b come together");
+    R4D_REQUIRE(!ln_fold_d || !ln_w_d, "conv1d_skinny: a folded LayerNorm (ln_fold) and a per-launch one (ln_w, ln_b) exclude each other");
+    R4D_REQUIRE((!ln_w_d && !ln_fold_d) || gemm_skinny_fuses_ln(M, K, N), "conv1d_skinny: LayerNorm needs K = 512 or 768, got K=%d", K);
+    R4D_REQUIRE(((uintptr_t)ln_w_d % 16) == 0 && ((uintptr_t)ln_b_d % 16) == 0, "conv1d_skinny: ln_w and ln_b must be 16-byte aligned");
+    if (workspace_bytes < r4d_conv1d_skinny_workspace_bytes(K, N)) {
+        set_error("conv1d_skinny: workspace too small (%zu < %zu bytes)", workspace_bytes, r4d_conv1d_skinny_workspace_bytes(K, N));
+        return R4D_ERR_WORKSPACE;
+    }
+    return launch_gemm_skinny(x_d, wT_d, bias_d, residual_d, M, K, N, epilogue, y_d, (float*)workspace_d, (hipStream_t)stream, ln_w_d,
+                              ln_b_d, ln_eps, counters_zeroed != 0, ln_fold_d);
+}
 
 int r4d_set_gemm_split3(int32_t mode) { g_gemm_split3 = mode == 2 ? 2 : (mode != 0); return R4D_OK; }
 int r4d_get_gemm_split3(void) { return g_gemm_split3; }

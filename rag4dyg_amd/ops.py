@@ -217,6 +217,38 @@ def fold_layernorm(wT, ln_w, ln_b):
     return wTg, lnc
 
 
+def conv1d_skinny_workspace(K, N):
+    """Bytes of the workspace :func:`conv1d_skinny` needs for a [N,K] weight (0 where the kernels do not serve K or N)."""
+    return int(_lib.load().r4d_conv1d_skinny_workspace_bytes(int(K), int(N)))
+
+
+def conv1d_skinny(x, wT, bias=None, epilogue="none", residual=None, ln=None, ln_fold=None, eps=1e-5, counters_zeroed=False,
+                  out=None, ws=None):
+    """The decode step's weight-stream GEMM alone (``csrc/gemm_skinny.hip``): y = epilogue(x' @ wT^T + bias) for 1 .. 32 rows ``x``
+    [M,K], ``wT`` [N,K], K a multiple of 256.  ``ln`` = (gain, shift): x' = LayerNorm(x), formed in the launch; ``ln_fold`` = the
+    ``lnc`` of :func:`fold_layernorm`, ``wT`` then being its ``wTg`` (both K = 512 or 768 only).  ``out``: a float32 tensor whose first
+    M * N elements receive y (it may be ``residual``); ``ws``: a uint8 workspace of :func:`conv1d_skinny_workspace` bytes whose first
+    1024 bytes the caller has zeroed if ``counters_zeroed``.  Both are allocated here when None."""
+    N, K = wT.shape
+    M = x.numel() // K
+    epi = {"none": 0, "gelu": 1, "residual": 2}[epilogue]
+    if out is None:
+        out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
+    elif out.numel() < M * N:
+        raise _lib.R4DError(f"conv1d_skinny: out holds {out.numel()} elements, fewer than M * N = {M * N}")
+    if ws is None:
+        ws = workspace(conv1d_skinny_workspace(K, N), x.device, "conv1d_skinny")
+        counters_zeroed = False
+    rp = _dev(residual, torch.float32, "residual") if residual is not None else None
+    bp = _dev(bias, torch.float32, "bias") if bias is not None else None
+    gp, sp = (_dev(ln[0], torch.float32, "ln gain"), _dev(ln[1], torch.float32, "ln shift")) if ln is not None else (None, None)
+    fp = _dev(ln_fold, torch.float32, "ln_fold") if ln_fold is not None else None
+    check(_lib.load().r4d_conv1d_skinny_f32(_dev(x, torch.float32, "x"), _dev(wT, torch.float32, "wT"), bp, rp, M, K, N, epi, gp, sp,
+                                            eps, fp, int(bool(counters_zeroed)), _dev(out, torch.float32, "out"),
+                                            _dev(ws, torch.uint8, "ws"), ws.numel(), _stream()), "conv1d_skinny")
+    return out
+
+
 def conv1d_s3(x, planes, bias, epilogue="none", residual=None):
     """:func:`conv1d` on the bf16 matrix cores at fp32 accuracy (three-way bf16 split of both operands, six partial
     products, fp32 accumulation); ``planes`` from :func:`split3_planes`."""
