@@ -97,16 +97,10 @@ PACKED_F32_FORMS = {
 }
 
 
-def check_packed_f32_forms(src):
+def check_packed_f32_forms(src, text=None):
     import re
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        asm = os.path.join(td, "k.s")
-        r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "--offload-device-only", "-S", src, "-o", asm],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc -S failed for {src}:\n{r.stderr}")
-        text = open(asm).read()
+    if text is None:
+        text = _assembly(src)
     seen = {}
     for ln in re.findall(r"^\s*(v_pk_(?:fma|mul|add)_f32 [^\n;]*)", text, re.M):
         if not re.search(r"\bs\[?\d", ln):
@@ -121,6 +115,46 @@ def check_packed_f32_forms(src):
     return seen
 
 
+# The inline asm of csrc/h2.h (v_fma_mixlo_f16 / v_fma_mixhi_f16).  The compiler inserts gfx950's wait states between instructions it
+# knows and does not look inside inline asm, so h2.h lets its asm read only results of plain VALU instructions.  This check makes
+# the convention a guard, on the assembly of every file that inlines the split: no transcendental instruction that writes a source
+# of a v_fma_mix* directly in front of it (one wait state wanted), no DPP read of its result within the next two instructions.
+H2_ASM_FILES = ("gemm_h2.hip", "gemm_h2p.hip", "attention_h2.hip", "encoder_ops.hip")
+TRANS_OPS = ("v_exp_", "v_log_", "v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_")
+
+
+def check_h2_asm_neighbours(text, name):
+    import re
+    ins = [ln.strip() for ln in text.split("\n") if re.match(r"\s+[a-z]", ln) and not ln.strip().startswith(".")]
+    regs = lambda tok: set(re.findall(r"\bv\d+\b", tok)) | {f"v{i}" for a, b in re.findall(r"v\[(\d+):(\d+)\]", tok) for i in range(int(a), int(b) + 1)}
+    bad = []
+    for i, ln in enumerate(ins):
+        if not ln.startswith("v_fma_mix"):
+            continue
+        ops = ln.split(None, 1)[1].split(",")
+        dst, srcs = regs(ops[0]), regs(",".join(ops[1:]))
+        if i and ins[i - 1].startswith(TRANS_OPS) and regs(ins[i - 1].split(None, 1)[1].split(",")[0]) & srcs:
+            bad.append((ins[i - 1], ln))
+        for nxt in ins[i + 1:i + 3]:
+            if "dpp" in nxt and regs(",".join(nxt.split(None, 1)[1].split(",")[1:])) & dst:
+                bad.append((ln, nxt))
+    if bad:
+        raise RuntimeError(f"h2.h asm check FAILED for {name}: an inline-asm v_fma_mix* stands where the compiler inserts no wait states: "
+                           f"{bad[:4]} -- let the asm read the result of a plain VALU instruction (csrc/h2.h)")
+    return sum(1 for ln in ins if ln.startswith("v_fma_mix"))
+
+
+def _assembly(src):
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        asm = os.path.join(td, "k.s")
+        r = subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "--offload-device-only", "-S", src, "-o", asm],
+                           capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc -S failed for {src}:\n{r.stderr}")
+        return open(asm).read()
+
+
 def build_library(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     hdr_m = _deps_mtime()
@@ -130,8 +164,14 @@ def build_library(force=False, verbose=True):
     for src, (_o, compiled) in zip(sources(), res):
         if compiled and os.path.basename(src) in HANDOFF_KERNELS:
             check_handoff_lowering(src)
-        if compiled and os.path.basename(src) in PACKED_F32_FILES:
-            check_packed_f32_forms(src)
+    # one assembly listing per file that a census reads, four compiles side by side, and only for files compiled in this run
+    todo = [src for src, (_o, compiled) in zip(sources(), res) if compiled and os.path.basename(src) in PACKED_F32_FILES + H2_ASM_FILES]
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        for src, text in zip(todo, ex.map(_assembly, todo)):
+            if os.path.basename(src) in PACKED_F32_FILES:
+                check_packed_f32_forms(src, text)
+            if os.path.basename(src) in H2_ASM_FILES:
+                check_h2_asm_neighbours(text, os.path.basename(src))
     # (also when an earlier run compiled objects but stopped before the link, e.g. on a failed hand-off check)
     stale = os.path.exists(LIB) and any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs)
     if force or stale or any(c for _, c in res) or not os.path.exists(LIB):

@@ -8,6 +8,11 @@
     constexpr int NBUF = 3;
     constexpr int NGA = BM / 8 / NW, NGB = BN / 8 / NW;               // 8-row groups per wavefront and k-tile: 2 of A, 4 (2) of W with 8 wavefronts
     constexpr int NDMA = NGA + NGB;
+    // a lane owns two neighbouring columns: the 128 x 256 tile of gemm_h2p_kernel, every output but the h2 words.  (The h2-word c_attn
+    // was built on the pair mapping too -- 8-byte word stores, the K slot by ONE exchange stage -- and measured no faster per launch,
+    // 312 against 311 us; the row-block map on it did not reproduce the full launch's bits, cause not found: DESIGN_LOG 12.30.  Both
+    // keep one column per lane)
+    constexpr bool PAIRS = TN == 2 && !ROWMAP && EPI != EPI_H2WORDS;
     static_assert(BM == 128 && (BN == 256 || BN == 128) && TM >= 1 && TN >= 1 && (NGA == 2 || NGA == 4) && (NGB == 2 || NGB == 4 || NGB == 8), "tile");
     __shared__ u32x4 lds[NBUF * STAGE];
 
@@ -46,8 +51,11 @@
     }
 #pragma unroll
     for (int i = 0; i < NGB; ++i) {
-        const int r = (wid * NGB + i) * 8 + lrow;                     // row of the W tile
-        vb[i] = (unsigned)min(n0 + r, g.N - 1) * (unsigned)(g.K * 4) + 16u * (unsigned)(lslot ^ ((r >> 1) & 7)) + 3072u - 1024u * (i & 3);
+        const int r = (wid * NGB + i) * 8 + lrow;                     // row of the W tile's LDS image
+        // PAIRS: image row 64a + 32j + l holds W row 64a + 2l + j, so that lane l of accumulator tiles j = 0 / 1 holds the
+        // NEIGHBOURING columns 2l, 2l + 1.  Only the source moves: the image, the swizzle and every sum stay what they were
+        const int rs = PAIRS ? (r & ~63) + 2 * (r & 31) + ((r >> 5) & 1) : r;
+        vb[i] = (unsigned)min(n0 + rs, g.N - 1) * (unsigned)(g.K * 4) + 16u * (unsigned)(lslot ^ ((r >> 1) & 7)) + 3072u - 1024u * (i & 3);
     }
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds);
     const unsigned wid_s = __builtin_amdgcn_readfirstlane((unsigned)wid);     // wave-uniform: the DMA destinations live in SGPRs (M0)
@@ -173,6 +181,45 @@
         static_assert(EPI == EPI_GELU, "line output: the c_fc epilogue only");
         unsigned char* __restrict__ L = reinterpret_cast<unsigned char*>(Cg);
         const long long row_bytes = (long long)g.N * 4;              // N/32 lines of 128 bytes
+        if constexpr (PAIRS) {
+            // PAIRS: the lane holds columns (2 li, 2 li + 1) of the wave's 64 in tiles j = 0 / 1 -- one packed word of a line for each of
+            // its 32 rows, no exchange.  The value arithmetic and the GELU stay packed over ROW pairs of one tile (adjacent
+            // registers), and so do the two scalings of the split; only v_cvt_pk and the two mix instructions take their sources
+            // from both tiles (split2_vq).  Stores through a descriptor: lane offset once, the row on the scalar unit
+            const int colp = n0 + wn * WN + 2 * li;
+            const bool col_ok = colp < g.N;                           // (N % 32 == 0: both columns or none)
+            const float bias0 = (biasg && col_ok) ? biasg[colp] : 0.f, bias1 = (biasg && col_ok) ? biasg[colp + 1] : 0.f;
+            const int rows_in = min(BM, g.M - m0), cols_in = min(BN, g.N - n0);
+            const __amdgpu_buffer_rsrc_t l_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                L + (long long)m0 * row_bytes + (long long)n0 * 4, 0, ((rows_in - 1) * g.N + cols_in) * 4, 0x00020000);
+            const int lane_l = (wm * WM + 4 * lh) * (g.N * 4) + (wn * (WN / 32) + (li >> 4)) * 128 + (li & 15) * 4;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                for (int r2 = 0; r2 < 16; r2 += 2) {
+                    f32x2 va2 = {__builtin_fmaf(acc1[i][0][r2], H2_LO_UNSCALE, acc0[i][0][r2]) * UNS + bias0,
+                                 __builtin_fmaf(acc1[i][0][r2 + 1], H2_LO_UNSCALE, acc0[i][0][r2 + 1]) * UNS + bias0};
+                    f32x2 vb2 = {__builtin_fmaf(acc1[i][1][r2], H2_LO_UNSCALE, acc0[i][1][r2]) * UNS + bias1,
+                                 __builtin_fmaf(acc1[i][1][r2 + 1], H2_LO_UNSCALE, acc0[i][1][r2 + 1]) * UNS + bias1};
+                    va2 = gelu_new2(va2);
+                    vb2 = gelu_new2(vb2);
+                    const f32x2 sa = va2 * H2_A_PRESCALE, sb = vb2 * H2_A_PRESCALE;
+                    const f32x2 qa = va2 * (H2_A_PRESCALE * H2_LO_SCALE), qb = vb2 * (H2_A_PRESCALE * H2_LO_SCALE);
+                    unsigned h[2], l[2];
+                    split2_vq(sa.x, sb.x, qa.x, qb.x, h[0], l[0]);   // row r2
+                    split2_vq(sa.y, sb.y, qa.y, qb.y, h[1], l[1]);   // row r2 + 1
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const int rr = i * 32 + ((r2 + t) & 3) + 8 * ((r2 + t) >> 2);      // row of the wave tile, less 4 lh
+                        if (interior || (m0 + wm * WM + rr + 4 * lh < g.M && col_ok)) {
+                            __builtin_amdgcn_raw_buffer_store_b32(h[t], l_rsrc, lane_l, rr * (g.N * 4), 0);
+                            __builtin_amdgcn_raw_buffer_store_b32(l[t], l_rsrc, lane_l + 64, rr * (g.N * 4), 0);     // the lo' half of the line
+                        }
+                    }
+                }
+            }
+            return;
+        }
         const bool odd = li & 1;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -204,7 +251,55 @@
         }
         return;
     } else {
-        if (interior) {
+        if constexpr (PAIRS) {
+            // PAIRS: the lane holds columns (2 li, 2 li + 1) of the wave's 64 in tiles j = 0 / 1 for each of its 32 rows: 8-byte stores
+            // and residual loads, half as many instructions, each still whole lines (residual launch 266 -> 262 us in the bench
+            // step).  An odd row stride takes the element-wise path below (the 8-byte accesses need dword alignment only, which
+            // every shape has; with even strides they are 8-byte aligned wherever the base pointers are)
+            if (interior && ((g.ldc | (EPI == EPI_RESIDUAL ? g.ldr : 0)) & 1) == 0) {
+                const int cb = n0 + wn * WN;
+                const int lane_c = ((wm * WM + 4 * lh) * g.ldc + wn * WN + 2 * li) * 4;
+                const int lane_r = ((wm * WM + 4 * lh) * g.ldr + wn * WN + 2 * li) * 4;
+                const __amdgpu_buffer_rsrc_t c_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                    C + (long long)m0 * g.ldc + n0, 0, ((BM - 1) * g.ldc + BN) * 4, 0x00020000);
+                const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                    const_cast<float*>(EPI == EPI_RESIDUAL ? residg + (long long)m0 * g.ldr + n0 : Cg), 0,
+                    EPI == EPI_RESIDUAL ? ((BM - 1) * g.ldr + BN) * 4 : 0, 0x00020000);
+                const float bias0 = biasg ? biasg[cb + 2 * li] : 0.f, bias1 = biasg ? biasg[cb + 2 * li + 1] : 0.f;
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    u32x2 res[16];
+                    if (EPI == EPI_RESIDUAL) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            res[r] = __builtin_amdgcn_raw_buffer_load_b64(r_rsrc, lane_r, ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldr) * 4, 0);
+                    }
+                    unsigned o[2][16];
+#pragma unroll
+                    for (int r2 = 0; r2 < 16; r2 += 2) {
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const float bias = j ? bias1 : bias0;
+                            f32x2 v2 = {__builtin_fmaf(acc1[i][j][r2], H2_LO_UNSCALE, acc0[i][j][r2]) * UNS + bias,
+                                         __builtin_fmaf(acc1[i][j][r2 + 1], H2_LO_UNSCALE, acc0[i][j][r2 + 1]) * UNS + bias};
+                            if (EPI == EPI_GELU) v2 = gelu_new2(v2);
+                            else if (EPI == EPI_RESIDUAL) {
+                                v2.x += __builtin_bit_cast(float, j ? res[r2].y : res[r2].x);
+                                v2.y += __builtin_bit_cast(float, j ? res[r2 + 1].y : res[r2 + 1].x);
+                            }
+                            const float vx = v2.x, vy = v2.y;     // (copies first: __builtin_bit_cast on an ext-vector ELEMENT reads element 0)
+                            o[j][r2] = __builtin_bit_cast(unsigned int, vx); o[j][r2 + 1] = __builtin_bit_cast(unsigned int, vy);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const u32x2 w = {o[0][r], o[1][r]};
+                        __builtin_amdgcn_raw_buffer_store_b64(w, c_rsrc, lane_c, ((i * 32 + (r & 3) + 8 * (r >> 2)) * g.ldc) * 4, 0);
+                    }
+                }
+                return;
+            }
+        } else if (interior) {
             // ROWMAP: the (wm, i) MFMA tile is ONE listed block: its rows start at that block's first global row (a scalar offset),
             // the resource spans every row
             const int lane_c = (((ROWMAP ? 0 : wm * WM) + 4 * lh) * g.ldc + wn * WN + li) * 4;
@@ -288,7 +383,7 @@
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {                                   // edge tiles: clamped reads, guarded stores
-            const int col = n0 + wn * WN + j * 32 + li;
+            const int col = n0 + wn * WN + (PAIRS ? 2 * li + j : j * 32 + li);
             const bool col_ok = col < g.N;
             const int colc = min(col, g.N - 1);
             const float bias = biasg ? biasg[colc] : 0.f;
