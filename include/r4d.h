@@ -130,7 +130,8 @@ typedef struct r4d_gpt2_weights {
  *   - the optimizer's m / v and sumsq[0] (r4d_adamw_step_f32, r4d_sumsq_accumulate_f32; sumsq[1..] is scratch);
  *   - a training workspace BETWEEN r4d_gpt2_train_forward*_f32 and the backward of the same step (the saved activations);
  *   - operands described as zero-padded by their entry (the rows of r4d_lm_head.wte_pad past vocab);
- *   - the sticky range-guard word (r4d_set_range_flag) and the greedy loop state (r4d_greedy_state).
+ *   - the sticky range-guard word (r4d_set_range_flag) and the greedy loop state (r4d_greedy_state);
+ *   - the sampled loop state (r4d_sample_state) and the seen bitmap of r4d_sample_logits_f32.
  */
 
 /* Scratch bytes r4d_gpt2_encode_f32 needs for a [B,T] batch. */
@@ -243,6 +244,63 @@ int r4d_gpt2_greedy_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weig
 /* replay it n_steps times on `stream` (asynchronous) */
 int r4d_decode_graph_launch(r4d_decode_graph* graph, int32_t n_steps, void* stream);
 void r4d_decode_graph_destroy(r4d_decode_graph* graph);
+
+/*
+ * Sampled decoding (additive ABI v6 entries): the choice of the next token of the reference's generate()
+ * (models/modeling_utils.py:608-927: enforce_repetition_penalty_, / temperature, top_k_top_p_filtering, multinomial) as ONE
+ * kernel in the greedy bookkeeping kernel's place -- one workgroup per sequence, no hand-off between workgroups.  Per row x[0..V):
+ *   1. repetition penalty r >= 1: for every id whose bit is set in `seen`, x = x < 0 ? x * r : x / r; the chosen id's bit is set
+ *      afterwards (seen_d NULL: no penalty, nothing set);
+ *   2. do_sample == 0: the argmax of the penalised row, lowest index among equal maxima; else
+ *   3. y = x / temperature in fp32 (only when temperature != 1);
+ *   4. top_k > 0: k' = min(max(top_k, 1), V), thr = the k'-th largest y; every y < thr is dropped (ties at thr are all kept);
+ *   5. top_p < 1: the survivors in the order (value descending, index ascending), weights w = exp(y - max); the i-th is kept iff
+ *      i == 0 or the weight of the i before it is <= top_p * (the weight of all survivors);
+ *   6. u = (word >> 8) * 2^-24 in [0, 1), word = the first output of Philox-4x32-10 with counter (step, stream, 0,
+ *      R4D_SAMPLE_PHILOX_SITE) and key (seed_lo, seed_hi); the token is the LOWEST kept index whose inclusive weight prefix in
+ *      INDEX order exceeds u * Z, Z the weight of the kept set.
+ * Weights are summed as 64-bit fixed point (floor(expf(y - max) * 2^40), integer additions): every sum is exact in that unit
+ * and independent of the order it was taken in, so the token depends on (row values, seen bits, parameters, seed, stream, step)
+ * alone -- not on B, on the row's place in the batch, or on a graph replay.  NaN counts as -inf (it is chosen only when no entry
+ * is above -inf); a row without an entry above -inf gives id 0; a row whose maximum is +inf gives the lowest-indexed +inf entry
+ * (for both, the kept set is that one id).  Any V >= 1.
+ *   fparams_d  device float[4]  {temperature > 0, top_p in [0,1], repetition_penalty >= 1, reserved}
+ *   iparams_d  device int32[4]  {do_sample, top_k >= 0, seed_lo, seed_hi}     both read by the kernel at every launch
+ */
+#define R4D_SAMPLE_PHILOX_SITE 0x53414d50u        /* "SAMP" */
+/* The single operation on logits_d [B,V]: step_d, stream_d device int32 [B]; seen_d device uint32 [B, ceil(V/32)] in/out or NULL;
+ * out_token_d device int64 [B]; out_keep_d device uint32 [B, ceil(V/32)] or NULL: bit j%32 of word j/32 = id j is in the kept set
+ * (every word written, bits past V clear; do_sample == 0: the chosen id alone); out_u_d device float [B] or NULL.  No workspace. */
+int r4d_sample_logits_f32(const float* logits_d, int32_t B, int32_t V, uint32_t* seen_d, const int32_t* step_d,
+                          const int32_t* stream_d, const float* fparams_d, const int32_t* iparams_d, int64_t* out_token_d,
+                          uint32_t* out_keep_d, float* out_u_d, void* stream);
+/* The loop state of the sampled step: r4d_greedy_state's fields with its conventions (the step counter of the draw is gen_len_d
+ * BEFORE the step increments it), plus the sampler's own.  Caller state like the greedy one: seen_d is read and updated. */
+typedef struct r4d_sample_state {
+    float* last_d;
+    float* logits_d;
+    int64_t* next_d;
+    int32_t* lens_d;
+    int32_t* pos_d;
+    int32_t* active_d;
+    int32_t* gen_len_d;
+    int32_t* out_tokens_d;
+    const int32_t* params_d;
+    int32_t out_cap;
+    uint32_t* seen_d;          /* device uint32 [B, ceil(V/32)] or NULL */
+    const int32_t* stream_d;   /* device int32 [B] */
+    const float* fparams_d;    /* device float[4], read every step (so one captured graph serves every call) */
+    const int32_t* iparams_d;  /* device int32[4], read every step */
+} r4d_sample_state;
+/* One step = the LM head on the greedy step's route, the choice above, r4d_gpt2_decode_step_f32 on the chosen ids.  The graph is an
+ * r4d_decode_graph: r4d_decode_graph_launch / _destroy serve it. */
+size_t r4d_gpt2_sample_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B);
+int r4d_gpt2_sample_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_sample_state* st,
+                             float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                             void* stream);
+int r4d_gpt2_sample_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_sample_state* st,
+                                 float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                                 r4d_decode_graph** out_graph);
 
 /* lm_logits = hidden @ wte^T  (tied lm_head, modeling_gpt2.py:585; modeling_rag.py:675).
  * hidden_d [M,d], wte_d [V,d] -> logits_d [M,V]. */

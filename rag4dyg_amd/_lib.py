@@ -37,6 +37,10 @@ class GreedyStateC(Structure):
                                          "out_tokens_d", "params_d")] + [("out_cap", c_int32)]
 
 
+class SampleStateC(Structure):                  # r4d_sample_state: the greedy fields, then the sampler's
+    _fields_ = GreedyStateC._fields_ + [(n, c_void_p) for n in ("seen_d", "stream_d", "fparams_d", "iparams_d")]
+
+
 class GPT2LayerGradsC(Structure):
     _fields_ = [(n, c_void_p) for n in ("ln_1_w", "ln_1_b", "c_attn_w", "c_attn_b", "attn_proj_w", "attn_proj_b",
                                          "ln_2_w", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b")]
@@ -98,6 +102,12 @@ PROTOTYPES = {
                                                c_int32, c_int32, _P, c_size_t, POINTER(_P)]),
     "r4d_decode_graph_launch": (c_int32, [_P, c_int32, _P]),
     "r4d_decode_graph_destroy": (None, [_P]),
+    "r4d_sample_logits_f32": (c_int32, [_P, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "r4d_gpt2_sample_workspace_bytes": (c_size_t, [POINTER(GPT2ConfigC), c_int32]),
+    "r4d_gpt2_sample_step_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(SampleStateC), _P, c_int32,
+                                           c_int32, _P, c_size_t, _P]),
+    "r4d_gpt2_sample_graph_create": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(SampleStateC), _P,
+                                               c_int32, c_int32, _P, c_size_t, POINTER(_P)]),
     "r4d_lm_logits_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "r4d_layernorm_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, c_float, _P, _P]),
     "r4d_conv1d_f32": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),

@@ -46,7 +46,7 @@ enum ProfClass {
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
     PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_GEMM_B1H_NT, PK_GEMM_B1H_NN,
-    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_ATTN_B1, PK_COUNT
+    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_ATTN_B1, PK_SAMPLE_ADVANCE, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -94,7 +94,8 @@ struct ProfScope {
     X(TAB_FWD, "tuning:train_act_bf16:fwd") X(TAB_WGRAD, "tuning:train_act_bf16:wgrad") X(TAB_LN, "tuning:train_act_bf16:ln") X(TAB_GELU, "tuning:train_act_bf16:gelu") \
     X(TAF_FWD, "tuning:train_attn_fused:fwd") X(TAF_ROWSUM, "tuning:train_attn_fused:rowsum") X(TAF_DKV, "tuning:train_attn_fused:dkv") X(TAF_DQ, "tuning:train_attn_fused:dq") \
     X(EBA_BF16, "tuning:encode_bf16_attn:bf16 qkv") X(EBA_F32, "tuning:encode_bf16_attn:fp32 qkv, rounded while staged") X(EBA_FALLBACK, "tuning:encode_bf16_attn:fallback to the exact-f32 attention") \
-    X(EAB_LN1, "tuning:encode_act_bf16:ln1") X(EAB_LN2, "tuning:encode_act_bf16:ln2") X(EAB_F, "tuning:encode_act_bf16:f") X(EAB_KEPT_F32, "tuning:encode_act_bf16:kept fp32")
+    X(EAB_LN1, "tuning:encode_act_bf16:ln1") X(EAB_LN2, "tuning:encode_act_bf16:ln2") X(EAB_F, "tuning:encode_act_bf16:f") X(EAB_KEPT_F32, "tuning:encode_act_bf16:kept fp32") \
+    X(SAMPLE_LDS, "tuning:sample:keyed row in LDS") X(SAMPLE_GLOBAL, "tuning:sample:row re-read from memory")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -364,6 +365,18 @@ struct GreedyState {
 // clearing of `n_zero` 32-bit words (the step's split-K ticket counters)
 struct GreedyEmbed { const float* wte; const float* wpe; float* x_out; unsigned* zero_words; int vocab, n_positions, d, n_zero; };
 int launch_greedy_advance(const float* logits, int B, int V, const GreedyState& st, hipStream_t s, const GreedyEmbed* embed = nullptr);
+// sampling.hip: sample_advance_kernel in the greedy kernel's place (repetition penalty, temperature, top-k, top-p, one Philox draw per
+// sequence).  seen (nullable) uint32 [B, ceil(V / 32)]; stream int32 [B]; fpar float[4] {temperature, top_p, repetition_penalty, -};
+// ipar int32[4] {do_sample, top_k, seed_lo, seed_hi}, both read on the device.  With `st` the step counter is st->gen_len and the
+// greedy bookkeeping follows (embed as in launch_greedy_advance); without it `step` int32 [B] counts and out_token int64 [B] is written.
+// out_keep (nullable) uint32 [B, ceil(V / 32)]: the kept set; out_u (nullable) float [B]: the uniform drawn
+struct SampleArgs {
+    unsigned* seen; const int32_t* step; const int32_t* stream; const float* fpar; const int32_t* ipar;
+    int64_t* out_token; unsigned* out_keep; float* out_u;
+};
+int launch_sample_advance(const float* logits, int B, int V, const SampleArgs& sa, const GreedyState* st, hipStream_t s,
+                          const GreedyEmbed* embed = nullptr);
+int sample_advance_prepare();      // the kernel's LDS attribute on the current device (also before a capture)
 // Up to ATT_MAXG right-padded batches (each with its own T) in ONE attention launch: the workgroup index walks the sequences
 // of all batches; the batch of a sequence is found by a short scan of the prefix table (kernel argument, by value).
 struct AttnGroups {

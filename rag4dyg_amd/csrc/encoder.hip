@@ -676,18 +676,20 @@ size_t r4d_gpt2_greedy_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B) {
     return carve(nullptr, (size_t)B, 0, greedy_pool_floats(cfg), cfg->n_embd).bytes;
 }
 
-int r4d_gpt2_greedy_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
-                             float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
-                             void* stream) {
+// One step of a device-side decode loop: the LM head, the choice of the next token -- argmax (sa == nullptr) or the sampler
+// (sampling.hip) -- with the bookkeeping, then the cached step on the chosen ids
+static int advance_step(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st, const SampleArgs* sa,
+                        float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     int rc = check_cfg(cfg);
     if (rc) return rc;
-    R4D_REQUIRE(w && w->wte && st && st->last_d && st->logits_d, "gpt2 greedy: null pointer");
-    R4D_REQUIRE(B >= 1 && t_cap >= 1, "gpt2 greedy: B=%d t_cap=%d", B, t_cap);
+    const char* who = sa ? "gpt2 sample" : "gpt2 greedy";
+    R4D_REQUIRE(w && w->wte && st && st->last_d && st->logits_d, "%s: null pointer", who);
+    R4D_REQUIRE(B >= 1 && t_cap >= 1, "%s: B=%d t_cap=%d", who, B, t_cap);
     const int d = cfg->n_embd, V = cfg->vocab;
     Workspace ws = carve(workspace_d, (size_t)B, 0, greedy_pool_floats(cfg), d);
     if (!workspace_d || workspace_bytes < ws.bytes) {
-        set_error("gpt2 greedy: workspace %zu bytes < required %zu", workspace_bytes, ws.bytes);
+        set_error("%s: workspace %zu bytes < required %zu", who, workspace_bytes, ws.bytes);
         return R4D_ERR_WORKSPACE;
     }
     const float* head = w->lm_head ? w->lm_head : w->wte;            // untied checkpoints carry their own lm_head.weight
@@ -705,28 +707,56 @@ int r4d_gpt2_greedy_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights*
     size_t cbytes = 0;
     void* cnt = ws.pool ? gemm_skinny_counters(ws.pool, &cbytes) : nullptr;
     ge.zero_words = (unsigned*)cnt; ge.n_zero = (int)(cbytes / 4);
-    if ((rc = launch_greedy_advance(st->logits_d, B, V, g, s, &ge))) return rc;
+    if ((rc = sa ? launch_sample_advance(st->logits_d, B, V, *sa, &g, s, &ge) : launch_greedy_advance(st->logits_d, B, V, g, s, &ge)))
+        return rc;
     return decode_step_impl(cfg, w, st->next_d, nullptr, st->pos_d, kv_cache_d, B, t_cap, st->last_d, workspace_d, workspace_bytes,
                             stream, true);
 }
 
+int r4d_gpt2_greedy_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
+                             float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                             void* stream) {
+    return advance_step(cfg, w, st, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, stream);
+}
+
+// the sampled step's state as the greedy fields + the sampler's arguments
+static bool split_sample_state(const r4d_sample_state* st, r4d_greedy_state* g, SampleArgs* sa) {
+    if (!st || !st->stream_d || !st->fparams_d || !st->iparams_d) return false;
+    *g = r4d_greedy_state{st->last_d, st->logits_d, st->next_d, st->lens_d, st->pos_d, st->active_d, st->gen_len_d, st->out_tokens_d,
+                          st->params_d, st->out_cap};
+    *sa = SampleArgs{st->seen_d, nullptr, st->stream_d, st->fparams_d, st->iparams_d, nullptr, nullptr, nullptr};
+    return true;
+}
+
+size_t r4d_gpt2_sample_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B) { return r4d_gpt2_greedy_workspace_bytes(cfg, B); }
+
+int r4d_gpt2_sample_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_sample_state* st,
+                             float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                             void* stream) {
+    r4d_greedy_state g;
+    SampleArgs sa;
+    R4D_REQUIRE(split_sample_state(st, &g, &sa), "gpt2 sample: null pointer");
+    return advance_step(cfg, w, &g, &sa, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, stream);
+}
+
 struct r4d_decode_graph { hipGraph_t graph; hipGraphExec_t exec; };
 
-int r4d_gpt2_greedy_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
-                                 float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
-                                 r4d_decode_graph** out_graph) {
-    R4D_REQUIRE(out_graph, "gpt2 greedy graph: null out_graph");
+static int capture_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
+                        const SampleArgs* sa, float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                        r4d_decode_graph** out_graph) {
+    R4D_REQUIRE(out_graph, "%s: null out_graph", who);
     *out_graph = nullptr;
-    R4D_REQUIRE(!g_prof_on, "gpt2 greedy graph: switch the launch profiler off before capturing");
+    R4D_REQUIRE(!g_prof_on, "%s: switch the launch profiler off before capturing", who);
+    if (sa) { const int prc = sample_advance_prepare(); if (prc) return prc; }
     hipStream_t cap = nullptr;                                       // the caller's stream may be the null stream: not capturable
     R4D_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
     hipError_t e = hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) {
         (void)hipStreamDestroy(cap);
-        set_error("gpt2 greedy graph: begin capture: %s", hipGetErrorString(e));
+        set_error("%s: begin capture: %s", who, hipGetErrorString(e));
         return R4D_ERR_HIP;
     }
-    const int rc = r4d_gpt2_greedy_step_f32(cfg, w, st, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, cap);
+    const int rc = advance_step(cfg, w, st, sa, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, cap);
     hipGraph_t graph = nullptr;
     e = hipStreamEndCapture(cap, &graph);                            // always end the capture, also after an error
     (void)hipStreamDestroy(cap);
@@ -735,18 +765,34 @@ int r4d_gpt2_greedy_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weig
         return rc;
     }
     if (e != hipSuccess || !graph) {
-        set_error("gpt2 greedy graph: end capture: %s", hipGetErrorString(e));
+        set_error("%s: end capture: %s", who, hipGetErrorString(e));
         return R4D_ERR_HIP;
     }
     hipGraphExec_t exec = nullptr;
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     if (e != hipSuccess) {
         (void)hipGraphDestroy(graph);
-        set_error("gpt2 greedy graph: instantiate: %s", hipGetErrorString(e));
+        set_error("%s: instantiate: %s", who, hipGetErrorString(e));
         return R4D_ERR_HIP;
     }
     *out_graph = new r4d_decode_graph{graph, exec};
     return R4D_OK;
+}
+
+int r4d_gpt2_greedy_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
+                                 float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                                 r4d_decode_graph** out_graph) {
+    return capture_step("gpt2 greedy graph", cfg, w, st, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, out_graph);
+}
+
+int r4d_gpt2_sample_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_sample_state* st,
+                                 float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                                 r4d_decode_graph** out_graph) {
+    r4d_greedy_state g;
+    SampleArgs sa;
+    if (out_graph) *out_graph = nullptr;
+    R4D_REQUIRE(split_sample_state(st, &g, &sa), "gpt2 sample graph: null pointer");
+    return capture_step("gpt2 sample graph", cfg, w, &g, &sa, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, out_graph);
 }
 
 int r4d_decode_graph_launch(r4d_decode_graph* graph, int32_t n_steps, void* stream) {

@@ -3,6 +3,7 @@
 // (no LDS, no atomics -> bitwise reproducible run to run).
 #include <string.h>
 #include "common.h"
+#include "advance_tail.h"
 #include "h2.h"
 
 namespace r4d {
@@ -573,8 +574,6 @@ __global__ __launch_bounds__(256) void greedy_advance_kernel(const float* __rest
     __shared__ int si[4];
     __shared__ int s_next, s_pos;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (b == 0)
-        for (int i = tid; i < emb.n_zero; i += 256) emb.zero_words[i] = 0u;
     const float* row = logits + (long long)b * V;
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -590,34 +589,10 @@ __global__ __launch_bounds__(256) void greedy_advance_kernel(const float* __rest
     }
     if (lane == 0) { sv[wid] = best; si[wid] = bi; }
     __syncthreads();
-    if (tid == 0) {
+    if (tid == 0)
         for (int w = 1; w < 4; ++w)
             if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        int a = st.active[b];
-        const int len = st.lens[b];
-        if (a) {
-            int g = st.gen_len[b];
-            if (g < st.out_cap) st.out_tokens[(long long)b * st.out_cap + g] = bi;
-            ++g;
-            st.gen_len[b] = g;
-            const int max_gen = st.params[0], len_limit = min(st.params[1], st.t_cap), n_eos = min(st.params[2], 4);
-            bool stop = g >= max_gen || g >= st.out_cap || len + 1 >= len_limit;      // the cache row written next is `len`
-            for (int e = 0; e < n_eos; ++e) stop |= bi == st.params[3 + e];
-            if (stop) a = 0;
-            st.active[b] = a;
-        }
-        st.next[b] = bi;
-        st.pos[b] = a ? len : 0;                 // finished sequences rewrite their row 0: harmless, they are never read again
-        st.lens[b] = len + a;
-        s_next = bi; s_pos = a ? len : 0;
-    }
-    if (!emb.x_out) return;                      // (uniform per launch)
-    __syncthreads();
-    const int id = s_next, p = s_pos;
-    const bool bad = p < 0 || p >= emb.n_positions || p >= st.t_cap || id < 0 || id >= emb.vocab;   // as embed_pos_ln_kernel: poison, never fault
-    const float* src = emb.wte + (long long)(bad ? 0 : id) * emb.d;
-    const float* pe = emb.wpe + (long long)(bad ? 0 : p) * emb.d;
-    for (int c = tid; c < emb.d; c += 256) emb.x_out[(long long)b * emb.d + c] = bad ? __builtin_nanf("") : src[c] + pe[c];
+    advance_tail(b, bi, st, emb, &s_next, &s_pos);       // bookkeeping, stop rules, the next step's input row (advance_tail.h)
 }
 
 int launch_greedy_advance(const float* logits, int B, int V, const GreedyState& st, hipStream_t s, const GreedyEmbed* embed) {

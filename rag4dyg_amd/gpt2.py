@@ -246,7 +246,7 @@ class GPT2Model(_PreTrained):
     # per-object caches and the back-link to an owning LM-head model: never copied or pickled (copy.deepcopy(model) -- the
     # reference's `best_model = copy.deepcopy(model)` -- and torch.save(model) go through __getstate__); an owner re-links
     # its own copy in _LMHeadBase.__setstate__
-    _TRANSIENT = ("_wt_cache", "_w3_cache", "_b1_cache", "_h2_cache", "_fold_cache", "_greedy_decoders", "_lm_head_weight")
+    _TRANSIENT = ("_wt_cache", "_w3_cache", "_b1_cache", "_h2_cache", "_fold_cache", "_greedy_decoders", "_sampling_decoders", "_lm_head_weight")
 
     def __getstate__(self):
         return {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
@@ -547,6 +547,18 @@ class GPT2Model(_PreTrained):
         dec = cache[(B, t_cap, slot)] = GreedyDecoder(self, B, t_cap)
         return dec
 
+    def sampling_decoder(self, B, t_cap, slot=0):
+        """``greedy_decoder``'s twin for the ``SamplingDecoder``: the same keys, a cache of its own."""
+        t_cap = (int(t_cap) + 127) // 128 * 128
+        cache = self.__dict__.setdefault("_sampling_decoders", {})
+        fits = [k for k in cache if k[0] == B and k[1] >= t_cap and k[2] == slot]
+        if fits:
+            return cache[min(fits)]
+        for k in [k for k in cache if k[0] == B and k[2] == slot]:
+            cache.pop(k).close()
+        dec = cache[(B, t_cap, slot)] = SamplingDecoder(self, B, t_cap)
+        return dec
+
     @torch.no_grad()
     def encode_groups_meanpool(self, batches):
         """Mean-pooled embeddings of several right-padded batches in one fused launch sequence
@@ -670,10 +682,8 @@ class GreedyDecoder:
                                                         self.ws.numel(), stream), "gpt2_greedy_step")
 
     @torch.no_grad()
-    def run(self, last, lens, max_gen, len_limit, eos=(), poll=8):
-        """Generate from the prefilled cache.  ``last`` [B,d]: ln_f row of every sequence's last prompt position;
-        ``lens`` [B]: positions cached.  A sequence stops after ``max_gen`` tokens, after any id in ``eos``, or once its
-        length reaches ``len_limit``.  Returns the generated ids per sequence (lists of ints)."""
+    def begin(self, last, lens, max_gen, len_limit, eos=()):
+        """The loop state of a new generation (``run``'s arguments); ``_steps(n)`` then advances every sequence by n tokens."""
         eos = [int(e) for e in eos][:4]
         self.last.copy_(last)
         self.lens.copy_(lens.to(torch.int32))
@@ -681,6 +691,13 @@ class GreedyDecoder:
         self.gen_len.zero_()
         self.params.copy_(torch.tensor([int(max_gen), int(min(len_limit, self.t_cap)), len(eos)] + eos + [0] * (5 - len(eos)),
                                        dtype=torch.int32))
+
+    @torch.no_grad()
+    def run(self, last, lens, max_gen, len_limit, eos=(), poll=8):
+        """Generate from the prefilled cache.  ``last`` [B,d]: ln_f row of every sequence's last prompt position;
+        ``lens`` [B]: positions cached.  A sequence stops after ``max_gen`` tokens, after any id in ``eos``, or once its
+        length reaches ``len_limit``.  Returns the generated ids per sequence (lists of ints)."""
+        self.begin(last, lens, max_gen, len_limit, eos)
         n, done = (int(max_gen) if max_gen <= 16 else poll), 0
         while True:
             self._steps(n)
@@ -692,7 +709,180 @@ class GreedyDecoder:
         return [out[i, :int(g[i])].tolist() for i in range(self.B)]
 
 
+class SamplingDecoder(GreedyDecoder):
+    """``GreedyDecoder`` with the sampler in the argmax's place (``r4d_gpt2_sample_step_f32`` / ``r4d_gpt2_sample_graph_create``):
+    repetition penalty, temperature, top-k, top-p and one Philox draw per sequence and token, on the device.  Owns, besides the
+    greedy decoder's buffers, the bitmap of ids already seen ``self.seen`` [B, ceil(V/32)], the Philox stream number of every row
+    ``self.stream`` [B] and the two parameter words, which the kernel reads at every step -- one captured graph serves every call."""
+
+    def __init__(self, transformer, B, t_cap):
+        super().__init__(transformer, B, t_cap)
+        dev, V = self.device, transformer.wte.num_embeddings
+        self.seen = torch.zeros(B, (V + 31) // 32, dtype=torch.int32, device=dev)
+        self.stream = torch.arange(B, dtype=torch.int32, device=dev)
+        self.fparams, self.iparams = ops.sample_params(dev)
+        self.sstate = _lib.SampleStateC(*[getattr(self.state, n) for n, _ in _lib.GreedyStateC._fields_], self.seen.data_ptr(),
+                                        self.stream.data_ptr(), self.fparams.data_ptr(), self.iparams.data_ptr())
+
+    def _steps(self, n):
+        lib = _lib.load()
+        c, w, layers = self.tr._c_structs(decode=True)
+        stream = torch.cuda.current_stream().cuda_stream
+        if self.use_graph:
+            key = bytes(layers) + bytes((ctypes.c_void_p * 5)(w.wte, w.wpe, w.ln_f_w, w.ln_f_b, w.lm_head))   # every weight pointer baked in
+            if self._graph is None or key != self._graph_key:
+                self.close()
+                g = ctypes.c_void_p()
+                _lib.check(lib.r4d_gpt2_sample_graph_create(ctypes.byref(c), ctypes.byref(w), ctypes.byref(self.sstate),
+                                                            self.cache.data_ptr(), self.B, self.t_cap, self.ws.data_ptr(),
+                                                            self.ws.numel(), ctypes.byref(g)), "gpt2_sample_graph_create")
+                self._graph, self._graph_key = g, key
+                self.graph_builds += 1
+            _lib.check(lib.r4d_decode_graph_launch(self._graph, n, stream), "decode_graph_launch")
+        else:
+            for _ in range(n):
+                _lib.check(lib.r4d_gpt2_sample_step_f32(ctypes.byref(c), ctypes.byref(w), ctypes.byref(self.sstate),
+                                                        self.cache.data_ptr(), self.B, self.t_cap, self.ws.data_ptr(),
+                                                        self.ws.numel(), stream), "gpt2_sample_step")
+
+    def set_seen(self, id_lists=None):
+        """The seen bitmap from one list of ids per sequence (``None``: nothing seen)."""
+        import numpy as np
+        bits = np.zeros(tuple(self.seen.shape), dtype=np.uint32)
+        V = self.tr.wte.num_embeddings
+        for i, ids in enumerate(id_lists or ()):
+            ids = np.unique(np.asarray(list(ids), dtype=np.int64))
+            if ids.size and (ids[0] < 0 or ids[-1] >= V):
+                raise ValueError(f"SamplingDecoder: an id outside [0, {V})")
+            np.bitwise_or.at(bits[i], ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+        self.seen.copy_(torch.from_numpy(bits.view(np.int32)))
+
+    def set_sampling(self, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0, stream=None):
+        f, i = ops.sample_params(self.device, do_sample, temperature, top_k, top_p, repetition_penalty, seed)
+        self.fparams.copy_(f)
+        self.iparams.copy_(i)
+        self.stream.copy_(torch.arange(self.B, dtype=torch.int32) if stream is None else torch.as_tensor(stream, dtype=torch.int32))
+
+    @torch.no_grad()
+    def run(self, last, lens, max_gen, len_limit, eos=(), poll=8, *, seen_ids=None, **sampling):
+        """``GreedyDecoder.run`` with the sampler: ``sampling`` holds ``set_sampling``'s arguments, ``seen_ids`` one list of ids
+        per sequence for the repetition penalty (the prompt)."""
+        self.set_sampling(**sampling)
+        self.set_seen(seen_ids)
+        return super().run(last, lens, max_gen, len_limit, eos, poll)
+
+    @torch.no_grad()
+    def begin_sampling(self, last, lens, max_gen, len_limit, eos=(), *, seen_ids=None, **sampling):
+        """``run`` without the loop: the state of a new generation, for a caller that steps (``_steps``) and looks itself."""
+        self.set_sampling(**sampling)
+        self.set_seen(seen_ids)
+        self.begin(last, lens, max_gen, len_limit, eos)
+
+
+_GENERATE_DEFAULTS = dict(max_length=20, do_sample=False, num_beams=1, temperature=1.0, top_k=50, top_p=1.0, repetition_penalty=1.0,
+                          bos_token_id=None, pad_token_id=None, eos_token_ids=None, length_penalty=1.0, num_return_sequences=1)
+
+
 class _LMHeadBase(_PreTrained):
+    @torch.no_grad()
+    def generate(self, input_ids=None, max_length=None, do_sample=None, num_beams=None, temperature=None, top_k=None, top_p=None,
+                 repetition_penalty=None, bos_token_id=None, pad_token_id=None, eos_token_ids=None, length_penalty=None,
+                 num_return_sequences=None, *, seed=0, inputs_embeds=None):
+        """The reference's ``generate`` without beam search (``modeling_utils.py:608-927``): greedy or sampled continuation of
+        ``input_ids`` [B, T] with the key/value cache, the choice of every token made on the device.  Arguments left ``None`` come
+        from the config where it carries them, else from the reference's defaults (``configuration_utils.py:72-82``).  Returns
+        int64 [B * num_return_sequences, L]: prompt, generated ids with the eos, finished rows padded with ``pad_token_id``;
+        rows ``i * n .. i * n + n - 1`` continue prompt ``i``.  Row ``j`` draws from Philox stream ``j`` of ``seed``: the same seed
+        repeats the call.  ``inputs_embeds`` [B, T, d] replaces the prompt's embedding rows (the RAG splice); ``input_ids`` are then
+        optional and used for the repetition penalty and the prompt columns of the output only.  WITHOUT ``input_ids`` there are
+        no prompt ids to return: the result is the generated part alone, int64 [B * num_return_sequences, L - T].  ``num_beams > 1`` is not built."""
+        cfg = self.config
+        given = dict(max_length=max_length, do_sample=do_sample, num_beams=num_beams, temperature=temperature, top_k=top_k, top_p=top_p,
+                     repetition_penalty=repetition_penalty, bos_token_id=bos_token_id, pad_token_id=pad_token_id,
+                     eos_token_ids=eos_token_ids, length_penalty=length_penalty, num_return_sequences=num_return_sequences)
+        a = {k: (v if v is not None else getattr(cfg, k, _GENERATE_DEFAULTS[k])) for k, v in given.items()}
+        max_length, do_sample, num_beams, temperature, top_k, top_p = (a[k] for k in ("max_length", "do_sample", "num_beams", "temperature", "top_k", "top_p"))
+        repetition_penalty, bos_token_id, pad_token_id, eos_token_ids = (a[k] for k in ("repetition_penalty", "bos_token_id", "pad_token_id", "eos_token_ids"))
+        length_penalty, n_ret = a["length_penalty"], a["num_return_sequences"]
+        if isinstance(eos_token_ids, int):
+            eos_token_ids = [eos_token_ids]
+        # the reference's asserts (:737-781)
+        assert isinstance(max_length, int) and max_length > 0, "`max_length` should be a strictly positive integer."
+        assert isinstance(do_sample, bool), "`do_sample` should be a boolean."
+        assert isinstance(num_beams, int) and num_beams > 0, "`num_beams` should be a strictly positive integer."
+        assert temperature > 0, "`temperature` should be strictly positive."
+        assert isinstance(top_k, int) and top_k >= 0, "`top_k` should be a positive integer."
+        assert 0 <= top_p <= 1, "`top_p` should be between 0 and 1."
+        assert repetition_penalty >= 1.0, "`repetition_penalty` should be >= 1."
+        assert input_ids is not None or inputs_embeds is not None or (isinstance(bos_token_id, int) and bos_token_id >= 0), \
+            "If input_ids is not defined, `bos_token_id` should be a positive integer."
+        assert pad_token_id is None or (isinstance(pad_token_id, int) and pad_token_id >= 0), "`pad_token_id` should be a positive integer."
+        assert eos_token_ids is None or (isinstance(eos_token_ids, (list, tuple)) and all(isinstance(e, int) and e >= 0 for e in eos_token_ids)), \
+            "`eos_token_ids` should be a positive integer or a list/tuple of positive integers."
+        assert length_penalty > 0, "`length_penalty` should be strictly positive."
+        assert isinstance(n_ret, int) and n_ret > 0, "`num_return_sequences` should be a strictly positive integer."
+        if num_beams > 1:
+            raise NotImplementedError("generate: beam search (num_beams > 1) is not built")
+        if not do_sample:
+            assert n_ret == 1, "Greedy decoding will always produce the same output for num_beams == 1 and num_return_sequences > 1. " \
+                               "Please set num_return_sequences = 1"
+        if eos_token_ids is not None and len(eos_token_ids) > 4:
+            raise NotImplementedError("generate: the device loop tests at most 4 eos ids")
+        tr = self.transformer
+        dev = tr.wte.weight.device
+        if input_ids is None and inputs_embeds is None:
+            input_ids = torch.full((1, 1), bos_token_id, dtype=torch.long, device=dev)
+        if input_ids is not None:
+            assert input_ids.dim() == 2, "Input prompt should be of shape (batch_size, sequence length)."
+            input_ids = input_ids.to(dev)
+        if inputs_embeds is not None:
+            assert inputs_embeds.dim() == 3, "inputs_embeds should be of shape (batch_size, sequence length, n_embd)."
+            if input_ids is not None and tuple(input_ids.shape) != tuple(inputs_embeds.shape[:2]):
+                raise ValueError("generate: input_ids and inputs_embeds differ in shape")
+            if input_ids is None and repetition_penalty != 1.0:
+                raise ValueError("generate: a repetition penalty over a prompt given as inputs_embeds needs its input_ids too")
+        if pad_token_id is None and eos_token_ids is not None:
+            pad_token_id = eos_token_ids[0]
+        src = inputs_embeds if inputs_embeds is not None else input_ids
+        B0, T = int(src.shape[0]), int(src.shape[1])
+        if T < 1:
+            raise ValueError("generate: an empty prompt")
+        if max_length > tr.wpe.num_embeddings:
+            raise ValueError(f"generate: max_length {max_length} exceeds n_positions {tr.wpe.num_embeddings}")
+        mult = n_ret if do_sample else 1
+        ids_rows = input_ids.repeat_interleave(mult, 0) if input_ids is not None else None          # rows i * n .. i * n + n - 1: prompt i
+        if max_length <= T:                                                                          # (the reference's loop does not run)
+            return ids_rows if ids_rows is not None else torch.empty(B0 * mult, 0, dtype=torch.long, device=dev)
+        B = B0 * mult
+        plain = not do_sample and repetition_penalty == 1.0
+        dec = tr.greedy_decoder(B, max_length) if plain else tr.sampling_decoder(B, max_length)
+        lens = [T] * B
+        if inputs_embeds is not None:
+            last = tr.prefill_last(dec.cache, lens, inputs_embeds=inputs_embeds.to(dev).repeat_interleave(mult, 0))
+        else:
+            last = tr.prefill_last(dec.cache, lens, input_ids=ids_rows)
+        lens_t = torch.tensor(lens, dtype=torch.int32, device=dev)
+        eos = list(eos_token_ids or ())
+        # a row of the cache holds the prompt and every generated id but the last: max_length - 1 positions are written at most
+        if plain:
+            gen = dec.run(last, lens_t, max_length - T, dec.t_cap + 1, eos)
+        else:
+            gen = dec.run(last, lens_t, max_length - T, dec.t_cap + 1, eos, do_sample=do_sample, temperature=temperature, top_k=top_k,
+                          top_p=top_p, repetition_penalty=repetition_penalty, seed=seed,
+                          seen_ids=ids_rows.tolist() if (ids_rows is not None and repetition_penalty != 1.0) else None)
+        L = T + max(len(g) for g in gen)
+        if any(len(g) != L - T for g in gen):
+            assert pad_token_id is not None, "`Pad_token_id` has to be defined if batches have different lengths"
+        out = torch.full((B, L), pad_token_id if pad_token_id is not None else 0, dtype=torch.long)
+        if ids_rows is not None:
+            out[:, :T] = ids_rows.cpu()
+        else:
+            out = out[:, T:]                                                                         # no ids for the prompt: the generated part
+            T = 0
+        for i, g in enumerate(gen):
+            out[i, T:T + len(g)] = torch.tensor(g, dtype=torch.long)
+        return out.to(dev)
+
     def __init__(self, config):
         super().__init__()
         self.config = config

@@ -667,6 +667,47 @@ def lm_logits(hidden, wte):
     return out
 
 
+def sample_params(device, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
+    """The two parameter words of the sampler (``r4d.h``: fparams_d float[4], iparams_d int32[4]) as device tensors."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lo, hi = seed & 0xFFFFFFFF, seed >> 32
+    i32 = lambda v: v - (1 << 32) if v >= (1 << 31) else v
+    f = torch.tensor([float(temperature), float(top_p), float(repetition_penalty), 0.0], dtype=torch.float32).to(device)
+    i = torch.tensor([1 if do_sample else 0, int(top_k), i32(lo), i32(hi)], dtype=torch.int32).to(device)
+    return f, i
+
+
+def sample_logits(logits, step, stream, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0,
+                  seen=None, want_keep=False, want_u=False):
+    """One sampled (or, ``do_sample=False``, arg-max) token per row of ``logits`` [B, V] (``r4d_sample_logits_f32``): repetition
+    penalty over the ids whose bit is set in ``seen`` (int32 [B, ceil(V/32)], updated with the chosen id), temperature, top-k,
+    top-p, and the Philox draw of (``seed``, ``stream[b]``, ``step[b]``).  Returns the ids, int64 [B]; with ``want_keep`` /
+    ``want_u`` a tuple that also holds the kept-set bitmap (int32 [B, ceil(V/32)]) and the uniforms (float32 [B])."""
+    B, V = logits.shape
+    dev = logits.device
+    if not (temperature > 0 and 0 <= top_p <= 1 and repetition_penalty >= 1 and int(top_k) >= 0):
+        raise ValueError("sample_logits: temperature > 0, 0 <= top_p <= 1, repetition_penalty >= 1, top_k >= 0")
+    nw = (V + 31) // 32
+    if seen is not None and tuple(seen.shape) != (B, nw):
+        raise ValueError(f"sample_logits: seen must be int32 [{B}, {nw}]")
+    step = step.to(device=dev, dtype=torch.int32).contiguous()
+    stream = stream.to(device=dev, dtype=torch.int32).contiguous()
+    if step.numel() != B or stream.numel() != B:
+        raise ValueError("sample_logits: step and stream hold one value per row")
+    fpar, ipar = sample_params(dev, do_sample, temperature, top_k, top_p, repetition_penalty, seed)
+    tok = torch.empty(B, dtype=torch.int64, device=dev)
+    keep = torch.empty(B, nw, dtype=torch.int32, device=dev) if want_keep else None
+    u = torch.empty(B, dtype=torch.float32, device=dev) if want_u else None
+    check(_lib.load().r4d_sample_logits_f32(_dev(logits, torch.float32, "logits"), B, V,
+                                            _dev(seen, torch.int32, "seen") if seen is not None else None, step.data_ptr(),
+                                            stream.data_ptr(), fpar.data_ptr(), ipar.data_ptr(), tok.data_ptr(),
+                                            keep.data_ptr() if want_keep else None, u.data_ptr() if want_u else None, _stream()),
+          "sample_logits")
+    if not (want_keep or want_u):
+        return tok
+    return (tok,) + ((keep,) if want_keep else ()) + ((u,) if want_u else ())
+
+
 # ------------------------------------------------------------------------------------------- range guard (include/r4d.h, ABI v6)
 RANGE_NONFINITE_HIDDEN, RANGE_BAD_NORM, RANGE_BAD_LABEL = 1, 2, 4
 _RANGE_FLAG = None
