@@ -131,7 +131,8 @@ typedef struct r4d_gpt2_weights {
  *   - a training workspace BETWEEN r4d_gpt2_train_forward*_f32 and the backward of the same step (the saved activations);
  *   - operands described as zero-padded by their entry (the rows of r4d_lm_head.wte_pad past vocab);
  *   - the sticky range-guard word (r4d_set_range_flag) and the greedy loop state (r4d_greedy_state);
- *   - the sampled loop state (r4d_sample_state) and the seen bitmap of r4d_sample_logits_f32.
+ *   - the sampled loop state (r4d_sample_state) and the seen bitmap of r4d_sample_logits_f32;
+ *   - the beam loop state (r4d_beam_state: the fields marked in/out; its candidate and hypothesis buffers are scratch until written).
  */
 
 /* Scratch bytes r4d_gpt2_encode_f32 needs for a [B,T] batch. */
@@ -301,6 +302,90 @@ int r4d_gpt2_sample_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights*
 int r4d_gpt2_sample_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_sample_state* st,
                                  float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
                                  r4d_decode_graph** out_graph);
+
+/*
+ * Beam search (additive ABI v6 entries): the reference's greedy beam search (models/modeling_utils.py:929-1153, BeamHypotheses
+ * :1205-1252; do_sample False) with the beam step on the device.  2 <= n_beams <= R4D_BEAM_MAX beams per prompt; the rows of
+ * every per-row array are R = B0 * n_beams, rows b n .. b n + n - 1 the beams of prompt b.  V >= 2 and n V < 2^31.
+ *
+ * Candidates of a row x[0..V) with beam score s (one workgroup per row):
+ *   1. the repetition penalty of the sampled step (its rule 1) through `seen`; NaN counts as -inf;
+ *   2. m = max x, lse = logf(sum expf(x - m)), score_j = ((x_j - m) - lse) + s, each an IEEE fp32 operation in that order; the sum
+ *      is taken in an order that the workgroup's shape alone fixes, so a row's scores depend on the row, not on R or its place;
+ *      a score that comes out NaN counts as -inf (a row without a finite maximum: every score is -inf);
+ *   3. the row's min(2n, V) best in the order (score descending, id ascending).
+ * Candidates of a prompt: its n lists merged into the 2n best in the order (score descending, flat index beam * V + id ascending)
+ * -- the tie rule that torch.topk leaves open.
+ *   fparams_d  device float[4]  {length_penalty > 0, repetition_penalty >= 1, reserved, reserved}     read at every launch
+ */
+#define R4D_BEAM_MAX 16
+/* The selection alone.  logits_d [R,V]; beam_scores_d [R]; seen_d uint32 [R, ceil(V/32)] or NULL (read only);
+ * cand_scores_d float / cand_ids_d int32 [R, 2n]: the rows' lists (entries past min(2n, V): -inf / -1);
+ * out_scores_d float / out_index_d int32 [B0, 2n]: the prompts' candidates, index = beam * V + id.  No workspace. */
+int r4d_beam_select_f32(const float* logits_d, const float* beam_scores_d, const uint32_t* seen_d, const float* fparams_d,
+                        int32_t B0, int32_t n_beams, int32_t V, float* cand_scores_d, int32_t* cand_ids_d, float* out_scores_d,
+                        int32_t* out_index_d, void* stream);
+/* Reorder a key/value cache [n_layer, R = B0 n, t_cap, 2d] in place: for every group b with active_d[b] != 0 (active_d NULL: every
+ * group) and every position p in [lo_d[b], hi_d[b]) (clipped to [0, t_cap)), row b n + i receives the K | V line of row
+ * src_row_d[b n + i].  A source outside the group's own rows is never read: the receiving row's lines are filled with NaN.  Groups
+ * whose permutation is the identity are skipped; only rows whose source differs are stored.  No workspace, no second cache.
+ * The copy moves 2 * n_layer * (rows that move) * (hi - lo) * 2d * 4 bytes. */
+int r4d_kv_cache_reorder_f32(float* kv_cache_d, const int32_t* src_row_d, const int32_t* lo_d, const int32_t* hi_d,
+                             const int32_t* active_d, int32_t n_layer, int32_t B0, int32_t n, int32_t t_cap, int32_t d,
+                             void* stream);
+/* The loop state of the beam step: r4d_greedy_state's fields PER ROW with its conventions, then the beams' own.  At the start of
+ * a step, per prompt (modeling_utils.py:1032-1075):
+ *     done |= hyp_count >= n && worst >= best candidate score / (T + max_gen - 1) ** length_penalty    (the reference's max_length - 1)
+ *     done: the prompt's rows go inactive and its state is no longer touched; else the 2n candidates are walked in order:
+ *       an eos id: the hypothesis (the source beam's ids so far, score = candidate score / (T + gen_len) ** length_penalty, in
+ *         double from the fp32 score) joins the list while it holds fewer than n, or when it beats `worst`: the entry with the
+ *         lowest (score, list position) leaves and worst becomes the lowest score that stays;
+ *       any other id becomes the next beam, until n are found (fewer than n: status bit 0, the reference's "Beam should always be full").
+ *     beam_scores, next, beam_idx (source row), pos, lens, active, gen_len are written; the prompt's rows of out_tokens and seen are
+ *     reordered in place and receive the new id; the rows stop after max_gen ids or at the cache's end, as the greedy rows do.
+ * params_d as in r4d_greedy_state, with [7] = T, the prompt length shared by all rows.  The caller starts a generation with
+ * beam_scores = {0, -1e9, ...} per prompt (:956-959), done = hyp_count = hyp_added = status = 0, hyp_worst = 1e9, active = 1, gen_len = 0.
+ * Nothing else needs a defined content on entry: candidates and hypotheses are written before they are read. */
+typedef struct r4d_beam_state {
+    float* last_d;
+    float* logits_d;
+    int64_t* next_d;
+    int32_t* lens_d;
+    int32_t* pos_d;
+    int32_t* active_d;
+    int32_t* gen_len_d;
+    int32_t* out_tokens_d;
+    const int32_t* params_d;
+    int32_t out_cap;
+    int32_t n_beams;
+    uint32_t* seen_d;           /* device uint32 [R, ceil(V/32)] or NULL; reordered with the beams */
+    const float* fparams_d;     /* device float[4], read every step */
+    float* beam_scores_d;       /* [R] in/out */
+    int32_t* beam_idx_d;        /* [R] out: the row each row continues (this step's src_row of the cache reorder) */
+    float* cand_scores_d;       /* [R, 2n] scratch */
+    int32_t* cand_ids_d;        /* [R, 2n] scratch */
+    int32_t* lo_d;              /* [B0] out: the reorder's range of this step, [T, positions cached) */
+    int32_t* hi_d;              /* [B0] out */
+    int32_t* group_active_d;    /* [B0] out: 1 = the prompt took new beams at this step */
+    int32_t* done_d;            /* [B0] in/out */
+    int32_t* hyp_count_d;       /* [B0] in/out: hypotheses held, <= n */
+    int32_t* hyp_added_d;       /* [B0] in/out: hypotheses ever added (hyp_seq_d counts with it) */
+    int32_t* status_d;          /* [B0] in/out: bit 0 = a step found fewer than n beams */
+    double* hyp_worst_d;        /* [B0] in/out */
+    double* hyp_score_d;        /* [B0, n] */
+    int32_t* hyp_len_d;         /* [B0, n] generated ids of the hypothesis (the prompt not counted) */
+    int32_t* hyp_seq_d;         /* [B0, n] order of arrival: the reference's list position is the rank of this number */
+    int32_t* hyp_ids_d;         /* [B0, n, out_cap] the generated ids */
+} r4d_beam_state;
+/* One step = the LM head on the greedy step's route (R rows), the candidates, the walk, r4d_kv_cache_reorder_f32 over
+ * [T, positions cached) by beam_idx_d -- valid because the n rows of a group are prefilled from one prompt and hold identical
+ * bits below T -- and r4d_gpt2_decode_step_f32 on the chosen ids.  kv_cache_d [n_layer, R, t_cap, 2d].  The graph is an
+ * r4d_decode_graph: r4d_decode_graph_launch / _destroy serve it. */
+size_t r4d_gpt2_beam_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B0, int32_t n_beams);
+int r4d_gpt2_beam_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_beam_state* st, float* kv_cache_d,
+                           int32_t B0, int32_t t_cap, void* workspace_d, size_t workspace_bytes, void* stream);
+int r4d_gpt2_beam_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_beam_state* st, float* kv_cache_d,
+                               int32_t B0, int32_t t_cap, void* workspace_d, size_t workspace_bytes, r4d_decode_graph** out_graph);
 
 /* lm_logits = hidden @ wte^T  (tied lm_head, modeling_gpt2.py:585; modeling_rag.py:675).
  * hidden_d [M,d], wte_d [V,d] -> logits_d [M,V]. */

@@ -41,6 +41,12 @@ class SampleStateC(Structure):                  # r4d_sample_state: the greedy f
     _fields_ = GreedyStateC._fields_ + [(n, c_void_p) for n in ("seen_d", "stream_d", "fparams_d", "iparams_d")]
 
 
+class BeamStateC(Structure):                    # r4d_beam_state: the greedy fields per row, then the beams' own
+    _fields_ = GreedyStateC._fields_ + [("n_beams", c_int32)] + [(n, c_void_p) for n in (
+        "seen_d", "fparams_d", "beam_scores_d", "beam_idx_d", "cand_scores_d", "cand_ids_d", "lo_d", "hi_d", "group_active_d", "done_d",
+        "hyp_count_d", "hyp_added_d", "status_d", "hyp_worst_d", "hyp_score_d", "hyp_len_d", "hyp_seq_d", "hyp_ids_d")]
+
+
 class GPT2LayerGradsC(Structure):
     _fields_ = [(n, c_void_p) for n in ("ln_1_w", "ln_1_b", "c_attn_w", "c_attn_b", "attn_proj_w", "attn_proj_b",
                                          "ln_2_w", "ln_2_b", "c_fc_w", "c_fc_b", "mlp_proj_w", "mlp_proj_b")]
@@ -108,6 +114,13 @@ PROTOTYPES = {
                                            c_int32, _P, c_size_t, _P]),
     "r4d_gpt2_sample_graph_create": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(SampleStateC), _P,
                                                c_int32, c_int32, _P, c_size_t, POINTER(_P)]),
+    "r4d_beam_select_f32": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "r4d_kv_cache_reorder_f32": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    "r4d_gpt2_beam_workspace_bytes": (c_size_t, [POINTER(GPT2ConfigC), c_int32, c_int32]),
+    "r4d_gpt2_beam_step_f32": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(BeamStateC), _P, c_int32,
+                                         c_int32, _P, c_size_t, _P]),
+    "r4d_gpt2_beam_graph_create": (c_int32, [POINTER(GPT2ConfigC), POINTER(GPT2WeightsC), POINTER(BeamStateC), _P,
+                                             c_int32, c_int32, _P, c_size_t, POINTER(_P)]),
     "r4d_lm_logits_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "r4d_layernorm_f32": (c_int32, [_P, _P, _P, c_int32, c_int32, c_float, _P, _P]),
     "r4d_conv1d_f32": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),

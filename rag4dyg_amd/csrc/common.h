@@ -46,7 +46,7 @@ enum ProfClass {
     PK_EMBED_LN, PK_LAYERNORM, PK_SOFTMAX, PK_DECODE_ATTN, PK_GREEDY_ADVANCE,
     PK_ATTN_FUSED, PK_LNF_MEANPOOL, PK_MEANPOOL_REDUCE, PK_NORMALIZE, PK_POOL_SCAN, PK_TOPK, PK_MERGE_TOPK, PK_RANK_COUNT, PK_JACCARD, PK_JACCARD_PREP, PK_LM_CE,
     PK_SPLICE_EMBED, PK_WEIGHTED_BAG, PK_EMB_SCATTER, PK_GEMM_B1, PK_GEMM_B1TN, PK_GEMM_H2_ROWMAP, PK_PAD_CLASSIFY, PK_PAD_FILL, PK_GEMM_B1H_NT, PK_GEMM_B1H_NN,
-    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_ATTN_B1, PK_SAMPLE_ADVANCE, PK_COUNT
+    PK_ATTN_TRAIN_FUSED_FWD, PK_ATTN_TRAIN_FUSED_ROWSUM, PK_ATTN_TRAIN_FUSED_DKV, PK_ATTN_TRAIN_FUSED_DQ, PK_ATTN_B1, PK_SAMPLE_ADVANCE, PK_BEAM_ROWS, PK_BEAM_ADVANCE, PK_KV_REORDER, PK_COUNT
 };
 extern bool g_prof_on;
 void prof_begin_impl(int cls, double work, hipStream_t s);
@@ -95,7 +95,8 @@ struct ProfScope {
     X(TAF_FWD, "tuning:train_attn_fused:fwd") X(TAF_ROWSUM, "tuning:train_attn_fused:rowsum") X(TAF_DKV, "tuning:train_attn_fused:dkv") X(TAF_DQ, "tuning:train_attn_fused:dq") \
     X(EBA_BF16, "tuning:encode_bf16_attn:bf16 qkv") X(EBA_F32, "tuning:encode_bf16_attn:fp32 qkv, rounded while staged") X(EBA_FALLBACK, "tuning:encode_bf16_attn:fallback to the exact-f32 attention") \
     X(EAB_LN1, "tuning:encode_act_bf16:ln1") X(EAB_LN2, "tuning:encode_act_bf16:ln2") X(EAB_F, "tuning:encode_act_bf16:f") X(EAB_KEPT_F32, "tuning:encode_act_bf16:kept fp32") \
-    X(SAMPLE_LDS, "tuning:sample:keyed row in LDS") X(SAMPLE_GLOBAL, "tuning:sample:row re-read from memory")
+    X(SAMPLE_LDS, "tuning:sample:keyed row in LDS") X(SAMPLE_GLOBAL, "tuning:sample:row re-read from memory") \
+    X(BEAM_LDS, "tuning:beam:keyed row in LDS") X(BEAM_GLOBAL, "tuning:beam:row re-read from memory")
 enum DispatchBranch {
 #define X(id, name) BR_##id,
     R4D_BRANCH_LIST(X)
@@ -377,6 +378,22 @@ struct SampleArgs {
 int launch_sample_advance(const float* logits, int B, int V, const SampleArgs& sa, const GreedyState* st, hipStream_t s,
                           const GreedyEmbed* embed = nullptr);
 int sample_advance_prepare();      // the kernel's LDS attribute on the current device (also before a capture)
+// beam.hip: the beam step's choice (r4d.h, "Beam search").  Rows R = B0 * n, rows b n .. b n + n - 1 the beams of prompt b.
+// fpar float[4] {length_penalty, repetition_penalty, -, -}, read on the device; the other fields as r4d_beam_state names them;
+// out_score / out_flat [B0, 2n]: the merged candidates, written by the single operation only
+struct BeamArgs {
+    int n;
+    unsigned* seen; const float* fpar; float* beam_scores; int32_t* beam_idx; float* cand_score; int32_t* cand_id;
+    int32_t *lo, *hi, *group_active, *done, *hyp_count, *hyp_added, *status;
+    double *worst, *hyp_score; int32_t *hyp_len, *hyp_seq, *hyp_ids;
+    float* out_score; int32_t* out_flat;
+};
+int launch_beam_rows(const float* logits, int R, int V, const BeamArgs& ba, hipStream_t s);       // the 2n best of every row
+// the prompts' 2n best; with `st`: the reference's walk over them, the bookkeeping and (embed) the decode step's input rows
+int launch_beam_advance(int B0, int V, const BeamArgs& ba, const GreedyState* st, const GreedyEmbed* embed, hipStream_t s);
+int beam_rows_prepare();           // as sample_advance_prepare
+int launch_kv_reorder(float* kv, const int* src_row, const int* lo, const int* hi, const int* active, int n_layer, int B0, int n, int t_cap,
+                      int d, hipStream_t s);
 // Up to ATT_MAXG right-padded batches (each with its own T) in ONE attention launch: the workgroup index walks the sequences
 // of all batches; the batch of a sequence is found by a short scan of the prefix table (kernel argument, by value).
 struct AttnGroups {

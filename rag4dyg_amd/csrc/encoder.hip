@@ -676,14 +676,16 @@ size_t r4d_gpt2_greedy_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B) {
     return carve(nullptr, (size_t)B, 0, greedy_pool_floats(cfg), cfg->n_embd).bytes;
 }
 
-// One step of a device-side decode loop: the LM head, the choice of the next token -- argmax (sa == nullptr) or the sampler
-// (sampling.hip) -- with the bookkeeping, then the cached step on the chosen ids
+// One step of a device-side decode loop: the LM head, the choice of the next token -- argmax (sa == ba == nullptr), the sampler
+// (sa: sampling.hip) or the beam step (ba: beam.hip; B rows in groups of ba->n, then the reordering of the cache) -- with the bookkeeping,
+// then the cached step on the chosen ids
 static int advance_step(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st, const SampleArgs* sa,
-                        float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes, void* stream) {
+                        const BeamArgs* ba, float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
+                        void* stream) {
     hipStream_t s = (hipStream_t)stream;
     int rc = check_cfg(cfg);
     if (rc) return rc;
-    const char* who = sa ? "gpt2 sample" : "gpt2 greedy";
+    const char* who = ba ? "gpt2 beam" : sa ? "gpt2 sample" : "gpt2 greedy";
     R4D_REQUIRE(w && w->wte && st && st->last_d && st->logits_d, "%s: null pointer", who);
     R4D_REQUIRE(B >= 1 && t_cap >= 1, "%s: B=%d t_cap=%d", who, B, t_cap);
     const int d = cfg->n_embd, V = cfg->vocab;
@@ -707,8 +709,15 @@ static int advance_step(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
     size_t cbytes = 0;
     void* cnt = ws.pool ? gemm_skinny_counters(ws.pool, &cbytes) : nullptr;
     ge.zero_words = (unsigned*)cnt; ge.n_zero = (int)(cbytes / 4);
-    if ((rc = sa ? launch_sample_advance(st->logits_d, B, V, *sa, &g, s, &ge) : launch_greedy_advance(st->logits_d, B, V, g, s, &ge)))
-        return rc;
+    if (ba) {
+        R4D_REQUIRE(kv_cache_d && B % ba->n == 0, "%s: null cache or %d rows in groups of %d", who, B, ba->n);
+        if ((rc = launch_beam_rows(st->logits_d, B, V, *ba, s))) return rc;
+        if ((rc = launch_beam_advance(B / ba->n, V, *ba, &g, &ge, s))) return rc;
+        rc = launch_kv_reorder(kv_cache_d, ba->beam_idx, ba->lo, ba->hi, ba->group_active, cfg->n_layer, B / ba->n, ba->n, t_cap, d, s);
+    } else {
+        rc = sa ? launch_sample_advance(st->logits_d, B, V, *sa, &g, s, &ge) : launch_greedy_advance(st->logits_d, B, V, g, s, &ge);
+    }
+    if (rc) return rc;
     return decode_step_impl(cfg, w, st->next_d, nullptr, st->pos_d, kv_cache_d, B, t_cap, st->last_d, workspace_d, workspace_bytes,
                             stream, true);
 }
@@ -716,7 +725,7 @@ static int advance_step(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, c
 int r4d_gpt2_greedy_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
                              float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
                              void* stream) {
-    return advance_step(cfg, w, st, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, stream);
+    return advance_step(cfg, w, st, nullptr, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, stream);
 }
 
 // the sampled step's state as the greedy fields + the sampler's arguments
@@ -736,18 +745,19 @@ int r4d_gpt2_sample_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights*
     r4d_greedy_state g;
     SampleArgs sa;
     R4D_REQUIRE(split_sample_state(st, &g, &sa), "gpt2 sample: null pointer");
-    return advance_step(cfg, w, &g, &sa, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, stream);
+    return advance_step(cfg, w, &g, &sa, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, stream);
 }
 
 struct r4d_decode_graph { hipGraph_t graph; hipGraphExec_t exec; };
 
 static int capture_step(const char* who, const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
-                        const SampleArgs* sa, float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
-                        r4d_decode_graph** out_graph) {
+                        const SampleArgs* sa, const BeamArgs* ba, float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d,
+                        size_t workspace_bytes, r4d_decode_graph** out_graph) {
     R4D_REQUIRE(out_graph, "%s: null out_graph", who);
     *out_graph = nullptr;
     R4D_REQUIRE(!g_prof_on, "%s: switch the launch profiler off before capturing", who);
     if (sa) { const int prc = sample_advance_prepare(); if (prc) return prc; }
+    if (ba) { const int prc = beam_rows_prepare(); if (prc) return prc; }
     hipStream_t cap = nullptr;                                       // the caller's stream may be the null stream: not capturable
     R4D_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
     hipError_t e = hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed);
@@ -756,7 +766,7 @@ static int capture_step(const char* who, const r4d_gpt2_config* cfg, const r4d_g
         set_error("%s: begin capture: %s", who, hipGetErrorString(e));
         return R4D_ERR_HIP;
     }
-    const int rc = advance_step(cfg, w, st, sa, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, cap);
+    const int rc = advance_step(cfg, w, st, sa, ba, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, cap);
     hipGraph_t graph = nullptr;
     e = hipStreamEndCapture(cap, &graph);                            // always end the capture, also after an error
     (void)hipStreamDestroy(cap);
@@ -782,7 +792,7 @@ static int capture_step(const char* who, const r4d_gpt2_config* cfg, const r4d_g
 int r4d_gpt2_greedy_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_greedy_state* st,
                                  float* kv_cache_d, int32_t B, int32_t t_cap, void* workspace_d, size_t workspace_bytes,
                                  r4d_decode_graph** out_graph) {
-    return capture_step("gpt2 greedy graph", cfg, w, st, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, out_graph);
+    return capture_step("gpt2 greedy graph", cfg, w, st, nullptr, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, out_graph);
 }
 
 int r4d_gpt2_sample_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_sample_state* st,
@@ -792,7 +802,42 @@ int r4d_gpt2_sample_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weig
     SampleArgs sa;
     if (out_graph) *out_graph = nullptr;
     R4D_REQUIRE(split_sample_state(st, &g, &sa), "gpt2 sample graph: null pointer");
-    return capture_step("gpt2 sample graph", cfg, w, &g, &sa, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, out_graph);
+    return capture_step("gpt2 sample graph", cfg, w, &g, &sa, nullptr, kv_cache_d, B, t_cap, workspace_d, workspace_bytes, out_graph);
+}
+
+// the beam step's state as the greedy fields (per row) + the beam kernels' arguments
+static bool split_beam_state(const r4d_beam_state* st, r4d_greedy_state* g, BeamArgs* ba) {
+    if (!st || !st->fparams_d || st->n_beams < 2 || st->n_beams > R4D_BEAM_MAX) return false;
+    *g = r4d_greedy_state{st->last_d, st->logits_d, st->next_d, st->lens_d, st->pos_d, st->active_d, st->gen_len_d, st->out_tokens_d,
+                          st->params_d, st->out_cap};
+    *ba = BeamArgs{st->n_beams, st->seen_d, st->fparams_d, st->beam_scores_d, st->beam_idx_d, st->cand_scores_d, st->cand_ids_d,
+                   st->lo_d, st->hi_d, st->group_active_d, st->done_d, st->hyp_count_d, st->hyp_added_d, st->status_d,
+                   st->hyp_worst_d, st->hyp_score_d, st->hyp_len_d, st->hyp_seq_d, st->hyp_ids_d, nullptr, nullptr};
+    return true;
+}
+
+size_t r4d_gpt2_beam_workspace_bytes(const r4d_gpt2_config* cfg, int32_t B0, int32_t n_beams) {
+    if (B0 <= 0 || n_beams < 2 || n_beams > R4D_BEAM_MAX || (long long)B0 * n_beams > 0x7fffffffLL) return 0;
+    return r4d_gpt2_greedy_workspace_bytes(cfg, B0 * n_beams);
+}
+
+int r4d_gpt2_beam_step_f32(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_beam_state* st, float* kv_cache_d,
+                           int32_t B0, int32_t t_cap, void* workspace_d, size_t workspace_bytes, void* stream) {
+    r4d_greedy_state g;
+    BeamArgs ba;
+    R4D_REQUIRE(split_beam_state(st, &g, &ba), "gpt2 beam: null pointer or n_beams outside [2, %d]", R4D_BEAM_MAX);
+    R4D_REQUIRE(B0 >= 1 && (long long)B0 * ba.n <= 0x7fffffffLL, "gpt2 beam: B0=%d", B0);
+    return advance_step(cfg, w, &g, nullptr, &ba, kv_cache_d, B0 * ba.n, t_cap, workspace_d, workspace_bytes, stream);
+}
+
+int r4d_gpt2_beam_graph_create(const r4d_gpt2_config* cfg, const r4d_gpt2_weights* w, const r4d_beam_state* st, float* kv_cache_d,
+                               int32_t B0, int32_t t_cap, void* workspace_d, size_t workspace_bytes, r4d_decode_graph** out_graph) {
+    r4d_greedy_state g;
+    BeamArgs ba;
+    if (out_graph) *out_graph = nullptr;
+    R4D_REQUIRE(split_beam_state(st, &g, &ba), "gpt2 beam graph: null pointer or n_beams outside [2, %d]", R4D_BEAM_MAX);
+    R4D_REQUIRE(B0 >= 1 && (long long)B0 * ba.n <= 0x7fffffffLL, "gpt2 beam graph: B0=%d", B0);
+    return capture_step("gpt2 beam graph", cfg, w, &g, nullptr, &ba, kv_cache_d, B0 * ba.n, t_cap, workspace_d, workspace_bytes, out_graph);
 }
 
 int r4d_decode_graph_launch(r4d_decode_graph* graph, int32_t n_steps, void* stream) {

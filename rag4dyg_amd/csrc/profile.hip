@@ -30,7 +30,7 @@ static const char* kNames[PK_COUNT] = {
     "gemm_f32_kc_128x64x16", "gemm_f32_kc_64x64x32", "gemm_s3_128x256x32", "gemm_s3_128x128x32", "gemm_s3tn_128x256x32", "gemm_h2_128x256x32", "gemm_h2_128x128x32", "gemm_skinny", "gemm_skinny_epilogue", "embed_layernorm",
     "layernorm", "causal_softmax", "decode_attention", "greedy_advance", "attn_fused", "lnf_partial", "meanpool_reduce", "normalize_rows", "pool_scan", "topk", "merge_topk", "argsort", "jaccard", "jaccard_prep", "lm_ce",
     "splice_embed_ln", "weighted_bag", "embedding_scatter", "gemm_bf16_32", "gemm_bf16tn_32", "gemm_h2_rowmap_c_attn0", "pad_rows_classify", "pad_rows_fill", "gemm_bf16h_nt", "gemm_bf16h_nn",
-    "attn_train_fused_fwd", "attn_train_fused_rowsum", "attn_train_fused_dkv", "attn_train_fused_dq", "attn_b1", "sample_advance"};
+    "attn_train_fused_fwd", "attn_train_fused_rowsum", "attn_train_fused_dkv", "attn_train_fused_dq", "attn_b1", "sample_advance", "beam_rows", "beam_advance", "kv_reorder"};
 
 unsigned long long g_branch_hits[BR_COUNT];
 static const char* kBranchNames[BR_COUNT] = {

@@ -559,6 +559,18 @@ class GPT2Model(_PreTrained):
         dec = cache[(B, t_cap, slot)] = SamplingDecoder(self, B, t_cap)
         return dec
 
+    def beam_decoder(self, B0, n, t_cap, slot=0):
+        """``greedy_decoder``'s twin for the ``BeamDecoder``: keyed by (prompts, beams, rounded t_cap, slot), a cache of its own."""
+        t_cap = (int(t_cap) + 127) // 128 * 128
+        cache = self.__dict__.setdefault("_beam_decoders", {})
+        fits = [k for k in cache if k[0] == (B0, n) and k[1] >= t_cap and k[2] == slot]
+        if fits:
+            return cache[min(fits)]
+        for k in [k for k in cache if k[0] == (B0, n) and k[2] == slot]:
+            cache.pop(k).close()
+        dec = cache[((B0, n), t_cap, slot)] = BeamDecoder(self, B0, n, t_cap)
+        return dec
+
     @torch.no_grad()
     def encode_groups_meanpool(self, batches):
         """Mean-pooled embeddings of several right-padded batches in one fused launch sequence
@@ -660,7 +672,9 @@ class GreedyDecoder:
         except Exception:
             pass
 
-    def _steps(self, n):
+    def _launch(self, n, create, step, state, B):
+        """``n`` steps on ``state``: ``create`` / ``step`` = (bound entry, its name in an error) of the graph's entry and of the
+        kernel-by-kernel one."""
         lib = _lib.load()
         c, w, layers = self.tr._c_structs(decode=True)
         stream = torch.cuda.current_stream().cuda_stream
@@ -669,17 +683,20 @@ class GreedyDecoder:
             if self._graph is None or key != self._graph_key:
                 self.close()
                 g = ctypes.c_void_p()
-                _lib.check(lib.r4d_gpt2_greedy_graph_create(ctypes.byref(c), ctypes.byref(w), ctypes.byref(self.state),
-                                                            self.cache.data_ptr(), self.B, self.t_cap, self.ws.data_ptr(),
-                                                            self.ws.numel(), ctypes.byref(g)), "gpt2_greedy_graph_create")
+                _lib.check(create[0](ctypes.byref(c), ctypes.byref(w), ctypes.byref(state), self.cache.data_ptr(), B, self.t_cap,
+                                     self.ws.data_ptr(), self.ws.numel(), ctypes.byref(g)), create[1])
                 self._graph, self._graph_key = g, key
                 self.graph_builds += 1
             _lib.check(lib.r4d_decode_graph_launch(self._graph, n, stream), "decode_graph_launch")
         else:
             for _ in range(n):
-                _lib.check(lib.r4d_gpt2_greedy_step_f32(ctypes.byref(c), ctypes.byref(w), ctypes.byref(self.state),
-                                                        self.cache.data_ptr(), self.B, self.t_cap, self.ws.data_ptr(),
-                                                        self.ws.numel(), stream), "gpt2_greedy_step")
+                _lib.check(step[0](ctypes.byref(c), ctypes.byref(w), ctypes.byref(state), self.cache.data_ptr(), B, self.t_cap,
+                                   self.ws.data_ptr(), self.ws.numel(), stream), step[1])
+
+    def _steps(self, n):
+        lib = _lib.load()
+        self._launch(n, (lib.r4d_gpt2_greedy_graph_create, "gpt2_greedy_graph_create"), (lib.r4d_gpt2_greedy_step_f32, "gpt2_greedy_step"),
+                     self.state, self.B)
 
     @torch.no_grad()
     def begin(self, last, lens, max_gen, len_limit, eos=()):
@@ -726,24 +743,8 @@ class SamplingDecoder(GreedyDecoder):
 
     def _steps(self, n):
         lib = _lib.load()
-        c, w, layers = self.tr._c_structs(decode=True)
-        stream = torch.cuda.current_stream().cuda_stream
-        if self.use_graph:
-            key = bytes(layers) + bytes((ctypes.c_void_p * 5)(w.wte, w.wpe, w.ln_f_w, w.ln_f_b, w.lm_head))   # every weight pointer baked in
-            if self._graph is None or key != self._graph_key:
-                self.close()
-                g = ctypes.c_void_p()
-                _lib.check(lib.r4d_gpt2_sample_graph_create(ctypes.byref(c), ctypes.byref(w), ctypes.byref(self.sstate),
-                                                            self.cache.data_ptr(), self.B, self.t_cap, self.ws.data_ptr(),
-                                                            self.ws.numel(), ctypes.byref(g)), "gpt2_sample_graph_create")
-                self._graph, self._graph_key = g, key
-                self.graph_builds += 1
-            _lib.check(lib.r4d_decode_graph_launch(self._graph, n, stream), "decode_graph_launch")
-        else:
-            for _ in range(n):
-                _lib.check(lib.r4d_gpt2_sample_step_f32(ctypes.byref(c), ctypes.byref(w), ctypes.byref(self.sstate),
-                                                        self.cache.data_ptr(), self.B, self.t_cap, self.ws.data_ptr(),
-                                                        self.ws.numel(), stream), "gpt2_sample_step")
+        self._launch(n, (lib.r4d_gpt2_sample_graph_create, "gpt2_sample_graph_create"), (lib.r4d_gpt2_sample_step_f32, "gpt2_sample_step"),
+                     self.sstate, self.B)
 
     def set_seen(self, id_lists=None):
         """The seen bitmap from one list of ids per sequence (``None``: nothing seen)."""
@@ -779,6 +780,133 @@ class SamplingDecoder(GreedyDecoder):
         self.begin(last, lens, max_gen, len_limit, eos)
 
 
+class BeamHyps:
+    """The finished hypotheses of one prompt -- the rule of the reference's ``BeamHypotheses`` (``modeling_utils.py:1205-1252``,
+    ``early_stopping`` off), stated once more for the host: ``beam_advance_kernel`` (csrc/beam.hip) states it for the device, and
+    both are tested against tests/_beam_ref.py.  ``beams``: (score, ids) in order of arrival."""
+
+    def __init__(self, num_beams, max_length, length_penalty, beams=(), worst=1e9):
+        self.n, self.limit, self.lp = num_beams, max_length - 1, length_penalty
+        self.beams, self.worst = list(beams), worst
+
+    def add(self, ids, sum_logprobs):
+        score = sum_logprobs / len(ids) ** self.lp
+        if len(self.beams) >= self.n and not score > self.worst:
+            return
+        self.beams.append((score, ids))
+        if len(self.beams) <= self.n:
+            self.worst = min(score, self.worst)
+            return
+        lowest = min(range(len(self.beams)), key=lambda i: (self.beams[i][0], i))      # equal scores: the earliest arrival leaves
+        del self.beams[lowest]
+        self.worst = min(sc for sc, _ in self.beams)
+
+    def is_done(self, best_sum_logprobs):
+        return len(self.beams) >= self.n and self.worst >= best_sum_logprobs / self.limit ** self.lp
+
+    def best(self, k):
+        """The ids of the ``k`` best, best first; among equal scores the latest arrival first (a stable sort, popped from its end)."""
+        ranked = sorted(self.beams, key=lambda h: h[0])
+        return [ranked.pop()[1] for _ in range(k)]
+
+
+def beam_finalize(hyps, n_ret, max_length, pad_token_id, eos_token_ids):
+    """The reference's last step (``modeling_utils.py:1120-1153``): per prompt the ``n_ret`` best hypotheses of ``hyps`` (one
+    ``BeamHyps`` each), row ``i * n_ret + j`` prompt ``i``'s ``j``-th best; rows of unequal length are padded with ``pad_token_id``, and a
+    row shorter than ``max_length`` then gets ``eos_token_ids[0]`` behind its last id.  Returns int64 [len(hyps) * n_ret, L] on the CPU."""
+    rows = [ids for h in hyps for ids in h.best(n_ret)]
+    lens = [len(r) for r in rows]
+    if min(lens) == max(lens):
+        return torch.tensor(rows, dtype=torch.long).view(len(rows), lens[0])
+    assert pad_token_id is not None, "`Pad_token_id` has to be defined"
+    out = torch.full((len(rows), min(max(lens) + 1, max_length)), pad_token_id, dtype=torch.long)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = torch.tensor(r, dtype=torch.long)
+        if len(r) < max_length:
+            out[i, len(r)] = eos_token_ids[0]
+    return out
+
+
+class BeamDecoder(GreedyDecoder):
+    """Greedy beam search with the loop state on the device (``r4d_gpt2_beam_step_f32`` / ``r4d_gpt2_beam_graph_create``): per token
+    the LM head on ``B0 * n`` rows, every row's 2n best continuations, the reference's walk over each prompt's merged 2n with its
+    finished hypotheses, the reordering of the key/value cache, and one cached step -- replayed as a captured graph without a host
+    round trip.  Rows ``b n .. b n + n - 1`` of every per-row buffer (and of ``self.cache``) are the beams of prompt ``b``.  Owns,
+    besides the greedy decoder's buffers, the beam scores, the candidate lists and the hypotheses (``r4d.h``: ``r4d_beam_state``)."""
+
+    def __init__(self, transformer, B0, n, t_cap):
+        if not 2 <= n <= ops.BEAM_MAX:
+            raise ValueError(f"BeamDecoder: 2 <= num_beams <= {ops.BEAM_MAX}")
+        super().__init__(transformer, B0 * n, t_cap)
+        dev, V, R = self.device, transformer.wte.num_embeddings, B0 * n
+        if V < 2:
+            raise ValueError("BeamDecoder: beam search needs a vocabulary of at least 2 ids (2n candidates out of n * V)")
+        self.B0, self.n = B0, n
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.seen = torch.zeros(R, (V + 31) // 32, **i32)
+        self.fparams = ops.beam_params(dev)
+        self.beam_scores = torch.zeros(R, dtype=torch.float32, device=dev)
+        self.beam_idx = torch.empty(R, **i32)
+        self.cand_scores, self.cand_ids = torch.empty(R, 2 * n, dtype=torch.float32, device=dev), torch.empty(R, 2 * n, **i32)
+        self.lo, self.hi, self.group_active = torch.empty(B0, **i32), torch.empty(B0, **i32), torch.empty(B0, **i32)
+        self.done, self.hyp_count, self.hyp_added, self.status = (torch.zeros(B0, **i32) for _ in range(4))
+        self.hyp_worst = torch.full((B0,), 1e9, dtype=torch.float64, device=dev)
+        self.hyp_score = torch.empty(B0, n, dtype=torch.float64, device=dev)
+        self.hyp_len, self.hyp_seq = torch.empty(B0, n, **i32), torch.empty(B0, n, **i32)
+        self.hyp_ids = torch.empty(B0, n, t_cap, **i32)
+        own = (self.seen, self.fparams, self.beam_scores, self.beam_idx, self.cand_scores, self.cand_ids, self.lo, self.hi, self.group_active,
+               self.done, self.hyp_count, self.hyp_added, self.status, self.hyp_worst, self.hyp_score, self.hyp_len, self.hyp_seq, self.hyp_ids)
+        self.bstate = _lib.BeamStateC(*[getattr(self.state, f) for f, _ in _lib.GreedyStateC._fields_], n, *[t.data_ptr() for t in own])
+
+    def _steps(self, k):
+        lib = _lib.load()
+        self._launch(k, (lib.r4d_gpt2_beam_graph_create, "gpt2_beam_graph_create"), (lib.r4d_gpt2_beam_step_f32, "gpt2_beam_step"),
+                     self.bstate, self.B0)
+
+    @torch.no_grad()
+    def begin_beams(self, last, T, max_gen, eos=(), length_penalty=1.0, repetition_penalty=1.0, seen_ids=None):
+        """The state of a new search: ``last`` [B0 * n, d] the ln_f rows of the prompts' last positions (the n rows of a prompt
+        alike), ``T`` the prompt length all rows share, ``seen_ids`` one list of ids per ROW for the repetition penalty."""
+        R, dev = self.B, self.device
+        self.begin(last, torch.full((R,), int(T), dtype=torch.int32), max_gen, self.t_cap + 1, eos)
+        self.params[7:8].copy_(torch.tensor([int(T)], dtype=torch.int32))
+        self.fparams.copy_(ops.beam_params(dev, length_penalty, repetition_penalty))
+        start = torch.full((self.B0, self.n), -1e9, dtype=torch.float32)
+        start[:, 0] = 0.0                                                      # every row holds the same prompt: one beam counts
+        self.beam_scores.copy_(start.view(-1))
+        for t in (self.done, self.hyp_count, self.hyp_added, self.status):
+            t.zero_()
+        self.hyp_worst.fill_(1e9)
+        SamplingDecoder.set_seen(self, seen_ids)
+
+    @torch.no_grad()
+    def run_beams(self, last, T, max_gen, eos=(), length_penalty=1.0, repetition_penalty=1.0, seen_ids=None, poll=8):
+        """Search from the prefilled cache until every prompt is done or ``max_gen`` ids are generated; one host synchronisation
+        per ``poll`` tokens.  Returns, per prompt, dict(done, hyps = [(score, generated ids)] in order of arrival, worst,
+        beams = [(beam score, generated ids)] the n live beams)."""
+        self.begin_beams(last, T, max_gen, eos, length_penalty, repetition_penalty, seen_ids)
+        k, steps = (int(max_gen) if max_gen <= 16 else poll), 0
+        while True:
+            self._steps(k)
+            steps += k
+            if steps > self.t_cap or not bool(self.active.any()):
+                break
+            k = poll
+        n = self.n
+        if bool(self.status.any()):
+            raise AssertionError("Beam should always be full")                 # (the reference's assert, :1073)
+        out, g, sc = self.out.cpu(), self.gen_len.cpu(), self.beam_scores.cpu()
+        done, cnt, worst = self.done.cpu(), self.hyp_count.cpu(), self.hyp_worst.cpu()
+        hs, hl, hq, hi = self.hyp_score.cpu(), self.hyp_len.cpu(), self.hyp_seq.cpu(), self.hyp_ids.cpu()
+        res = []
+        for b in range(self.B0):
+            order = sorted(range(int(cnt[b])), key=lambda i: int(hq[b, i]))
+            res.append(dict(done=bool(done[b]), worst=float(worst[b]),
+                            hyps=[(float(hs[b, i]), hi[b, i, :int(hl[b, i])].tolist()) for i in order],
+                            beams=[(float(sc[b * n + i]), out[b * n + i, :int(g[b * n + i])].tolist()) for i in range(n)]))
+        return res
+
+
 _GENERATE_DEFAULTS = dict(max_length=20, do_sample=False, num_beams=1, temperature=1.0, top_k=50, top_p=1.0, repetition_penalty=1.0,
                           bos_token_id=None, pad_token_id=None, eos_token_ids=None, length_penalty=1.0, num_return_sequences=1)
 
@@ -788,14 +916,17 @@ class _LMHeadBase(_PreTrained):
     def generate(self, input_ids=None, max_length=None, do_sample=None, num_beams=None, temperature=None, top_k=None, top_p=None,
                  repetition_penalty=None, bos_token_id=None, pad_token_id=None, eos_token_ids=None, length_penalty=None,
                  num_return_sequences=None, *, seed=0, inputs_embeds=None):
-        """The reference's ``generate`` without beam search (``modeling_utils.py:608-927``): greedy or sampled continuation of
+        """The reference's ``generate`` (``modeling_utils.py:608-1153``): greedy, sampled or beam-search continuation of
         ``input_ids`` [B, T] with the key/value cache, the choice of every token made on the device.  Arguments left ``None`` come
         from the config where it carries them, else from the reference's defaults (``configuration_utils.py:72-82``).  Returns
         int64 [B * num_return_sequences, L]: prompt, generated ids with the eos, finished rows padded with ``pad_token_id``;
         rows ``i * n .. i * n + n - 1`` continue prompt ``i``.  Row ``j`` draws from Philox stream ``j`` of ``seed``: the same seed
         repeats the call.  ``inputs_embeds`` [B, T, d] replaces the prompt's embedding rows (the RAG splice); ``input_ids`` are then
         optional and used for the repetition penalty and the prompt columns of the output only.  WITHOUT ``input_ids`` there are
-        no prompt ids to return: the result is the generated part alone, int64 [B * num_return_sequences, L - T].  ``num_beams > 1`` is not built."""
+        no prompt ids to return: the result is the generated part alone, int64 [B * num_return_sequences, L - T].
+        ``num_beams = n``, 2 <= n <= 16, is the reference's greedy beam search (``do_sample`` False only): ``n`` beams per prompt on the
+        device, ``length_penalty``, ``num_return_sequences <= n`` best hypotheses per prompt, the shorter ones padded and closed with
+        ``eos_token_ids[0]`` as the reference does."""
         cfg = self.config
         given = dict(max_length=max_length, do_sample=do_sample, num_beams=num_beams, temperature=temperature, top_k=top_k, top_p=top_p,
                      repetition_penalty=repetition_penalty, bos_token_id=bos_token_id, pad_token_id=pad_token_id,
@@ -821,11 +952,23 @@ class _LMHeadBase(_PreTrained):
             "`eos_token_ids` should be a positive integer or a list/tuple of positive integers."
         assert length_penalty > 0, "`length_penalty` should be strictly positive."
         assert isinstance(n_ret, int) and n_ret > 0, "`num_return_sequences` should be a strictly positive integer."
-        if num_beams > 1:
-            raise NotImplementedError("generate: beam search (num_beams > 1) is not built")
         if not do_sample:
-            assert n_ret == 1, "Greedy decoding will always produce the same output for num_beams == 1 and num_return_sequences > 1. " \
-                               "Please set num_return_sequences = 1"
+            if num_beams == 1:
+                assert n_ret == 1, "Greedy decoding will always produce the same output for num_beams == 1 and num_return_sequences > 1. " \
+                                   "Please set num_return_sequences = 1"
+            else:
+                assert num_beams >= n_ret, "Greedy beam search decoding cannot return more sequences than it has beams. " \
+                                           "Please set num_beams >= num_return_sequences"
+        if num_beams > 1:
+            if num_beams > ops.BEAM_MAX:
+                raise NotImplementedError(f"generate: at most {ops.BEAM_MAX} beams are built")
+            if do_sample:
+                raise NotImplementedError("generate: sampled beam search (do_sample=True with num_beams > 1) is not built: the reference "
+                                          "draws 2 * num_beams ids without replacement, which the Philox sampler has no counterpart of")
+            if self.transformer.wte.num_embeddings < 2:
+                raise ValueError("generate: beam search needs a vocabulary of at least 2 ids (2 * num_beams candidates out of num_beams * V)")
+            if not self.transformer.wte.weight.is_cuda:                         # (the refusals above hold wherever the weights are)
+                raise NotImplementedError("generate: beam search runs on the GPU only (the beam step is a device loop; there is no CPU path)")
         if eos_token_ids is not None and len(eos_token_ids) > 4:
             raise NotImplementedError("generate: the device loop tests at most 4 eos ids")
         tr = self.transformer
@@ -849,6 +992,9 @@ class _LMHeadBase(_PreTrained):
             raise ValueError("generate: an empty prompt")
         if max_length > tr.wpe.num_embeddings:
             raise ValueError(f"generate: max_length {max_length} exceeds n_positions {tr.wpe.num_embeddings}")
+        if num_beams > 1:
+            return self._generate_beams(input_ids, inputs_embeds, B0, T, max_length, num_beams, n_ret, eos_token_ids, pad_token_id,
+                                        length_penalty, repetition_penalty)
         mult = n_ret if do_sample else 1
         ids_rows = input_ids.repeat_interleave(mult, 0) if input_ids is not None else None          # rows i * n .. i * n + n - 1: prompt i
         if max_length <= T:                                                                          # (the reference's loop does not run)
@@ -882,6 +1028,32 @@ class _LMHeadBase(_PreTrained):
         for i, g in enumerate(gen):
             out[i, T:T + len(g)] = torch.tensor(g, dtype=torch.long)
         return out.to(dev)
+
+    def _generate_beams(self, input_ids, inputs_embeds, B0, T, max_length, n, n_ret, eos_token_ids, pad_token_id, length_penalty,
+                        repetition_penalty):
+        """``generate`` with ``num_beams = n > 1``: the search on the device (``BeamDecoder``), the reference's last step on the host."""
+        tr = self.transformer
+        dev = tr.wte.weight.device
+        prompts = input_ids.cpu().tolist() if input_ids is not None else [[0] * T for _ in range(B0)]
+        hyps = [BeamHyps(n, max_length, length_penalty) for _ in range(B0)]
+        if max_length > T:
+            dec = tr.beam_decoder(B0, n, max_length)
+            lens = [T] * (B0 * n)
+            if inputs_embeds is not None:
+                last = tr.prefill_last(dec.cache, lens, inputs_embeds=inputs_embeds.to(dev).repeat_interleave(n, 0))
+            else:
+                last = tr.prefill_last(dec.cache, lens, input_ids=input_ids.repeat_interleave(n, 0))
+            seen_ids = [p for p in prompts for _ in range(n)] if (input_ids is not None and repetition_penalty != 1.0) else None
+            res = dec.run_beams(last, T, max_length - T, list(eos_token_ids or ()), length_penalty, repetition_penalty, seen_ids)
+        else:                                                                 # (the reference's loop does not run: the start scores)
+            res = [dict(done=False, worst=1e9, hyps=[], beams=[(0.0 if i == 0 else -1e9, []) for i in range(n)]) for _ in range(B0)]
+        for b, (h, r) in enumerate(zip(hyps, res)):
+            h.beams, h.worst = [(sc, prompts[b] + ids) for sc, ids in r["hyps"]], r["worst"]
+            if not r["done"]:                                                 # open beams join with their beam scores (:1098-1118)
+                for sc, ids in r["beams"]:
+                    h.add(prompts[b] + ids, sc)
+        out = beam_finalize(hyps, n_ret, max_length, pad_token_id, eos_token_ids)
+        return (out if input_ids is not None else out[:, T:]).to(dev)
 
     def __init__(self, config):
         super().__init__()

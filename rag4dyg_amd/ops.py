@@ -708,6 +708,74 @@ def sample_logits(logits, step, stream, do_sample=True, temperature=1.0, top_k=0
     return (tok,) + ((keep,) if want_keep else ()) + ((u,) if want_u else ())
 
 
+BEAM_MAX = 16
+
+
+def beam_params(device, length_penalty=1.0, repetition_penalty=1.0):
+    """The parameter word of the beam step (``r4d.h``: fparams_d float[4]) as a device tensor."""
+    return torch.tensor([float(length_penalty), float(repetition_penalty), 0.0, 0.0], dtype=torch.float32).to(device)
+
+
+def beam_select(logits, beam_scores, num_beams, repetition_penalty=1.0, seen=None, want_rows=False):
+    """The 2n best continuations of every prompt (``r4d_beam_select_f32``): ``logits`` [B0 * n, V] (rows ``b n .. b n + n - 1`` the
+    beams of prompt ``b``), ``beam_scores`` [B0 * n]; score = log_softmax(penalised row) + beam score in fp32, order (score descending,
+    flat index ``beam * V + id`` ascending).  Returns (scores float32 [B0, 2n], flat indices int32 [B0, 2n]); with ``want_rows`` also
+    the rows' own lists (float32 / int32 [B0 * n, 2n], entries past min(2n, V): -inf / -1).  ``seen`` is read, not updated."""
+    R, V = logits.shape
+    n = int(num_beams)
+    dev = logits.device
+    if not 2 <= n <= BEAM_MAX or R % n:
+        raise ValueError(f"beam_select: 2 <= num_beams <= {BEAM_MAX} and rows in groups of num_beams")
+    if V < 2 or n * V >= 1 << 31:
+        raise ValueError("beam_select: 2 <= V and num_beams * V < 2^31")
+    if repetition_penalty < 1:
+        raise ValueError("beam_select: repetition_penalty >= 1")
+    nw = (V + 31) // 32
+    if seen is not None and tuple(seen.shape) != (R, nw):
+        raise ValueError(f"beam_select: seen must be int32 [{R}, {nw}]")
+    B0 = R // n
+    fpar = beam_params(dev, 1.0, repetition_penalty)
+    cs = torch.empty(R, 2 * n, dtype=torch.float32, device=dev)
+    ci = torch.empty(R, 2 * n, dtype=torch.int32, device=dev)
+    out_s = torch.empty(B0, 2 * n, dtype=torch.float32, device=dev)
+    out_i = torch.empty(B0, 2 * n, dtype=torch.int32, device=dev)
+    check(_lib.load().r4d_beam_select_f32(_dev(logits, torch.float32, "logits"), _dev(beam_scores, torch.float32, "beam_scores"),
+                                          _dev(seen, torch.int32, "seen") if seen is not None else None, fpar.data_ptr(), B0, n, V,
+                                          cs.data_ptr(), ci.data_ptr(), out_s.data_ptr(), out_i.data_ptr(), _stream()), "beam_select")
+    return (out_s, out_i, cs, ci) if want_rows else (out_s, out_i)
+
+
+def kv_cache_reorder(kv_cache, src_row, num_beams, lo, hi, active=None):
+    """Reorder ``kv_cache`` [n_layer, B0 * n, t_cap, 2d] IN PLACE (``r4d_kv_cache_reorder_f32``): for every group ``b`` (``active[b]``
+    != 0) and position in ``[lo[b], hi[b])``, row ``b n + i`` receives the K | V line of row ``src_row[b n + i]``.  This front end
+    reads ``src_row`` on the host (one synchronisation) and refuses a source outside its own group; the decode loop calls the entry
+    itself, where such a row is poisoned instead."""
+    if kv_cache.dim() != 4 or kv_cache.shape[3] % 4:
+        raise ValueError("kv_cache_reorder: kv_cache must be [n_layer, rows, t_cap, 2d] with d even")
+    L, R, t_cap, d2 = kv_cache.shape
+    n = int(num_beams)
+    if not 1 <= n <= BEAM_MAX or R % n:
+        raise ValueError(f"kv_cache_reorder: 1 <= num_beams <= {BEAM_MAX} and rows in groups of num_beams")
+    B0 = R // n
+    dev = kv_cache.device
+    i32 = lambda t, m, name: _check_len(t.to(device=dev, dtype=torch.int32).contiguous(), m, name)
+    src_row, lo, hi = i32(src_row, R, "src_row"), i32(lo, B0, "lo"), i32(hi, B0, "hi")
+    active = i32(active, B0, "active") if active is not None else None
+    group = torch.arange(R, device=dev, dtype=torch.int32) // n
+    if bool(((src_row // n != group) | (src_row < 0)).any()):
+        raise ValueError("kv_cache_reorder: a src_row outside its own group")
+    check(_lib.load().r4d_kv_cache_reorder_f32(_dev(kv_cache, torch.float32, "kv_cache"), src_row.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                               active.data_ptr() if active is not None else None, L, B0, n, t_cap, d2 // 2, _stream()),
+          "kv_cache_reorder")
+    return kv_cache
+
+
+def _check_len(t, m, name):
+    if t.numel() != m:
+        raise ValueError(f"{name}: expected {m} values, got {t.numel()}")
+    return t
+
+
 # ------------------------------------------------------------------------------------------- range guard (include/r4d.h, ABI v6)
 RANGE_NONFINITE_HIDDEN, RANGE_BAD_NORM, RANGE_BAD_LABEL = 1, 2, 4
 _RANGE_FLAG = None
